@@ -9,6 +9,7 @@ batch of 256 frames that is already resident in HBM.  Frames shard across ranks 
 
   python bench.py                      (N = 1, 320 timed steps ~ 1 s over a 4096-frame pool, + parity / f16 / PCIe / ViT / BC legs)
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   (+ DIR/embeddings.npy: what the last timed step computed)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N --steps K --warmup W        (no launcher: starts that torch.distributed.run command itself as a child process)
 """
@@ -18,8 +19,6 @@ import json
 import os
 import sys
 import time
-
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')      # five busy streams (see pvr_habitat_amd/__init__.py); read at the first GPU call
 
 import numpy as np
 import torch
@@ -749,6 +748,23 @@ def _r(x, nd=6):
     return float('%.*g' % (nd, x))
 
 
+DUMP_LIMIT_BYTES = 63 * 10 ** 6                           # all .npy files of --dump-outputs together, headers included, stay under 64 MB
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: DIR/<name>.npy of every array, float32 / float64 as computed.  An array larger than its share of DUMP_LIMIT_BYTES
+    keeps a fixed, seeded sample of its rows (in row order), so that two runs with the same arguments write the same elements."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) - 4096
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > share:
+            keep = share // (a.nbytes // a.shape[0])
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a))
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: start `python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py <same
     arguments>` as a CHILD process (this process has not touched a GPU and never does: no HIP call, no exec after one), let rank 0's single
@@ -780,7 +796,8 @@ def self_launch(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=320, help='timed steps; the default makes the timed region ~1 s and cycles the 4096-frame pool 20 times')
+    ap.add_argument('--steps', type=int, default=320, help='timed steps of every embedding leg (each leg is timed once); the default makes the '
+                                                             'headline\'s timed region ~1 s and cycles the 4096-frame pool 20 times')
     ap.add_argument('--warmup', type=int, default=4)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--frame', type=int, default=256)
@@ -805,6 +822,10 @@ def main():
     ap.add_argument('--per-op', action='store_true', help='print per-launch ms / TFLOP/s of one chunk to stderr')
     ap.add_argument('--dump-plan', default='', help='write the launch plan of the timed model (names in launch order) to this JSON file; '
                     'scripts/pmc_summary.py stores it next to the PMC bytes so that a later run can tell whether they still describe its plan')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='after the timed headline leg, write what its last step computed (the fp32 embeddings a caller of forward_into receives) '
+                         'to DIR/embeddings.npy (rank 0; at most 64 MB, a fixed seeded row sample beyond that).  The frames and weights are '
+                         'seeded, so two builds run with the same arguments can be compared output for output')
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -900,34 +921,21 @@ def main():
             model.forward_into(batches[i % len(batches)], chk, lane=0)
             torch.cuda.synchronize()
             assert torch.equal(chk, outs[i % lanes]), 'lane %d result differs from a sequential forward' % (i % lanes)
-        return model, el, lanes
+        return model, el, lanes, outs[(steps - 1) % lanes]
 
-    def repeated_leg(dtype, steps, warmup, lanes_req, min_total_s=1.0, max_reps=25):
-        """The contract's timed leg (exactly `steps` forwards between barrier + synchronize) repeated until the timed regions add up to
-        >= 1 s, so that a short --steps (the driver passes 20: 61 ms) is not one noisy sample: the MEDIAN leg is reported, `steps`
-        stays what was passed.  All ranks take the same number of repeats (rank 0's clock decides)."""
-        model_, el_, lanes_ = embed_leg(dtype, steps, warmup, lanes_req)
-        els = [el_]
-        while len(els) < max_reps:
-            more = torch.tensor([1.0 if sum(els) < min_total_s else 0.0], device='cuda')
-            if dist is not None:
-                dist.broadcast(more, 0)
-            if float(more.item()) == 0.0:
-                break
-            els.append(embed_leg(dtype, steps, 0, lanes_req)[1])
-        els_sorted = sorted(els)
-        return model_, els_sorted[(len(els) - 1) // 2], lanes_, els
-
-    model, el, lanes, el_all = repeated_leg(args.dtype, args.steps, args.warmup, args.lanes)
-    head_spread = [sp for sp in spread if sp[0] == el][:1] or spread[:1]          # the median leg's own (slowest, fastest) pair
+    # every leg is timed once: exactly `steps` forwards between barrier + synchronize
+    model, el, lanes, last_out = embed_leg(args.dtype, args.steps, args.warmup, args.lanes)
+    head_spread = spread[:1]                                  # the headline leg's (slowest, fastest) rank pair
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'embeddings': last_out})
     # the same leg with ONE batch in flight (the headline keeps `--lanes` batches in flight; the roofline object below is a one-lane measurement)
-    el_one = repeated_leg(args.dtype, args.steps, 1, 1, min_total_s=0.4)[1] if lanes > 1 else el
+    el_one = embed_leg(args.dtype, args.steps, 1, 1)[1] if lanes > 1 else el
     # the parity mode at the headline configuration, back to back with the headline leg (all ranks run it: weak scaling)
     leg16 = None
     if alt:
         k16 = args.steps                                      # full length: the two 16-bit types are reported side by side
-        m16, el16, l16, el16_all = repeated_leg(alt, k16, args.warmup, args.lanes)
-        leg16 = (m16, el16, l16, k16, el16_all)
+        m16, el16, l16, _ = embed_leg(alt, k16, args.warmup, args.lanes)
+        leg16 = (m16, el16, l16, k16)
     out = torch.empty((args.batch, model.out_size), dtype=torch.float32, device='cuda')
     frames = batches[0]
 
@@ -1014,10 +1022,6 @@ def main():
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(el / args.steps * 1e3, 3),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
             'timed_region_s': round(el, 3),
-            'timed_repeats': {'n': len(el_all), 'total_s': round(sum(el_all), 3), 'ms_per_step_min': round(min(el_all) / args.steps * 1e3, 3),
-                              'ms_per_step_max': round(max(el_all) / args.steps * 1e3, 3),
-                              'note': 'the %d-step leg (barrier + synchronize on both sides) repeated until the timed regions total >= 1 s; '
-                                      'value / ms_per_step / timed_region_s are the MEDIAN leg' % args.steps},
             'config': {'workload': 'configs[1]: ResNet50 (MoCo-v2 layout) frozen, %dx%d uint8 frames resident in HBM, batch %d/GPU, '
                                    'random-init synthetic weights, %s storage / MFMA inputs with fp32 accumulation%s'
                                    % (args.frame, args.frame, args.batch, args.dtype,
@@ -1026,7 +1030,7 @@ def main():
                        'frame_pool': '%d distinct frames per GPU resident in HBM, cycled batch by batch (every step embeds a different batch)' % n_pool,
                        'parallelism': 'frame shards, no collective (dp%d)' % world},
             'per_rank_ms_per_step': {'max': round(head_spread[0][0] / args.steps * 1e3, 3), 'min': round(head_spread[0][1] / args.steps * 1e3, 3),
-                                     'note': 'slowest / fastest rank of the reported (median) leg; value uses the slowest'},
+                                     'note': 'slowest / fastest rank of the headline leg; value uses the slowest'},
             'tflops_whole_net': round(fps * GFLOP_PER_FRAME / 1e3, 2),
             'one_lane': {'value': round(world * args.steps * args.batch / el_one, 1), 'unit': 'frames/s', 'ms_per_step': round(el_one / args.steps * 1e3, 3),
                          'note': 'the same %d-step leg with one batch in flight per GPU (strictly one forward at a time)' % args.steps},
@@ -1060,12 +1064,12 @@ def main():
                                'relative error distribution.  North-star bound 1e-3: met by f16 (the product default and, since round 5, the headline); bf16 '
                                'storage (8-bit significand) sits at ~3e-3')
     if leg16 is not None and rank == 0:
-        m16, el16, l16, k16, el16_all = leg16
+        m16, el16, l16, k16 = leg16
         ps16 = parity_stats(m16, sd, pool_np)
         line['parity'][alt] = {'rel_l2': _r(ps16['rel_l2']), 'max_norm': _r(ps16['max_norm']), 'elementwise': {k: (_r(v) if isinstance(v, float) else v) for k, v in ps16['elementwise'].items()}}
         line[alt] = {'metric': 'frames/sec embedded (ResNet50, 256x256), %s storage' % alt, 'value': round(world * k16 * args.batch / el16, 1),
                      'unit': 'frames/s', 'dtype': alt, 'steps': k16, 'ms_per_step': round(el16 / k16 * 1e3, 3), 'batches_in_flight': l16,
-                     'timed_region_s': round(el16, 3), 'timed_repeats': len(el16_all), 'parity_rel_l2': round(ps16['rel_l2'], 6),
+                     'timed_region_s': round(el16, 3), 'parity_rel_l2': round(ps16['rel_l2'], 6),
                      'note': 'the same leg as the headline (same steps, same frame pool, same kernels) with the other 16-bit storage type'}
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:

@@ -651,7 +651,7 @@ def _streams(dev_index=None):
         dev_index = torch.cuda.current_device()
     if dev_index not in _STREAM_CACHE:
         # a / b = compute lanes, h = H2D, d = D2H, x = a spare stream that is never used.  'xabhd' was the one order that measured the
-        # full rate in every context tried (fresh process, after other streams, GPU_MAX_HW_QUEUES 4 and 8; 'abhd' and 'hdab' each lose
+        # full rate in every context tried (fresh process, after other streams, four and eight hardware queues; 'abhd' and 'hdab' each lose
         # 25 % in one of them): profiles/experiments/r02_stream_creation_order.txt
         order = os.environ.get('PVR_STREAM_ORDER', 'xabhd')
         made = {}

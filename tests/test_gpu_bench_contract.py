@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -51,12 +52,18 @@ def _check(line, n):
     return d
 
 
-def test_bench_line_single_gpu():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + FAST, capture_output=True, text=True, timeout=600, cwd=ROOT)
+def test_bench_line_single_gpu(tmp_path):
+    dump = str(tmp_path / 'outputs')
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + FAST + ['--dump-outputs', dump], capture_output=True, text=True,
+                         timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1
     _check(lines[0], 1)
+    # --dump-outputs: the fp32 embeddings of the headline leg's last timed step, one row per frame of the batch
+    assert os.listdir(dump) == ['embeddings.npy']
+    e = np.load(os.path.join(dump, 'embeddings.npy'))
+    assert e.dtype == np.float32 and e.shape == (256, 2048) and np.isfinite(e).all() and float(e.std()) > 0
 
 
 def test_bench_line_two_ranks_on_one_gpu():

@@ -36,8 +36,7 @@ def test_rccl_binding_example_compiles_and_links():
 @pytest.mark.gpu
 @pytest.mark.skipif(not torch.cuda.is_available(), reason='needs an MI355X')
 def test_rccl_binding_example_runs():
-    if not os.path.exists(OUT):
-        _build()
+    _build()                          # always against this tree's library: a binary left from another build or checkout may be stale
     ranks = '2' if torch.cuda.device_count() >= 2 else '1'
     r = subprocess.run([OUT], capture_output=True, text=True, timeout=600, env=dict(os.environ, RANKS=ranks))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
