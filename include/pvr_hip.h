@@ -53,7 +53,7 @@ typedef int pvr_status;
 #define PVR_ARCH_MAE_VIT_B16 5   /* MAE/timm ViT-B/16 encoder, CLS token  -> 768 (mae.py:202-222, embeddings.py:137-140,377-379) */
 
 const char *pvr_version(void);
-/* 1 if the library was built with its measured-slower experiment kernels (make EXPERIMENTS=1: conv_w4 = pvr_debug_set_conv_algo(4), the
+/* 1 if the library was built with its measured-slower experiment kernels (make EXPERIMENTS=1: conv_w4 = conv_algo 4, the
  * split-bf16 GEMM = pvr_debug_set_gemm_mode(1..3), PVR_POLICY_BWD_FUSED, PVR_POLICY_PERSIST_BWD); the shipped build returns 0 and refuses them */
 int32_t pvr_has_experiments(void);
 /* test hook for the uint8-reading stem (stem.hip): 1 if frames of h x w uint8 pixels at `frames` with the 224 x 224 crop window at (top, left)
@@ -158,8 +158,11 @@ pvr_status pvr_encoder_profile_span(pvr_encoder *enc, const uint8_t *frames_dev,
 pvr_status pvr_encoder_check_range(pvr_encoder *enc, const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, float *out_dev, int64_t out_stride,
                                    void *hip_stream, int32_t *first_bad);
 /* Debug / A-B: the run-time switches of a finalized encoder - "pool_fuse" (the trunk's last convolution writes the average pool itself), "stem_u8" (the
- * fused stem reads uint8 frames that need no resize), "frame_min_n" (frames per forward from which layer3 runs one workgroup per frame).  Every other
- * PVR_* switch shapes the plan and is read from the environment ONCE, in pvr_encoder_create; nothing reads the environment on the forward path. */
+ * fused stem reads uint8 frames that need no resize), "frame_min_n" (frames per forward from which layer3 runs one workgroup per frame), "frame_run" /
+ * "frame_stagger" (layer3.1 .. 3.5 as one launch), "conv_algo" (the kernel of the shape-dispatched convolutions, as pvr_debug_set_conv_algo), "frame64"
+ * (the tiling of the whole-bottleneck frame launches, as pvr_debug_set_frame64), "stem_regpool" (1 the fused stem's max pool in registers, 0 the LDS-tile
+ * pooling of rounds 3-5; same bits).  Every other PVR_* switch shapes the plan and is read from the environment ONCE, in pvr_encoder_create; nothing
+ * reads the environment on the forward path. */
 pvr_status pvr_encoder_debug_set_switch(pvr_encoder *enc, const char *name, int32_t value);
 /* Which kernel family launch `index` (pvr_encoder_launch_name's indices) runs as in a forward of n frames, e.g. "bneck_frame(front1)", "conv_wfrag(pool)",
  * "conv_pp256(dual)", "chain_wave" / "chain_wave128" / "bottleneck_chain" (the three forms of the fused bottleneck tail), "conv_split16", "conv" (the shape-dispatched implicit GEMMs).  The choice is tabulated per batch size when the encoder is
@@ -210,7 +213,8 @@ pvr_status pvr_debug_bneck_frame_stamps(const void *t1_dev, const void *w2_dev, 
 int64_t pvr_debug_bneck_frame_launches(void);
 /* round 6: which kernel runs the whole-bottleneck form (w1f given; torchvision Bottleneck conv1 -> conv2 -> conv3 + identity reached from reference
  * src/embeddings.py:118-120): 1 bneck_frame64.hip (one wave per SIMD, 64 output channels x 13 pixel tiles per wave: half the LDS reads per MFMA), 0 the
- * 32-channel tiling of round 5, -1 back to the environment (PVR_FRAME64, default 0: bit-identical, measured slower).  Both give the same bits.  Process-global. */
+ * 32-channel tiling of round 5, -1 back to the environment (PVR_FRAME64, default 0: bit-identical, measured slower).  Both give the same bits.  Sets the
+ * pvr_op_* calls' choice only (process-wide); an encoder handle reads PVR_FRAME64 at create and changes it with pvr_encoder_debug_set_switch("frame64"). */
 pvr_status pvr_debug_set_frame64(int32_t mode);
 int64_t pvr_debug_bneck_frame64_launches(void);
 /* the 64-channel tiling with s_memtime stamps of workgroup 8, wave 0 (8 x uint64 on the device) - diagnostics only */
@@ -248,15 +252,13 @@ pvr_status pvr_op_conv2d_f32(const float *in_dev, const float *wgt_dev, const fl
                              int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t relu, void *hip_stream);
 int64_t pvr_debug_conv_split16_launches(void);
 /* launches of the layer2 wave-form tail (chain_wave128.hip: torchvision Bottleneck conv2 -> conv3 + identity -> the next conv1 at Cm = 128, reference
- * src/embeddings.py:118-120) so far (tests: the layer2 plan really took it; PVR_CHAIN_WAVE_L2=0 keeps the block form) */
+ * src/embeddings.py:118-120) so far (tests: the layer2 plan really took it).  The form is opt-in: PVR_CHAIN_WAVE_L2=1 at pvr_encoder_create selects it,
+ * the default (0) keeps the block form. */
 int64_t pvr_debug_chain_wave128_launches(void);
-/* debug / A-B: which form of the fused stem (conv1 7x7/2 + bn1 + relu + maxpool, torchvision ResNet stem reached from reference src/embeddings.py:118-120)
- * runs: 1 the max pool in registers straight from the MFMA accumulators (stem_pool_reg_kernel, default since round 6), 0 the pooling pass over an LDS tile
- * of rounds 3-5, -1 back to the environment (PVR_STEM_REGPOOL).  Both forms give the same bits.  Process-global. */
-pvr_status pvr_debug_set_stem_regpool(int32_t mode);
-/* debug / A-B: which implicit-GEMM kernel pvr_op_conv2d and the encoder plans use.  -1 = automatic choice by shape
- * (default), 0 = conv_igemm (128x128 tiles) only, 1 / 2 / 3 = conv_pp256 (ping-pong kernel, 256x256 / 128x256 / 224x256 tiles) whenever it
- * accepts the shape.  All kernels accumulate every output in the same K order and give bit-identical results. Process-global. */
+/* debug / A-B: which implicit-GEMM kernel pvr_op_conv2d uses.  -1 = automatic choice by shape (default), 0 = conv_igemm (128x128 tiles) only,
+ * 1 / 2 / 3 = conv_pp256 (ping-pong kernel, 256x256 / 128x256 / 224x256 tiles) whenever it accepts the shape.  All kernels accumulate every output in
+ * the same K order and give bit-identical results.  Sets the pvr_op_* calls' choice only (process-wide); an encoder handle reads PVR_CONV_ALGO at create
+ * and changes it with pvr_encoder_debug_set_switch("conv_algo"). */
 pvr_status pvr_debug_set_conv_algo(int32_t algo);
 /* debug: launches of the persistent weight-stationary 1x1 kernel (conv_expand.hip) so far in this process - lets a test assert that the
  * automatic choice really took that kernel for a shape.  PVR_CONV_EXPAND=0 disables the kernel (A/B; bit-identical). */

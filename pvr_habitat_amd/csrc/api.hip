@@ -1,6 +1,6 @@
 // C-ABI glue: error state, version, single-operator entry points (include/pvr_hip.h).
 #include <stdarg.h>
-#include "common.h"
+#include "encoder_internal.h"
 #include "sample_rng.h"
 #include <dlfcn.h>
 
@@ -42,42 +42,17 @@ const Roctx &roctx() { static Roctx r; return r; }
 void trace_push(const char *name) { if (roctx().push) roctx().push(name); }
 void trace_pop() { if (roctx().pop) roctx().pop(); }
 
-pvr_status launch_preprocess(const uint8_t *, int, int, int, int, int, void *, int, hipStream_t, int crop_pos = 0);
-pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
-pvr_status launch_maxpool(const void *, void *, int, int, int, int, int, hipStream_t);
-pvr_status launch_avgpool(const void *, float *, int64_t, int, int, int, int, int, hipStream_t);
-bool stem_pool_u8_ok(const void *, int, int, int, int);
-pvr_status launch_conv(const void *, const void *, const float *, const void *, void *, const void *, int, int, int, int,
-                       int, int, int, int, int, int, int, int, hipStream_t);
-
-void set_conv_algo(int a);
+// (the launchers the encoder shares: encoder_internal.h)
 long long conv_expand_launches();
 long long bneck_frame_launches();
-pvr_status launch_pack_frag_weights(const void *w, void *out, int rows, int K, hipStream_t stream);
-pvr_status launch_bneck_frame(const void *t1, const void *w2, const float *b2, const void *w3, const float *b3, const void *res, void *y,
-                              void *t2_out, int n, int phases, int dtype, hipStream_t stream, unsigned long long *stamps = nullptr,
-                              const void *w1np = nullptr, const float *b1n = nullptr, void *t1n = nullptr, const void *w1fp = nullptr, const float *b1f = nullptr);
-pvr_status launch_bneck_frame64(const void *w1p, const float *b1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *x, void *y, int n,
-                                int dtype, hipStream_t stream, unsigned long long *stamps);
-void set_frame64(int mode);
-long long bneck_frame64_launches();
 long long pp_persistent_launches();
-pvr_status launch_conv_pp256(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
-                             int cout, int kh, int kw, int stride, int pad, int act, int out_f32, int res_f32, int dtype, int bm, hipStream_t stream,
-                             const void *in2 = nullptr, int h2 = 0, int w2 = 0, int cin2 = 0, int stride2 = 1);
 long long conv_wfrag_launches();
-pvr_status launch_conv_wfrag(const void *in, const void *wp, const float *bias, const void *res, void *out, int n, int h, int w, int cin, int cout,
-                             int kh, int kw, int stride, int pad, int act, int out_f32, int dtype, hipStream_t stream, float *pool_out = nullptr,
-                             int64_t pool_stride = 0);
-
-void set_stem_regpool(int v);
 long long conv_split16_launches();
 long long chain_wave128_launches();
 pvr_status launch_split16_pack(const float *w, void *out, int rows, int K, hipStream_t stream);
 pvr_status launch_conv_split16(const float *in, const void *wsp, const float *bias, const float *res, float *out, int n, int h, int w, int cin,
                                int cout, int k, int stride, int pad, int relu, hipStream_t stream, float *out2 = nullptr, int n1 = 0, void *out16 = nullptr,
                                int terms = 3);
-pvr_status launch_conv_f32(const float *, const float *, const float *, const float *, float *, int, int, int, int, int, int, int, int, int, hipStream_t);
 
 static void *g_zero = nullptr;
 static pvr_status zero_page(void **out) {
@@ -110,21 +85,23 @@ pvr_status pvr_op_bneck_frame(const void *t1, const void *w2, const float *b2, c
                               void *t2_out, const void *w1n, const float *b1n, void *t1n, const void *w1f, const float *b1f, int32_t n, int32_t phases,
                               int32_t dtype, void *stream) {
     PVR_REQUIRE(n > 0 && n <= 1300, "pvr_op_bneck_frame: n must be 1..1300");
-    return launch_bneck_frame(t1, w2, b2, w3, b3, residual, y, t2_out, n, phases, dtype, (hipStream_t)stream, nullptr, w1n, b1n, t1n, w1f, b1f);
+    return launch_bneck_frame(op_switches(), t1, w2, b2, w3, b3, residual, y, t2_out, n, phases, dtype, (hipStream_t)stream, nullptr, w1n, b1n, t1n, w1f, b1f);
 }
 // the same launch with s_memtime stamps of block 8 (20 x uint64 on the device: waves 0 and 4, ten phase boundaries each) - diagnostics only
 pvr_status pvr_debug_bneck_frame_stamps(const void *t1, const void *w2, const float *b2, const void *w3, const float *b3, const void *residual, void *y,
                                         const void *w1n, const float *b1n, void *t1n, const void *w1f, const float *b1f, int32_t n, int32_t dtype,
                                         uint64_t *stamps_dev, void *stream) {
     PVR_REQUIRE(stamps_dev && n > 8, "pvr_debug_bneck_frame_stamps: needs a stamp buffer and more than 8 frames");
-    return launch_bneck_frame(t1, w2, b2, w3, b3, residual, y, nullptr, n, (w1n ? 7 : 3) | (w1f ? 8 : 0), dtype, (hipStream_t)stream, (unsigned long long *)stamps_dev,
+    return launch_bneck_frame(op_switches(), t1, w2, b2, w3, b3, residual, y, nullptr, n, (w1n ? 7 : 3) | (w1f ? 8 : 0), dtype, (hipStream_t)stream, (unsigned long long *)stamps_dev,
                               w1n, b1n, t1n, w1f, b1f);
 }
-// round 6: which kernel runs the whole-bottleneck frame launches (pvr_op_bneck_frame with w1f, the plan's bneck_frame(front1) launches): 1 the 64-channel tiling
-// (bneck_frame64.hip), 0 bneck_frame_kernel<.., FRONT1>, -1 back to the environment (PVR_FRAME64, default 0: bit-identical, measured slower).  Same bits either way.  Process-global.
+// round 6: which kernel runs pvr_op_bneck_frame's whole-bottleneck launches (w1f given): 1 the 64-channel tiling (bneck_frame64.hip), 0 bneck_frame_kernel<..,
+// FRONT1>, -1 back to the environment (PVR_FRAME64, default 0: bit-identical, measured slower).  Same bits either way.  The pvr_op_* calls only (op_switches);
+// an encoder handle has its own switch (pvr_encoder_debug_set_switch "frame64").
 pvr_status pvr_debug_set_frame64(int32_t mode) {
     PVR_REQUIRE(mode >= -1 && mode <= 1, "pvr_debug_set_frame64: -1 (environment: PVR_FRAME64, default off), 0 or 1");
-    set_frame64(mode);
+    if (mode < 0) { PlanSwitches env; read_switches(env); mode = env.frame64; }
+    op_switches().frame64 = mode;
     return PVR_OK;
 }
 int64_t pvr_debug_bneck_frame64_launches(void) { return (int64_t)bneck_frame64_launches(); }
@@ -140,7 +117,7 @@ pvr_status pvr_op_conv_wfrag(const void *in, const void *wgt_packed, const float
                              int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t relu, int32_t out_f32, int32_t dtype,
                              void *stream) {
     PVR_REQUIRE(n > 0 && h > 0 && w > 0, "pvr_op_conv_wfrag: empty input");
-    return launch_conv_wfrag(in, wgt_packed, bias, residual, out, n, h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, dtype, (hipStream_t)stream);
+    return launch_conv_wfrag(op_switches(), in, wgt_packed, bias, residual, out, n, h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, dtype, (hipStream_t)stream);
 }
 // conv_pp256's two-operand form (conv3 & downsample in one accumulation), for the op-level parity tests
 pvr_status pvr_op_conv2d_dual(const void *in, const void *in2, const void *wgt, const float *bias, void *out, int32_t n, int32_t h, int32_t w, int32_t cin,
@@ -148,14 +125,14 @@ pvr_status pvr_op_conv2d_dual(const void *in, const void *in2, const void *wgt, 
                               int32_t relu, int32_t dtype, void *stream) {
     PVR_REQUIRE(in && in2 && wgt && bias && out && n > 0, "pvr_op_conv2d_dual: null argument");
     PVR_REQUIRE(dtype == PVR_BF16 || dtype == PVR_F16, "pvr_op_conv2d_dual: 16-bit storage types only");
-    return launch_conv_pp256(in, wgt, bias, nullptr, out, n, h, w, cin, cout, kh, kw, stride, pad, relu, 0, 0, dtype, 224, (hipStream_t)stream, in2, h2, w2,
+    return launch_conv_pp256(op_switches(), in, wgt, bias, nullptr, out, n, h, w, cin, cout, kh, kw, stride, pad, relu, 0, 0, dtype, 224, (hipStream_t)stream, in2, h2, w2,
                              cin2, stride2);
 }
 // the pooled form of conv_wfrag: a 1 x 1 convolution on 7 x 7 maps + identity + ReLU whose only output is the average over each frame's 49 pixels
 pvr_status pvr_op_conv_wfrag_pool(const void *in, const void *wgt_packed, const float *bias, const void *residual, float *pool_out, int64_t pool_stride,
                                   int32_t n, int32_t cin, int32_t cout, int32_t dtype, void *stream) {
     PVR_REQUIRE(n > 0 && pool_out, "pvr_op_conv_wfrag_pool: empty input");
-    return launch_conv_wfrag(in, wgt_packed, bias, residual, nullptr, n, 7, 7, cin, cout, 1, 1, 1, 0, 1, 1, dtype, (hipStream_t)stream, pool_out, pool_stride);
+    return launch_conv_wfrag(op_switches(), in, wgt_packed, bias, residual, nullptr, n, 7, 7, cin, cout, 1, 1, 1, 0, 1, 1, dtype, (hipStream_t)stream, pool_out, pool_stride);
 }
 int64_t pvr_debug_conv_wfrag_launches(void) { return (int64_t)conv_wfrag_launches(); }
 // fp32 convolution on the 16-bit matrix pipe (conv_split16.hip): weights packed once, fp32 NHWC activations in and out
@@ -174,11 +151,6 @@ pvr_status pvr_op_conv2d_f32(const float *in, const float *wgt, const float *bia
     return launch_conv_f32(in, wgt, bias, residual, out, n, h, w, cin, cout, k, stride, pad, relu, (hipStream_t)stream);
 }
 int64_t pvr_debug_conv_split16_launches(void) { return (int64_t)conv_split16_launches(); }
-pvr_status pvr_debug_set_stem_regpool(int32_t mode) {
-    PVR_REQUIRE(mode >= -1 && mode <= 1, "pvr_debug_set_stem_regpool: -1 (environment: PVR_STEM_REGPOOL, default on), 0 (LDS-tile pooling) or 1 (register pooling)");
-    set_stem_regpool(mode);
-    return PVR_OK;
-}
 int64_t pvr_debug_chain_wave128_launches(void) { return (int64_t)chain_wave128_launches(); }
 int64_t pvr_debug_pp_persistent_launches(void) { return (int64_t)pp_persistent_launches(); }
 
@@ -219,16 +191,17 @@ pvr_status pvr_op_conv2d(const void *in, const void *wgt, const float *bias, con
     void *z;
     pvr_status s = zero_page(&z);
     if (s) return s;
-    return launch_conv(in, wgt, bias, residual, out, z, n, h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, dtype,
+    return launch_conv(op_switches(), in, wgt, bias, residual, out, z, n, h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, dtype,
                        (hipStream_t)stream);
 }
 
+// the pvr_op_* calls' kernel choice (op_switches); an encoder handle has its own switch (pvr_encoder_debug_set_switch "conv_algo")
 pvr_status pvr_debug_set_conv_algo(int32_t algo) {
     PVR_REQUIRE(algo >= -1 && algo <= 4, "pvr_debug_set_conv_algo: algo must be -1 (auto), 0 (conv_igemm), 1 / 2 / 3 (conv_pp256 with 256- / 128- / 224-pixel tiles), 4 (conv_w4)");
 #ifndef PVR_EXPERIMENTS
     PVR_REQUIRE(algo != 4, "pvr_debug_set_conv_algo: conv_w4 is an experiment kernel; this library was built without it (make EXPERIMENTS=1)");
 #endif
-    set_conv_algo(algo);
+    op_switches().conv_algo = algo;
     return PVR_OK;
 }
 

@@ -628,22 +628,20 @@ pvr_status launch_pack_frag_weights(const void *w, void *out, int rows, int K, h
 static long long g_bneck_frame_launches = 0;
 long long bneck_frame_launches() { return g_bneck_frame_launches; }
 
-// shapes the kernel is built for: layer3's stride-1 bottlenecks (14 x 14 x 256 -> 14 x 14 x 1024) in the 16-bit storage types
-bool bneck_frame_supported(int n, int h, int w, int cm, int cout, int stride) {
-    const char *e = getenv("PVR_FRAME_BNECK");                  // (read when a plan is built: A/B switch, default on)
-    const int on = e ? atoi(e) : 1;
-    return on && h == 14 && w == 14 && cm == 256 && cout == 1024 && stride == 1 && n >= 1 && (int64_t)n * 196 * 1024 * 2 < 0x7ffffff0ll;
+// shapes the kernel is built for: layer3's stride-1 bottlenecks (14 x 14 x 256 -> 14 x 14 x 1024) in the 16-bit storage types (sw.frame_bneck: A/B switch)
+bool bneck_frame_supported(const PlanSwitches &sw, int n, int h, int w, int cm, int cout, int stride) {
+    return sw.frame_bneck && h == 14 && w == 14 && cm == 256 && cout == 1024 && stride == 1 && n >= 1 && (int64_t)n * 196 * 1024 * 2 < 0x7ffffff0ll;
 }
 
 // w2p / w3p / w1np / w1fp: fragment-blocked weights (launch_pack_frag_weights of the (256, 2304) / (1024, 256) / (256, 1024) / (256, 1024) matrices).
 // phases: 1 conv2 only (t2_out), 3 conv2 + conv3, 7 + the NEXT block's conv1 (w1np, b1n -> t1n); + 8: the block's OWN conv1 in front (w1fp, b1f; the
 // launch reads the block input `res` instead of t1); + 16 / 32: timing knock-outs.
-pvr_status launch_bneck_frame(const void *t1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *res, void *y,
+pvr_status launch_bneck_frame(const PlanSwitches &sw, const void *t1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *res, void *y,
                               void *t2_out, int n, int phases, int dtype, hipStream_t stream, unsigned long long *stamps, const void *w1np,
                               const float *b1n, void *t1n, const void *w1fp, const float *b1f) {
     const int ph = phases & 7, front = (phases & 8) != 0;
-    // the whole bottleneck (own conv1 in front) in the 64-channel tiling (bneck_frame64.hip, round 6) unless switched off or a diagnostic form is asked for
-    if (front && ph == 3 && !(phases & ~15) && !t2_out && !stamps && !w1np && w1fp && b1f && w2p && b2 && w3p && b3 && res && y && frame64_on()) {
+    // the whole bottleneck (own conv1 in front) in the 64-channel tiling (bneck_frame64.hip, round 6) when sw.frame64 asks for it and no diagnostic form is
+    if (front && ph == 3 && !(phases & ~15) && !t2_out && !stamps && !w1np && w1fp && b1f && w2p && b2 && w3p && b3 && res && y && sw.frame64) {
         ++g_bneck_frame_launches;                                 // (a per-frame bottleneck launch either way; bneck_frame64_launches() counts this tiling)
         return launch_bneck_frame64(w1fp, b1f, w2p, b2, w3p, b3, res, y, n, dtype, stream, nullptr);
     }
@@ -656,7 +654,7 @@ pvr_status launch_bneck_frame(const void *t1, const void *w2p, const float *b2, 
     p.y = (u16 *)y; p.t2_out = (u16 *)t2_out; p.n = n; p.phases = phases & ~8; p.stamps = stamps;
     p.stagger = 0;
 #ifdef PVR_EXPERIMENTS
-    { static const int stg = [] { const char *e = getenv("PVR_FRAME_STAGGER"); return e ? atoi(e) : 0; }(); p.stagger = stg; }   // (negative result of round 5; read once)
+    p.stagger = sw.bneck_stagger;                                 // (negative result of round 5)
 #endif
     p.w1n = (const u16 *)w1np; p.b1n = b1n; p.t1n = (u16 *)t1n; p.w1f = (const u16 *)w1fp; p.b1f = b1f;
     p.t1_bytes = p.t2_bytes = p.t1n_bytes = (unsigned)((size_t)n * 196 * 256 * 2);

@@ -420,16 +420,6 @@ __global__ __launch_bounds__(256, 1) void bneck_frame64_kernel(BF64P p) {
 static long long g_bneck_frame64_launches = 0;
 long long bneck_frame64_launches() { return g_bneck_frame64_launches; }
 
-// 1 the 64-channel tiling runs the whole-bottleneck frame launches, 0 bneck_frame_kernel<.., FRONT1>; -1 (default) the environment (PVR_FRAME64, default 0:
-// measured slower, profiles/experiments/r06_bneck_frame64.txt)
-static int g_frame64_mode = -1;
-void set_frame64(int mode) { g_frame64_mode = mode; }
-bool frame64_on() {
-    if (g_frame64_mode >= 0) return g_frame64_mode != 0;
-    static const bool on = [] { const char *e = getenv("PVR_FRAME64"); return e && atoi(e) != 0; }();
-    return on;
-}
-
 // w1p / w2p / w3p: fragment-blocked weights (launch_pack_frag_weights of the (256, 1024) / (256, 2304) / (1024, 256) matrices); x: the block input (n,14,14,1024)
 pvr_status launch_bneck_frame64(const void *w1p, const float *b1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *x, void *y, int n,
                                 int dtype, hipStream_t stream, unsigned long long *stamps) {

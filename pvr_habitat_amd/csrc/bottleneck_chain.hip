@@ -22,7 +22,7 @@
 //     the W3 group; only the W1' slice lives beside them.
 //   * phase-B weights and the next group's residual are prefetched into registers one group ahead; plain loads, so
 //     hipcc's counted vmcnt keeps them in flight across the barriers.
-#include "chain_params.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
@@ -586,39 +586,21 @@ static pvr_status launch_chain_one(ChainP &p, hipStream_t stream) {
     return PVR_OK;
 }
 
-// PVR_CHAIN_HALO=0 keeps every block on the per-tap global-load form of phase A (A/B runs; both forms are bit-identical)
-static bool chain_halo_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("PVR_CHAIN_HALO"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
-// DS instance: 184 VGPRs uncapped (two blocks per CU) or capped at 168 with 8 spilled (three); PVR_CHAIN_DS_OCC selects, default 3
-static int chain_ds_occ() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("PVR_CHAIN_DS_OCC"); v = e ? atoi(e) : 3; }
-    return v;
-}
-
-static int chain_pfk() {
-    static int v = -2;
-    if (v < -1) { const char *e = getenv("PVR_CHAIN_PFK"); v = e ? atoi(e) : 12; }
-    return v;
-}
-
+// sw.chain_halo = 0 (PVR_CHAIN_HALO=0) keeps every block on the per-tap global-load form of phase A (A/B runs; both forms are bit-identical).
+// DS instance: 184 VGPRs uncapped (two blocks per CU) or capped at 168 with 8 spilled (three); sw.chain_ds_occ (PVR_CHAIN_DS_OCC) selects, default 3
 template <int CM, int CMN, bool F16, int RD, int OCC, bool DS = false>
-static pvr_status launch_chain_inst(ChainP &p, hipStream_t stream) {
+static pvr_status launch_chain_inst(ChainP &p, const PlanSwitches &sw, hipStream_t stream) {
     // halo form: stride 1 and the 128 + 2W + 2 halo rows (+ the zero row) fit the LDS tile
-    const bool halo = p.stride == 1 && 128 + 2 * p.W + 2 <= (CM == 64 ? 256 : 192) - 1 && chain_halo_enabled();
+    const bool halo = p.stride == 1 && 128 + 2 * p.W + 2 <= (CM == 64 ? 256 : 192) - 1 && sw.chain_halo;
     if constexpr (DS) {
-        if (halo) return chain_ds_occ() == 3 ? launch_chain_one<CM, CMN, F16, RD, 3, true, true>(p, stream) : launch_chain_one<CM, CMN, F16, RD, 2, true, true>(p, stream);
+        if (halo) return sw.chain_ds_occ == 3 ? launch_chain_one<CM, CMN, F16, RD, 3, true, true>(p, stream) : launch_chain_one<CM, CMN, F16, RD, 2, true, true>(p, stream);
         return launch_chain_one<CM, CMN, F16, RD, 2, false, true>(p, stream);
     } else {
         if (halo) {
             // Cm = 128: phase B's first prefetch is issued at slice 12 of phase A's 18 (its 48 VGPRs are free for fragment reads until
             // then): 0.184 -> 0.178 ms per layer2 tail; PVR_CHAIN_PFK=-1 keeps it in front of phase A
             if constexpr (CM == 128) {
-                if (chain_pfk() == 12) return launch_chain_one<CM, CMN, F16, RD, 2, true, false, 12>(p, stream);
+                if (sw.chain_pfk == 12) return launch_chain_one<CM, CMN, F16, RD, 2, true, false, 12>(p, stream);
             }
             return launch_chain_one<CM, CMN, F16, RD, (CM == 64 ? OCC : 2), true>(p, stream);
         }
@@ -626,52 +608,41 @@ static pvr_status launch_chain_inst(ChainP &p, hipStream_t stream) {
     }
 }
 
-// tuning knob for A/B runs: PVR_CHAIN_CFG = 10*RD + OCC for the Cm = 64 instances (default 12: measured best, profiles/experiments)
-static int chain_cfg() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("PVR_CHAIN_CFG"); v = e ? atoi(e) : 12; }
-    return v;
-}
-
+// tuning knob for A/B runs: sw.chain_cfg (PVR_CHAIN_CFG) = 10*RD + OCC for the Cm = 64 instances (default 12: measured best, profiles/experiments)
 template <bool F16>
-static pvr_status launch_chain_dt(ChainP &p, int cm, int cmn, hipStream_t stream) {
+static pvr_status launch_chain_dt(ChainP &p, int cm, int cmn, const PlanSwitches &sw, hipStream_t stream) {
     if (p.xds) {                                  // downsample inside the chain: layer1's block 0 (Cm = 64, next block's conv1 64 wide)
-        if (cm == 64 && cmn == 64) return launch_chain_inst<64, 64, F16, 1, 2, true>(p, stream);
+        if (cm == 64 && cmn == 64) return launch_chain_inst<64, 64, F16, 1, 2, true>(p, sw, stream);
         set_error("bottleneck chain with downsample: no instance for Cm=%d, next Cm=%d", cm, cmn);
         return PVR_ERR_INVALID;
     }
-    const int cfg = chain_cfg();
+    const int cfg = sw.chain_cfg;
 #define PVR_CHAIN64(CMN_)                                                                 \
     switch (cfg) {                                                                        \
-    case 12: return launch_chain_inst<64, CMN_, F16, 1, 2>(p, stream);                    \
-    case 13: return launch_chain_inst<64, CMN_, F16, 1, 3>(p, stream);                    \
-    case 22: return launch_chain_inst<64, CMN_, F16, 2, 2>(p, stream);                    \
-    case 23: return launch_chain_inst<64, CMN_, F16, 2, 3>(p, stream);                    \
-    default: return launch_chain_inst<64, CMN_, F16, 4, 2>(p, stream);                    \
+    case 12: return launch_chain_inst<64, CMN_, F16, 1, 2>(p, sw, stream);                \
+    case 13: return launch_chain_inst<64, CMN_, F16, 1, 3>(p, sw, stream);                \
+    case 22: return launch_chain_inst<64, CMN_, F16, 2, 2>(p, sw, stream);                \
+    case 23: return launch_chain_inst<64, CMN_, F16, 2, 3>(p, sw, stream);                \
+    default: return launch_chain_inst<64, CMN_, F16, 4, 2>(p, sw, stream);                \
     }
     if (cm == 64 && cmn == 64) PVR_CHAIN64(64)
     if (cm == 64 && cmn == 128) {                 // 64 KB of LDS: two blocks per CU whatever the register cap
-        if (cfg / 10 == 1) return launch_chain_inst<64, 128, F16, 1, 2>(p, stream);
-        if (cfg / 10 == 2) return launch_chain_inst<64, 128, F16, 2, 2>(p, stream);
-        return launch_chain_inst<64, 128, F16, 4, 2>(p, stream);
+        if (cfg / 10 == 1) return launch_chain_inst<64, 128, F16, 1, 2>(p, sw, stream);
+        if (cfg / 10 == 2) return launch_chain_inst<64, 128, F16, 2, 2>(p, sw, stream);
+        return launch_chain_inst<64, 128, F16, 4, 2>(p, sw, stream);
     }
     if (cm == 64 && cmn == 0) PVR_CHAIN64(0)
 #undef PVR_CHAIN64
-    if (cm == 128 && cmn == 128) return launch_chain_inst<128, 128, F16, 1, 2>(p, stream);
-    if (cm == 128 && cmn == 0) return launch_chain_inst<128, 0, F16, 1, 2>(p, stream);
+    if (cm == 128 && cmn == 128) return launch_chain_inst<128, 128, F16, 1, 2>(p, sw, stream);
+    if (cm == 128 && cmn == 0) return launch_chain_inst<128, 0, F16, 1, 2>(p, sw, stream);
     set_error("bottleneck chain: no instance for Cm=%d, next Cm=%d", cm, cmn);
     return PVR_ERR_INVALID;
 }
 
-// PVR_CHAIN_WAVE=0 keeps the stride-1 Cm = 64 tails on the block form above (A/B runs; both forms are bit-identical); read per plan
-static bool chain_wave_enabled() {
-    const char *e = getenv("PVR_CHAIN_WAVE");
-    return !e || atoi(e) != 0;
-}
+// sw.chain_wave = 0 (PVR_CHAIN_WAVE=0) keeps the stride-1 tails on the block form above (A/B runs; both forms are bit-identical)
+bool chain_uses_wave_form(const PlanSwitches &sw, int cm, int cmn, int stride, bool ds) { return sw.chain_wave && chain_wave_supported(sw, cm, cmn, stride, ds); }
 
-bool chain_uses_wave_form(int cm, int cmn, int stride, bool ds) { return chain_wave_enabled() && chain_wave_supported(cm, cmn, stride, ds); }
-
-bool chain_uses_wave128(int cm, int cmn, int stride, int64_t M) { return chain_wave_enabled() && chain_wave128_supported(cm, cmn, stride, M); }
+bool chain_uses_wave128(const PlanSwitches &sw, int cm, int cmn, int stride, int64_t M) { return sw.chain_wave && chain_wave128_supported(sw, cm, cmn, stride, M); }
 
 bool chain_ds_supported(int cm, int cmn, int cin, int stride) { return cm == 64 && cmn == 64 && cin == 64 && stride == 1; }
 bool chain_supported(int cm, int cmn) { return (cm == 64 && (cmn == 0 || cmn == 64 || cmn == 128)) || (cm == 128 && (cmn == 0 || cmn == 128)); }
@@ -679,7 +650,7 @@ bool chain_supported(int cm, int cmn) { return (cm == 64 && (cmn == 0 || cmn == 
 // row permutation of the chain's 1x1 weights: inside every 32-row block, row 16t + 4a + c holds cout 8a + 4t + c
 int chain_row_source(int row) { return (row & ~31) + 8 * ((row >> 2) & 3) + 4 * ((row >> 4) & 1) + (row & 3); }
 
-pvr_status launch_bottleneck_chain(const void *t1, const void *w2, const float *b2, const void *w3p, const float *b3, const void *res,
+pvr_status launch_bottleneck_chain(const PlanSwitches &sw, const void *t1, const void *w2, const float *b2, const void *w3p, const float *b3, const void *res,
                                    void *y, const void *w1np, const float *b1n, void *t1n, int n, int h, int w, int cm, int cmn,
                                    int stride, int dtype, hipStream_t stream, const void *xds, const void *wdsp, const void *w3pb, const void *wdspb,
                                    int wave, int in_blk, int out_blk, const void *wpk) {
@@ -703,19 +674,19 @@ pvr_status launch_bottleneck_chain(const void *t1, const void *w2, const float *
     p.xds_bytes = xds ? (unsigned)(M * 64 * 2) : 0; p.wds_bytes = xds ? (unsigned)(4 * cm * 64 * 2) : 0;
     p.w2_bytes = (unsigned)(cm * 9 * cm * 2); p.w3_bytes = (unsigned)(4 * cm * cm * 2); p.w1n_bytes = (unsigned)(cmn * 4 * cm * 2);
     if (wave == 2) {
-        PVR_REQUIRE(chain_wave128_supported(cm, cmn, stride, M) && !xds, "bottleneck chain: no layer2 wave form for Cm=%d next=%d stride=%d", cm, cmn, stride);
+        PVR_REQUIRE(chain_wave128_supported(sw, cm, cmn, stride, M) && !xds, "bottleneck chain: no layer2 wave form for Cm=%d next=%d stride=%d", cm, cmn, stride);
         p.wpk = (const u16 *)wpk; p.in_blk = in_blk; p.out_blk = out_blk & 1;
         return launch_chain_wave128(p, cmn, dtype, stream);
     }
     if (wave) {
-        PVR_REQUIRE(chain_wave_supported(cm, cmn, stride, xds != nullptr), "bottleneck chain: no wave form for Cm=%d next=%d stride=%d", cm, cmn, stride);
+        PVR_REQUIRE(chain_wave_supported(sw, cm, cmn, stride, xds != nullptr), "bottleneck chain: no wave form for Cm=%d next=%d stride=%d", cm, cmn, stride);
         p.w3b = (const u16 *)w3pb; p.wdsb = (const u16 *)wdspb; p.in_blk = in_blk; p.out_blk = out_blk;
-        return launch_chain_wave(p, cmn, dtype, stream);
+        return launch_chain_wave(p, cmn, sw.chain_wave_halo, dtype, stream);
     }
     PVR_REQUIRE(!(in_blk || out_blk) || M % 16 == 0, "bottleneck chain: the blocked layout needs a multiple of 16 pixels");
     p.res_blk = xds ? 0 : in_blk; p.y_blk = out_blk & 1;       // block form: y / the residual travel blocked; t1 stays NHWC, t1' too unless a layer2 wave form follows
     p.t_blk = (out_blk & 2) && cmn > 0;
-    return dtype == PVR_F16 ? launch_chain_dt<true>(p, cm, cmn, stream) : launch_chain_dt<false>(p, cm, cmn, stream);
+    return dtype == PVR_F16 ? launch_chain_dt<true>(p, cm, cmn, sw, stream) : launch_chain_dt<false>(p, cm, cmn, sw, stream);
 }
 
 }  // namespace pvr

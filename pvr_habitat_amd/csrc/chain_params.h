@@ -4,6 +4,8 @@
 
 namespace pvr {
 
+struct PlanSwitches;   // encoder_internal.h
+
 struct ChainP {
     const u16 *in, *w2, *w3, *w1n, *res;
     const float *b2, *b3, *b1n;
@@ -27,9 +29,9 @@ struct ChainP {
 
 bool chain_supported(int cm, int cmn);
 bool chain_ds_supported(int cm, int cmn, int cin, int stride);
-bool chain_uses_wave_form(int cm, int cmn, int stride, bool ds);   // PVR_CHAIN_WAVE (default 1) and an instance exists; read when a plan is built
+bool chain_uses_wave_form(const PlanSwitches &sw, int cm, int cmn, int stride, bool ds);   // sw.chain_wave and an instance exists
 int chain_row_source(int row);
-pvr_status launch_bottleneck_chain(const void *t1, const void *w2, const float *b2, const void *w3p, const float *b3, const void *res,
+pvr_status launch_bottleneck_chain(const PlanSwitches &sw, const void *t1, const void *w2, const float *b2, const void *w3p, const float *b3, const void *res,
                                    void *y, const void *w1np, const float *b1n, void *t1n, int n, int h, int w, int cm, int cmn,
                                    int stride, int dtype, hipStream_t stream, const void *xds = nullptr, const void *wdsp = nullptr,
                                    const void *w3pb = nullptr, const void *wdspb = nullptr, int wave = 0, int in_blk = 0, int out_blk = 0,
@@ -37,14 +39,13 @@ pvr_status launch_bottleneck_chain(const void *t1, const void *w2, const float *
 
 
 // chain_wave.hip: the barrier-free form (stride-1 blocks with Cm = 64)
-bool chain_wave_supported(int cm, int cmn, int stride, bool ds);
+bool chain_wave_supported(const PlanSwitches &sw, int cm, int cmn, int stride, bool ds);
 bool chain_wave_blocked_ok(int cmn_first, int h, int w);
-bool chain_wave_halo_enabled();                    // PVR_CHAIN_WAVE_HALO != 0
-pvr_status launch_chain_wave(ChainP &p, int cmn, int dtype, hipStream_t stream);
+pvr_status launch_chain_wave(ChainP &p, int cmn, int halo, int dtype, hipStream_t stream);
 
 // chain_wave128.hip: the wave form of layer2's stride-1 tails (Cm = 128): wave-owned pixels, weights streamed through an LDS ring
-bool chain_wave128_supported(int cm, int cmn, int stride, int64_t M);
-bool chain_uses_wave128(int cm, int cmn, int stride, int64_t M);     // ... and PVR_CHAIN_WAVE != 0 (the all-block-form A/B baseline); read when a plan is built
+bool chain_wave128_supported(const PlanSwitches &sw, int cm, int cmn, int stride, int64_t M);
+bool chain_uses_wave128(const PlanSwitches &sw, int cm, int cmn, int stride, int64_t M);     // ... and sw.chain_wave (the all-block-form A/B baseline)
 size_t chain_wave128_pack_bytes();
 pvr_status launch_chain_wave128_pack(const void *w2, const void *w3p, const void *w1np, void *out, hipStream_t stream);
 pvr_status launch_chain_wave128(ChainP &p, int cmn, int dtype, hipStream_t stream);

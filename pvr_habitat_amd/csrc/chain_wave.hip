@@ -34,7 +34,7 @@
 //
 // Numerics: the same rounding points and the same K order per accumulator as bottleneck_chain.hip and the unfused launches -
 // bit-identical outputs (tests/test_gpu_encoder.py::test_fused_bottleneck_chain_is_bit_identical, scripts/chain_wave_bench.hip).
-#include "chain_params.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
@@ -524,15 +524,10 @@ static pvr_status launch_cw_one(ChainP &p, hipStream_t stream) {
     return PVR_OK;
 }
 
-// PVR_CHAIN_WAVE_HALO=0: blocked inputs through the per-K-step load ring instead of the halo registers (A/B runs)
-static int cw_halo() {                                     // (read per call: plans built under different settings coexist in the tests)
-    const char *e = getenv("PVR_CHAIN_WAVE_HALO");
-    return e ? atoi(e) : 1;
-}
-
+// halo_on = 0 (PVR_CHAIN_WAVE_HALO=0): blocked inputs through the per-K-step load ring instead of the halo registers (A/B runs)
 template <bool F16>
-static pvr_status launch_cw_dt(ChainP &p, int cmn, hipStream_t stream) {
-    const bool ib = p.in_blk, ob = p.out_blk, halo = ib && p.W == 56 && cw_halo();
+static pvr_status launch_cw_dt(ChainP &p, int cmn, int halo_on, hipStream_t stream) {
+    const bool ib = p.in_blk, ob = p.out_blk, halo = ib && p.W == 56 && halo_on;
     if (p.xds) {                                           // layer1 block 0: x (from the stem) is NHWC; t1 is blocked when conv1's launch wrote it so
         if (cmn == 64 && halo && ob) return launch_cw_one<64, F16, true, false, true, true, true, 1, 1, 2>(p, stream);
         if (cmn == 64 && !ib) return ob ? launch_cw_one<64, F16, true, false, false, true, false, 4, 1, 2>(p, stream)
@@ -560,22 +555,21 @@ static pvr_status launch_cw_dt(ChainP &p, int cmn, hipStream_t stream) {
 // Cmn = 128 (layer1's last block, t1' for layer2): as a launch of its own this instance is no faster than the block form (0.299 vs 0.279 ms
 // inside the forward: W3 from L2, NHWC outputs, 228 VGPRs), but it takes its inputs in the blocked layout, which is what lets the tail in
 // front of it run all-blocked (0.205 instead of 0.238 ms; with NHWC outputs that one takes 0.261).  PVR_CHAIN_WAVE_128=0 for the A/B.
-bool chain_wave_supported(int cm, int cmn, int stride, bool ds) {
+bool chain_wave_supported(const PlanSwitches &sw, int cm, int cmn, int stride, bool ds) {
     if (cm != 64 || stride != 1) return false;
     if (ds) return cmn == 64;
-    if (cmn == 128) { const char *e = getenv("PVR_CHAIN_WAVE_128"); return !e || atoi(e) != 0; }
+    if (cmn == 128) return sw.chain_wave_128 != 0;
     return cmn == 0 || cmn == 64;
 }
 
 // can the tensors between two consecutive wave-form launches (y = the next residual, t1' = the next conv2 input) use the blocked layout?
 bool chain_wave_blocked_ok(int cmn_first, int h, int w) { return cmn_first == 64 && (h * w) % 32 == 0; }
-bool chain_wave_halo_enabled() { return cw_halo() != 0; }
 
-pvr_status launch_chain_wave(ChainP &p, int cmn, int dtype, hipStream_t stream) {
+pvr_status launch_chain_wave(ChainP &p, int cmn, int halo, int dtype, hipStream_t stream) {
     PVR_REQUIRE((int64_t)(p.M + 64) * 512 < 0x7ffffff0ll, "bottleneck chain (wave form): operand larger than 2 GiB (use a smaller chunk)");
     PVR_REQUIRE(p.xds ? p.wdsb != nullptr : (cmn != 128 || p.w3b != nullptr), "bottleneck chain (wave form): the blocked copy of W3 / Wd is missing");
     PVR_REQUIRE(!(p.in_blk || p.out_blk) || p.M % 32 == 0, "bottleneck chain (wave form): the blocked layout needs a multiple of 32 pixels");
-    return dtype == PVR_F16 ? launch_cw_dt<true>(p, cmn, stream) : launch_cw_dt<false>(p, cmn, stream);
+    return dtype == PVR_F16 ? launch_cw_dt<true>(p, cmn, halo, stream) : launch_cw_dt<false>(p, cmn, halo, stream);
 }
 
 }  // namespace pvr

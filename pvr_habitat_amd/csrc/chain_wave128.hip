@@ -26,7 +26,7 @@
 // STATUS (end of round 6): correct and bit-identical, but NOT faster than the block form (0.154-0.167 ms against 0.156 per launch at batch 256) - LDS bandwidth
 // sets the pace once the weights stream through it (every wave re-reads 544 KB of fragments per 32 pixels).  Opt-in (PVR_CHAIN_WAVE_L2=1); the measurements, the
 // s_memtime stamps of both schedules and the knock-outs are in profiles/experiments/r06_chain_wave128.txt.
-#include "chain_params.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
@@ -492,11 +492,9 @@ static long long g_cw8_launches = 0;
 long long chain_wave128_launches() { return g_cw8_launches; }
 
 // OPT-IN: PVR_CHAIN_WAVE_L2=1 runs layer2's stride-1 tails on this form (bit-identical to the block form, measured no faster: profiles/experiments/
-// r06_chain_wave128.txt); read when a plan is built
-bool chain_wave128_supported(int cm, int cmn, int stride, int64_t M) {
-    const char *e = getenv("PVR_CHAIN_WAVE_L2");              // (plan time only: plans built under different settings coexist in the tests)
-    const int on = e ? atoi(e) : 0;
-    return on && cm == 128 && (cmn == 128 || cmn == 0) && stride == 1 && M % 16 == 0;
+// r06_chain_wave128.txt)
+bool chain_wave128_supported(const PlanSwitches &sw, int cm, int cmn, int stride, int64_t M) {
+    return sw.chain_wave_l2 && cm == 128 && (cmn == 128 || cmn == 0) && stride == 1 && M % 16 == 0;
 }
 
 static int cw8_num_cus() {

@@ -13,7 +13,7 @@
 //
 // Weight rows are permuted on their way into LDS (row 32b + 16t + 4a + c holds cout 32b + 8a + 4t + c) so that a lane's accumulators of
 // an MFMA tile pair are 8 consecutive output channels of one pixel: 16-byte residual loads and stores straight from registers.
-#include "common.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
@@ -183,16 +183,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(HaloP p) {
     }
 }
 
-// PVR_CONV_HALO=0: these shapes stay on conv_igemm (A/B runs; bit-identical)
-static bool halo_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("PVR_CONV_HALO"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
-bool conv3x3_halo_supported(int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32, int64_t in_bytes) {
+// sw.conv_halo = 0 (PVR_CONV_HALO=0): these shapes stay on conv_igemm (A/B runs; bit-identical)
+bool conv3x3_halo_supported(const PlanSwitches &sw, int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32,
+                            int64_t in_bytes) {
     (void)h;
-    return halo_enabled() && kh == 3 && kw == 3 && stride == 1 && pad == 1 && cin == cout && (cin == 64 || cin == 128) && relu <= 1 && out_f32 == 0 &&
+    return sw.conv_halo && kh == 3 && kw == 3 && stride == 1 && pad == 1 && cin == cout && (cin == 64 || cin == 128) && relu <= 1 && out_f32 == 0 &&
            128 + 2 * w + 2 <= (cin == 64 ? 256 : 192) - 1 && M * cin * 2 < 0x7ffffff0ll && in_bytes < 0x7ffffff0ll;
 }
 

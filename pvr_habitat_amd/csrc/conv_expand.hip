@@ -18,7 +18,7 @@
 //   * the n-tiles of one pixel-tile group sit on one XCD (blocks b, b+8, ... share an L2), so X is fetched into that L2 once.
 // Same GEMM view, K order (64-wide slices ascending, two 32-deep MFMA steps each), operand layouts and epilogue arithmetic as
 // conv_igemm.hip / conv_pp256.hip: results are bit-identical (tests/test_gpu_encoder.py).
-#include "common.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
@@ -300,11 +300,10 @@ static int expand_bn(int cin, int cout) {
     return 0;
 }
 
-// PVR_CONV_EXPAND=0 keeps these convolutions on conv_igemm / conv_pp256 (A/B runs; bit-identical)
-bool conv_expand_supported(int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32, bool has_res) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("PVR_CONV_EXPAND"); on = e ? atoi(e) : 1; }
-    if (!on || out_f32 != 0 || relu > 1 || kh != 1 || kw != 1 || pad != 0 || (stride != 1 && stride != 2)) return false;
+// sw.conv_expand = 0 (PVR_CONV_EXPAND=0) keeps these convolutions on conv_igemm / conv_pp256 (A/B runs; bit-identical)
+bool conv_expand_supported(const PlanSwitches &sw, int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32,
+                           bool has_res) {
+    if (!sw.conv_expand || out_f32 != 0 || relu > 1 || kh != 1 || kw != 1 || pad != 0 || (stride != 1 && stride != 2)) return false;
     if (has_res && stride != 1) return false;
     if (cin == 512 && !has_res) return false;        // (layer3.0.downsample: 52.6 GFLOP on 154 MB is MFMA-bound; conv_pp256 is faster, measured)
     if (stride == 2 && ((h | w) & 1)) return false;

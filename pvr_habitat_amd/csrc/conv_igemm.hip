@@ -15,24 +15,17 @@
 //   * 2-stage software pipeline: global loads for K-slice t+1 are issued before the MFMAs of slice t
 //     and written to the other LDS buffer after them (one barrier per slice).
 //   * block -> tile map is XCD-aware: consecutive tiles on one XCD share the activation rows (L2 reuse).
-#include "common.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
-// conv_expand.hip / conv3x3_halo.hip
-bool conv_expand_supported(int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32, bool has_res);
-pvr_status launch_conv_expand(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
-                              int cout, int stride, int relu, int dtype, hipStream_t stream, int out_blk);
-bool conv3x3_halo_supported(int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32, int64_t in_bytes);
+// conv3x3_halo.hip (conv_expand.hip, conv_pp256.hip: encoder_internal.h)
+bool conv3x3_halo_supported(const PlanSwitches &sw, int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32,
+                            int64_t in_bytes);
 pvr_status launch_conv3x3_halo(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int c, int relu,
                                int dtype, hipStream_t stream);
-// conv_pp256.hip
-bool pp256_supported(int64_t M, int cin, int cout, int kh, int kw, int64_t in_bytes, int64_t w_bytes, int64_t out_bytes, int64_t res_bytes);
 pvr_status launch_conv_w4(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
                           int cout, int kh, int kw, int stride, int pad, int act, int out_f32, int res_f32, int dtype, hipStream_t stream);
-pvr_status launch_conv_pp256(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
-                             int cout, int kh, int kw, int stride, int pad, int act, int out_f32, int res_f32, int dtype, int bm, hipStream_t stream,
-                             const void *in2 = nullptr, int h2 = 0, int w2 = 0, int cin2 = 0, int stride2 = 1);
 
 struct ConvP {
     const u16 *in;
@@ -424,57 +417,44 @@ static pvr_status launch_inst2(ConvP &p, hipStream_t stream) {
     return PVR_OK;
 }
 
-// PVR_IGEMM_NK4=0: the four-slice launches keep the generic double-buffered loop (A/B runs; bit-identical)
-static bool nk4_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("PVR_IGEMM_NK4"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
+// nk4 = 0 (PVR_IGEMM_NK4=0): the four-slice launches keep the generic double-buffered loop (A/B runs; bit-identical)
 template <int BM, int BN, bool F16, int STAGES>
-static pvr_status launch_inst(ConvP &p, hipStream_t stream) {
+static pvr_status launch_inst(ConvP &p, bool nk4, hipStream_t stream) {
     if constexpr (STAGES == 2 && BM == 128 && BN == 128) {
-        if (p.KH == 1 && p.KW == 1 && p.K == 256 && p.res && !p.res_f32 && !p.out_f32 && p.act <= 1 && nk4_enabled()) return launch_inst2<BM, BN, F16, 2, 1, true>(p, stream);
+        if (p.KH == 1 && p.KW == 1 && p.K == 256 && p.res && !p.res_f32 && !p.out_f32 && p.act <= 1 && nk4) return launch_inst2<BM, BN, F16, 2, 1, true>(p, stream);
     }
     if (!p.res) return launch_inst2<BM, BN, F16, STAGES, 0>(p, stream);
     return p.res_f32 ? launch_inst2<BM, BN, F16, STAGES, 2>(p, stream) : launch_inst2<BM, BN, F16, STAGES, 1>(p, stream);
 }
 
 template <int BM, int BN>
-static pvr_status launch_cfg(ConvP &p, int dtype, hipStream_t stream) {
+static pvr_status launch_cfg(ConvP &p, int dtype, bool nk4, hipStream_t stream) {
     p.m_tiles = (p.M + BM - 1) / BM;
     p.n_tiles = (p.Cout + BN - 1) / BN;
     const bool single = p.K == 64;
     if (dtype == PVR_F16)
-        return single ? launch_inst<BM, BN, true, 1>(p, stream) : launch_inst<BM, BN, true, 2>(p, stream);
-    return single ? launch_inst<BM, BN, false, 1>(p, stream) : launch_inst<BM, BN, false, 2>(p, stream);
+        return single ? launch_inst<BM, BN, true, 1>(p, nk4, stream) : launch_inst<BM, BN, true, 2>(p, nk4, stream);
+    return single ? launch_inst<BM, BN, false, 1>(p, nk4, stream) : launch_inst<BM, BN, false, 2>(p, nk4, stream);
 }
 
-// kernel choice: -1 auto (measured crossover), 0 conv_igemm only, 1 / 2 conv_pp256 with 256- / 128-pixel tiles
-// whenever it accepts the shape
-static int g_conv_algo = -2;
-int conv_algo() {
-    if (g_conv_algo == -2) { const char *e = getenv("PVR_CONV_ALGO"); g_conv_algo = e ? atoi(e) : -1; }
-    return g_conv_algo;
-}
-void set_conv_algo(int a) { g_conv_algo = a; }
-
-pvr_status launch_conv(const void *in, const void *wgt, const float *bias, const void *res, void *out, const void *zero,
+// kernel choice (sw.conv_algo): -1 auto (measured crossover), 0 conv_igemm only, 1 / 2 / 3 conv_pp256 with 256- / 128- / 224-pixel
+// tiles whenever it accepts the shape
+pvr_status launch_conv(const PlanSwitches &sw, const void *in, const void *wgt, const float *bias, const void *res, void *out, const void *zero,
                        int n, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu,
                        int out_f32, int dtype, hipStream_t stream) {
     PVR_REQUIRE(cin % 64 == 0, "conv: cin %d not a multiple of 64", cin);
     PVR_REQUIRE(cout % 8 == 0, "conv: cout %d not a multiple of 8", cout);
     PVR_REQUIRE(zero != nullptr, "conv: zero page missing");
-    if (conv_algo() != 0 && conv3x3_halo_supported((int64_t)n * h * w, h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, (int64_t)n * h * w * cin * 2))
+    const int algo = sw.conv_algo;
+    if (algo != 0 && conv3x3_halo_supported(sw, (int64_t)n * h * w, h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, (int64_t)n * h * w * cin * 2))
         return launch_conv3x3_halo(in, wgt, bias, res, out, n, h, w, cin, relu, dtype, stream);
-    if (conv_algo() == -1 && kh == 1 && kw == 1 && (stride == 1 || stride == 2) &&
-        conv_expand_supported((int64_t)n * (h / stride) * (w / stride), h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, res != nullptr))
+    if (algo == -1 && kh == 1 && kw == 1 && (stride == 1 || stride == 2) &&
+        conv_expand_supported(sw, (int64_t)n * (h / stride) * (w / stride), h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, res != nullptr))
         return launch_conv_expand(in, wgt, bias, res, out, n, h, w, cin, cout, stride, relu, dtype, stream, 0);
     {
         const int ho = (h + 2 * pad - kh) / stride + 1, wo = (w + 2 * pad - kw) / stride + 1;
         const int64_t M = (int64_t)n * ho * wo, K = (int64_t)kh * kw * cin;
         const int of32 = out_f32 & 1, rf32 = (out_f32 >> 1) & 1;
-        const int algo = conv_algo();
         const bool ok = pp256_supported(M, cin, cout, kh, kw, (int64_t)n * h * w * cin * 2, (int64_t)((cout + 63) / 64 * 64) * K * 2,
                                         M * cout * (of32 ? 4 : 2), res ? M * cout * (rf32 ? 4 : 2) : 0);
         // auto (measured per launch at batch 256, profiles/experiments/r01_pp256_vs_igemm_per_op.txt): the 256x256 kernel runs one
@@ -485,13 +465,11 @@ pvr_status launch_conv(const void *in, const void *wgt, const float *bias, const
         // algo 1 / 2 / 3: force the 256- / 128- / 224-pixel tile; auto: 256 when that grid fills ~2/3 of the CUs, else 128 when that one does;
         // 224 instead of 256 when it needs fewer CU-rounds x rows (batch 256 at 14 x 14: 196 tiles of 256 on 256 CUs vs 224 tiles of 224)
         const int64_t tiles224 = ((M + 223) / 224) * nt;
-        static const bool use224 = [] { const char *e = getenv("PVR_PP_BM224"); return !e || atoi(e) != 0; }();
         // Rounds first: a tile iteration of the persistent form costs about the same for 224 and 256 rows (its cadence is set by the feed
         // half-phases and ~12 k cycles of epilogue / setup, scripts/pp256_tile_stamps.hip), so more, smaller tiles only pay when they do not
-        // add a round (fc1 of ViT-B/16: 10 rounds of 256 rows instead of 11 of 224).  PVR_PP_BM224=2 restores round 2's rows-only rule.
-        static const int rule224 = [] { const char *e = getenv("PVR_PP_BM224"); return e ? atoi(e) : 1; }();
+        // add a round (fc1 of ViT-B/16: 10 rounds of 256 rows instead of 11 of 224).  PVR_PP_BM224=2 restores round 2's rows-only rule, 0 never takes 224.
         const int64_t r224 = (tiles224 + 255) / 256, r256 = (tiles + 255) / 256;
-        const bool better224 = use224 && (rule224 == 2 ? r224 * 224 < r256 * 256 : (r224 <= r256 && r224 * 224 < r256 * 256));
+        const bool better224 = sw.pp_bm224 && (sw.pp_bm224 == 2 ? r224 * 224 < r256 * 256 : (r224 <= r256 && r224 * 224 < r256 * 256));
         const int bm = algo == 1 ? 256 : algo == 2 ? 128 : algo == 3 ? 224
                      : (algo == -1 && deep) ? (tiles >= 160 ? (better224 ? 224 : 256) : (tiles128 >= 160 ? 128 : 0)) : 0;
         // algo 4 (round 3): the four-wave 128 x 128-per-wave kernel (conv_w4.hip) wherever it accepts the shape
@@ -500,14 +478,12 @@ pvr_status launch_conv(const void *in, const void *wgt, const float *bias, const
             return launch_conv_w4(in, wgt, bias, res, out, n, h, w, cin, cout, kh, kw, stride, pad, relu, of32, rf32, dtype, stream);
 #endif
         if (ok && bm)
-            return launch_conv_pp256(in, wgt, bias, res, out, n, h, w, cin, cout, kh, kw, stride, pad, relu, of32, rf32, dtype, bm, stream);
+            return launch_conv_pp256(sw, in, wgt, bias, res, out, n, h, w, cin, cout, kh, kw, stride, pad, relu, of32, rf32, dtype, bm, stream);
     }
     ConvP p;
     p.nk_split = 0;
     p.in = (const u16 *)in; p.wgt = (const u16 *)wgt; p.bias = bias; p.res = (const u16 *)res; p.out = out;
     p.zero = (const u16 *)zero;
-    static int bm64 = -1;
-    if (bm64 < 0) { const char *e = getenv("PVR_IGEMM_BM64"); bm64 = e ? atoi(e) : 0; }
     p.N = n; p.H = h; p.W = w; p.Cin = cin; p.Cout = cout; p.CoutPad = (cout + 63) / 64 * 64;
     p.KH = kh; p.KW = kw; p.stride = stride; p.pad = pad;
     p.Ho = (h + 2 * pad - kh) / stride + 1;
@@ -519,13 +495,13 @@ pvr_status launch_conv(const void *in, const void *wgt, const float *bias, const
     PVR_REQUIRE(inb < 0x7ffffff0ll && wb < 0x7ffffff0ll && kh <= 3 && kw <= 3, "conv: operand larger than 2 GiB or filter larger than 3x3");
     p.in_bytes = (unsigned)inb; p.w_bytes = (unsigned)wb;
     p.act = relu; p.out_f32 = out_f32 & 1; p.res_f32 = (out_f32 >> 1) & 1;   // out_f32 bit1: residual is fp32
-    if (cout <= 64) return launch_cfg<128, 64>(p, dtype, stream);
+    if (cout <= 64) return launch_cfg<128, 64>(p, dtype, sw.igemm_nk4, stream);
     // experiment (PVR_IGEMM_BM64=1): 64-pixel tiles for the K = 256 expand convolutions with residual -> three blocks per CU
-    if (bm64 && kh == 1 && kw == 1 && p.K == 256 && res && !p.res_f32 && !p.out_f32 && relu <= 1 && nk4_enabled()) {
+    if (sw.igemm_bm64 && kh == 1 && kw == 1 && p.K == 256 && res && !p.res_f32 && !p.out_f32 && relu <= 1 && sw.igemm_nk4) {
         p.m_tiles = (p.M + 63) / 64; p.n_tiles = (p.Cout + 127) / 128;
         return dtype == PVR_F16 ? launch_inst2<64, 128, true, 2, 1, true>(p, stream) : launch_inst2<64, 128, false, 2, 1, true>(p, stream);
     }
-    return launch_cfg<128, 128>(p, dtype, stream);
+    return launch_cfg<128, 128>(p, dtype, sw.igemm_nk4, stream);
 }
 
 // ---- split-K for long, narrow convolutions ---------------------------------------------------------------------------------

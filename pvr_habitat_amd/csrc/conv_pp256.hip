@@ -32,7 +32,7 @@
 //            tile t (other buffer, tile t+1).
 //       RAW  one counted wait per K tile, in phase 3 after that phase's DMA issue: vmcnt(4) leaves X-lo/X-hi(t+2) in flight
 //            and retires everything of tile t+1; every wave then passes at least one barrier before any wave reads tile t+1.
-#include "common.h"
+#include "encoder_internal.h"
 #include <type_traits>
 
 namespace pvr {
@@ -596,16 +596,10 @@ __global__ __launch_bounds__(512, 1) void conv_pp256_kernel(PPP p) {
 static long long g_pp_persistent_launches = 0;
 long long pp_persistent_launches() { return g_pp_persistent_launches; }
 
-// PVR_PP_PERSIST: tiles per launch from which the persistent form is used (default 384 = 1.5 tiles per CU; 0 disables it)
-static int pp_persist_min() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("PVR_PP_PERSIST"); v = e ? atoi(e) : 384; }
-    return v;
-}
-
-// DUAL launches (conv3 & downsample of a stride-2 bottleneck): 224-pixel tiles, no residual operand
+// DUAL launches (conv3 & downsample of a stride-2 bottleneck): 224-pixel tiles, no residual operand.  persist_min (sw.pp_persist, PVR_PP_PERSIST): tiles
+// per launch from which the persistent form is used (default 384 = 1.5 tiles per CU; 0 disables it)
 template <bool F16>
-static pvr_status launch_pp_dual(PPP &p, hipStream_t stream) {
+static pvr_status launch_pp_dual(PPP &p, int persist_min, hipStream_t stream) {
     constexpr int BM = 224, lds = 2 * (256 * 128 + 32768) + 16384;
     static DeviceOnce attr_done;
     if (attr_done.needed()) {
@@ -617,7 +611,7 @@ static pvr_status launch_pp_dual(PPP &p, hipStream_t stream) {
     p.total_tiles = grid;
     p.pointwise = 0;
     p.bias_lds = p.CoutPad <= 4096 ? 1 : 0;
-    if (pp_persist_min() > 0 && grid >= pp_persist_min()) {
+    if (persist_min > 0 && grid >= persist_min) {
         ++g_pp_persistent_launches;
         hipLaunchKernelGGL((conv_pp256_kernel<BM, F16, 0, true, true>), dim3(256), dim3(512), lds, stream, p);
     } else {
@@ -628,7 +622,7 @@ static pvr_status launch_pp_dual(PPP &p, hipStream_t stream) {
 }
 
 template <int BM, bool F16, int RES>
-static pvr_status launch_pp_inst(PPP &p, hipStream_t stream) {
+static pvr_status launch_pp_inst(PPP &p, int persist_min, hipStream_t stream) {
     constexpr int lds = 2 * ((BM == 224 ? 256 : BM) * 128 + 32768) + 16384;      // two staging buffers + the bias vector (<= 4096 floats)
     static DeviceOnce attr_done;          // per device: a second GPU of the process needs the attribute too
     if (attr_done.needed()) {
@@ -642,7 +636,7 @@ static pvr_status launch_pp_inst(PPP &p, hipStream_t stream) {
     p.pointwise = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0;
     p.bias_lds = p.CoutPad <= 4096 ? 1 : 0;
     if constexpr (BM != 128) {
-        if (pp_persist_min() > 0 && grid >= pp_persist_min()) {       // one block per CU (128 KB of LDS each), several tiles per block
+        if (persist_min > 0 && grid >= persist_min) {                 // one block per CU (128 KB of LDS each), several tiles per block
             ++g_pp_persistent_launches;
             hipLaunchKernelGGL((conv_pp256_kernel<BM, F16, RES, true>), dim3(256), dim3(512), lds, stream, p);
             PVR_LAUNCH_CHECK();
@@ -655,13 +649,13 @@ static pvr_status launch_pp_inst(PPP &p, hipStream_t stream) {
 }
 
 template <int BM>
-static pvr_status launch_pp_bm(PPP &p, int rmode, int dtype, hipStream_t stream) {
+static pvr_status launch_pp_bm(PPP &p, int rmode, int dtype, int persist_min, hipStream_t stream) {
     if (dtype == PVR_F16) {
-        if (rmode == 0) return launch_pp_inst<BM, true, 0>(p, stream);
-        return rmode == 1 ? launch_pp_inst<BM, true, 1>(p, stream) : launch_pp_inst<BM, true, 2>(p, stream);
+        if (rmode == 0) return launch_pp_inst<BM, true, 0>(p, persist_min, stream);
+        return rmode == 1 ? launch_pp_inst<BM, true, 1>(p, persist_min, stream) : launch_pp_inst<BM, true, 2>(p, persist_min, stream);
     }
-    if (rmode == 0) return launch_pp_inst<BM, false, 0>(p, stream);
-    return rmode == 1 ? launch_pp_inst<BM, false, 1>(p, stream) : launch_pp_inst<BM, false, 2>(p, stream);
+    if (rmode == 0) return launch_pp_inst<BM, false, 0>(p, persist_min, stream);
+    return rmode == 1 ? launch_pp_inst<BM, false, 1>(p, persist_min, stream) : launch_pp_inst<BM, false, 2>(p, persist_min, stream);
 }
 
 // shapes the kernel accepts (the caller decides whether it is the faster choice)
@@ -670,7 +664,7 @@ bool pp256_supported(int64_t M, int cin, int cout, int kh, int kw, int64_t in_by
            out_bytes < 0x7ffffff0ll && res_bytes < 0x7ffffff0ll;
 }
 
-pvr_status launch_conv_pp256(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
+pvr_status launch_conv_pp256(const PlanSwitches &sw, const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
                              int cout, int kh, int kw, int stride, int pad, int act, int out_f32, int res_f32, int dtype, int bm,
                              hipStream_t stream, const void *in2, int h2, int w2, int cin2, int stride2) {
     PPP p;
@@ -697,9 +691,9 @@ pvr_status launch_conv_pp256(const void *in, const void *wgt, const float *bias,
     p.act = act; p.out_f32 = out_f32;
     p.n_tiles = (cout + 255) / 256;
     const int rmode = !res ? 0 : (res_f32 ? 2 : 1);
-    if (in2) return dtype == PVR_F16 ? launch_pp_dual<true>(p, stream) : launch_pp_dual<false>(p, stream);
-    if (bm == 224) return launch_pp_bm<224>(p, rmode, dtype, stream);
-    return bm == 256 ? launch_pp_bm<256>(p, rmode, dtype, stream) : launch_pp_bm<128>(p, rmode, dtype, stream);
+    if (in2) return dtype == PVR_F16 ? launch_pp_dual<true>(p, sw.pp_persist, stream) : launch_pp_dual<false>(p, sw.pp_persist, stream);
+    if (bm == 224) return launch_pp_bm<224>(p, rmode, dtype, sw.pp_persist, stream);
+    return bm == 256 ? launch_pp_bm<256>(p, rmode, dtype, sw.pp_persist, stream) : launch_pp_bm<128>(p, rmode, dtype, sw.pp_persist, stream);
 }
 
 }  // namespace pvr

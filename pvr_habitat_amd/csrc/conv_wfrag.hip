@@ -10,7 +10,7 @@
 // Torchvision Bottleneck convolutions reached from reference src/embeddings.py:118-120 (resnet50) and src/vision_models/moco.py:6-26.
 // Same operand roles (A = weights, B = pixels), K order (tap-major, then channels, 32 per MFMA) and rounding points as conv_igemm / conv_pp256:
 // bit-identical outputs (tests/test_gpu_encoder.py::test_conv_wfrag_is_bit_identical).
-#include "common.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
@@ -300,15 +300,15 @@ bool conv_wfrag_supported(int64_t M, int64_t in_bytes, int cin, int cout, int kh
 
 // the plan's rule: deep-K launches whose 256 x 256 (224 x 256) tiling leaves CUs idle - fewer than 160 such tiles - and whose 112 x 256 tiling fills
 // at least 3/4 of them (layer4's conv1 / conv2 at batch 256: 98 -> 224 tiles)
-bool conv_wfrag_preferred(int64_t M, int cin, int cout, int kh, int kw) {
-    static const int on = [] { const char *e = getenv("PVR_CONV_WFRAG"); return e ? atoi(e) : 1; }();
+bool conv_wfrag_preferred(const PlanSwitches &sw, int64_t M, int cin, int cout, int kh, int kw) {
+    const int on = sw.conv_wfrag;
     const int64_t K = (int64_t)kh * kw * cin, nct = cout / 256, t256 = ((M + 255) / 256) * nct, t112 = ((M + 111) / 112) * nct;
     if (on == 2) return K >= 512;                          // (A/B: every launch the kernel accepts)
     return on && K >= 1024 && t256 < 160 && t112 >= 192;
 }
 
 // wp: the fragment-blocked copy (launch_pack_frag_weights) of the (cout, kh * kw * cin) matrix
-pvr_status launch_conv_wfrag(const void *in, const void *wp, const float *bias, const void *res, void *out, int n, int h, int w, int cin, int cout,
+pvr_status launch_conv_wfrag(const PlanSwitches &sw, const void *in, const void *wp, const float *bias, const void *res, void *out, int n, int h, int w, int cin, int cout,
                              int kh, int kw, int stride, int pad, int act, int out_f32, int dtype, hipStream_t stream, float *pool_out, int64_t pool_stride) {
     // pool_out != nullptr: `out` is not written; pool_out[f * pool_stride + c] = mean over frame f's 7 x 7 outputs (fp32)
     PVR_REQUIRE(in && wp && bias && (out || pool_out), "conv_wfrag: null argument");
@@ -334,9 +334,9 @@ pvr_status launch_conv_wfrag(const void *in, const void *wp, const float *bias, 
     const bool f16 = dtype == PVR_F16, o32 = out_f32 & 1;
 #define WF_GO(F_, R_, O_) hipLaunchKernelGGL((conv_wfrag_kernel<F_, R_, O_>), grid, block, lds, stream, p)
 #ifdef PVR_EXPERIMENTS
-    if (const char *e = getenv("PVR_WFRAG_KO"); e && atoi(e) && dtype == PVR_F16 && !res && !(out_f32 & 1)) {
+    if (sw.wfrag_ko && dtype == PVR_F16 && !res && !(out_f32 & 1)) {
 #define WF_KO(k_) case k_: hipLaunchKernelGGL((conv_wfrag_kernel<true, 0, false, k_>), grid, block, lds, stream, p); break;
-        switch (atoi(e)) { WF_KO(1) WF_KO(2) WF_KO(3) WF_KO(4) WF_KO(7) WF_KO(8) WF_KO(9) WF_KO(10) WF_KO(11) WF_KO(15) default: break; }
+        switch (sw.wfrag_ko) { WF_KO(1) WF_KO(2) WF_KO(3) WF_KO(4) WF_KO(7) WF_KO(8) WF_KO(9) WF_KO(10) WF_KO(11) WF_KO(15) default: break; }
 #undef WF_KO
         PVR_LAUNCH_CHECK();
         return PVR_OK;

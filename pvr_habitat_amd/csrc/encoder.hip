@@ -19,17 +19,29 @@ pvr_status launch_conv_split16(const float *in, const void *wsp, const float *bi
                                int cout, int k, int stride, int pad, int relu, hipStream_t stream, float *out2 = nullptr, int n1 = 0, void *out16 = nullptr,
                                int terms = 3);
 
-// every environment switch of the encoder plans, read ONCE per encoder in pvr_encoder_create (never on the forward path)
-static void read_switches(PlanSwitches &sw) {
+// every environment switch of the encoder path (PlanSwitches), read ONCE per encoder in pvr_encoder_create (never on the forward path)
+void read_switches(PlanSwitches &sw) {
     auto get = [](const char *name, int def) { const char *v = getenv(name); return v ? atoi(v) : def; };
     sw.pool_fuse = get("PVR_POOL_FUSE", 1);
     sw.stem_u8 = get("PVR_STEM_U8", 1);
     sw.stem_lds = get("PVR_STEM_LDS", 1);
+    sw.stem_regpool = get("PVR_STEM_REGPOOL", 1);
     sw.frame_front1 = get("PVR_FRAME_FRONT1", 1);
     sw.frame_next1 = get("PVR_FRAME_NEXT1", 0);
+    sw.frame_bneck = get("PVR_FRAME_BNECK", 1);
+    sw.frame64 = get("PVR_FRAME64", 0);           // (measured slower: opt-in, profiles/experiments/r06_bneck_frame64.txt)
+    sw.bneck_stagger = get("PVR_FRAME_STAGGER", 0);
     sw.dual_ds = get("PVR_DUAL_DS", 1);
     sw.chain_ds = get("PVR_CHAIN_DS", 1);
     sw.chain_blocked = get("PVR_CHAIN_BLOCKED", 1);
+    sw.chain_halo = get("PVR_CHAIN_HALO", 1);
+    sw.chain_ds_occ = get("PVR_CHAIN_DS_OCC", 3);
+    sw.chain_pfk = get("PVR_CHAIN_PFK", 12);
+    sw.chain_cfg = get("PVR_CHAIN_CFG", 12);
+    sw.chain_wave = get("PVR_CHAIN_WAVE", 1);
+    sw.chain_wave_halo = get("PVR_CHAIN_WAVE_HALO", 1);
+    sw.chain_wave_128 = get("PVR_CHAIN_WAVE_128", 1);
+    sw.chain_wave_l2 = get("PVR_CHAIN_WAVE_L2", 0);   // (measured no faster than the block form: opt-in, profiles/experiments/r06_chain_wave128.txt)
     sw.splitk = get("PVR_SPLITK", 1);
     sw.smallk_div = get("PVR_SMALLK_DIV", 4);
     if (sw.smallk_div < 1) sw.smallk_div = 1;
@@ -41,6 +53,20 @@ static void read_switches(PlanSwitches &sw) {
     sw.resid32 = get("PVR_RESID32", 1);
     sw.tail_f32 = get("PVR_TAIL_F32", 1);
     sw.fuse = get("PVR_FUSE", 1);
+    sw.conv_algo = get("PVR_CONV_ALGO", -1);
+    sw.conv_halo = get("PVR_CONV_HALO", 1);
+    sw.conv_expand = get("PVR_CONV_EXPAND", 1);
+    sw.conv_wfrag = get("PVR_CONV_WFRAG", 1);
+    sw.wfrag_ko = get("PVR_WFRAG_KO", 0);
+    sw.igemm_nk4 = get("PVR_IGEMM_NK4", 1);
+    sw.igemm_bm64 = get("PVR_IGEMM_BM64", 0);
+    sw.pp_bm224 = get("PVR_PP_BM224", 1);
+    sw.pp_persist = get("PVR_PP_PERSIST", 384);
+}
+
+PlanSwitches &op_switches() {
+    static PlanSwitches sw = [] { PlanSwitches v; read_switches(v); return v; }();
+    return sw;
 }
 
 // f16 range validation (pvr_encoder_check_range): any inf / NaN among the first `n` 16-bit (or fp32) values of a launch's output -> flags[idx] = 1
@@ -430,7 +456,7 @@ static pvr_status build_schedules(pvr_encoder *e) {
                 const ConvOp &o2 = e->ops[i + 1], &o3 = e->ops[i + 2];
                 if (ends_with(o2.conv, ".conv2") && o2.k == 3 && !o2.f32op && o2.relu == 1 && o2.cin == o2.cout && o2.cin_real == o2.cin && o2.in_buf == op.out_buf &&
                     ends_with(o3.conv, ".conv3") && !o3.f32op && !o3.out_f32 && o3.relu == 1 && o3.res_buf == op.in_buf && o3.cout == op.cin && o3.cout_real == o3.cout &&
-                    o3.in_buf == o2.out_buf && op.cout == o2.cin && bneck_frame_supported(e->desc.chunk, o2.h, o2.w, o2.cout, o3.cout, o2.stride)) {
+                    o3.in_buf == o2.out_buf && op.cout == o2.cin && bneck_frame_supported(e->sw, e->desc.chunk, o2.h, o2.w, o2.cout, o3.cout, o2.stride)) {
                     Launch l;
                     l.conv1 = i; l.conv2 = i + 1; l.conv3 = i + 2; l.frame = 1; l.t1_in = op.out_buf;
                     e->sched_fused.push_back(l);
@@ -451,7 +477,7 @@ static pvr_status build_schedules(pvr_encoder *e) {
         // next block's conv1 rides in the same launch (it then reads / writes the two t1 buffers in turns, as the layer1 / layer2 chains do)
         if (ends_with(op.conv, ".conv2") && op.k == 3 && !op.f32op && i + 1 < n && ends_with(e->ops[i + 1].conv, ".conv3") && !e->ops[i + 1].f32op &&
             !e->ops[i + 1].out_f32 && e->ops[i + 1].relu == 1 && e->ops[i + 1].res_buf != B_NONE && op.relu == 1 && op.cin == op.cout && op.cin_real == op.cin &&
-            e->ops[i + 1].cout_real == e->ops[i + 1].cout && bneck_frame_supported(e->desc.chunk, op.h, op.w, op.cout, e->ops[i + 1].cout, op.stride)) {
+            e->ops[i + 1].cout_real == e->ops[i + 1].cout && bneck_frame_supported(e->sw, e->desc.chunk, op.h, op.w, op.cout, e->ops[i + 1].cout, op.stride)) {
             Launch l;
             l.conv2 = i; l.conv3 = i + 1; l.frame = 1; l.t1_in = conv1_frame_out >= 0 ? conv1_frame_out : op.in_buf;
             conv1_frame_out = -1;
@@ -460,7 +486,7 @@ static pvr_status build_schedules(pvr_encoder *e) {
             if (next1_on && nx + 2 < n && ends_with(e->ops[nx].conv, ".conv1") && e->ops[nx].k == 1 && e->ops[nx].stride == 1 && e->ops[nx].relu == 1 && !e->ops[nx].f32op &&
                 e->ops[nx].cin == e->ops[i + 1].cout && e->ops[nx].cout == op.cout && e->ops[nx].in_buf == e->ops[i + 1].out_buf && e->ops[nx].cout_real == e->ops[nx].cout &&
                 e->ops[i + 1].tap.empty() && ends_with(e->ops[nx + 1].conv, ".conv2") && ends_with(e->ops[nx + 2].conv, ".conv3") &&
-                bneck_frame_supported(e->desc.chunk, e->ops[nx + 1].h, e->ops[nx + 1].w, e->ops[nx + 1].cout, e->ops[nx + 2].cout, e->ops[nx + 1].stride)) {
+                bneck_frame_supported(e->sw, e->desc.chunk, e->ops[nx + 1].h, e->ops[nx + 1].w, e->ops[nx + 1].cout, e->ops[nx + 2].cout, e->ops[nx + 1].stride)) {
                 l.next1 = nx;
                 l.t1_out = l.t1_in == B_T1 ? B_T2 : B_T1;
                 conv1_frame_out = l.t1_out;
@@ -610,7 +636,7 @@ static pvr_status build_schedules(pvr_encoder *e) {
     for (Launch &l : e->sched_fused)
         if (l.conv3 >= 0 && !l.frame) {
             const ConvOp &c2 = e->ops[l.conv2];
-            l.wave = chain_uses_wave_form(c2.cout, l.next1 >= 0 ? e->ops[l.next1].cout : 0, c2.stride, l.ds >= 0);
+            l.wave = chain_uses_wave_form(e->sw, c2.cout, l.next1 >= 0 ? e->ops[l.next1].cout : 0, c2.stride, l.ds >= 0);
         }
     // layer2's stride-1 tails on their wave form (chain_wave128.hip, round 6).  That kernel reads t1 and the residual blocked and writes t1' blocked, so a
     // launch can take it only if (i) the launch in front is a chain that carries this block's conv1 and hands y and t1' over untapped - the block form (it can
@@ -629,7 +655,7 @@ static pvr_status build_schedules(pvr_encoder *e) {
             const Launch &B = sc[b];
             if (B.conv3 < 0 || B.frame || B.ds >= 0 || B.wave) return false;
             const ConvOp &b2 = e->ops[B.conv2];
-            return (b2.h * b2.w) % 16 == 0 && e->sw.chain_blocked && chain_uses_wave128(b2.cout, B.next1 >= 0 ? e->ops[B.next1].cout : 0, b2.stride, (int64_t)b2.h * b2.w);
+            return (b2.h * b2.w) % 16 == 0 && e->sw.chain_blocked && chain_uses_wave128(e->sw, b2.cout, B.next1 >= 0 ? e->ops[B.next1].cout : 0, b2.stride, (int64_t)b2.h * b2.w);
         };
         std::vector<char> can(ns, 0);
         for (int b = ns - 1; b >= 1; --b)
@@ -668,7 +694,7 @@ static pvr_status build_schedules(pvr_encoder *e) {
         A.out_blk = 1; B.in_blk = 1;
         // ... and when A is layer1's first tail (downsample inside), its conv2 input t1 can arrive blocked too: from conv1's own launch,
         // which directly precedes it (conv_expand.hip writes either layout; whether THAT kernel runs is known per forward: batch size)
-        if (A.ds >= 0 && a > 0 && a2.w == 56 && chain_wave_halo_enabled()) {   // (the downsample tail reads a blocked t1 through the halo form only)
+        if (A.ds >= 0 && a > 0 && a2.w == 56 && e->sw.chain_wave_halo) {   // (the downsample tail reads a blocked t1 through the halo form only)
             Launch &C = e->sched_fused[a - 1];
             if (C.conv3 < 0 && C.conv2 >= 0) {
                 const ConvOp &c1 = e->ops[C.conv2];
@@ -810,7 +836,7 @@ static uint8_t resolve_kind(const pvr_encoder *enc, const std::vector<Launch> &p
     const Launch &l = plan[li];
     const ConvOp &op = enc->ops[l.conv3 >= 0 ? l.conv3 : l.conv2];
     const bool ll = enc->low_latency && nb <= 4;                 // (the low-latency plan covers forwards of <= 4 frames: small_batch_ksplit)
-    const bool autoalgo = conv_algo() == -1;
+    const bool autoalgo = enc->sw.conv_algo == -1;
     if (l.frame) {
         // small batches (a frame per workgroup leaves most CUs idle): the member convolutions as their own launches - bit-identical
         if (nb >= enc->sw.frame_min_n && !enc->low_latency) return l.conv1 >= 0 ? LK_FRAME_FRONT1 : LK_FRAME;
@@ -826,13 +852,13 @@ static uint8_t resolve_kind(const pvr_encoder *enc, const std::vector<Launch> &p
     if (op.ksplit > 1) return LK_SPLITK;
     const int ho = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo = (op.w + 2 * op.pad - op.k) / op.stride + 1;
     if (l.out_blk && autoalgo && op.cin == 64 &&                 // (blocked output: the cin = 64 instances of conv_expand only)
-        conv_expand_supported((int64_t)nb * op.h * op.w, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0, op.relu, 0, false))
+        conv_expand_supported(enc->sw, (int64_t)nb * op.h * op.w, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0, op.relu, 0, false))
         return LK_EXPAND_BLOCKED;
     if (allow_pool && enc->sw.pool_fuse && li + 1 == plan.size() && op.d_wfb && pooled_head(enc) && enc->final_hw == 49 && op.h == 7 && op.w == 7 && op.k == 1 &&
         op.stride == 1 && op.relu == 1 && (op.out_f32 & 1) && !(op.out_f32 & 2) && op.res_buf != B_NONE && op.out_buf == B_F32 && enc->final_c == op.cout &&
         autoalgo && !ll)
         return LK_WFRAG_POOL;
-    if (op.d_wfb && autoalgo && !ll && conv_wfrag_preferred((int64_t)nb * ho * wo, op.cin, op.cout, op.k, op.k) &&
+    if (op.d_wfb && autoalgo && !ll && conv_wfrag_preferred(enc->sw, (int64_t)nb * ho * wo, op.cin, op.cout, op.k, op.k) &&
         conv_wfrag_supported((int64_t)nb * ho * wo, (int64_t)nb * op.h * op.w * op.cin * 2, op.cin, op.cout, op.k, op.k, op.pad, op.relu, op.out_f32))
         return LK_WFRAG;
     return LK_CONV;
@@ -841,13 +867,13 @@ static uint8_t resolve_kind(const pvr_encoder *enc, const std::vector<Launch> &p
 static const std::vector<Launch> &cur_plan(const pvr_encoder *enc) { return enc->fuse ? enc->sched_fused : enc->sched_plain; }
 
 // kinds[(nb - 1) * launches + i] for nb = 1 .. chunk: rebuilt whenever something it depends on changes (finalize, set_low_latency,
-// debug_set_fusion, debug_set_switch; pvr_debug_set_conv_algo is process-wide, so the forward compares kinds_algo first)
+// debug_set_fusion, debug_set_switch)
 static void resolve_kinds(pvr_encoder *enc) {
     const std::vector<Launch> &plan = cur_plan(enc);
     const int chunk = enc->desc.chunk;
     enc->kinds_stride = plan.size();
     enc->kinds.assign((size_t)chunk * plan.size(), LK_CONV);
-    if (enc->desc.dtype == PVR_F32 || enc->desc.arch == PVR_ARCH_CLIP_RN50 || enc->vit || enc->rnd || enc->host) { enc->kinds_algo = conv_algo(); return; }
+    if (enc->desc.dtype == PVR_F32 || enc->desc.arch == PVR_ARCH_CLIP_RN50 || enc->vit || enc->rnd || enc->host) return;
     for (int nb = 1; nb <= chunk; ++nb)
         for (size_t i = 0; i < plan.size(); ++i) enc->kinds[(size_t)(nb - 1) * plan.size() + i] = resolve_kind(enc, plan, i, nb);
     // consecutive whole-bottleneck frame launches, each reading its predecessor's output (layer3.1 .. 3.5): one launch for the run (bneck_frame.hip RUN)
@@ -863,7 +889,6 @@ static void resolve_kinds(pvr_encoder *enc) {
                 i = j;
             }
         }
-    enc->kinds_algo = conv_algo();
 }
 
 // activation workspace of the current lane (ResNet50 family)
@@ -1030,7 +1055,7 @@ static pvr_status clip_rn50_chunk(pvr_encoder *enc, const uint8_t *fr, int nb, i
     if ((s = launch_stem(enc->d_img, enc->d_stem_w, enc->d_stem_b, enc->d_stem, nb, crop, dt, st))) return s;
     for (const ConvOp &op : enc->ops) {
         if (op.kind == 1) s = launch_avgpool2(bufp(enc, op.in_buf), bufp(enc, op.out_buf), nb, op.h, op.w, op.cin, dt, st);
-        else s = launch_conv(bufp(enc, op.in_buf), op.d_w, op.d_b, op.res_buf == B_NONE ? nullptr : bufp(enc, op.res_buf), bufp(enc, op.out_buf),
+        else s = launch_conv(enc->sw, bufp(enc, op.in_buf), op.d_w, op.d_b, op.res_buf == B_NONE ? nullptr : bufp(enc, op.res_buf), bufp(enc, op.out_buf),
                              enc->d_zero, nb, op.h, op.w, op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
         if (s) return s;
         if (!enc->stop_after.empty() && op.tap == enc->stop_after) return PVR_OK;
@@ -1038,11 +1063,11 @@ static pvr_status clip_rn50_chunk(pvr_encoder *enc, const uint8_t *fr, int nb, i
     // AttentionPool2d(7, 2048, 32 heads, 1024)
     const int C = 2048, T = 50;
     if ((s = launch_attnpool_tokens((const float *)enc->d_buf[B_F32], enc->ap_pos, enc->d_buf[B_T1], nb, 49, C, dt, st))) return s;
-    if ((s = launch_conv(enc->d_buf[B_T1], enc->ap_wqkv, enc->ap_bqkv, nullptr, enc->d_buf[B_X0], enc->d_zero, nb * T, 1, 1, C, 3 * C, 1, 1, 1, 0, 0, 0, dt, st))) return s;
+    if ((s = launch_conv(enc->sw, enc->d_buf[B_T1], enc->ap_wqkv, enc->ap_bqkv, nullptr, enc->d_buf[B_X0], enc->d_zero, nb * T, 1, 1, C, 3 * C, 1, 1, 1, 0, 0, 0, dt, st))) return s;
     if ((s = launch_attention(enc->d_buf[B_X0], enc->d_buf[B_T2], T, C, 32, nb, dt, st))) return s;
     // c_proj of token 0 only: a 1x1 "convolution" over (n, T, 1) with stride T picks row 0 of every image; fp32 out
     float *dense = enc->ap_out + (size_t)enc->cur_lane * enc->desc.chunk * 1024;
-    if ((s = launch_conv(enc->d_buf[B_T2], enc->ap_wc, enc->ap_bc, nullptr, dense, enc->d_zero, nb, T, 1, C, 1024, 1, 1, T, 0, 0, 1, dt, st))) return s;
+    if ((s = launch_conv(enc->sw, enc->d_buf[B_T2], enc->ap_wc, enc->ap_bc, nullptr, dense, enc->d_zero, nb, T, 1, C, 1024, 1, 1, T, 0, 0, 1, dt, st))) return s;
     PVR_HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * 4, dense, 1024 * 4, 1024 * 4, nb, hipMemcpyDeviceToDevice, st));
     return PVR_OK;
 }
@@ -1112,13 +1137,13 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
         int fused_u8 = 0;
         // layer1.0.conv1 has no launch in the fused schedule (build_schedules): the stem's register-pooling form runs it
         const bool c1_pending = enc->fuse && enc->stem_c1 >= 0;
-        const bool c1_in_stem = c1_pending && enc->stop_after.empty() && stem_conv1_capable();
+        const bool c1_in_stem = c1_pending && enc->stop_after.empty() && stem_conv1_capable(enc->sw);
         if (enc->sw.stem_u8 && enc->sw.stem_lds && enc->stop_after.empty() && enc->desc.crop == 224 && enc->crop_pos >= 0 && enc->crop_pos <= 4) {
             int rn = 1, top = 0, left = 0;
             preprocess_geometry(h, w, enc->desc.resize, enc->desc.crop, enc->crop_pos, &rn, &top, &left);
             if (!rn && stem_pool_u8_ok(fr, h, w, top, left)) {
                 if ((s = mark())) return s;                  // (launch index of the preprocess stays: pvr_encoder_profile)
-                if ((s = launch_stem_pool_u8(fr, nb, h, w, top, left, enc->d_stem_w, enc->d_stem_b, enc->d_buf[B_X0], dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
+                if ((s = launch_stem_pool_u8(enc->sw, fr, nb, h, w, top, left, enc->d_stem_w, enc->d_stem_b, enc->d_buf[B_X0], dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
                                              c1_in_stem ? enc->ops[enc->stem_c1].d_b : nullptr, c1_in_stem ? enc->d_buf[B_T1] : nullptr, enc->stem_c1_blk))) return s;
                 fused_u8 = 1;
             }
@@ -1134,7 +1159,7 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
             return PVR_OK;
         }
         // conv1 + bn1 + relu + maxpool fused: the 112x112x64 activation stays in LDS
-        if (!fused_u8 && (s = launch_stem_pool(enc->d_img, enc->d_stem_w, enc->d_stem_b, enc->d_buf[B_X0], nb, enc->desc.crop, dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
+        if (!fused_u8 && (s = launch_stem_pool(enc->sw, enc->d_img, enc->d_stem_w, enc->d_stem_b, enc->d_buf[B_X0], nb, enc->desc.crop, dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
                                                c1_in_stem ? enc->ops[enc->stem_c1].d_b : nullptr, c1_in_stem ? enc->d_buf[B_T1] : nullptr, enc->stem_c1_blk))) return s;
         if (enc->range_flags) {                      // pvr_encoder_check_range: the pooled stem output (flag slot behind the plan's launches)
             const size_t n8 = (size_t)nb * 56 * 56 * 64 / 8;
@@ -1146,18 +1171,17 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
         bool stopped = false, t1_blocked = false;   // t1_blocked: the conv1 launch in front of layer1's first tail wrote t1 in the blocked layout
         if (c1_in_stem) t1_blocked = enc->stem_c1_blk != 0;
         else if (c1_pending && enc->stop_after != "pool") {
-            // ... or, where that stem form did not run (debug stops, PVR_STEM_REGPOOL=0), as its own launch in front of the plan - blocked t1 when the tail wants it
+            // ... or, where that stem form did not run (debug stops, PVR_STEM_REGPOOL=0, PVR_STEM_LDS=0), as its own launch in front of the plan - blocked t1 when the tail wants it
             const ConvOp &c1 = enc->ops[enc->stem_c1];
-            if (enc->stem_c1_blk && conv_algo() == -1 && conv_expand_supported((int64_t)nb * c1.h * c1.w, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, false)) {
+            if (enc->stem_c1_blk && enc->sw.conv_algo == -1 && conv_expand_supported(enc->sw, (int64_t)nb * c1.h * c1.w, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, false)) {
                 s = launch_conv_expand(enc->d_buf[c1.in_buf], c1.d_w, c1.d_b, nullptr, enc->d_buf[c1.out_buf], nb, c1.h, c1.w, c1.cin, c1.cout, 1, c1.relu, dt, st, 1);
                 t1_blocked = true;
             } else
-                s = launch_conv(enc->d_buf[c1.in_buf], c1.d_w, c1.d_b, nullptr, enc->d_buf[c1.out_buf], enc->d_zero, nb, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, dt, st);
+                s = launch_conv(enc->sw, enc->d_buf[c1.in_buf], c1.d_w, c1.d_b, nullptr, enc->d_buf[c1.out_buf], enc->d_zero, nb, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, dt, st);
             if (s) return s;
         }
         bool pooled = false;                         // the plan's last convolution wrote the average pool itself (conv_wfrag's pooled form)
         const std::vector<Launch> &plan_ = cur_plan(enc);
-        if (enc->kinds_algo != conv_algo() || enc->kinds_stride != plan_.size()) resolve_kinds(enc);   // (pvr_debug_set_conv_algo is process-wide; same size: no allocation)
         const uint8_t *kinds = enc->kinds.data() + (size_t)(nb - 1) * plan_.size();
         float *smallk = enc->d_smallk[enc->cur_lane];
         // the pooled epilogue stores 16-byte pieces of the caller's rows: a property of this call's arguments, not of the plan
@@ -1171,7 +1195,7 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
                 if (!smallk) { set_error("low-latency plan without its scratch (pvr_encoder_set_low_latency allocates it)"); return PVR_ERR_STATE; }
                 return launch_conv_splitk(in, o.d_w, o.d_b, r_, out_, enc->d_zero, smallk, ks, nb, o.h, o.w, o.cin, o.cout, o.k, o.k, o.stride, o.pad, o.relu, o.out_f32, dt, st);
             }
-            return launch_conv(in, o.d_w, o.d_b, r_, out_, enc->d_zero, nb, o.h, o.w, o.cin, o.cout, o.k, o.k, o.stride, o.pad, o.relu, o.out_f32, dt, st);
+            return launch_conv(enc->sw, in, o.d_w, o.d_b, r_, out_, enc->d_zero, nb, o.h, o.w, o.cin, o.cout, o.k, o.k, o.stride, o.pad, o.relu, o.out_f32, dt, st);
         };
         for (size_t li = 0; li < plan_.size(); ++li) {
             const Launch &l = plan_[li];
@@ -1198,14 +1222,14 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
                 break;
             case LK_FRAME_FRONT1: {
                 const ConvOp &c2 = enc->ops[l.conv2], &cf = enc->ops[l.conv1];
-                s = launch_bneck_frame(nullptr, c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nullptr, nb, 3 | 8, dt, st,
+                s = launch_bneck_frame(enc->sw, nullptr, c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nullptr, nb, 3 | 8, dt, st,
                                        nullptr, nullptr, nullptr, nullptr, cf.d_wfb, cf.d_b);
                 break;
             }
             case LK_FRAME: {
                 const ConvOp &c2 = enc->ops[l.conv2];
                 const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
-                s = launch_bneck_frame(enc->d_buf[l.t1_in], c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nullptr, nb, c1 ? 7 : 3, dt, st,
+                s = launch_bneck_frame(enc->sw, enc->d_buf[l.t1_in], c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nullptr, nb, c1 ? 7 : 3, dt, st,
                                        nullptr, c1 ? c1->d_wfb : nullptr, c1 ? c1->d_b : nullptr, c1 ? enc->d_buf[l.t1_out] : nullptr);
                 break;
             }
@@ -1225,7 +1249,7 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
             case LK_DUAL: {
                 // conv3 & downsample as one two-operand launch (layer3.0 / layer4.0)
                 const ConvOp &cd = enc->ops[l.ds];
-                s = launch_conv_pp256(enc->d_buf[op.in_buf], op.d_wcat, op.d_bsum, nullptr, enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0,
+                s = launch_conv_pp256(enc->sw, enc->d_buf[op.in_buf], op.d_wcat, op.d_bsum, nullptr, enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0,
                                       op.relu, 0, 0, dt, 224, st, enc->d_buf[cd.in_buf], cd.h, cd.w, cd.cin, cd.stride);
                 break;
             }
@@ -1239,7 +1263,7 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
                 const ConvOp &c2 = enc->ops[l.conv2];
                 const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
                 const ConvOp *cd = l.ds >= 0 ? &enc->ops[l.ds] : nullptr;
-                s = launch_bottleneck_chain(enc->d_buf[l.t1_in], c2.d_w, c2.d_b, op.d_wp, cd ? op.d_bsum : op.d_b, res, enc->d_buf[op.out_buf],
+                s = launch_bottleneck_chain(enc->sw, enc->d_buf[l.t1_in], c2.d_w, c2.d_b, op.d_wp, cd ? op.d_bsum : op.d_b, res, enc->d_buf[op.out_buf],
                                             c1 ? c1->d_wp : nullptr, c1 ? c1->d_b : nullptr, c1 ? enc->d_buf[l.t1_out] : nullptr, nb,
                                             c2.h, c2.w, c2.cout, c1 ? c1->cout : 0, c2.stride, dt, st,
                                             cd ? enc->d_buf[cd->in_buf] : nullptr, cd ? cd->d_wp : nullptr, op.d_wpb, cd ? cd->d_wpb : nullptr,
@@ -1284,17 +1308,17 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
                 break;
             case LK_WFRAG_POOL:
                 // the trunk's last conv3 + identity + ReLU with AdaptiveAvgPool2d(1) in its epilogue: the (n,7,7,2048) fp32 activation is never written
-                s = launch_conv_wfrag(enc->d_buf[op.in_buf], op.d_wfb, op.d_b, res, nullptr, nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0, 1, 1, dt, st,
+                s = launch_conv_wfrag(enc->sw, enc->d_buf[op.in_buf], op.d_wfb, op.d_b, res, nullptr, nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0, 1, 1, dt, st,
                                       out + (size_t)f0 * out_stride, out_stride);
                 pooled = true;
                 break;
             case LK_WFRAG:
                 // few pixels, deep K (layer4 at batch 256): 112 x 256 tiles, weights as L2 fragments
-                s = launch_conv_wfrag(enc->d_buf[op.in_buf], op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, op.k, op.k,
+                s = launch_conv_wfrag(enc->sw, enc->d_buf[op.in_buf], op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, op.k, op.k,
                                       op.stride, op.pad, op.relu, op.out_f32, dt, st);
                 break;
             default:
-                s = launch_conv(enc->d_buf[op.in_buf], op.d_w, op.d_b, res, enc->d_buf[op.out_buf], enc->d_zero, nb, op.h, op.w,
+                s = launch_conv(enc->sw, enc->d_buf[op.in_buf], op.d_w, op.d_b, res, enc->d_buf[op.out_buf], enc->d_zero, nb, op.h, op.w,
                                 op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
             }
             if (s) return s;
@@ -1473,8 +1497,9 @@ pvr_status pvr_encoder_debug_set_fusion(pvr_encoder *enc, int32_t on) {
     return PVR_OK;
 }
 
-// The switches of a finalized encoder that do not shape its plan (PlanSwitches, "live"): pool_fuse, stem_u8, frame_min_n.  The A/B tests flip them
-// between two forwards of ONE handle; everything else is fixed by the environment at pvr_encoder_create.
+// The switches of a finalized encoder that do not shape its plan (PlanSwitches, "live"): pool_fuse, stem_u8, frame_min_n, frame_run, frame_stagger,
+// conv_algo, frame64, stem_regpool.  The A/B tests flip them between two forwards of ONE handle; everything else is fixed by the environment at
+// pvr_encoder_create.
 pvr_status pvr_encoder_debug_set_switch(pvr_encoder *enc, const char *name, int32_t value) {
     PVR_REQUIRE(enc && name, "pvr_encoder_debug_set_switch: null argument");
     const std::string nm = name;
@@ -1483,7 +1508,14 @@ pvr_status pvr_encoder_debug_set_switch(pvr_encoder *enc, const char *name, int3
     else if (nm == "frame_min_n") enc->sw.frame_min_n = value;
     else if (nm == "frame_run") enc->sw.frame_run = value;
     else if (nm == "frame_stagger") enc->sw.frame_stagger = value;
-    else { set_error("pvr_encoder_debug_set_switch: '%s' is not a live switch (pool_fuse, stem_u8, frame_min_n, frame_run, frame_stagger); plan switches are read from the environment at create", name); return PVR_ERR_INVALID; }
+    else if (nm == "conv_algo") enc->sw.conv_algo = value;
+    else if (nm == "frame64") enc->sw.frame64 = value;
+    else if (nm == "stem_regpool") enc->sw.stem_regpool = value;
+    else {
+        set_error("pvr_encoder_debug_set_switch: '%s' is not a live switch (pool_fuse, stem_u8, frame_min_n, frame_run, frame_stagger, conv_algo, frame64, "
+                  "stem_regpool); plan switches are read from the environment at create", name);
+        return PVR_ERR_INVALID;
+    }
     if (enc->finalized && !enc->vit && !enc->rnd && !enc->host) resolve_kinds(enc);
     return PVR_OK;
 }
@@ -1532,7 +1564,7 @@ int32_t pvr_encoder_launch_kernel(const pvr_encoder *enc, int32_t n, int32_t ind
     if (i >= (int)plan.size()) return 0;
     const int nb = n < enc->desc.chunk ? n : enc->desc.chunk;
     // the forward's own table when it is current (it knows the runs: several plan entries in one launch), else the per-entry rule
-    const bool tab = enc->kinds_stride == plan.size() && enc->kinds.size() == (size_t)enc->desc.chunk * plan.size() && enc->kinds_algo == conv_algo();
+    const bool tab = enc->kinds_stride == plan.size() && enc->kinds.size() == (size_t)enc->desc.chunk * plan.size();
     const int kind = tab ? enc->kinds[(size_t)(nb - 1) * plan.size() + i] : resolve_kind(enc, plan, (size_t)i, nb);
     const char *nm = enc->desc.dtype == PVR_F32 ? "conv_f32" : launch_kind_name(kind);
     if (enc->desc.dtype != PVR_F32 && kind == LK_CHAIN) nm = plan[i].wave == 2 ? "chain_wave128" : plan[i].wave == 1 ? "chain_wave" : "bottleneck_chain";

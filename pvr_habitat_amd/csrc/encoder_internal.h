@@ -1,4 +1,4 @@
-// Internal declarations shared by encoder.hip (ResNet50 family) and vit.hip (CLIP ViT).
+// Internal declarations shared by encoder.hip (ResNet50 family), vit.hip (CLIP ViT) and the kernel files whose launchers take the encoder's switches.
 #pragma once
 #include <map>
 #include <string>
@@ -9,16 +9,64 @@
 
 namespace pvr {
 
+// Every A/B switch of the encoder path, read from the environment ONCE per encoder (pvr_encoder_create: read_switches) - never on the forward path, and
+// nowhere else: the planner and the launchers take their choices from here (launchers: `sw`).  The ones marked (live) can be changed on a finalized encoder
+// with pvr_encoder_debug_set_switch; the others shape the plan or its launches and are fixed at finalize.  The pvr_op_* entry points have no handle: they
+// share one process-level instance, op_switches().
+struct PlanSwitches {
+    int pool_fuse = 1;        // PVR_POOL_FUSE (live): the pooled form of conv_wfrag for the trunk's last launch
+    int stem_u8 = 1;          // PVR_STEM_U8 (live): the fused stem reads uint8 frames itself when no resize is needed
+    int stem_lds = 1;         // PVR_STEM_LDS: the round-3 forms of the fused stem (0: round 2's stem_pool_kernel - no uint8 form, no conv1 inside)
+    int stem_regpool = 1;     // PVR_STEM_REGPOOL (live): the stem's max pool in registers (0: the LDS-tile pooling of rounds 3-5; bit-identical)
+    int frame_front1 = 1;     // PVR_FRAME_FRONT1: layer3's per-frame launches carry their own conv1
+    int frame_next1 = 0;      // PVR_FRAME_NEXT1: ... carry the NEXT block's conv1 instead (measured slower)
+    int frame_bneck = 1;      // PVR_FRAME_BNECK: layer3's per-frame launches (bneck_frame.hip) at all
+    int frame64 = 0;          // PVR_FRAME64 (live, opt-in: measured slower): the whole-bottleneck frame launches in the 64-channel tiling (bneck_frame64.hip)
+    int bneck_stagger = 0;    // PVR_FRAME_STAGGER (EXPERIMENTS=1 builds only): odd workgroups of a single bottleneck's frame launch start late
+    int dual_ds = 1;          // PVR_DUAL_DS: conv3 & downsample of layer3.0 / layer4.0 as one two-operand launch
+    int chain_ds = 1;         // PVR_CHAIN_DS: layer1.0's downsample inside the chain
+    int chain_blocked = 1;    // PVR_CHAIN_BLOCKED: blocked hand-off between consecutive tails
+    int chain_halo = 1;       // PVR_CHAIN_HALO: the block form's phase A through the LDS halo (0: per-tap global loads; bit-identical)
+    int chain_ds_occ = 3;     // PVR_CHAIN_DS_OCC: blocks per CU of the block form's downsample instance (3: capped at 168 VGPRs, else 2)
+    int chain_pfk = 12;       // PVR_CHAIN_PFK: slice of phase A at which the Cm = 128 block form issues phase B's first prefetch (-1: in front of phase A)
+    int chain_cfg = 12;       // PVR_CHAIN_CFG: 10 * RD + OCC of the block form's Cm = 64 instances
+    int chain_wave = 1;       // PVR_CHAIN_WAVE: the wave forms of the tails at all (0: every tail on the block form; bit-identical)
+    int chain_wave_halo = 1;  // PVR_CHAIN_WAVE_HALO: the wave form reads blocked inputs through the halo registers (0: the per-K-step load ring)
+    int chain_wave_128 = 1;   // PVR_CHAIN_WAVE_128: the wave form for layer1's last tail (next conv1 128 wide)
+    int chain_wave_l2 = 0;    // PVR_CHAIN_WAVE_L2 (opt-in: measured no faster): layer2's stride-1 tails on their wave form (chain_wave128.hip)
+    int splitk = 1;           // PVR_SPLITK: planned split-K of the *_l4 head
+    int smallk_div = 4;       // PVR_SMALLK_DIV: K slices per block of the low-latency plan
+    int frame_run = 0;        // PVR_FRAME_RUN (live, opt-in: measured equal): consecutive whole-bottleneck frame launches (layer3.1 .. 3.5) as one launch
+    int frame_stagger = 0;    // PVR_FRAME_RUN_STAGGER (live): odd workgroups of that launch start this many x 8128 cycles late
+    int frame_min_n = 128;    // PVR_FRAME_MIN_N (live): frames per forward from which layer3's per-frame launches run as such
+    int stem_conv1 = 1;       // PVR_STEM_CONV1: layer1.0.conv1 runs inside the fused stem (no launch of its own; round 6)
+    int split16 = 1;          // PVR_SPLIT16: the fp32 stage / head of the compressed PVRs' parity plan on the 16-bit MFMA (0: f32-input MFMA)
+    int resid32 = 1;          // PVR_RESID32: fp32 residual stream of that plan (0: all-16-bit plan)
+    int tail_f32 = 1;         // PVR_TAIL_F32: its last trunk stage entirely in fp32
+    int fuse = 1;             // PVR_FUSE: the fused schedule (0: one launch per convolution; also pvr_encoder_debug_set_fusion)
+    int conv_algo = -1;       // PVR_CONV_ALGO (live): launch_conv's kernel: -1 auto by shape, 0 conv_igemm only, 1 / 2 / 3 conv_pp256 with 256- / 128- / 224-pixel tiles
+    int conv_halo = 1;        // PVR_CONV_HALO: the 3x3 stride-1 convolutions on conv3x3_halo.hip (0: conv_igemm; bit-identical)
+    int conv_expand = 1;      // PVR_CONV_EXPAND: the 1x1 convolutions conv_expand.hip accepts on it (0: conv_igemm / conv_pp256; bit-identical)
+    int conv_wfrag = 1;       // PVR_CONV_WFRAG: the few-pixel deep-K launches on conv_wfrag.hip (2: every launch it accepts)
+    int wfrag_ko = 0;         // PVR_WFRAG_KO (EXPERIMENTS=1 builds only): timing knock-out instance of conv_wfrag
+    int igemm_nk4 = 1;        // PVR_IGEMM_NK4: conv_igemm's four-slice instance for the K = 256 1x1 convolutions with residual (bit-identical)
+    int igemm_bm64 = 0;       // PVR_IGEMM_BM64: 64-pixel tiles for those convolutions (experiment)
+    int pp_bm224 = 1;         // PVR_PP_BM224: conv_pp256's 224-pixel tile where it needs fewer CU-rounds (0 off, 2 round 2's rows-only rule)
+    int pp_persist = 384;     // PVR_PP_PERSIST: tiles per launch from which conv_pp256 runs persistent (0 never)
+};
+void read_switches(PlanSwitches &sw);
+PlanSwitches &op_switches();   // the pvr_op_* entry points' instance: read_switches on first use; pvr_debug_set_conv_algo / _frame64 change it
+
 pvr_status launch_preprocess(const uint8_t *, int, int, int, int, int, void *, int, hipStream_t, int crop_pos = 0);
 pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
 pvr_status launch_maxpool(const void *, void *, int, int, int, int, int, hipStream_t);
-// (c1_*: layer1.0.conv1 inside the stem - stem.hip, StemC1; only when stem_conv1_capable())
-pvr_status launch_stem_pool(const void *, const void *, const float *, void *, int, int, int, hipStream_t, const void *c1_w = nullptr, const float *c1_b = nullptr,
-                            void *c1_t1 = nullptr, int c1_blk = 0);
+// (c1_*: layer1.0.conv1 inside the stem - stem.hip, StemC1; only when stem_conv1_capable(sw))
+pvr_status launch_stem_pool(const PlanSwitches &sw, const void *, const void *, const float *, void *, int, int, int, hipStream_t, const void *c1_w = nullptr,
+                            const float *c1_b = nullptr, void *c1_t1 = nullptr, int c1_blk = 0);
 bool stem_pool_u8_ok(const void *, int, int, int, int);   // geometry only; the PVR_STEM_U8 / PVR_STEM_LDS switches live in PlanSwitches
-pvr_status launch_stem_pool_u8(const uint8_t *, int, int, int, int, int, const void *, const float *, void *, int, hipStream_t, const void *c1_w = nullptr,
-                               const float *c1_b = nullptr, void *c1_t1 = nullptr, int c1_blk = 0);
-bool stem_conv1_capable();
+pvr_status launch_stem_pool_u8(const PlanSwitches &sw, const uint8_t *, int, int, int, int, int, const void *, const float *, void *, int, hipStream_t,
+                               const void *c1_w = nullptr, const float *c1_b = nullptr, void *c1_t1 = nullptr, int c1_blk = 0);
+bool stem_conv1_capable(const PlanSwitches &sw);
 void stem_c1_pack(const u16 *w, u16 *img);
 void preprocess_geometry(int h, int w, int resize, int crop, int crop_pos, int *resize_needed, int *top, int *left);
 pvr_status launch_avgpool(const void *, float *, int64_t, int, int, int, int, int, hipStream_t);
@@ -27,26 +75,24 @@ pvr_status launch_h_to_f32(const void *, float *, size_t, int, hipStream_t);
 pvr_status launch_f32_to_h(const float *, void *, size_t, int, hipStream_t);
 pvr_status launch_conv_splitk(const void *, const void *, const float *, const void *, void *, const void *, float *, int, int, int, int, int, int,
                               int, int, int, int, int, int, int, hipStream_t);
-pvr_status launch_conv(const void *, const void *, const float *, const void *, void *, const void *, int, int, int, int,
+pvr_status launch_conv(const PlanSwitches &sw, const void *, const void *, const float *, const void *, void *, const void *, int, int, int, int,
                        int, int, int, int, int, int, int, int, hipStream_t);
 
 // conv_expand.hip: persistent weight-stationary 1x1 convolutions (out_blk: blocked output layout for chain_wave.hip)
-bool conv_expand_supported(int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32, bool has_res);
+bool conv_expand_supported(const PlanSwitches &sw, int64_t M, int h, int w, int cin, int cout, int kh, int kw, int stride, int pad, int relu, int out_f32, bool has_res);
 pvr_status launch_conv_expand(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
                               int cout, int stride, int relu, int dtype, hipStream_t stream, int out_blk = 0);
 
 // conv_pp256.hip: 256x256-tile ping-pong kernel for deep-K convolutions / linear layers
 bool pp256_supported(int64_t M, int cin, int cout, int kh, int kw, int64_t in_bytes, int64_t w_bytes, int64_t out_bytes, int64_t res_bytes);
-pvr_status launch_conv_pp256(const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
+pvr_status launch_conv_pp256(const PlanSwitches &sw, const void *in, const void *wgt, const float *bias, const void *res, void *out, int n, int h, int w, int cin,
                              int cout, int kh, int kw, int stride, int pad, int act, int out_f32, int res_f32, int dtype, int bm, hipStream_t stream,
                              const void *in2 = nullptr, int h2 = 0, int w2 = 0, int cin2 = 0, int stride2 = 1);
-int conv_algo();
-void set_conv_algo(int a);
 
 // bneck_frame.hip: per-frame fused tail of the layer3 bottlenecks (conv2 -> conv3 + residual [-> the next block's conv1]); weights in the fragment-blocked layout
-bool bneck_frame_supported(int n, int h, int w, int cm, int cout, int stride);
+bool bneck_frame_supported(const PlanSwitches &sw, int n, int h, int w, int cm, int cout, int stride);
 pvr_status launch_pack_frag_weights(const void *w, void *out, int rows, int K, hipStream_t stream);
-pvr_status launch_bneck_frame(const void *t1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *res, void *y,
+pvr_status launch_bneck_frame(const PlanSwitches &sw, const void *t1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *res, void *y,
                               void *t2_out, int n, int phases, int dtype, hipStream_t stream, unsigned long long *stamps = nullptr,
                               const void *w1np = nullptr, const float *b1n = nullptr, void *t1n = nullptr, const void *w1fp = nullptr, const float *b1f = nullptr);
 // round 6: consecutive whole bottlenecks of the stage per frame in ONE launch (blocks[k + 1].res == blocks[k].y); odd workgroups start `stagger` x 8128 cycles late
@@ -59,14 +105,12 @@ pvr_status launch_bneck_frame_run(const BFBlk *blocks, int nblk, int n, int dtyp
 // bneck_frame64.hip (round 6): the whole bottleneck per frame with ONE wave per SIMD, 64 output channels x 13 pixel tiles per wave (half the LDS reads per MFMA)
 pvr_status launch_bneck_frame64(const void *w1p, const float *b1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *x, void *y, int n,
                                 int dtype, hipStream_t stream, unsigned long long *stamps);
-bool frame64_on();
-void set_frame64(int mode);
 long long bneck_frame64_launches();
 
 // conv_wfrag.hip: implicit GEMM in 112-pixel x 256-cout tiles with the weights read from L2 as MFMA fragments (layer4 at batch 256)
 bool conv_wfrag_supported(int64_t M, int64_t in_bytes, int cin, int cout, int kh, int kw, int pad, int act, int out_f32);
-bool conv_wfrag_preferred(int64_t M, int cin, int cout, int kh, int kw);
-pvr_status launch_conv_wfrag(const void *in, const void *wp, const float *bias, const void *res, void *out, int n, int h, int w, int cin, int cout,
+bool conv_wfrag_preferred(const PlanSwitches &sw, int64_t M, int cin, int cout, int kh, int kw);
+pvr_status launch_conv_wfrag(const PlanSwitches &sw, const void *in, const void *wp, const float *bias, const void *res, void *out, int n, int h, int w, int cin, int cout,
                              int kh, int kw, int stride, int pad, int act, int out_f32, int dtype, hipStream_t stream, float *pool_out = nullptr,
                              int64_t pool_stride = 0);
 
@@ -145,28 +189,6 @@ enum LaunchKind : uint8_t {
 };
 const char *launch_kind_name(int k);
 
-// A/B switches of the plan, read from the environment ONCE per encoder (pvr_encoder_create) - never on the forward path.  The ones marked
-// (live) can be changed on a finalized encoder with pvr_encoder_debug_set_switch; the others shape the plan and are fixed at finalize.
-struct PlanSwitches {
-    int pool_fuse = 1;        // PVR_POOL_FUSE (live): the pooled form of conv_wfrag for the trunk's last launch
-    int stem_u8 = 1;          // PVR_STEM_U8 (live): the fused stem reads uint8 frames itself when no resize is needed
-    int stem_lds = 1;         // PVR_STEM_LDS
-    int frame_front1 = 1;     // PVR_FRAME_FRONT1: layer3's per-frame launches carry their own conv1
-    int frame_next1 = 0;      // PVR_FRAME_NEXT1: ... carry the NEXT block's conv1 instead (measured slower)
-    int dual_ds = 1;          // PVR_DUAL_DS: conv3 & downsample of layer3.0 / layer4.0 as one two-operand launch
-    int chain_ds = 1;         // PVR_CHAIN_DS: layer1.0's downsample inside the chain
-    int chain_blocked = 1;    // PVR_CHAIN_BLOCKED: blocked hand-off between consecutive tails
-    int splitk = 1;           // PVR_SPLITK: planned split-K of the *_l4 head
-    int smallk_div = 4;       // PVR_SMALLK_DIV: K slices per block of the low-latency plan
-    int frame_run = 0;        // PVR_FRAME_RUN (live, opt-in: measured equal): consecutive whole-bottleneck frame launches (layer3.1 .. 3.5) as one launch
-    int frame_stagger = 0;    // PVR_FRAME_RUN_STAGGER: odd workgroups of that launch start this many x 8128 cycles late
-    int frame_min_n = 128;    // PVR_FRAME_MIN_N (live): frames per forward from which layer3's per-frame launches run as such
-    int stem_conv1 = 1;       // PVR_STEM_CONV1: layer1.0.conv1 runs inside the fused stem (no launch of its own; round 6)
-    int split16 = 1;          // PVR_SPLIT16: the fp32 stage / head of the compressed PVRs' parity plan on the 16-bit MFMA (0: f32-input MFMA)
-    int resid32 = 1;          // PVR_RESID32: fp32 residual stream of that plan (0: all-16-bit plan)
-    int tail_f32 = 1;         // PVR_TAIL_F32: its last trunk stage entirely in fp32
-    int fuse = 1;             // PVR_FUSE: the fused schedule (0: one launch per convolution; also pvr_encoder_debug_set_fusion)
-};
 
 }  // namespace pvr
 
@@ -187,7 +209,6 @@ struct pvr_encoder {
     u16 *d_stem_c1w = nullptr;                      // its weights as the stem's fragment image (stem_c1_pack)
     std::vector<uint8_t> kinds;                     // LaunchKind of launch i for a forward of nb frames: kinds[(nb - 1) * plan.size() + i] (resolve_kinds)
     size_t kinds_stride = 0;
-    int kinds_algo = -2;                            // conv_algo() the table was resolved under
     int *range_flags = nullptr;                     // pvr_encoder_check_range: per-launch "output holds inf / NaN" flags of the forward in progress (else null)
     bool last_pooled = false;                       // the last forward wrote the pooled rows from the last convolution: the B_F32 tap does not exist
     float *d_smallk[PVR_MAX_LANES] = {nullptr};     // the low-latency plan's fp32 partial planes, per lane (pvr_encoder_set_low_latency / first use of a lane: never in a forward)

@@ -12,7 +12,7 @@
 //   * Normalize((x/255-mean)/std) lives in the weights; the validity channel carries -sum(w*mean/std)
 //     per tap, so zero padding in the NORMALISED domain (what the reference pads) stays exact at the border.
 // Weights (64 x 224, 28 KB) stay in registers: 28 fragments per wave, reused over 7 pixel tiles.
-#include "common.h"
+#include "encoder_internal.h"
 
 namespace pvr {
 
@@ -792,21 +792,14 @@ pvr_status launch_stem(const void *img, const void *wgt, const float *bias, void
 
 // Fused form for frames that need no resize: uint8 NHWC frames [n][h][w][3] in, pooled stem output out; (top, left) = crop origin.
 // stem_pool_u8_ok: the geometry fits the kernel's 16-byte row DMA (the PVR_STEM_U8 / PVR_STEM_LDS switches are the encoder's: PlanSwitches).
-// PVR_STEM_REGPOOL=0: the LDS-tile pooling of rounds 3-5 (A/B; both forms are bit-identical).  Process-wide, read once.
-static bool stem_regpool() {
-    static const bool on = [] { const char *e = getenv("PVR_STEM_REGPOOL"); return !e || atoi(e) != 0; }();
-    return on;
-}
-static int g_stem_regpool_override = -1;                         // pvr_debug_set_stem_regpool: -1 environment, 0 / 1 forced (the A/B test flips it inside one process)
-void set_stem_regpool(int v) { g_stem_regpool_override = v; }
-static bool stem_regpool_now() { return g_stem_regpool_override >= 0 ? g_stem_regpool_override != 0 : stem_regpool(); }
+// sw.stem_regpool = 0 (PVR_STEM_REGPOOL=0): the LDS-tile pooling of rounds 3-5 (A/B; both forms are bit-identical).
 bool stem_pool_u8_ok(const void *frames, int h, int w, int top, int left) {
     // 16-byte row DMA: every source chunk aligned; the crop window inside the frame (an out-of-frame window would read wrong rows, not fail)
     return ((uintptr_t)frames & 15) == 0 && ((long long)h * w * 3) % 16 == 0 && (w * 3) % 16 == 0 && (left * 3) % 16 == 0 &&
            top >= 0 && left >= 0 && top + 224 <= h && left + 224 <= w && (long long)h * w * 3 < 0x7ffffff0ll;
 }
-// The stem can run layer1.0.conv1 itself (register-pooling form only): callers ask first
-bool stem_conv1_capable() { return stem_regpool_now(); }
+// The stem can run layer1.0.conv1 itself (register-pooling form, which runs only with the LDS tile): callers ask first
+bool stem_conv1_capable(const PlanSwitches &sw) { return sw.stem_regpool && sw.stem_lds; }
 
 // (64, 64) 16-bit weights of a 1 x 1 convolution in pvr_op_conv2d's layout -> the 8 KB image stem_pool_reg_kernel reads: fragment (cout tile i, K step ks) =
 // [k chunk][row & 15][8], rows permuted inside the two 32-row blocks (row 16 t + 4 a + c holds cout 8 a + 4 t + c); host side, once per plan
@@ -820,7 +813,7 @@ void stem_c1_pack(const u16 *w, u16 *img) {
                 }
 }
 
-pvr_status launch_stem_pool_u8(const uint8_t *frames, int n, int h, int w, int top, int left, const void *wgt, const float *bias, void *out,
+pvr_status launch_stem_pool_u8(const PlanSwitches &sw, const uint8_t *frames, int n, int h, int w, int top, int left, const void *wgt, const float *bias, void *out,
                                int dtype, hipStream_t stream, const void *c1_w, const float *c1_b, void *c1_t1, int c1_blk) {
     PVR_REQUIRE(stem_pool_u8_ok(frames, h, w, top, left), "stem (uint8 form): geometry h=%d w=%d top=%d left=%d not supported", h, w, top, left);
     static const int cus = [] { int v = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v > 0 ? v : 256; }();
@@ -829,7 +822,7 @@ pvr_status launch_stem_pool_u8(const uint8_t *frames, int n, int h, int w, int t
     const int ipb = n <= 8 ? 1 : (ipb_fit > STEM_IPB ? ipb_fit : STEM_IPB);
     dim3 grid(28, (n + ipb - 1) / ipb);
     const size_t lds = 5 * 112 * 128 + 2 * 28672 + 3 * 10240, lds_reg = 1024 + 2 * 28672 + 3 * 10240 + 2 * 2 * 56 * 128 + 8192 + 256;
-    PVR_REQUIRE(!c1_w || (stem_regpool_now() && c1_b && c1_t1), "stem: layer1.0.conv1 inside the stem needs the register-pooling form");
+    PVR_REQUIRE(!c1_w || (stem_conv1_capable(sw) && c1_b && c1_t1), "stem: layer1.0.conv1 inside the stem needs the register-pooling form");
     StemC1 c1; c1.w = (const u16 *)c1_w; c1.b = c1_b; c1.t1 = (u16 *)c1_t1; c1.blk = c1_blk;
     static DeviceOnce attr_done;          // per device: a second GPU of the process needs the attribute too
     if (attr_done.needed()) {
@@ -841,7 +834,7 @@ pvr_status launch_stem_pool_u8(const uint8_t *frames, int n, int h, int w, int t
     }
     U8Geo g;
     g.src = frames; g.pitch = w * 3; g.img_bytes = h * w * 3; g.off0 = (top * w + left) * 3;
-    if (stem_regpool_now()) {                                    // round 6: the max pool in registers (stem_pool_reg_kernel)
+    if (sw.stem_regpool) {                                       // round 6: the max pool in registers (stem_pool_reg_kernel)
         if (dtype == PVR_F16)
             hipLaunchKernelGGL((stem_pool_reg_kernel<true, true>), grid, dim3(512), lds_reg, stream, (const u16 *)nullptr, (const u16 *)wgt, bias, (u16 *)out, n, ipb, g, c1);
         else
@@ -857,12 +850,12 @@ pvr_status launch_stem_pool_u8(const uint8_t *frames, int n, int h, int w, int t
     return PVR_OK;
 }
 
-pvr_status launch_stem_pool(const void *img, const void *wgt, const float *bias, void *out, int n, int crop, int dtype,
+pvr_status launch_stem_pool(const PlanSwitches &sw, const void *img, const void *wgt, const float *bias, void *out, int n, int crop, int dtype,
                             hipStream_t stream, const void *c1_w, const float *c1_b, void *c1_t1, int c1_blk) {
     PVR_REQUIRE(crop == 224, "stem: crop must be 224 (got %d)", crop);
-    PVR_REQUIRE(!c1_w || (stem_regpool_now() && c1_b && c1_t1), "stem: layer1.0.conv1 inside the stem needs the register-pooling form");
+    PVR_REQUIRE(!c1_w || (stem_conv1_capable(sw) && c1_b && c1_t1), "stem: layer1.0.conv1 inside the stem needs the register-pooling form");
     StemC1 c1; c1.w = (const u16 *)c1_w; c1.b = c1_b; c1.t1 = (u16 *)c1_t1; c1.blk = c1_blk;
-    static const bool use_lds = [] { const char *e = getenv("PVR_STEM_LDS"); return !e || atoi(e) != 0; }();
+    const bool use_lds = sw.stem_lds != 0;
     // images per block: a handful of frames (online embedding) -> one image per block (28 n blocks); else as many as it takes for the
     // 28 x ceil(n / ipb) blocks to fit the chip in ONE round (n = 256 on 256 CUs: 9 block rows of 29 images = 252 blocks), never fewer
     // than STEM_IPB: a block's prologue (weights, first rows) costs about what 0.7 images do
@@ -871,7 +864,7 @@ pvr_status launch_stem_pool(const void *img, const void *wgt, const float *bias,
     const int ipb_fit = (n + yb - 1) / yb;
     const int ipb = n <= 8 ? 1 : (ipb_fit > STEM_IPB && use_lds ? ipb_fit : STEM_IPB);
     dim3 grid(28, (n + ipb - 1) / ipb);
-    if (use_lds && stem_regpool_now()) {                         // round 6: the max pool in registers (stem_pool_reg_kernel), padded 16-bit image in
+    if (use_lds && sw.stem_regpool) {                         // round 6: the max pool in registers (stem_pool_reg_kernel), padded 16-bit image in
         const size_t lds_reg = 1024 + 2 * 32768 + 2 * 2 * 56 * 128 + 8192 + 256;
         static DeviceOnce attr3_done;
         if (attr3_done.needed()) {

@@ -677,7 +677,7 @@ static pvr_status vit_forward_t(pvr_encoder *e, const uint8_t *frames, int n, in
         }
         PVR_LAUNCH_CHECK();
         // patch embedding GEMM -> fp32 [prow][W]
-        if ((s = launch_conv(v->A, v->w_patch, v->b_patch, nullptr, v->pe, v->zero, prow, 1, 1, K, W, 1, 1, 1, 0, 0, 1, dt, st))) return s;
+        if ((s = launch_conv(e->sw, v->A, v->w_patch, v->b_patch, nullptr, v->pe, v->zero, prow, 1, 1, K, W, 1, 1, 1, 0, 0, 1, dt, st))) return s;
         // tokens + positional embedding + ln_pre -> residual stream x0 (fp32)
         hipLaunchKernelGGL((layernorm_kernel<F16, WD>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *)nullptr, v->pe, v->cls,
                            v->pos, v->lnpre_w, v->lnpre_b, v->x0, (u16 *)nullptr, rows, T, v->eps, v->mae ? 0 : 1);
@@ -690,19 +690,19 @@ static pvr_status vit_forward_t(pvr_encoder *e, const uint8_t *frames, int n, in
         for (auto &b : v->blocks) {
             hipLaunchKernelGGL((layernorm_kernel<F16, WD>), dim3((rows + 3) / 4), dim3(256), 0, st, x, (const float *)nullptr,
                                (const float *)nullptr, (const float *)nullptr, b.ln1_w, b.ln1_b, (float *)nullptr, v->y, rows, T, v->eps, 1);
-            if ((s = launch_conv(v->y, b.w_qkv, b.b_qkv, nullptr, v->qkv, v->zero, rows, 1, 1, W, 3 * W, 1, 1, 1, 0, 0, 0, dt, st))) return s;
+            if ((s = launch_conv(e->sw, v->y, b.w_qkv, b.b_qkv, nullptr, v->qkv, v->zero, rows, 1, 1, W, 3 * W, 1, 1, 1, 0, 0, 0, dt, st))) return s;
             if (bi == 0 && stop == "qkv0") return PVR_OK;
             if ((s = launch_attention_any<F16>(v->qkv, v->att, T, v->TK, W, v->heads, nb, st))) return s;
             PVR_LAUNCH_CHECK();
             if (bi == 0 && stop == "att0") return PVR_OK;
             // x' = x + out_proj(att): fp32 residual in (bit1), fp32 out (bit0)
-            if ((s = launch_conv(v->att, b.w_out, b.b_out, x, xn, v->zero, rows, 1, 1, W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
+            if ((s = launch_conv(e->sw, v->att, b.w_out, b.b_out, x, xn, v->zero, rows, 1, 1, W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
             if (bi == 0 && stop == "res0") return PVR_OK;
             hipLaunchKernelGGL((layernorm_kernel<F16, WD>), dim3((rows + 3) / 4), dim3(256), 0, st, xn, (const float *)nullptr,
                                (const float *)nullptr, (const float *)nullptr, b.ln2_w, b.ln2_b, (float *)nullptr, v->y, rows, T, v->eps, 1);
-            if ((s = launch_conv(v->y, b.w_fc, b.b_fc, nullptr, v->hid, v->zero, rows, 1, 1, W, 4 * W, 1, 1, 1, 0, v->act, 0, dt, st))) return s;   // QuickGELU / GELU
+            if ((s = launch_conv(e->sw, v->y, b.w_fc, b.b_fc, nullptr, v->hid, v->zero, rows, 1, 1, W, 4 * W, 1, 1, 1, 0, v->act, 0, dt, st))) return s;   // QuickGELU / GELU
             if (bi == 0 && stop == "fc0") return PVR_OK;
-            if ((s = launch_conv(v->hid, b.w_proj, b.b_proj, xn, x, v->zero, rows, 1, 1, 4 * W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
+            if ((s = launch_conv(e->sw, v->hid, b.w_proj, b.b_proj, xn, x, v->zero, rows, 1, 1, 4 * W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
             if (stop == "block" + std::to_string(bi)) return PVR_OK;
             ++bi;
         }

@@ -7,10 +7,11 @@
 #include <algorithm>
 namespace pvr {
 // (the wave form lives in chain_wave.hip; this harness times the block form only)
-bool chain_wave_supported(int, int, int, bool) { return false; }
+bool chain_wave_supported(const PlanSwitches &, int, int, int, bool) { return false; }
+bool chain_wave128_supported(const PlanSwitches &, int, int, int, int64_t) { return false; }
 bool chain_wave_blocked_ok(int, int, int) { return false; }
-bool chain_wave_halo_enabled() { return false; }
-pvr_status launch_chain_wave(ChainP &, int, int, hipStream_t) { return PVR_ERR_INVALID; }
+pvr_status launch_chain_wave(ChainP &, int, int, int, hipStream_t) { return PVR_ERR_INVALID; }
+pvr_status launch_chain_wave128(ChainP &, int, int, hipStream_t) { return PVR_ERR_INVALID; }
 void set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
 const std::string &last_error() { static std::string s; return s; }
 }
@@ -32,7 +33,7 @@ int main(int argc, char **argv) {
     const int reps = 20;
     for (int rep = 0; rep < reps + 3; ++rep) {
         if (rep == 3) hipEventRecord(e0, 0);
-        if (launch_bottleneck_chain(t1, w2, b, w3, b, res, y, w1, b, t1n, n, h, w, cm, cmn, 1, PVR_BF16, 0, xds, wds)) { fprintf(stderr, "launch failed\n"); return 1; }
+        if (launch_bottleneck_chain(PlanSwitches{}, t1, w2, b, w3, b, res, y, w1, b, t1n, n, h, w, cm, cmn, 1, PVR_BF16, 0, xds, wds)) { fprintf(stderr, "launch failed\n"); return 1; }
     }
     hipEventRecord(e1, 0); hipDeviceSynchronize();
     float ms; hipEventElapsedTime(&ms, e0, e1);

@@ -859,12 +859,8 @@ def test_halo_conv3x3_is_bit_identical_to_conv_igemm(variant, dtype, n):
     fr = torch.from_numpy(synth.smooth_frames(40 + n, n, 150, 210)).cuda()
     m = HipResNet50(sd, variant, compute_dtype=dtype, max_batch=8)
     a = m(fr).clone()
-    L = _lib.lib()
-    L.pvr_debug_set_conv_algo(0)
-    try:
-        b = m(fr).clone()
-    finally:
-        L.pvr_debug_set_conv_algo(-1)
+    m.set_switch('conv_algo', 0)
+    b = m(fr).clone()
     assert torch.equal(a, b), float((a - b).abs().max())
     assert torch.isfinite(a).all() and float(a.std()) > 0
 
@@ -1060,28 +1056,25 @@ def test_frame64_tiling_is_bit_identical(dtype):
     from pvr_habitat_amd.embeddings import HipResNet50
     L = _lib.lib()
     sd = synth.resnet50_state_dict(12)
-    try:
-        for n in (256, 133):
-            fr = torch.from_numpy(synth.smooth_frames(90 + n, n, 64, 64)).cuda()
-            m = HipResNet50(sd, 'conv5', compute_dtype=dtype, max_batch=256)
-            _lib.check(L.pvr_debug_set_frame64(0))
-            c32 = L.pvr_debug_bneck_frame_launches(); c64 = L.pvr_debug_bneck_frame64_launches()
-            ref = m(fr).clone()
-            assert L.pvr_debug_bneck_frame_launches() - c32 == 5 and L.pvr_debug_bneck_frame64_launches() == c64
-            m.set_switch('frame_min_n', 100000)                      # separate launches (member convolutions)
-            sep = m(fr).clone()
-            m.set_switch('frame_min_n', 128)
-            assert torch.equal(ref, sep)
-            _lib.check(L.pvr_debug_set_frame64(1))
-            c64 = L.pvr_debug_bneck_frame64_launches()
-            for _ in range(3):
-                out = m(fr)
-                nd = int((out != ref).sum())
-                assert nd == 0, (n, nd, float((out - ref).abs().max()))
-            assert L.pvr_debug_bneck_frame64_launches() - c64 == 15
-            m.close()
-    finally:
-        _lib.check(L.pvr_debug_set_frame64(-1))
+    for n in (256, 133):
+        fr = torch.from_numpy(synth.smooth_frames(90 + n, n, 64, 64)).cuda()
+        m = HipResNet50(sd, 'conv5', compute_dtype=dtype, max_batch=256)
+        m.set_switch('frame64', 0)
+        c32 = L.pvr_debug_bneck_frame_launches(); c64 = L.pvr_debug_bneck_frame64_launches()
+        ref = m(fr).clone()
+        assert L.pvr_debug_bneck_frame_launches() - c32 == 5 and L.pvr_debug_bneck_frame64_launches() == c64
+        m.set_switch('frame_min_n', 100000)                      # separate launches (member convolutions)
+        sep = m(fr).clone()
+        m.set_switch('frame_min_n', 128)
+        assert torch.equal(ref, sep)
+        m.set_switch('frame64', 1)
+        c64 = L.pvr_debug_bneck_frame64_launches()
+        for _ in range(3):
+            out = m(fr)
+            nd = int((out != ref).sum())
+            assert nd == 0, (n, nd, float((out - ref).abs().max()))
+        assert L.pvr_debug_bneck_frame64_launches() - c64 == 15
+        m.close()
 
 
 @pytest.mark.parametrize('dtype', ['f16', 'bf16'])
@@ -1433,6 +1426,11 @@ def test_layer2_wave_form_equals_block_form(dtype, n, monkeypatch):
         assert torch.equal(emb, m(fr))
         ran = L.pvr_debug_chain_wave128_launches() - before
         assert ran == (9 if on == '1' else 0), ran                  # layer2.1 / 2.2 / 2.3, three forwards
+        if on == '1':                                               # the handle keeps the form it was built with (read once, at create)
+            monkeypatch.delenv('PVR_CHAIN_WAVE_L2')
+            before = L.pvr_debug_chain_wave128_launches()
+            assert torch.equal(m(fr), emb)
+            assert L.pvr_debug_chain_wave128_launches() > before
         m.close()
         got[key] = (t2, emb, names)
     assert got['wave'][2] == got['block'][2]
@@ -1448,7 +1446,6 @@ def test_stem_register_pooling_equals_the_lds_tile_form(dt, n):
     the pooled stem output and the embedding bit for bit, for the uint8-reading form (256 x 256 frames, every crop window) and the padded-image form
     (frames that are resized first).  x -> round(relu(x + b)) is monotone, so the maximum commutes with it."""
     from pvr_habitat_amd.embeddings import HipResNet50
-    L = _lib.lib()
     sd = synth.resnet50_state_dict(1, 'conv5')
     m = HipResNet50(sd, 'conv5', compute_dtype=dt, max_batch=max(8, n))
     cases = [(torch.from_numpy(synth.frames(90 + n, n, 256, 256)).cuda(), pos) for pos in (0, 1, 4)]          # uint8 form: no resize
@@ -1458,7 +1455,7 @@ def test_stem_register_pooling_equals_the_lds_tile_form(dt, n):
             m.set_crop(pos)
             got = {}
             for mode in (1, 0):
-                _lib.check(L.pvr_debug_set_stem_regpool(mode))
+                m.set_switch('stem_regpool', mode)
                 m.debug_stop_after('pool'); m(fr)
                 pool = m.tap('pool', n * 56 * 56 * 64).clone()
                 m.debug_stop_after('')
@@ -1467,7 +1464,6 @@ def test_stem_register_pooling_equals_the_lds_tile_form(dt, n):
             assert torch.equal(got[1][0], got[0][0]), ('pool', pos, int((got[1][0] != got[0][0]).sum()))
             assert torch.equal(got[1][1], got[0][1]), ('embedding', pos, int((got[1][1] != got[0][1]).sum()))
     finally:
-        _lib.check(L.pvr_debug_set_stem_regpool(-1))
         m.set_crop(0)
         m.close()
 
@@ -1477,24 +1473,27 @@ def test_layer1_conv1_inside_the_stem(variant, dt, n, monkeypatch):
     """Round 6: layer1.0.conv1 (1 x 1, 64 -> 64 on the pooled stem output) runs inside the fused stem - seven waves take one 16-pixel MFMA tile each of the block's
     pooled tile in LDS - instead of as a launch of its own: one launch and one read of the pooled tensor fewer, t1 in the layout the tail behind it reads (blocked).
     Against the plan with the separate launch (PVR_STEM_CONV1=0): layer1's output and the embedding bit for bit (same K order, same rounding), for frames the stem
-    reads as uint8 and for frames that are resized first; with a debug stop (the stem form that cannot carry the convolution) the forward launches it itself."""
+    reads as uint8 and for frames that are resized first; with a debug stop (the stem form that cannot carry the convolution) the forward launches it itself.
+    PVR_STEM_LDS=0 (round 2's stem kernel, which cannot carry it either): the plan still has no launch of its own for it, so the forward launches it."""
     from pvr_habitat_amd.embeddings import HipResNet50
     sd = synth.resnet50_state_dict(4, variant)
     frames = [torch.from_numpy(synth.frames(60 + n, n, 256, 256)).cuda(), torch.from_numpy(synth.smooth_frames(61 + n, n, 120, 160)).cuda()]
-    got = {}
-    for key, on in (('inside', '1'), ('launch', '0')):
-        monkeypatch.setenv('PVR_STEM_CONV1', on)
-        m = HipResNet50(sd, variant, compute_dtype=dt, max_batch=max(8, n))
-        names = m.op_names()
-        res = []
-        for fr in frames:
-            m.debug_stop_after('layer1'); m(fr)
-            res.append(m.tap('layer1', n * 56 * 56 * 256).clone())
-            m.debug_stop_after('')
-            res.append(m(fr).clone())
-        m.close()
-        got[key] = (names, res)
-    assert 'layer1.0.conv1' in got['launch'][0] and 'layer1.0.conv1' not in got['inside'][0] and len(got['inside'][0]) == len(got['launch'][0]) - 1
-    for a, b in zip(got['inside'][1], got['launch'][1]):
-        assert torch.isfinite(b).all() and float(b.abs().max()) > 0
-        assert torch.equal(a, b), (int((a != b).sum()), float((a - b).abs().max()))
+    for lds in ('1', '0'):
+        monkeypatch.setenv('PVR_STEM_LDS', lds)
+        got = {}
+        for key, on in (('inside', '1'), ('launch', '0')):
+            monkeypatch.setenv('PVR_STEM_CONV1', on)
+            m = HipResNet50(sd, variant, compute_dtype=dt, max_batch=max(8, n))
+            names = m.op_names()
+            res = []
+            for fr in frames:
+                m.debug_stop_after('layer1'); m(fr)
+                res.append(m.tap('layer1', n * 56 * 56 * 256).clone())
+                m.debug_stop_after('')
+                res.append(m(fr).clone())
+            m.close()
+            got[key] = (names, res)
+        assert 'layer1.0.conv1' in got['launch'][0] and 'layer1.0.conv1' not in got['inside'][0] and len(got['inside'][0]) == len(got['launch'][0]) - 1
+        for a, b in zip(got['inside'][1], got['launch'][1]):
+            assert torch.isfinite(b).all() and float(b.abs().max()) > 0
+            assert torch.equal(a, b), (lds, int((a != b).sum()), float((a - b).abs().max()))

@@ -1,0 +1,44 @@
+"""CPU checks of the encoder's switch contract: every A/B switch of the encoder path is read from the environment in ONE place
+(encoder.hip: read_switches, into PlanSwitches) - no kernel file reads it on its own, at first use or per launch."""
+import os
+import re
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'pvr_habitat_amd', 'csrc')
+# getenv outside the encoder's switch table: roctx ranges, host-backend threads, the policy handle's switches, an experiment kernel's stamps
+ALLOWED = {'api.hip', 'host_encoder.hip', 'host_math.h', 'policy.hip', 'conv_w4.hip'}
+
+
+def _src(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def _body(src, head):
+    """text of the brace block that follows the first occurrence of `head`"""
+    i = src.index('{', src.index(head))
+    depth = 0
+    for j in range(i, len(src)):
+        depth += {'{': 1, '}': -1}.get(src[j], 0)
+        if depth == 0:
+            return src[i:j + 1]
+    raise AssertionError('unbalanced braces after ' + head)
+
+
+def test_encoder_path_reads_the_environment_only_in_read_switches():
+    hits = {}
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith(('.hip', '.h')):
+            n = sum('getenv' in line for line in _src(name).splitlines())
+            if n:
+                hits[name] = n
+    assert set(hits) - ALLOWED == {'encoder.hip'}, hits
+    assert hits['encoder.hip'] == 1, hits
+    assert 'getenv' in _body(_src('encoder.hip'), 'void read_switches(PlanSwitches &sw)')
+
+
+def test_plan_switches_is_the_one_list():
+    """each member of PlanSwitches names its variable and default in its declaration, and read_switches reads exactly those"""
+    decl = _body(_src('encoder_internal.h'), 'struct PlanSwitches')
+    members = {m: (env, int(d)) for m, d, env in re.findall(r'int (\w+) = (-?\d+);\s*// (PVR_\w+)', decl)}
+    reads = {m: (env, int(d)) for m, env, d in re.findall(r'sw\.(\w+) = get\("(PVR_\w+)", (-?\d+)\)', _body(_src('encoder.hip'), 'void read_switches'))}
+    assert len(members) == len(re.findall(r'^\s*int ', decl, re.M)) and members == reads, (set(members.items()) ^ set(reads.items()))
