@@ -7,11 +7,14 @@ ResNet50 MoCo-v2 frozen, 256x256 uint8 frames, batch 256, bf16, synthetic frames
 batch of 256 frames that is already resident in HBM.  Frames shard across ranks with no collective
 (SURVEY 8e): weak scaling, value = frames all ranks embedded / max-over-ranks time.
 
-  python bench.py                      (N = 1, 320 timed steps ~ 1 s over a 4096-frame pool, + parity / f16 / PCIe / ViT / BC legs)
+  python bench.py                      (N = 1, 320 timed steps ~ 1 s over a 4096-frame pool: the headline leg alone)
   python bench.py --gpus 1 --steps 20 --warmup 3
   python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   (+ DIR/embeddings.npy: what the last timed step computed)
+  python bench.py --full               (+ one-lane / bf16 / roofline / parity / CPU baseline / PNG / PCIe / e2e / 5-crop / ViT / BC legs)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N --steps K --warmup W        (no launcher: starts that torch.distributed.run command itself as a child process)
+
+Without --full a run sets up, warms up, times the steps, writes --dump-outputs and prints the headline line: nothing else.
 """
 import argparse
 import ctypes as C
@@ -793,6 +796,19 @@ def self_launch(n):
         return 3
 
 
+def finish(line, dist, failed=None):
+    """rank 0 (the only rank with a line) prints it; every rank leaves the process group; a failed leg exits non-zero once the line is out"""
+    if line is not None:
+        print(json.dumps(line), flush=True)
+    if dist is not None:
+        try:
+            dist.destroy_process_group()
+        except Exception:
+            pass
+    if failed is not None:
+        sys.exit(3)                                             # the headline line is out; the launcher still sees the failed leg
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -807,6 +823,11 @@ def main():
     ap.add_argument('--chunk', type=int, default=0)
     ap.add_argument('--lanes', type=int, default=2, help='batches in flight per GPU (1 = strictly one forward at a time)')
     ap.add_argument('--pool', type=int, default=4096, help='distinct frames resident in HBM, cycled batch by batch (SURVEY 8d frame pool)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline leg, run everything else the line can carry: the one-lane leg, the other 16-bit leg, the roofline passes, '
+                         'parity against the fp32 CPU oracle, the CPU baseline and the PNG / PCIe / e2e / 5-crop / ViT / BC legs (N = 1), the '
+                         'data-parallel finetune leg (N > 1); the --no-* options below leave parts of it out.  Without --full a run does only '
+                         'what the headline needs')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-bc', action='store_true', help='skip the BC steps/sec legs')
     ap.add_argument('--no-pcie', action='store_true', help='skip the PCIe-inclusive streaming leg')
@@ -819,14 +840,16 @@ def main():
     ap.add_argument('--no-uber', action='store_true', help='skip the configs[4] leg (5-crop moco_aug_uber_345 streamed to the host)')
     ap.add_argument('--no-dp', action='store_true', help='skip the data-parallel finetune leg (N > 1)')
     ap.add_argument('--no-fuse', action='store_true', help='one launch per convolution (A/B against the fused bottleneck tails)')
-    ap.add_argument('--per-op', action='store_true', help='print per-launch ms / TFLOP/s of one chunk to stderr')
-    ap.add_argument('--dump-plan', default='', help='write the launch plan of the timed model (names in launch order) to this JSON file; '
+    ap.add_argument('--per-op', action='store_true', help='print per-launch ms / TFLOP/s of one chunk to stderr (--full)')
+    ap.add_argument('--dump-plan', default='', help='(--full) write the launch plan of the timed model (names in launch order) to this JSON file; '
                     'scripts/pmc_summary.py stores it next to the PMC bytes so that a later run can tell whether they still describe its plan')
     ap.add_argument('--dump-outputs', default='', metavar='DIR',
                     help='after the timed headline leg, write what its last step computed (the fp32 embeddings a caller of forward_into receives) '
                          'to DIR/embeddings.npy (rank 0; at most 64 MB, a fixed seeded row sample beyond that).  The frames and weights are '
                          'seeded, so two builds run with the same arguments can be compared output for output')
     args = ap.parse_args()
+    if (args.per_op or args.dump_plan) and not args.full:
+        ap.error('--per-op and --dump-plan report on the roofline passes, which only --full runs')
 
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
@@ -872,7 +895,7 @@ def main():
     # resident, ten back-to-back 1 s legs give bf16 80.3 k and f16 79.3 k frames/s, flat).
     models = {args.dtype: make_model(args.dtype, args.lanes)}
     alt = {'f16': 'bf16', 'bf16': 'f16'}.get(args.dtype)        # the other 16-bit storage type, timed at the same length beside the headline
-    if args.no_f16:
+    if args.no_f16 or not args.full:
         alt = None
     if alt:
         models[alt] = make_model(alt, args.lanes)
@@ -912,15 +935,16 @@ def main():
         el = time.perf_counter() - t0
         el, el_fastest = rank_spread(dist, el)                   # MAX over ranks is the leg's time; the fastest rank's beside it (stragglers)
         spread.append((el, el_fastest))
-        for o_ in outs:
-            assert torch.isfinite(o_).all()
-        # the last batch each lane embedded, against a fresh forward of the same frames: what was timed produced these embeddings
-        last = [(steps - 1 - j) for j in range(lanes)]
-        for j, i in enumerate(last):
-            chk = torch.empty_like(outs[0])
-            model.forward_into(batches[i % len(batches)], chk, lane=0)
-            torch.cuda.synchronize()
-            assert torch.equal(chk, outs[i % lanes]), 'lane %d result differs from a sequential forward' % (i % lanes)
+        if args.full:
+            for o_ in outs:
+                assert torch.isfinite(o_).all()
+            # the last batch each lane embedded, against a fresh forward of the same frames: what was timed produced these embeddings
+            last = [(steps - 1 - j) for j in range(lanes)]
+            for j, i in enumerate(last):
+                chk = torch.empty_like(outs[0])
+                model.forward_into(batches[i % len(batches)], chk, lane=0)
+                torch.cuda.synchronize()
+                assert torch.equal(chk, outs[i % lanes]), 'lane %d result differs from a sequential forward' % (i % lanes)
         return model, el, lanes, outs[(steps - 1) % lanes]
 
     # every leg is timed once: exactly `steps` forwards between barrier + synchronize
@@ -928,6 +952,30 @@ def main():
     head_spread = spread[:1]                                  # the headline leg's (slowest, fastest) rank pair
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, {'embeddings': last_out})
+    chunk = args.chunk if args.chunk else args.batch
+    line = None
+    if rank == 0:
+        fps = world * args.steps * args.batch / el
+        line = {
+            'metric': 'frames/sec embedded (ResNet50, 256x256)', 'value': round(fps, 1), 'unit': 'frames/s',
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(el / args.steps * 1e3, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
+            'timed_region_s': round(el, 3),
+            'config': {'workload': 'configs[1]: ResNet50 (MoCo-v2 layout) frozen, %dx%d uint8 frames resident in HBM, batch %d/GPU, '
+                                   'random-init synthetic weights, %s storage / MFMA inputs with fp32 accumulation%s'
+                                   % (args.frame, args.frame, args.batch, args.dtype,
+                                      ' (the product default, inside the 1e-3 parity bound; configs[1] names bf16%s)'
+                                      % (': the `bf16` leg of the same length is in this line' if alt else '') if args.dtype == 'f16' else ''),
+                       'global_batch': world * args.batch, 'frame': args.frame, 'chunk': chunk, 'batches_in_flight': lanes,
+                       'frame_pool': '%d distinct frames per GPU resident in HBM, cycled batch by batch (every step embeds a different batch)' % n_pool,
+                       'parallelism': 'frame shards, no collective (dp%d)' % world},
+            'per_rank_ms_per_step': {'max': round(head_spread[0][0] / args.steps * 1e3, 3), 'min': round(head_spread[0][1] / args.steps * 1e3, 3),
+                                     'note': 'slowest / fastest rank of the headline leg; value uses the slowest'},
+            'tflops_whole_net': round(fps * GFLOP_PER_FRAME / 1e3, 2),
+        }
+    if not args.full:
+        finish(line, dist)
+        return
     # the same leg with ONE batch in flight (the headline keeps `--lanes` batches in flight; the roofline object below is a one-lane measurement)
     el_one = embed_leg(args.dtype, args.steps, 1, 1)[1] if lanes > 1 else el
     # the parity mode at the headline configuration, back to back with the headline leg (all ranks run it: weak scaling)
@@ -945,7 +993,6 @@ def main():
         torch.cuda.synchronize()
 
     # roofline of the dominant kernel family (implicit-GEMM convolutions): HIP events between launches on the launch stream
-    chunk = args.chunk if args.chunk else args.batch
     cap = 128
     op_ms = (C.c_float * cap)(); op_fl = (C.c_double * cap)(); n_ops = C.c_int32()
     conv_ms, conv_fl, other_ms, bound_ms = 0.0, 0.0, 0.0, 0.0
@@ -1014,24 +1061,8 @@ def main():
     peak = PEAK_F32_TFLOPS if args.dtype == 'f32' else PEAK_BF16_TFLOPS
     barrier()
 
-    line = None
     if rank == 0:
-        fps = world * args.steps * args.batch / el
-        line = {
-            'metric': 'frames/sec embedded (ResNet50, 256x256)', 'value': round(fps, 1), 'unit': 'frames/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(el / args.steps * 1e3, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': args.dtype, 'data': 'synthetic',
-            'timed_region_s': round(el, 3),
-            'config': {'workload': 'configs[1]: ResNet50 (MoCo-v2 layout) frozen, %dx%d uint8 frames resident in HBM, batch %d/GPU, '
-                                   'random-init synthetic weights, %s storage / MFMA inputs with fp32 accumulation%s'
-                                   % (args.frame, args.frame, args.batch, args.dtype,
-                                      ' (the product default, inside the 1e-3 parity bound; configs[1] names bf16: the `bf16` leg of the same length is in this line)' if args.dtype == 'f16' else ''),
-                       'global_batch': world * args.batch, 'frame': args.frame, 'chunk': chunk, 'batches_in_flight': lanes,
-                       'frame_pool': '%d distinct frames per GPU resident in HBM, cycled batch by batch (every step embeds a different batch)' % n_pool,
-                       'parallelism': 'frame shards, no collective (dp%d)' % world},
-            'per_rank_ms_per_step': {'max': round(head_spread[0][0] / args.steps * 1e3, 3), 'min': round(head_spread[0][1] / args.steps * 1e3, 3),
-                                     'note': 'slowest / fastest rank of the headline leg; value uses the slowest'},
-            'tflops_whole_net': round(fps * GFLOP_PER_FRAME / 1e3, 2),
+        line.update({
             'one_lane': {'value': round(world * args.steps * args.batch / el_one, 1), 'unit': 'frames/s', 'ms_per_step': round(el_one / args.steps * 1e3, 3),
                          'note': 'the same %d-step leg with one batch in flight per GPU (strictly one forward at a time)' % args.steps},
             'roofline': {'bound': 'mfma', 'achieved': round(achieved, 2), 'peak': peak, 'unit': 'TFLOP/s',
@@ -1055,7 +1086,7 @@ def main():
                          'two_roof': None if bound_ms == 0.0 else {'bound_ms_per_chunk': round(bound_ms / reps, 3), 'frac': round(bound_ms / conv_ms, 4),
                                                                   'note': 'per launch max(flops / %.0f TFLOP/s, algorithmic bytes / 8 TB/s), summed, / measured conv_ms_per_chunk' % PEAK_BF16_TFLOPS},
                          'stages': stages},
-        }
+        })
         # parity of what was timed: the same model handle / dtype vs the fp32 CPU oracle (north-star tolerance 1e-3 relative fp32)
         ps = parity_stats(model, sd, pool_np)
         line['parity_rel_l2'] = round(ps['rel_l2'], 6)
@@ -1145,15 +1176,7 @@ def main():
                 line['bc_finetune_dp'] = {'error': dp_failed}
         done.set()
     guard.close()
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if dist is not None:
-        try:
-            dist.destroy_process_group()
-        except Exception:
-            pass
-    if dp_failed is not None:
-        sys.exit(3)                                             # the headline line is out; the launcher still sees the failed leg
+    finish(line, dist, dp_failed)
 
 
 if __name__ == '__main__':

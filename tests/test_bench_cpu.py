@@ -1,6 +1,8 @@
-"""bench.py's host-side helpers (no GPU): the --dump-outputs writer."""
+"""bench.py's host-side helpers (no GPU): the --dump-outputs writer, the options that only --full serves."""
 import importlib.util
 import os
+import subprocess
+import sys
 
 import numpy as np
 import torch
@@ -31,3 +33,12 @@ def test_dump_outputs_stays_under_64_mb_with_a_fixed_row_sample(tmp_path):
     assert idx == sorted(idx) and len(set(idx)) == len(idx)
     s = np.load(str(tmp_path / 'a' / 'small.npy'))
     assert s.dtype == np.float64 and np.array_equal(s, small.numpy())                      # small outputs are written whole
+
+
+def test_roofline_options_are_refused_without_full():
+    """--per-op and --dump-plan come from the roofline passes, which only --full runs: a plain run refuses them before it touches a GPU
+    instead of ignoring them."""
+    for extra in (['--per-op'], ['--dump-plan', 'plan.json']):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '4'] + extra, capture_output=True, text=True, timeout=300,
+                             cwd=ROOT)
+        assert out.returncode == 2 and '--full' in out.stderr, out.stderr[-2000:]

@@ -1,10 +1,12 @@
 """bench.py prints ONE JSON line with the driver's contract (metric / value / unit / n_gpus / steps / warmup / ms_per_step /
-higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the `roofline` object; the N > 1 path (one process
-per GPU, barrier + MAX over ranks) is exercised with two ranks sharing the one test GPU (PVR_BENCH_ONE_GPU=1, gloo)."""
+higher_is_better / scaling / vs_baseline / dtype / data / config.workload); with --full the line adds the `roofline` object and the other
+legs.  The N > 1 path (one process per GPU, barrier + MAX over ranks) is exercised with two ranks sharing the one test GPU
+(PVR_BENCH_ONE_GPU=1, gloo)."""
 import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -12,7 +14,7 @@ import torch
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason='needs an MI355X')]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FAST = ['--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-bc', '--no-vit', '--no-pcie', '--png-traj', '3']
+FAST = ['--full', '--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-bc', '--no-vit', '--no-pcie', '--png-traj', '3']
 
 
 def _check(line, n):
@@ -64,6 +66,38 @@ def test_bench_line_single_gpu(tmp_path):
     assert os.listdir(dump) == ['embeddings.npy']
     e = np.load(os.path.join(dump, 'embeddings.npy'))
     assert e.dtype == np.float32 and e.shape == (256, 2048) and np.isfinite(e).all() and float(e.std()) > 0
+
+
+def test_plain_bench_line_is_the_headline_alone(tmp_path):
+    """Without --full: set-up, warm-up, the timed steps, --dump-outputs and the headline's line - no other leg, pass or check - and at most
+    30 s of wall time besides the warm-up and timed steps.  The dump is what the last timed step computed."""
+    dump = str(tmp_path / 'outputs')
+    steps, warmup = 20, 3
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup),
+                          '--dump-outputs', dump], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['metric'] == 'frames/sec embedded (ResNet50, 256x256)' and d['unit'] == 'frames/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f16' and d['n_gpus'] == 1 and d['steps'] == steps and d['warmup'] == warmup and d['value'] > 8000
+    assert abs(d['value'] * d['ms_per_step'] * 1e-3 - 256) < 0.5                     # frames/s x s/step = the 256-frame batch
+    full_only = {'one_lane', 'roofline', 'parity', 'parity_rel_l2', 'bf16', 'cpu_baseline', 'png_source', 'pcie_inclusive', 'value_pcie_inclusive',
+                 'save_embedded_obs_e2e', 'uber5crop', 'vit', 'bc', 'bc_finetune'}
+    assert not full_only & set(d), sorted(full_only & set(d))
+    assert wall - (steps + warmup) * d['ms_per_step'] * 1e-3 < 30.0, wall
+    # the last timed step embedded batch (steps - 1) of the seeded 16-batch pool: a fresh model of the same weights gives the same rows
+    from pvr_habitat_amd import synth
+    from pvr_habitat_amd.embeddings import HipResNet50
+    i = (steps - 1) % 16
+    m = HipResNet50(synth.resnet50_state_dict(1, 'conv5'), 'conv5', compute_dtype='f16', max_batch=256)
+    ref = m(torch.from_numpy(synth.frames(1, (i + 1) * 256, 256, 256)[i * 256:]).cuda()).cpu().numpy()
+    m.close()
+    e = np.load(os.path.join(dump, 'embeddings.npy'))
+    assert os.listdir(dump) == ['embeddings.npy'] and e.dtype == np.float32 and e.shape == (256, 2048)
+    assert np.array_equal(e, ref)
 
 
 def test_bench_line_two_ranks_on_one_gpu():
