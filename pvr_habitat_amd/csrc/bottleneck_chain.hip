@@ -653,11 +653,12 @@ int chain_row_source(int row) { return (row & ~31) + 8 * ((row >> 2) & 3) + 4 * 
 pvr_status launch_bottleneck_chain(const PlanSwitches &sw, const void *t1, const void *w2, const float *b2, const void *w3p, const float *b3, const void *res,
                                    void *y, const void *w1np, const float *b1n, void *t1n, int n, int h, int w, int cm, int cmn,
                                    int stride, int dtype, hipStream_t stream, const void *xds, const void *wdsp, const void *w3pb, const void *wdspb,
-                                   int wave, int in_blk, int out_blk, const void *wpk) {
+                                   int wave, int in_blk, int out_blk, const void *wpk, int y_s2) {
     // wave: 1 run the wave form (chain_wave.hip; the plan decided with chain_uses_wave_form), 2 the layer2 wave form (chain_wave128.hip; wpk: its packed
     // weights); w3pb / wdspb: blocked copies of w3p / wdsp for the former; in_blk / out_blk: blocked activations between two wave-form launches
     // (block form: out_blk bit 1 = t1' blocked too, for a layer2 wave-form launch that follows)
     // xds != null: `res` is unused; the identity branch is Wd . x (x = xds: [pixels][64], wdsp: [4Cm][64] row-permuted) and b3 = b3 + bd
+    // y_s2 (wave form): y holds only the pixels of even row and column, as an (n, h / 2, w / 2, 4 Cm) tensor (ChainP::y_s2)
     PVR_REQUIRE(chain_supported(cm, cmn), "bottleneck chain: unsupported widths Cm=%d next=%d", cm, cmn);
     PVR_REQUIRE(t1 && w2 && b2 && w3p && b3 && (res || xds) && y && (cmn == 0 || (w1np && b1n && t1n)), "bottleneck chain: null argument");
     PVR_REQUIRE(!xds || (wdsp && chain_ds_supported(cm, cmn, 64, stride)), "bottleneck chain with downsample: unsupported shape");
@@ -680,9 +681,10 @@ pvr_status launch_bottleneck_chain(const PlanSwitches &sw, const void *t1, const
     }
     if (wave) {
         PVR_REQUIRE(chain_wave_supported(sw, cm, cmn, stride, xds != nullptr), "bottleneck chain: no wave form for Cm=%d next=%d stride=%d", cm, cmn, stride);
-        p.w3b = (const u16 *)w3pb; p.wdsb = (const u16 *)wdspb; p.in_blk = in_blk; p.out_blk = out_blk;
+        p.w3b = (const u16 *)w3pb; p.wdsb = (const u16 *)wdspb; p.in_blk = in_blk; p.out_blk = out_blk; p.y_s2 = y_s2;
         return launch_chain_wave(p, cmn, sw.chain_wave_halo, dtype, stream);
     }
+    PVR_REQUIRE(!y_s2, "bottleneck chain: y_s2 is a store of the wave form");
     PVR_REQUIRE(!(in_blk || out_blk) || M % 16 == 0, "bottleneck chain: the blocked layout needs a multiple of 16 pixels");
     p.res_blk = xds ? 0 : in_blk; p.y_blk = out_blk & 1;       // block form: y / the residual travel blocked; t1 stays NHWC, t1' too unless a layer2 wave form follows
     p.t_blk = (out_blk & 2) && cmn > 0;

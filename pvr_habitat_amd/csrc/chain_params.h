@@ -25,6 +25,9 @@ struct ChainP {
     const u16 *wpk = nullptr;
     unsigned wpk_bytes = 0;
     int t_blk = 0;
+    // wave form, NHWC y: y_s2 = 1 stores only the pixels of even row and column, at (n, h / 2, w / 2) of an (N, H / 2, W / 2, 4 Cm) tensor (the only
+    // reader is a 1 x 1 stride-2 downsample; the next conv1 inside the launch still sees every pixel)
+    int y_s2 = 0;
 };
 
 bool chain_supported(int cm, int cmn);
@@ -35,12 +38,13 @@ pvr_status launch_bottleneck_chain(const PlanSwitches &sw, const void *t1, const
                                    void *y, const void *w1np, const float *b1n, void *t1n, int n, int h, int w, int cm, int cmn,
                                    int stride, int dtype, hipStream_t stream, const void *xds = nullptr, const void *wdsp = nullptr,
                                    const void *w3pb = nullptr, const void *wdspb = nullptr, int wave = 0, int in_blk = 0, int out_blk = 0,
-                                   const void *wpk = nullptr);
+                                   const void *wpk = nullptr, int y_s2 = 0);
 
 
 // chain_wave.hip: the barrier-free form (stride-1 blocks with Cm = 64)
 bool chain_wave_supported(const PlanSwitches &sw, int cm, int cmn, int stride, bool ds);
 bool chain_wave_blocked_ok(int cmn_first, int h, int w);
+bool chain_wave_y_s2_ok(int cm, int cmn, int h, int w, int out_blk);   // an instance with the y_s2 store exists for this tail
 pvr_status launch_chain_wave(ChainP &p, int cmn, int halo, int dtype, hipStream_t stream);
 
 // chain_wave128.hip: the wave form of layer2's stride-1 tails (Cm = 128): wave-owned pixels, weights streamed through an LDS ring

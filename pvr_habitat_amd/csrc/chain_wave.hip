@@ -113,7 +113,26 @@ struct CwTile {
     int xs[2];      // DS: byte offset of the lane's piece of the block input x (always NHWC: the stem writes it)
 };
 
-template <int CMN, bool INB, bool OUTB>
+// CY (y_s2): y only at the pixels of even row and column, to pixel (n, h / 2, w / 2) of an (N, 28, 28, 256) tensor (layer1: 56 x 56, the launcher
+// checks).  A lane stores the same 16 bytes of the lines of pixels m and m + 8 (cw_f2m_pair); both are kept only when they share a row, and then
+// m + 8 is 4 compact pixels (2048 bytes) behind m.  Returned: the byte offset for m's line (m + 8's less 2048 when only that one is kept) | bit 0:
+// store m's line | bit 1: store m + 8's line.  (The eight lanes of a line share the pixel: a skipped pixel skips whole 128-byte lines.)
+constexpr int CW_YS2_HW = 56;
+__device__ __forceinline__ int cw_y_s2_offset(int m, int c16, int M) {
+    constexpr int S = CW_YS2_HW;
+    int f = 0, off = 0;
+#pragma unroll
+    for (int e = 1; e >= 0; --e) {
+        const int me = m + 8 * e, q = me / S, wo = me - q * S, ho = q % S, ni = q / S;
+        if (me < M && !((wo | ho) & 1)) {
+            f |= 1 << e;
+            off = ((ni * (S / 2) + (ho >> 1)) * (S / 2) + (wo >> 1)) * 512 - 2048 * e + c16;
+        }
+    }
+    return f ? (off | f) : 0;
+}
+
+template <int CMN, bool INB, bool OUTB, bool CY = false>
 __device__ __forceinline__ void cw_setup(CwTile &a, int m0, int lane, int M, int H, int W) {
     const int fr = lane & 15, fq = lane >> 4, lp = lane >> 2, lc = (lane & 3) ^ ((lane >> 3) & 3);   // NHWC lanes: row lp, chunk lc (cw_m2f)
     a.hb = ((m0 >> 4) - 4) * 2048 + fq * 256 + fr * 16;
@@ -139,14 +158,15 @@ __device__ __forceinline__ void cw_setup(CwTile &a, int m0, int lane, int M, int
         a.yi[j] = INB ? blk * 8192 + fq * 256 + fr * 16 : (m0 + 16 * j + lp) * 512 + lc * 16;
         // NHWC outputs leave as FULL 128-byte lines (cw_f2m_pair): lane l stores rows (l >> 3) and (l >> 3) + 8, chunk (l & 7) ^ (l >> 3) of a 64-channel group
         a.yo[j] = OUTB ? blk * 8192 + fq * 256 + fr * 16 : (m0 + 16 * j + (lane >> 3)) * 512 + (((lane & 7) ^ (lane >> 3)) << 4);
+        if constexpr (CY) a.yo[j] = cw_y_s2_offset(m0 + 16 * j + (lane >> 3), ((lane & 7) ^ (lane >> 3)) << 4, M);
         a.to[j] = OUTB ? blk * (CMN * 32) + fq * 256 + fr * 16 : (m0 + 16 * j + (lane >> 3)) * (CMN * 2) + (((lane & 7) ^ (lane >> 3)) << 4);
     }
 }
 
 // INB / OUTB: t1 + residual / y + t1' in the blocked layout; HALO (with INB, W = 56): conv2's pixels from halo registers
 // XD: conv2 K-steps of pixel pieces in flight (ring forms; 8 VGPRs each); RD: residual half-groups in flight (8 VGPRs each);
-// WD: half-groups of W3 / Wd pieces in flight when they come from L2 (16 VGPRs each)
-template <int CMN, bool F16, bool DS, bool W3G, bool INB, bool OUTB, bool HALO, int XD, int RD, int WD>
+// WD: half-groups of W3 / Wd pieces in flight when they come from L2 (16 VGPRs each); CY: y_s2 (NHWC y at the stride-2 pixels only: cw_y_s2_offset)
+template <int CMN, bool F16, bool DS, bool W3G, bool INB, bool OUTB, bool HALO, int XD, int RD, int WD, bool CY>
 __global__ __launch_bounds__(512, 2) void chain_wave_kernel(ChainP p) {
     typedef typename HT<F16>::V8 V8;
     constexpr int WW = 56, HB = 10;                        // HALO: image width (the launcher checks), 16-pixel blocks m0 / 16 - 4 .. + 5 cover m0 - 57 .. m0 + 88
@@ -158,6 +178,7 @@ __global__ __launch_bounds__(512, 2) void chain_wave_kernel(ChainP p) {
     constexpr int YH = INB ? 1024 : 64;                    // byte step of a half-group (32 channels) in the residual
     static_assert(XD >= 1 && XD <= NK && RD >= 1 && RD <= NH && NH % RD == 0 && WD >= 1 && WD <= NH, "prefetch depths (the residual ring must close over a tile)");
     static_assert(!HALO || INB, "the halo form reads the blocked layout");
+    static_assert(!CY || !OUTB, "y_s2 is an NHWC store");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
@@ -212,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void chain_wave_kernel(ChainP p) {
     const int Wb = p.W * 128;
 
     CwTile cur, nxt;
-    cw_setup<CMN, INB, OUTB>(cur, chunk * 256 + wave * 32, lane, p.M, p.H, p.W);
+    cw_setup<CMN, INB, OUTB, CY>(cur, chunk * 256 + wave * 32, lane, p.M, p.H, p.W);
 
     u32x4 xr[HALO ? 1 : XD][2];                            // ring forms: conv2 pixel pieces, K-steps kt .. kt + XD - 1
     u32x4 xh[HALO ? HB : 1][2];                            // HALO: fragments of the ten 16-pixel blocks around the tile, K halves 0 / 1
@@ -348,7 +369,7 @@ __global__ __launch_bounds__(512, 2) void chain_wave_kernel(ChainP p) {
         }
 
         // ---- the next tile's addresses and its conv2 pixels: requested before this tile's stores are issued -----------------------
-        cw_setup<CMN, INB, OUTB>(nxt, more ? chunk_n * 256 + wave * 32 : ((p.M + 31) & ~31), lane, p.M, p.H, p.W);
+        cw_setup<CMN, INB, OUTB, CY>(nxt, more ? chunk_n * 256 + wave * 32 : ((p.M + 31) & ~31), lane, p.M, p.H, p.W);
         if (!more) nxt.hb = OOB;
         if constexpr (HALO) CW_ISSUE_HALO(nxt)
         else {
@@ -446,8 +467,14 @@ __global__ __launch_bounds__(512, 2) void chain_wave_kernel(ChainP p) {
                 else if (h & 1) {                          // NHWC: the pair (h - 1, h) = 128 bytes per pixel leaves as full lines
                     u32x4 lo, hi;
                     cw_f2m_pair(slot0, lane, oe[j], o[j], lo, hi);
-                    cw_store(lo, rs_y, cur.yo[j], (h >> 1) * 128, p.stride == 77);
-                    cw_store(hi, rs_y, cur.yo[j], (h >> 1) * 128 + 8 * 512, p.stride == 77);
+                    if constexpr (CY) {                    // y_s2: the kept ones of the two pixels, compacted (the other store's offset is past the buffer: dropped)
+                        const int yb = cur.yo[j] & ~15;
+                        cw_store(lo, rs_y, (cur.yo[j] & 1) ? yb : OOB, (h >> 1) * 128, p.stride == 77);
+                        cw_store(hi, rs_y, (cur.yo[j] & 2) ? yb : OOB, (h >> 1) * 128 + 4 * 512, p.stride == 77);
+                    } else {
+                        cw_store(lo, rs_y, cur.yo[j], (h >> 1) * 128, p.stride == 77);
+                        cw_store(hi, rs_y, cur.yo[j], (h >> 1) * 128 + 8 * 512, p.stride == 77);
+                    }
                 } else oe[j] = o[j];
             }
             if constexpr (CMN > 0) {
@@ -506,12 +533,12 @@ static int cw_num_cus() {
     return v;
 }
 
-template <int CMN, bool F16, bool DS, bool W3G, bool INB, bool OUTB, bool HALO, int XD, int RD, int WD>
+template <int CMN, bool F16, bool DS, bool W3G, bool INB, bool OUTB, bool HALO, int XD, int RD, int WD, bool CY = false>
 static pvr_status launch_cw_one(ChainP &p, hipStream_t stream) {
     const size_t lds = (size_t)(W3G ? 73728 : 73728 + 32768) + (size_t)CMN * 512 + 256 + 1024 + 512 + 8 * 2048;
     static DeviceOnce attr_done;                           // per device; NOT per launch: the call costs host time that shows up as a gap in front of the kernel
     if (attr_done.needed()) {
-        PVR_HIP_TRY(hipFuncSetAttribute((const void *)chain_wave_kernel<CMN, F16, DS, W3G, INB, OUTB, HALO, XD, RD, WD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        PVR_HIP_TRY(hipFuncSetAttribute((const void *)chain_wave_kernel<CMN, F16, DS, W3G, INB, OUTB, HALO, XD, RD, WD, CY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_done.mark();
     }
     const int nch = (p.M + 255) / 256;
@@ -519,7 +546,7 @@ static pvr_status launch_cw_one(ChainP &p, hipStream_t stream) {
     if (grid < 8) grid = 8;
     const int need = ((nch + 7) / 8) * 8;                  // small launches: one chunk per block
     if (grid > need) grid = need;
-    hipLaunchKernelGGL((chain_wave_kernel<CMN, F16, DS, W3G, INB, OUTB, HALO, XD, RD, WD>), dim3(grid), dim3(512), lds, stream, p);
+    hipLaunchKernelGGL((chain_wave_kernel<CMN, F16, DS, W3G, INB, OUTB, HALO, XD, RD, WD, CY>), dim3(grid), dim3(512), lds, stream, p);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }
@@ -539,6 +566,10 @@ static pvr_status launch_cw_dt(ChainP &p, int cmn, int halo_on, hipStream_t stre
         if (!ib && ob) return launch_cw_one<64, F16, false, false, false, true, false, 4, 4, 1>(p, stream);
         return halo ? launch_cw_one<64, F16, false, false, true, false, true, 1, 4, 1>(p, stream)
                     : launch_cw_one<64, F16, false, false, true, false, false, 4, 4, 1>(p, stream);
+    } else if (cmn == 128 && !ob && p.y_s2) {              // ... storing y only where layer2.0's stride-2 downsample reads it
+        if (halo) return launch_cw_one<128, F16, false, true, true, false, true, 1, 1, 1, true>(p, stream);
+        return ib ? launch_cw_one<128, F16, false, true, true, false, false, 3, 4, 2, true>(p, stream)
+                  : launch_cw_one<128, F16, false, true, false, false, false, 3, 4, 2, true>(p, stream);
     } else if (cmn == 128 && !ob) {                        // layer1's last block: t1' feeds layer2's block form (NHWC)
         if (halo) return launch_cw_one<128, F16, false, true, true, false, true, 1, 1, 1>(p, stream);   // 254 VGPRs: residual / W3 rings of depth 1 make room for the halo
         return ib ? launch_cw_one<128, F16, false, true, true, false, false, 3, 4, 2>(p, stream)
@@ -565,10 +596,14 @@ bool chain_wave_supported(const PlanSwitches &sw, int cm, int cmn, int stride, b
 // can the tensors between two consecutive wave-form launches (y = the next residual, t1' = the next conv2 input) use the blocked layout?
 bool chain_wave_blocked_ok(int cmn_first, int h, int w) { return cmn_first == 64 && (h * w) % 32 == 0; }
 
+// the y_s2 store (CY): the Cmn = 128 instances with an NHWC y, 56 x 56 (cw_y_s2_offset)
+bool chain_wave_y_s2_ok(int cm, int cmn, int h, int w, int out_blk) { return cm == 64 && cmn == 128 && !out_blk && h == CW_YS2_HW && w == CW_YS2_HW; }
+
 pvr_status launch_chain_wave(ChainP &p, int cmn, int halo, int dtype, hipStream_t stream) {
     PVR_REQUIRE((int64_t)(p.M + 64) * 512 < 0x7ffffff0ll, "bottleneck chain (wave form): operand larger than 2 GiB (use a smaller chunk)");
     PVR_REQUIRE(p.xds ? p.wdsb != nullptr : (cmn != 128 || p.w3b != nullptr), "bottleneck chain (wave form): the blocked copy of W3 / Wd is missing");
     PVR_REQUIRE(!(p.in_blk || p.out_blk) || p.M % 32 == 0, "bottleneck chain (wave form): the blocked layout needs a multiple of 32 pixels");
+    PVR_REQUIRE(!p.y_s2 || (!p.xds && p.stride == 1 && chain_wave_y_s2_ok(64, cmn, p.H, p.W, p.out_blk)), "bottleneck chain (wave form): no y_s2 instance for this tail");
     return dtype == PVR_F16 ? launch_cw_dt<true>(p, cmn, halo, stream) : launch_cw_dt<false>(p, cmn, halo, stream);
 }
 

@@ -41,6 +41,7 @@ void read_switches(PlanSwitches &sw) {
     sw.chain_wave = get("PVR_CHAIN_WAVE", 1);
     sw.chain_wave_halo = get("PVR_CHAIN_WAVE_HALO", 1);
     sw.chain_wave_128 = get("PVR_CHAIN_WAVE_128", 1);
+    sw.strided_y = get("PVR_STRIDED_Y", 1);
     sw.chain_wave_l2 = get("PVR_CHAIN_WAVE_L2", 0);   // (measured no faster than the block form: opt-in, profiles/experiments/r06_chain_wave128.txt)
     sw.splitk = get("PVR_SPLITK", 1);
     sw.smallk_div = get("PVR_SMALLK_DIV", 4);
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void range_flag_kernel(const void *x, size_t n
 const char *launch_kind_name(int k) {
     static const char *nm[] = {"conv", "bneck_frame(front1)", "bneck_frame", "bneck_frame(run)", "(in the run)", "frame_members", "conv_pp256(dual)", "dual_members", "chain", "cast",
                                "conv_f32", "conv_split16", "conv_split16(pair)", "conv_split16(in32)", "splitk(small)", "splitk", "conv_expand(blocked)",
-                               "conv_wfrag(pool)", "conv_wfrag"};
+                               "conv_wfrag(pool)", "conv_wfrag", "chain(y_s2)", "conv_expand(y_s2)"};
     return k >= 0 && k < (int)(sizeof nm / sizeof nm[0]) ? nm[k] : "?";
 }
 
@@ -720,6 +721,40 @@ static pvr_status build_schedules(pvr_encoder *e) {
             }
         }
     }
+    // A wave-form tail that carries the next block's conv1 and whose y has ONE other reader, a 1 x 1 stride-2 convolution (layer1.2 -> layer2.0's
+    // downsample): three quarters of y are never read.  The tail may store only the (even row, even column) pixels, compacted into the front of
+    // the same buffer, and the reader then runs at stride 1 over them (y_s2).  Whether a forward does so is decided per batch size (resolve_kinds:
+    // the reader must be conv_expand at both strides - the same K order, bit-identical) and per call (taps, debug stops and range checks see full y).
+    if (e->sw.strided_y) {
+        std::vector<Launch> &sc = e->sched_fused;
+        for (size_t a = 0; a < sc.size(); ++a) {
+            Launch &A = sc[a];
+            if (A.conv3 < 0 || A.frame || A.wave != 1 || A.next1 < 0 || A.ds >= 0) continue;
+            const ConvOp &a2 = e->ops[A.conv2], &a3 = e->ops[A.conv3];
+            if (a2.stride != 1 || !chain_wave_y_s2_ok(a2.cout, e->ops[A.next1].cout, a2.h, a2.w, A.out_blk)) continue;   // (a tap on y: forwards that stop there run LK_CHAIN)
+            const int yb = a3.out_buf;
+            int reader = -1, readers = 0;
+            for (size_t b = a + 1; b < sc.size(); ++b) {       // every later read of yb until a launch writes it again
+                const Launch &B = sc[b];
+                bool writes = false;
+                if (B.t1_in == yb) ++readers;
+                for (int oi : {B.conv1, B.conv2, B.ds, B.conv3, B.next1, B.pair}) {   // (members in launch order: a read behind the write is the launch's own y)
+                    if (oi < 0) continue;
+                    const ConvOp &o = e->ops[oi];
+                    if (!writes && (o.in_buf == yb || o.res_buf == yb)) { ++readers; reader = (int)b; }
+                    writes |= o.out_buf == yb;
+                }
+                if (writes) break;
+            }
+            if (readers != 1) continue;
+            const Launch &R = sc[reader];
+            const ConvOp &r = e->ops[R.conv2];
+            if (R.conv3 >= 0 || R.ds >= 0 || R.pair >= 0 || R.frame || R.out_blk || r.kind != 0 || r.f32op || r.from32 || r.k != 1 || r.stride != 2 || r.pad != 0 ||
+                r.in_buf != yb || r.res_buf != B_NONE || r.out_f32 || r.ksplit > 1 || !r.tap.empty() || r.h != a2.h || r.w != a2.w || r.cin != a3.cout)
+                continue;
+            A.y_s2 = reader;
+        }
+    }
     return PVR_OK;
 }
 
@@ -876,6 +911,22 @@ static void resolve_kinds(pvr_encoder *enc) {
     if (enc->desc.dtype == PVR_F32 || enc->desc.arch == PVR_ARCH_CLIP_RN50 || enc->vit || enc->rnd || enc->host) return;
     for (int nb = 1; nb <= chunk; ++nb)
         for (size_t i = 0; i < plan.size(); ++i) enc->kinds[(size_t)(nb - 1) * plan.size() + i] = resolve_kind(enc, plan, i, nb);
+    // a tail that stores y only at its stride-2 reader's pixels (Launch::y_s2): where that reader runs on conv_expand at stride 2 and would at stride 1
+    // over the compacted tensor - the two instances differ only in the address of a pixel, so the output is bit-identical
+    for (int nb = 1; nb <= chunk; ++nb) {
+        uint8_t *k = enc->kinds.data() + (size_t)(nb - 1) * plan.size();
+        for (size_t i = 0; i < plan.size(); ++i) {
+            const int j = plan[i].y_s2;
+            if (j < 0 || k[i] != LK_CHAIN || k[j] != LK_CONV || enc->sw.conv_algo != -1) continue;
+            const ConvOp &r = enc->ops[plan[j].conv2];
+            const int64_t M = (int64_t)nb * (r.h / 2) * (r.w / 2);
+            if (conv_expand_supported(enc->sw, M, r.h, r.w, r.cin, r.cout, 1, 1, 2, 0, r.relu, 0, false) &&
+                conv_expand_supported(enc->sw, M, r.h / 2, r.w / 2, r.cin, r.cout, 1, 1, 1, 0, r.relu, 0, false)) {
+                k[i] = LK_CHAIN_YS2;
+                k[j] = LK_CONV_YS2;
+            }
+        }
+    }
     // consecutive whole-bottleneck frame launches, each reading its predecessor's output (layer3.1 .. 3.5): one launch for the run (bneck_frame.hip RUN)
     if (enc->sw.frame_run)
         for (int nb = 1; nb <= chunk; ++nb) {
@@ -1204,6 +1255,8 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
             int kind = kinds[li];
             if (kind == LK_WFRAG_POOL && !pool_args_ok) kind = resolve_kind(enc, plan_, li, nb, false);
             if ((kind == LK_FRAME_RUN || kind == LK_FRAME_RUN_TAIL) && !run_ok) kind = LK_FRAME_FRONT1;     // (taps, debug stops, range validation: one launch per bottleneck)
+            if (kind == LK_CHAIN_YS2 && !run_ok) kind = LK_CHAIN;                                           // (... and all of y)
+            if (kind == LK_CONV_YS2 && !run_ok) kind = LK_CONV;
             switch (kind) {
             case LK_FRAME_RUN: {
                 BFBlk blks[6];
@@ -1259,7 +1312,8 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
                 if (!s) s = member(op, enc->d_buf[op.in_buf], res, enc->d_buf[op.out_buf]);
                 break;
             }
-            case LK_CHAIN: {
+            case LK_CHAIN:
+            case LK_CHAIN_YS2: {
                 const ConvOp &c2 = enc->ops[l.conv2];
                 const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
                 const ConvOp *cd = l.ds >= 0 ? &enc->ops[l.ds] : nullptr;
@@ -1267,10 +1321,14 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
                                             c1 ? c1->d_wp : nullptr, c1 ? c1->d_b : nullptr, c1 ? enc->d_buf[l.t1_out] : nullptr, nb,
                                             c2.h, c2.w, c2.cout, c1 ? c1->cout : 0, c2.stride, dt, st,
                                             cd ? enc->d_buf[cd->in_buf] : nullptr, cd ? cd->d_wp : nullptr, op.d_wpb, cd ? cd->d_wpb : nullptr,
-                                            l.wave, cd ? (l.in_blk && t1_blocked) : l.in_blk, l.out_blk, c2.d_wpk);
+                                            l.wave, cd ? (l.in_blk && t1_blocked) : l.in_blk, l.out_blk, c2.d_wpk, kind == LK_CHAIN_YS2);
                 t1_blocked = false;
                 break;
             }
+            case LK_CONV_YS2:
+                // the 1 x 1 stride-2 reader of a y_s2 tail: stride 1 over the (n, h / 2, w / 2, cin) tensor in the front of the same buffer
+                s = launch_conv_expand(enc->d_buf[op.in_buf], op.d_w, op.d_b, nullptr, enc->d_buf[op.out_buf], nb, op.h / 2, op.w / 2, op.cin, op.cout, 1, op.relu, dt, st);
+                break;
             case LK_CAST:
                 s = launch_f32_to_h((const float *)enc->d_buf[op.in_buf], enc->d_buf[op.out_buf], (size_t)nb * op.h * op.w * op.cin, dt, st);
                 break;
@@ -1567,7 +1625,7 @@ int32_t pvr_encoder_launch_kernel(const pvr_encoder *enc, int32_t n, int32_t ind
     const bool tab = enc->kinds_stride == plan.size() && enc->kinds.size() == (size_t)enc->desc.chunk * plan.size();
     const int kind = tab ? enc->kinds[(size_t)(nb - 1) * plan.size() + i] : resolve_kind(enc, plan, (size_t)i, nb);
     const char *nm = enc->desc.dtype == PVR_F32 ? "conv_f32" : launch_kind_name(kind);
-    if (enc->desc.dtype != PVR_F32 && kind == LK_CHAIN) nm = plan[i].wave == 2 ? "chain_wave128" : plan[i].wave == 1 ? "chain_wave" : "bottleneck_chain";
+    if (enc->desc.dtype != PVR_F32 && (kind == LK_CHAIN || kind == LK_CHAIN_YS2)) nm = plan[i].wave == 2 ? "chain_wave128" : plan[i].wave == 1 ? "chain_wave" : "bottleneck_chain";
     snprintf(buf, (size_t)cap, "%s", nm);
     return (int32_t)strlen(nm);
 }

@@ -34,6 +34,7 @@ struct PlanSwitches {
     int chain_wave_halo = 1;  // PVR_CHAIN_WAVE_HALO: the wave form reads blocked inputs through the halo registers (0: the per-K-step load ring)
     int chain_wave_128 = 1;   // PVR_CHAIN_WAVE_128: the wave form for layer1's last tail (next conv1 128 wide)
     int chain_wave_l2 = 0;    // PVR_CHAIN_WAVE_L2 (opt-in: measured no faster): layer2's stride-1 tails on their wave form (chain_wave128.hip)
+    int strided_y = 1;        // PVR_STRIDED_Y: a tail whose y is read only by a 1x1 stride-2 downsample stores just those pixels (layer1.2 -> layer2.0; bit-identical)
     int splitk = 1;           // PVR_SPLITK: planned split-K of the *_l4 head
     int smallk_div = 4;       // PVR_SMALLK_DIV: K slices per block of the low-latency plan
     int frame_run = 0;        // PVR_FRAME_RUN (live, opt-in: measured equal): consecutive whole-bottleneck frame launches (layer3.1 .. 3.5) as one launch
@@ -162,6 +163,8 @@ struct Launch {
     int pair = -1;                            // conv_split16 pair form: ops[conv2] and ops[pair] read the same fp32 input and run as one launch (the compression head)
     int in_blk = 0, out_blk = 0;              // chain, wave form: t1 + residual / y + t1' travel in the blocked layout between two such launches (chain_wave.hip);
                                               // block form: out_blk 1 = y blocked, 3 = y and t1' blocked (a layer2 wave-form launch follows)
+    int y_s2 = -1;                            // chain, wave form: index of the plan's only other reader of y, a 1 x 1 stride-2 convolution - plain forwards store
+                                              // just the (even row, even column) pixels of y, compacted to (n, h / 2, w / 2, c), and that launch reads them at stride 1
 };
 
 // What one launch of the plan runs as for a forward of nb frames: resolved off the hot path (resolve_kinds: finalize, set_low_latency,
@@ -186,6 +189,8 @@ enum LaunchKind : uint8_t {
     LK_EXPAND_BLOCKED,    // conv_expand writing the blocked layout in front of a wave-form tail
     LK_WFRAG_POOL,        // conv_wfrag with AdaptiveAvgPool2d(1) in the epilogue
     LK_WFRAG,             // conv_wfrag
+    LK_CHAIN_YS2,         // LK_CHAIN storing y only at the pixels its stride-2 reader takes (Launch::y_s2; plain forwards: no tap, stop or range check)
+    LK_CONV_YS2,          // ... and that reader: conv_expand at stride 1 over the compacted y
 };
 const char *launch_kind_name(int k);
 

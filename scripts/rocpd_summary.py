@@ -31,7 +31,7 @@ def load(db, counter):
 
 def pmc(fdb, wdb, out_json, out_txt=None, plan_json=None, label=None):
     f, w = load(fdb, 'FETCH_SIZE'), load(wdb, 'WRITE_SIZE')
-    rows = []
+    rows, fam = [], []
     for k in sorted(f, key=lambda k: -f[k][2]):
         n = f[k][0]
         fetch = 2.0 * f[k][1] * 1024 / n
@@ -39,7 +39,8 @@ def pmc(fdb, wdb, out_json, out_txt=None, plan_json=None, label=None):
         dur = f[k][2] / n * 1e-9
         rows.append(dict(kernel=k[-70:], launches=n, fetch_MB=round(fetch / 1e6, 2), write_MB=round(write / 1e6, 2),
                          avg_us=round(dur * 1e6, 1), hbm_TBps=round((fetch + write) / dur / 1e12, 2)))
-    conv = [r for r in rows if any(t in r['kernel'] for t in ('conv_igemm', 'conv_pp256', 'bottleneck_chain', 'chain_wave', 'conv_expand', 'bneck_frame', 'conv_wfrag'))]
+        fam.append(any(t in k for t in ('conv_igemm', 'conv_pp256', 'bottleneck_chain', 'chain_wave', 'conv_expand', 'bneck_frame', 'conv_wfrag')))   # (full name: the row keeps its last 70 characters)
+    conv = [r for r, c in zip(rows, fam) if c]
     tot_b = sum((r['fetch_MB'] + r['write_MB']) * r['launches'] for r in conv); tot_n = sum(r['launches'] for r in conv)
     lines = [json.dumps(r) for r in rows[:16]] + ['conv family: avg HBM traffic per launch = %.1f MB over %d launches' % (tot_b / tot_n, tot_n)]
     print('\n'.join(lines))
