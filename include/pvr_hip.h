@@ -165,7 +165,8 @@ pvr_status pvr_encoder_check_range(pvr_encoder *enc, const uint8_t *frames_dev, 
  * reads the environment on the forward path. */
 pvr_status pvr_encoder_debug_set_switch(pvr_encoder *enc, const char *name, int32_t value);
 /* Which kernel family launch `index` (pvr_encoder_launch_name's indices) runs as in a forward of n frames, e.g. "bneck_frame(front1)", "conv_wfrag(pool)",
- * "conv_pp256(dual)", "chain_wave" / "chain_wave128" / "bottleneck_chain" (the three forms of the fused bottleneck tail), "conv_split16", "conv" (the shape-dispatched implicit GEMMs).  The choice is tabulated per batch size when the encoder is
+ * "conv_pp256(dual)", "chain_wave" / "chain_wave128" / "bottleneck_chain" (the three forms of the fused bottleneck tail), "conv_split16", "conv" (the shape-dispatched implicit GEMMs).  The plan and this choice,
+ * tabulated per batch size, are made in pvr_encoder_create from the desc and the PVR_* switches alone (no weights, no device), so the handle need not be
  * finalized; returns the name's length, 0 past the end of the plan. */
 int32_t pvr_encoder_launch_kernel(const pvr_encoder *enc, int32_t n, int32_t index, char *buf, int32_t cap);
 void pvr_encoder_destroy(pvr_encoder *enc);

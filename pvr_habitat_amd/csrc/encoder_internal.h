@@ -11,7 +11,7 @@ namespace pvr {
 
 // Every A/B switch of the encoder path, read from the environment ONCE per encoder (pvr_encoder_create: read_switches) - never on the forward path, and
 // nowhere else: the planner and the launchers take their choices from here (launchers: `sw`).  The ones marked (live) can be changed on a finalized encoder
-// with pvr_encoder_debug_set_switch; the others shape the plan or its launches and are fixed at finalize.  The pvr_op_* entry points have no handle: they
+// with pvr_encoder_debug_set_switch; the others shape the plan or its launches and are fixed at create.  The pvr_op_* entry points have no handle: they
 // share one process-level instance, op_switches().
 struct PlanSwitches {
     int pool_fuse = 1;        // PVR_POOL_FUSE (live): the pooled form of conv_wfrag for the trunk's last launch
@@ -132,11 +132,14 @@ struct ConvOp {
     bool f32op = false;            // convolution on fp32 buffers with fp32 weights on the f32-input MFMA (conv_f32.hip) inside a 16-bit plan
     bool from32 = false;           // a 16-bit convolution (16-bit weights, one MFMA per product) whose INPUT is the fp32 residual stream: conv_split16's single-term
                                    // form rounds the operand in its staging pass - the fp32 -> 16-bit copy launch of the stream is gone (round 6)
+    // plan facts, set by the planner at create (encoder_plan.hip) - finalize makes the device images they call for
+    bool split16 = false;          // an f32op / from32 convolution of an f16 plan that runs on conv_split16.hip (d_wsp)
+    bool wfrag = false;            // a per-frame launch's member, or a stand-alone launch conv_wfrag.hip may take by the batch: reads d_wfb
     u16 *d_w = nullptr;
     u16 *d_wp = nullptr;           // row-permuted copy for the fused bottleneck chain (bottleneck_chain.hip)
     u16 *d_wfb = nullptr;          // fragment-blocked copy of d_w for the per-frame layer3 tail (bneck_frame.hip: launch_pack_frag_weights)
     u16 *d_wpb = nullptr;          // ... and that copy in the blocked layout [row >> 4][cin >> 3][row & 15][8] (chain_wave.hip reads W3 / Wd pieces from L2)
-    std::vector<u16> h_w;          // host copy, kept until finalize has built the chain copies
+    std::vector<u16> h_w;          // host copy, kept until finalize has built the packed copies (prepare_weights)
     float *d_wf = nullptr;         // fp32 weights (PVR_F32 mode)
     u16 *d_wpk = nullptr;          // conv2 of a layer2 wave-form tail: the launch's 17 weight units as LDS images (chain_wave128.hip: launch_chain_wave128_pack)
     u16 *d_wsp_pair = nullptr;     // compression head: [conv1 ; downsample] rows as ONE split weight image (both read the same fp32 input: one launch, round 6)
@@ -167,7 +170,7 @@ struct Launch {
                                               // just the (even row, even column) pixels of y, compacted to (n, h / 2, w / 2, c), and that launch reads them at stride 1
 };
 
-// What one launch of the plan runs as for a forward of nb frames: resolved off the hot path (resolve_kinds: finalize, set_low_latency,
+// What one launch of the plan runs as for a forward of nb frames: resolved off the hot path (resolve_kinds: create, set_low_latency,
 // debug_set_fusion, debug_set_switch), one byte per (nb, launch); the forward is a switch over these.
 enum LaunchKind : uint8_t {
     LK_CONV = 0,          // launch_conv (conv_igemm.hip picks igemm / pp256 / expand / halo by shape)
@@ -250,6 +253,16 @@ struct pvr_encoder {
 
 
 namespace pvr {
+// encoder_plan.hip: the ResNet family's launch plan - ops, split-K, both schedules, the kinds table.  Host arithmetic on the desc and the switches only (no
+// weights, no device), so pvr_encoder_create calls it; pvr_encoder_finalize prepares what the plan's launches read (encoder.hip: prepare_weights).
+void plan_encoder(pvr_encoder *e);
+void resolve_kinds(pvr_encoder *enc);                          // again after low_latency, fuse or a live switch changed
+uint8_t resolve_kind(const pvr_encoder *enc, const std::vector<Launch> &plan, size_t li, int nb, bool allow_pool = true);
+const std::vector<Launch> &cur_plan(const pvr_encoder *enc);
+bool pooled_head(const pvr_encoder *enc);
+constexpr size_t SMALLK_BYTES = (size_t)32 << 20;               // the low-latency plan's fp32 partial planes, per lane
+int small_batch_ksplit(const pvr_encoder *enc, const ConvOp &op, int nb);
+bool conv_split16_supported(int cin, int cout, int k);         // conv_split16.hip
 const HostTensor *enc_find(pvr_encoder *e, const std::string &name);
 pvr_status enc_need(pvr_encoder *e, const std::string &name, const HostTensor **out, size_t numel);
 template <typename T>

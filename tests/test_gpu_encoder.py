@@ -1497,3 +1497,39 @@ def test_layer1_conv1_inside_the_stem(variant, dt, n, monkeypatch):
         for a, b in zip(got['inside'][1], got['launch'][1]):
             assert torch.isfinite(b).all() and float(b.abs().max()) > 0
             assert torch.equal(a, b), (lds, int((a != b).sum()), float((a - b).abs().max()))
+
+
+# ------------------------------------------------------------------------------------------------
+# the plan is made at create: what a handle reports before pvr_encoder_finalize is what its forwards run after it
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('arch,variant,dt', [(_lib.ARCH_RESNET50, 'conv5', 'f16'), (_lib.ARCH_RESNET50_L4, 'conv4', 'f16'), (10, 'r18', 'bf16')])
+def test_plan_is_the_same_before_and_after_finalize(arch, variant, dt):
+    """tests/test_encoder_plan_cpu.py pins the plan of handles that are never finalized; this ties that plan to the one a finalized handle runs"""
+    L = _lib.lib()
+
+    def names(fn, *front):
+        out, buf, i = [], C.create_string_buffer(256), 3
+        while fn(h, *front, i, buf, 256) > 0:
+            out.append(buf.value.decode())
+            i += 1
+        return out
+
+    def plan():
+        return names(L.pvr_encoder_launch_name), {n: names(L.pvr_encoder_launch_kernel, n) for n in (1, 3, 64, 127, 128, 256)}
+
+    h = C.c_void_p()
+    d = _lib.EncoderDesc(arch=arch, dtype=DT[dt][1], max_batch=256, chunk=0, resize=256, crop=224)
+    d.mean[:] = (0.485, 0.456, 0.406)
+    d.std_[:] = (0.229, 0.224, 0.225)
+    _lib.check(L.pvr_encoder_create(C.byref(d), C.byref(h)))
+    try:
+        before = plan()
+        assert len(before[0]) > 10 and all(len(k) == len(before[0]) - 1 for k in before[1].values())      # (launch_name ends with 'pool/flatten')
+        for k, v in synth.resnet50_state_dict(1, variant).items():
+            a = np.ascontiguousarray(v, dtype=np.float32)
+            shp = (C.c_int64 * max(a.ndim, 1))(*(a.shape or (1,)))
+            _lib.check(L.pvr_encoder_load_weights(h, k.encode(), a.ctypes.data_as(C.c_void_p), shp, a.ndim))
+        _lib.check(L.pvr_encoder_finalize(h))
+        assert plan() == before
+    finally:
+        L.pvr_encoder_destroy(h)

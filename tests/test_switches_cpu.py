@@ -42,3 +42,14 @@ def test_plan_switches_is_the_one_list():
     members = {m: (env, int(d)) for m, d, env in re.findall(r'int (\w+) = (-?\d+);\s*// (PVR_\w+)', decl)}
     reads = {m: (env, int(d)) for m, env, d in re.findall(r'sw\.(\w+) = get\("(PVR_\w+)", (-?\d+)\)', _body(_src('encoder.hip'), 'void read_switches'))}
     assert len(members) == len(re.findall(r'^\s*int ', decl, re.M)) and members == reads, (set(members.items()) ^ set(reads.items()))
+
+
+def test_the_planner_is_host_code_and_owns_the_name_matching():
+    """encoder_plan.hip decides the plan from the desc and the switches: it calls no HIP runtime function and no launcher, so pvr_encoder_create can run it
+    on a machine without a GPU; encoder.hip (weights, workspace, forward) does not recognise blocks by state-dict names"""
+    plan = re.sub(r'/\*.*?\*/', '', re.sub(r'//[^\n]*', '', _src('encoder_plan.hip')), flags=re.S)
+    assert 'plan_encoder' in plan and len(plan) > 10000
+    assert not re.findall(r'\bhip[A-Z]\w*\(', plan)
+    assert not re.findall(r'\blaunch_(?!kind_name)\w+\(', plan)
+    assert 'ends_with(' not in _src('encoder.hip')
+
