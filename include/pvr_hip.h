@@ -293,6 +293,22 @@ pvr_status pvr_op_avgpool(const void *in_dev, float *out_dev, int64_t out_stride
  * reads the flag once per call (the reference has no such check: its fp32 path cannot overflow a 16-bit storage type). */
 pvr_status pvr_op_nonfinite_flag(const float *x_dev, int64_t rows, int64_t cols, int64_t stride, int32_t *flag_dev, void *hip_stream);
 
+/* The ViT plans' kernels one at a time (test entry points; the encoder reaches the same launch dispatchers).  A shape that is not built returns a
+ * status with a message and launches nothing.
+ * Multi-head softmax attention: qkv (nb*T, 3W) 16-bit rows of [q | k | v], head h at columns h*HD.. of each third, HD = W / heads in {64, 80},
+ * 1 <= T <= 288; out (nb*T, W) 16-bit.  Scores are scaled by 1/sqrt(HD). */
+pvr_status pvr_op_attention(const void *qkv_dev, void *out_dev, int32_t T, int32_t W, int32_t heads, int32_t nb, int32_t dtype, void *hip_stream);
+/* LayerNorm over rows of W fp32 values (W in {768, 1024, 1280}).  Input: x (rows, W), or - when patch_emb is given - the assembled token sequence
+ * row b*T + t = (t == 0 ? cls : patch_emb[b*(T-1) + t-1]) + pos[t] (rows a multiple of T).  normalize = 0 writes the (assembled) input unchanged.
+ * Outputs: out_f32 (rows, W) and / or out_h (rows, W) in the 16-bit type `dtype`; either may be null, not both. */
+pvr_status pvr_op_layernorm(const float *x_dev, const float *patch_emb_dev, const float *cls_dev, const float *pos_dev, const float *gamma_dev,
+                            const float *beta_dev, float *out_f32_dev, void *out_h_dev, int32_t rows, int32_t T, int32_t W, float eps, int32_t normalize,
+                            int32_t dtype, void *hip_stream);
+/* LayerNorm of token 0 of each of nb images (x: (nb*T, W) fp32) times proj (W, out_dim) fp32 -> out[b*out_stride + j], j < out_dim; with a null proj the
+ * normalised token itself (out_dim <= W). */
+pvr_status pvr_op_cls_head(const float *x_dev, const float *gamma_dev, const float *beta_dev, const float *proj_or_null_dev, float *out_dev,
+                           int64_t out_stride, int32_t nb, int32_t T, int32_t W, int32_t out_dim, float eps, void *hip_stream);
+
 /* host-only: the fp32 -> bf16/f16 round-to-nearest-even conversion finalize() applies to weights */
 pvr_status pvr_debug_convert(const float *src, uint16_t *dst, int64_t n, int32_t dtype);
 

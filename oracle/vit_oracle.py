@@ -58,13 +58,17 @@ def _ln(x, w, b):
 
 
 def encode_image(sd, x, heads=12, taps=None):
-    """x: fp32 (N,3,R,R) normalised -> (N, out_dim)."""
+    """x: fp32 (N,3,R,R) normalised -> (N, out_dim).  taps (a dict, optional) receives every stage the HIP plan can stop after, each
+    computed from the preceding oracle stage: 'pe' (patch embedding), 'ln_pre', block 0's 'qkv0' / 'att0' (heads merged) / 'res0'
+    (x + out_proj) / 'fc0' (after the activation), and 'block<i>' after every block - all (N, tokens, features)."""
     pre = 'visual.'
     w1 = _t(sd[pre + 'conv1.weight'])
     patch = w1.shape[-1]
     x = F.conv2d(x, w1, None, patch)                              # (N, width, g, g)
     n, width = x.shape[0], x.shape[1]
     x = x.reshape(n, width, -1).permute(0, 2, 1)
+    if taps is not None:
+        taps['pe'] = x
     cls = _t(sd[pre + 'class_embedding']).view(1, 1, -1).expand(n, 1, width)
     x = torch.cat([cls, x], dim=1) + _t(sd[pre + 'positional_embedding'])
     x = _ln(x, sd[pre + 'ln_pre.weight'], sd[pre + 'ln_pre.bias'])
@@ -81,9 +85,13 @@ def encode_image(sd, x, heads=12, taps=None):
         a = torch.softmax((sh(q) @ sh(k).transpose(-1, -2)) / (hd ** 0.5), dim=-1) @ sh(v)
         a = a.permute(0, 2, 1, 3).reshape(n, T, width)
         x = x + a @ _t(sd[p + 'attn.out_proj.weight']).t() + _t(sd[p + 'attn.out_proj.bias'])
+        if taps is not None and i == 0:
+            taps['qkv0'], taps['att0'], taps['res0'] = qkv, a, x
         y = _ln(x, sd[p + 'ln_2.weight'], sd[p + 'ln_2.bias'])
         y = y @ _t(sd[p + 'mlp.c_fc.weight']).t() + _t(sd[p + 'mlp.c_fc.bias'])
         y = y * torch.sigmoid(1.702 * y)                          # QuickGELU
+        if taps is not None and i == 0:
+            taps['fc0'] = y
         x = x + y @ _t(sd[p + 'mlp.c_proj.weight']).t() + _t(sd[p + 'mlp.c_proj.bias'])
         if taps is not None:
             taps['block%d' % i] = x
@@ -131,15 +139,20 @@ def mae_preprocess(frames_nhwc_u8):
 
 
 def mae_encode(sd, x, heads=12, taps=None):
+    """taps: as in encode_image"""
     w1 = _t(sd['patch_embed.proj.weight'])
     patch, width = w1.shape[-1], w1.shape[0]
     x = F.conv2d(x, w1, _t(sd['patch_embed.proj.bias']), patch)
     n = x.shape[0]
     x = x.reshape(n, width, -1).permute(0, 2, 1)
+    if taps is not None:
+        taps['pe'] = x
     pos = _t(sd['pos_embed'])
     x = x + pos[:, 1:, :]
     cls = (_t(sd['cls_token']) + pos[:, :1, :]).expand(n, -1, -1)
     x = torch.cat([cls, x], dim=1)
+    if taps is not None:
+        taps['ln_pre'] = x                                        # MAE has no ln_pre: the plan's tap of that name holds tokens + pos-emb
     T, hd = x.shape[1], width // heads
     ln = lambda t, w, b: F.layer_norm(t, (width,), _t(w), _t(b), 1e-6)
     i = 0
@@ -152,8 +165,12 @@ def mae_encode(sd, x, heads=12, taps=None):
         a = torch.softmax((sh(q) @ sh(k).transpose(-1, -2)) * (hd ** -0.5), dim=-1) @ sh(v)
         a = a.permute(0, 2, 1, 3).reshape(n, T, width)
         x = x + a @ _t(sd[p + 'attn.proj.weight']).t() + _t(sd[p + 'attn.proj.bias'])
+        if taps is not None and i == 0:
+            taps['qkv0'], taps['att0'], taps['res0'] = qkv, a, x
         y = ln(x, sd[p + 'norm2.weight'], sd[p + 'norm2.bias'])
         y = F.gelu(y @ _t(sd[p + 'mlp.fc1.weight']).t() + _t(sd[p + 'mlp.fc1.bias']))
+        if taps is not None and i == 0:
+            taps['fc0'] = y
         x = x + y @ _t(sd[p + 'mlp.fc2.weight']).t() + _t(sd[p + 'mlp.fc2.bias'])
         if taps is not None:
             taps['block%d' % i] = x

@@ -234,6 +234,21 @@ pvr_status pvr_op_nonfinite_flag(const float *x, int64_t rows, int64_t cols, int
     return PVR_OK;
 }
 
+// ViT kernels one by one (tests/test_gpu_vit_kernels.py): the launch dispatchers of vit.hip the encoder plans use, nothing else
+pvr_status pvr_op_attention(const void *qkv, void *out, int32_t T, int32_t W, int32_t heads, int32_t nb, int32_t dtype, void *stream) {
+    return launch_attention(qkv, out, T, W, heads, nb, dtype, (hipStream_t)stream);
+}
+
+pvr_status pvr_op_layernorm(const float *x, const float *patch_emb, const float *cls, const float *pos, const float *gamma, const float *beta,
+                            float *out_f32, void *out_h, int32_t rows, int32_t T, int32_t W, float eps, int32_t normalize, int32_t dtype, void *stream) {
+    return launch_layernorm(x, patch_emb, cls, pos, gamma, beta, out_f32, out_h, rows, T, W, eps, normalize, dtype, (hipStream_t)stream);
+}
+
+pvr_status pvr_op_cls_head(const float *x, const float *gamma, const float *beta, const float *proj_or_null, float *out, int64_t out_stride, int32_t nb,
+                           int32_t T, int32_t W, int32_t out_dim, float eps, void *stream) {
+    return launch_cls_head(x, gamma, beta, proj_or_null, out, out_stride, nb, T, W, out_dim, eps, (hipStream_t)stream);
+}
+
 int32_t pvr_debug_stem_u8_geometry_ok(const void *frames, int32_t h, int32_t w, int32_t top, int32_t left) { return stem_pool_u8_ok(frames, h, w, top, left) ? 1 : 0; }
 
 // test hook: the uniform in (0, 1) the action sampler makes of 32 random bits (sample_rng.h) - host arithmetic, no GPU work

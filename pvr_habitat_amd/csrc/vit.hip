@@ -646,6 +646,45 @@ static pvr_status launch_attention_any(const u16 *qkv, u16 *out, int T, int TK, 
     return launch_attention_inst<F16, 80, 18, false>(qkv, out, T, TK, W, heads, nb, st);
 }
 
+// LayerNorm (+ optional token assembly) launch for every width / storage type the plans use: the ViT forward and pvr_op_layernorm share it.
+template <bool F16, int WD>
+static void launch_layernorm_inst(const float *x, const float *patch_emb, const float *cls, const float *pos, const float *gamma, const float *beta,
+                                  float *out_f32, u16 *out_h, int rows, int T, float eps, int normalize, hipStream_t st) {
+    hipLaunchKernelGGL((layernorm_kernel<F16, WD>), dim3((rows + 3) / 4), dim3(256), 0, st, x, patch_emb, cls, pos, gamma, beta, out_f32, out_h, rows, T,
+                       eps, normalize);
+}
+
+pvr_status launch_layernorm(const float *x, const float *patch_emb, const float *cls, const float *pos, const float *gamma, const float *beta,
+                            float *out_f32, void *out_h, int rows, int T, int W, float eps, int normalize, int dtype, hipStream_t st) {
+    PVR_REQUIRE(W == 768 || W == 1024 || W == 1280, "layernorm: width %d not built (768 / 1024 / 1280)", W);
+    PVR_REQUIRE(dtype == PVR_F16 || dtype == PVR_BF16, "layernorm: 16-bit storage types only");
+    PVR_REQUIRE(rows > 0 && T > 0 && eps > 0.f, "layernorm: %d rows of %d tokens, eps %g", rows, T, (double)eps);
+    PVR_REQUIRE(out_f32 || out_h, "layernorm: no output");
+    PVR_REQUIRE(patch_emb ? (cls && pos && rows % T == 0) : x != nullptr, "layernorm: needs x, or patch_emb with cls and pos and whole token sequences");
+    PVR_REQUIRE(!normalize || (gamma && beta), "layernorm: gamma / beta missing");
+    const bool f16 = dtype == PVR_F16;
+#define PVR_LN(WD_) (f16 ? launch_layernorm_inst<true, WD_>(x, patch_emb, cls, pos, gamma, beta, out_f32, (u16 *)out_h, rows, T, eps, normalize, st) \
+                         : launch_layernorm_inst<false, WD_>(x, patch_emb, cls, pos, gamma, beta, out_f32, (u16 *)out_h, rows, T, eps, normalize, st))
+    if (W == 768) PVR_LN(768); else if (W == 1024) PVR_LN(1024); else PVR_LN(1280);
+#undef PVR_LN
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// ln_post of every image's token 0 (+ projection): the ViT forward and pvr_op_cls_head share it
+pvr_status launch_cls_head(const float *x, const float *gamma, const float *beta, const float *proj, float *out, int64_t out_stride, int nb, int T, int W,
+                           int out_dim, float eps, hipStream_t st) {
+    PVR_REQUIRE(W == 768 || W == 1024 || W == 1280, "cls_head: width %d not built (768 / 1024 / 1280)", W);
+    PVR_REQUIRE(x && gamma && beta && out, "cls_head: null pointer");
+    PVR_REQUIRE(nb > 0 && T > 0 && eps > 0.f && out_dim > 0 && out_stride >= out_dim, "cls_head: %d images of %d tokens, %d outputs", nb, T, out_dim);
+    PVR_REQUIRE(proj || out_dim <= W, "cls_head: without a projection the output is the %d-wide token", W);
+    if (W == 768) hipLaunchKernelGGL((cls_head_kernel<768>), dim3(nb), dim3(256), 0, st, x, gamma, beta, proj, out, out_stride, T, out_dim, eps);
+    else if (W == 1024) hipLaunchKernelGGL((cls_head_kernel<1024>), dim3(nb), dim3(256), 0, st, x, gamma, beta, proj, out, out_stride, T, out_dim, eps);
+    else hipLaunchKernelGGL((cls_head_kernel<1280>), dim3(nb), dim3(256), 0, st, x, gamma, beta, proj, out, out_stride, T, out_dim, eps);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
 template <bool F16, int WD>
 static pvr_status vit_forward_t(pvr_encoder *e, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st) {
     pvr_vit *v = e->vit;
@@ -679,17 +718,14 @@ static pvr_status vit_forward_t(pvr_encoder *e, const uint8_t *frames, int n, in
         // patch embedding GEMM -> fp32 [prow][W]
         if ((s = launch_conv(e->sw, v->A, v->w_patch, v->b_patch, nullptr, v->pe, v->zero, prow, 1, 1, K, W, 1, 1, 1, 0, 0, 1, dt, st))) return s;
         // tokens + positional embedding + ln_pre -> residual stream x0 (fp32)
-        hipLaunchKernelGGL((layernorm_kernel<F16, WD>), dim3((rows + 3) / 4), dim3(256), 0, st, (const float *)nullptr, v->pe, v->cls,
-                           v->pos, v->lnpre_w, v->lnpre_b, v->x0, (u16 *)nullptr, rows, T, v->eps, v->mae ? 0 : 1);
-        PVR_LAUNCH_CHECK();
+        if ((s = launch_layernorm(nullptr, v->pe, v->cls, v->pos, v->lnpre_w, v->lnpre_b, v->x0, nullptr, rows, T, W, v->eps, v->mae ? 0 : 1, dt, st))) return s;
         e->last_n = nb;
         const std::string &stop = e->stop_after;
         if (stop == "pe" || stop == "ln_pre") return PVR_OK;
         float *x = v->x0, *xn = v->x1;
         int bi = 0;
         for (auto &b : v->blocks) {
-            hipLaunchKernelGGL((layernorm_kernel<F16, WD>), dim3((rows + 3) / 4), dim3(256), 0, st, x, (const float *)nullptr,
-                               (const float *)nullptr, (const float *)nullptr, b.ln1_w, b.ln1_b, (float *)nullptr, v->y, rows, T, v->eps, 1);
+            if ((s = launch_layernorm(x, nullptr, nullptr, nullptr, b.ln1_w, b.ln1_b, nullptr, v->y, rows, T, W, v->eps, 1, dt, st))) return s;
             if ((s = launch_conv(e->sw, v->y, b.w_qkv, b.b_qkv, nullptr, v->qkv, v->zero, rows, 1, 1, W, 3 * W, 1, 1, 1, 0, 0, 0, dt, st))) return s;
             if (bi == 0 && stop == "qkv0") return PVR_OK;
             if ((s = launch_attention_any<F16>(v->qkv, v->att, T, v->TK, W, v->heads, nb, st))) return s;
@@ -698,17 +734,14 @@ static pvr_status vit_forward_t(pvr_encoder *e, const uint8_t *frames, int n, in
             // x' = x + out_proj(att): fp32 residual in (bit1), fp32 out (bit0)
             if ((s = launch_conv(e->sw, v->att, b.w_out, b.b_out, x, xn, v->zero, rows, 1, 1, W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
             if (bi == 0 && stop == "res0") return PVR_OK;
-            hipLaunchKernelGGL((layernorm_kernel<F16, WD>), dim3((rows + 3) / 4), dim3(256), 0, st, xn, (const float *)nullptr,
-                               (const float *)nullptr, (const float *)nullptr, b.ln2_w, b.ln2_b, (float *)nullptr, v->y, rows, T, v->eps, 1);
+            if ((s = launch_layernorm(xn, nullptr, nullptr, nullptr, b.ln2_w, b.ln2_b, nullptr, v->y, rows, T, W, v->eps, 1, dt, st))) return s;
             if ((s = launch_conv(e->sw, v->y, b.w_fc, b.b_fc, nullptr, v->hid, v->zero, rows, 1, 1, W, 4 * W, 1, 1, 1, 0, v->act, 0, dt, st))) return s;   // QuickGELU / GELU
             if (bi == 0 && stop == "fc0") return PVR_OK;
             if ((s = launch_conv(e->sw, v->hid, b.w_proj, b.b_proj, xn, x, v->zero, rows, 1, 1, 4 * W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
             if (stop == "block" + std::to_string(bi)) return PVR_OK;
             ++bi;
         }
-        hipLaunchKernelGGL((cls_head_kernel<WD>), dim3(nb), dim3(256), 0, st, x, v->lnpost_w, v->lnpost_b, v->proj,
-                           out + (size_t)f0 * out_stride, out_stride, T, v->out_dim, v->eps);
-        PVR_LAUNCH_CHECK();
+        if ((s = launch_cls_head(x, v->lnpost_w, v->lnpost_b, v->proj, out + (size_t)f0 * out_stride, out_stride, nb, T, W, v->out_dim, v->eps, st))) return s;
         e->last_n = nb;
     }
     return PVR_OK;
@@ -753,6 +786,9 @@ pvr_status vit_tap(pvr_encoder *e, const char *name, float *out, int64_t cap, in
 
 // attention core for callers outside the ViT plan (CLIP RN50 attention pool)
 pvr_status launch_attention(const void *qkv, void *out, int T, int W, int heads, int nb, int dtype, hipStream_t st) {
+    PVR_REQUIRE(qkv && out, "attention: null pointer");
+    PVR_REQUIRE(T > 0 && T <= 288 && heads > 0 && nb > 0 && W > 0, "attention: %d tokens (1..288), %d heads, %d images not built", T, heads, nb);
+    PVR_REQUIRE(dtype == PVR_F16 || dtype == PVR_BF16, "attention: 16-bit storage types only");
     const int TK = (T + 31) / 32 * 32;
     return dtype == PVR_F16 ? launch_attention_any<true>((const u16 *)qkv, (u16 *)out, T, TK, W, heads, nb, st)
                             : launch_attention_any<false>((const u16 *)qkv, (u16 *)out, T, TK, W, heads, nb, st);

@@ -141,3 +141,43 @@ def test_clip_rn50_matches_oracle(h, w):
     l2, mx = _rel(out, ref)
     print('\n[clip_rn50 f16 %dx%d] stages %s embedding rel-L2 %.2e max-norm %.2e' % (h, w, {k: '%.1e' % v for k, v in errs.items()}, l2, mx))
     assert l2 < 1e-3 and max(errs.values()) < 1e-3
+
+
+VIT_STAGES = ('pe', 'ln_pre', 'qkv0', 'att0', 'res0', 'fc0', 'block0', 'block11')
+
+
+@pytest.mark.parametrize('variant', ['clip_b32', 'clip_b16', 'mae_b16'])
+def test_vit_block0_stage_parity(variant):
+    """Every stage of block 0 and the last block, EVERY token row of every image (not the CLS row of the last block alone), against the fp32
+    oracle computed from its own preceding stage: relative L2 over the whole stage and the largest per-row relative L2, both <= 1e-3
+    (the f16 parity bound of test_gpu_encoder.py).  The frames have the short side the transform resizes to (224 for CLIP, 256 for MAE), so
+    Resize is the identity and every stage sees exactly the oracle's pixels: with 224 x 224 frames through MAE's Resize(256) one bicubic .5 tie
+    rounds the other way (the <= 1 LSB the resized-tap checks above allow), and that single pixel moves its patch's 'pe' row by 1.5e-3."""
+    from oracle import vit_oracle as vo
+    from pvr_habitat_amd.embeddings import HipResNet50
+    torch.set_num_threads(16)
+    n = 2
+    taps = {}
+    with torch.no_grad():
+        if variant == 'mae_b16':
+            sd = synth.mae_vit_state_dict(1)
+            fr = synth.smooth_frames(47, n, 256, 256)
+            vo.mae_encode(sd, vo.mae_preprocess(fr), taps=taps)
+        else:
+            sd = synth.clip_vit_state_dict(1, patch=32 if variant == 'clip_b32' else 16)
+            fr = synth.smooth_frames(41, n, 224, 224)
+            vo.encode_image(sd, vo.preprocess(fr), taps=taps)
+    m = HipResNet50(sd, variant, compute_dtype='f16', max_batch=4)
+    d = torch.from_numpy(fr).cuda()
+    errs = {}
+    for name in VIT_STAGES:
+        r = taps[name].reshape(-1, taps[name].shape[-1]).numpy()
+        m.debug_stop_after(name); m(d)
+        g = m.tap(name, r.size).cpu().numpy().reshape(r.shape)
+        assert np.isfinite(g).all(), name
+        rows = np.linalg.norm(g - r, axis=1) / np.linalg.norm(r, axis=1)
+        errs[name] = (_rel(g, r)[0], float(rows.max()), int(rows.argmax()))
+    m.debug_stop_after('')
+    print('\n[%s f16 stages] %s' % (variant, {k: 'L2 %.2e worst row %.2e (row %d)' % v for k, v in errs.items()}))
+    over = {k: v for k, v in errs.items() if not (v[0] <= 1e-3 and v[1] <= 1e-3)}
+    assert not over, over
