@@ -33,10 +33,14 @@ typedef int pvr_status;
 
 /* storage / MFMA input type of the encoder ("throughput" = bf16, "parity" = f16); accumulation
  * is always fp32.  PVR_F32 (ResNet50 family only) stores and multiplies in fp32 on the f32-input MFMA: the
- * reference's own arithmetic type, ~1e-6 from the fp32 oracle, at the f32 MFMA rate */
+ * reference's own arithmetic type, ~1e-6 from the fp32 oracle, at the f32 MFMA rate.  PVR_F32S (same architectures) stores fp32 exactly as PVR_F32 and
+ * multiplies on the 16-bit matrix pipe: every fp32 operand as an exact (hi, lo) pair of f16 values, three MFMAs per fragment pair (conv_split16.hip,
+ * stem_split16.hip) - within ~1e-6 of PVR_F32 at several times its rate.  The high part is an f16: activations must stay below 65504 in magnitude
+ * (pvr_encoder_check_range validates that); PVR_F32 has the full fp32 range */
 #define PVR_BF16 0
 #define PVR_F16 1
 #define PVR_F32 2
+#define PVR_F32S 3
 
 /* encoder architectures */
 #define PVR_ARCH_RESNET50 0      /* torchvision resnet50, fc=Identity  -> 2048 (embeddings.py:118-120, moco.py:6-26) */
@@ -75,7 +79,7 @@ typedef struct pvr_encoder pvr_encoder;
 
 typedef struct pvr_encoder_desc {
     int32_t arch;          /* PVR_ARCH_* */
-    int32_t dtype;         /* PVR_BF16, PVR_F16, or PVR_F32 (ResNet50 family) */
+    int32_t dtype;         /* PVR_BF16, PVR_F16, or PVR_F32 / PVR_F32S (torchvision ResNet family) */
     int32_t max_batch;     /* frames per forward call the workspace is sized for */
     int32_t chunk;         /* frames pushed through the layer stack at a time (0 = max_batch) */
     int32_t resize;        /* short-side target, 256 (embeddings.py:81) */
@@ -99,7 +103,8 @@ pvr_status pvr_encoder_finalize(pvr_encoder *enc);
  * present (src/embeddings.py:367-370; BASELINE configs[0] is a CPU plumbing run).  on != 0: finalize keeps fp32 BN-folded weights on the
  * host and makes no HIP call; pvr_encoder_forward / _forward_lane then take HOST pointers for frames and output and run plain C++ loops
  * over the same op list on this process's threads (PVR_HOST_THREADS, default all cores); hip_stream is ignored.  torchvision ResNet family
- * (arch RESNET50 / _L3 / _L4 / RESNET18 / RESNET34) with dtype PVR_F32 only; taps, profiling and lanes are GPU-plan features. */
+ * (arch RESNET50 / _L3 / _L4 / RESNET18 / RESNET34) with dtype PVR_F32 only (a PVR_F32S handle is refused: the CPU plan has no split product); taps,
+ * profiling and lanes are GPU-plan features. */
 pvr_status pvr_encoder_set_host_backend(pvr_encoder *enc, int32_t on);
 int32_t pvr_encoder_out_size(const pvr_encoder *enc);
 /* frames_dev: uint8 (n,h,w,3) on the device; out_dev: fp32, row i written at
@@ -154,7 +159,8 @@ pvr_status pvr_encoder_profile_span(pvr_encoder *enc, const uint8_t *frames_dev,
  * the UNFUSED plan with every launch's output checked for inf / NaN.  An overflow inside the network does not always reach the embedding (+inf x a negative
  * weight = -inf, and ReLU maps -inf and NaN to 0), so a finite check of the output alone can miss it.  *first_bad = index of the first launch whose output is
  * non-finite (pvr_encoder_launch_name numbering of the unfused plan; its name says which convolution) or -1.  n <= chunk frames; synchronises; the embeddings of
- * this forward are written to out_dev as usual.  ResNet family, 16-bit plans. */
+ * this forward are written to out_dev as usual.  ResNet family, 16-bit plans - and PVR_F32S plans, where the stem's and every launch's output is checked for
+ * non-finite values AND magnitudes above 65504: the next convolution rounds the high part of its operand to f16, so such an activation becomes inf there. */
 pvr_status pvr_encoder_check_range(pvr_encoder *enc, const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, float *out_dev, int64_t out_stride,
                                    void *hip_stream, int32_t *first_bad);
 /* Debug / A-B: the run-time switches of a finalized encoder - "pool_fuse" (the trunk's last convolution writes the average pool itself), "stem_u8" (the
@@ -252,6 +258,14 @@ pvr_status pvr_op_conv2d_split16(const float *in_dev, const void *wgt_split_dev,
 pvr_status pvr_op_conv2d_f32(const float *in_dev, const float *wgt_dev, const float *bias_dev, const float *residual_dev, float *out_dev, int32_t n,
                              int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t relu, void *hip_stream);
 int64_t pvr_debug_conv_split16_launches(void);
+/* conv1 7x7/2 pad 3 + folded BN + ReLU of the PVR_F32S plan (stem_split16.hip; torchvision ResNet conv1 / bn1 / relu, reference src/embeddings.py:112-120) as the
+ * same exact split product.  img_padded: the normalised fp32 image in the zero-bordered NHWC4 layout (n, S+6, S+8, 4), pixel (y,x) at [y+3][x+3], channel 3 and
+ * the border (3 rows above / below, 3 columns left, 5 right) zero; wgt_split: pvr_op_split16_pack_weights (rows 64, k 224) of the folded fp32 (64, 7, 8, 4)
+ * weights (K index (a*8+b)*4+c; column 7 and channel 3 zero); bias: 64 floats; out: fp32 (n, S/2, S/2, 64).  S even. */
+pvr_status pvr_op_stem_split16(const float *img_padded_dev, const void *wgt_split_dev, const float *bias_dev, float *out_dev, int32_t n, int32_t S,
+                               void *hip_stream);
+/* launches of that kernel so far (tests: one per chunk of a PVR_F32S forward) */
+int64_t pvr_debug_stem_split16_launches(void);
 /* launches of the layer2 wave-form tail (chain_wave128.hip: torchvision Bottleneck conv2 -> conv3 + identity -> the next conv1 at Cm = 128, reference
  * src/embeddings.py:118-120) so far (tests: the layer2 plan really took it).  The form is opt-in: PVR_CHAIN_WAVE_L2=1 at pvr_encoder_create selects it,
  * the default (0) keeps the block form. */

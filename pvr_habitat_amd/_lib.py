@@ -6,7 +6,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PVR_LIB') or os.path.join(_HERE, 'lib', 'libpvr_hip.so')      # PVR_LIB: e.g. the host-ASan build (`make asan`)
 
-PVR_BF16, PVR_F16, PVR_F32 = 0, 1, 2
+PVR_BF16, PVR_F16, PVR_F32, PVR_F32S = 0, 1, 2, 3
 ARCH_RESNET50, ARCH_RESNET50_L4, ARCH_RESNET50_L3 = 0, 1, 2
 
 
@@ -72,6 +72,8 @@ _SIGS = {
     'pvr_op_conv2d_split16': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 9 + [C.c_void_p]),
     'pvr_op_conv2d_f32': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 9 + [C.c_void_p]),
     'pvr_debug_conv_split16_launches': (C.c_int64, []),
+    'pvr_op_stem_split16': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p]),
+    'pvr_debug_stem_split16_launches': (C.c_int64, []),
     'pvr_debug_chain_wave128_launches': (C.c_int64, []),
     'pvr_op_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'pvr_op_layernorm': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_int32, C.c_void_p]),

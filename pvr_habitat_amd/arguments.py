@@ -47,8 +47,9 @@ def make_parser():
     parser.add_argument('--n_trajectories', type=int, default=-1)
     parser.add_argument('--source', type=str, default='png', choices=['png', 'pickle'])
     # MI355X additions (not in the reference)
-    parser.add_argument('--compute_dtype', type=str, default=None, choices=[None, 'bf16', 'f16'],
-                        help='encoder storage/MFMA input type (default: $PVR_DTYPE or f16 = inside the 1e-3 parity bound; bf16 = wider range, 3e-3)')
+    parser.add_argument('--compute_dtype', type=str, default=None, choices=[None, 'bf16', 'f16', 'f32', 'f32s'],
+                        help='encoder storage/MFMA input type (default: $PVR_DTYPE or f16 = inside the 1e-3 parity bound; bf16 = wider range, 3e-3; '
+                             'f32 = fp32 storage on the f32 MFMA, ~1e-6; f32s = the same on the 16-bit MFMA as exact split products, ResNet family)')
     parser.add_argument('--embed_batch', type=int, default=256, help='frames per encoder launch (the reference '
                         'pushes batch_size x n_frames = 64 per forward, save_embedded_obs.py:151-153)')
     parser.add_argument('--embed_block', type=int, default=0, help='observation rows a rank reads, embeds and appends to its shard file at a '

@@ -151,6 +151,11 @@ pvr_status pvr_op_conv2d_f32(const float *in, const float *wgt, const float *bia
     return launch_conv_f32(in, wgt, bias, residual, out, n, h, w, cin, cout, k, stride, pad, relu, (hipStream_t)stream);
 }
 int64_t pvr_debug_conv_split16_launches(void) { return (int64_t)conv_split16_launches(); }
+// conv1 of the PVR_F32S plan (stem_split16.hip): the zero-bordered fp32 NHWC4 image, split weights (rows 64, K 224)
+pvr_status pvr_op_stem_split16(const float *img_padded, const void *wgt_split, const float *bias, float *out, int32_t n, int32_t S, void *stream) {
+    return launch_stem_split16(img_padded, wgt_split, bias, out, n, S, (hipStream_t)stream);
+}
+int64_t pvr_debug_stem_split16_launches(void) { return (int64_t)stem_split16_launches(); }
 int64_t pvr_debug_chain_wave128_launches(void) { return (int64_t)chain_wave128_launches(); }
 int64_t pvr_debug_pp_persistent_launches(void) { return (int64_t)pp_persistent_launches(); }
 

@@ -91,6 +91,22 @@ __global__ __launch_bounds__(256) void range_flag_kernel(const void *x, size_t n
     if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(flags + idx, 1);
 }
 
+// ... of a PVR_F32S plan: the next convolution rounds the high part of its fp32 operand to f16, so a finite activation above 65504 becomes inf there (and its low
+// part NaN) - flagged here, on the fp32 value, together with inf / NaN (both compare above 65504 as magnitudes of the bit pattern)
+__global__ __launch_bounds__(256) void range_flag_split_kernel(const float *x, size_t n4, int *flags, int idx) {
+    bool bad = false;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const u32x4 a = reinterpret_cast<const u32x4 *>(x)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) bad |= (a[e] & 0x7fffffffu) > 0x477fe000u;      // 65504.0f
+    }
+    if (__builtin_amdgcn_ballot_w64(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(flags + idx, 1);
+}
+static void launch_range_flag_split(const void *x, size_t elems, int *flags, int idx, hipStream_t st) {
+    const size_t n4 = elems / 4;
+    hipLaunchKernelGGL(range_flag_split_kernel, dim3((unsigned)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048)), dim3(256), 0, st, (const float *)x, n4, flags, idx);
+}
+
 const HostTensor *enc_find(pvr_encoder *e, const std::string &name) {
     auto it = e->weights.find(name);
     return it == e->weights.end() ? nullptr : &it->second;
@@ -147,7 +163,7 @@ static pvr_status finalize_conv(pvr_encoder *e, ConvOp &op) {
                 }
     std::vector<float> hb(cout_pad, 0.f);
     for (int co = 0; co < cor; ++co) hb[co] = shift[co];
-    if (e->desc.dtype == PVR_F32 || op.f32op || op.from32) {   // reference-precision mode / fp32 head of a 16-bit plan / a 16-bit conv reading fp32: same layout, fp32 values
+    if (stores_f32(e->desc.dtype) || op.f32op || op.from32) {   // reference-precision modes / fp32 head of a 16-bit plan / a 16-bit conv reading fp32: same layout, fp32 values
         std::vector<float> hf(cout_pad * K, 0.f);
         for (int co = 0; co < cor; ++co)
             for (int ci = 0; ci < cr; ++ci)
@@ -156,7 +172,7 @@ static pvr_status finalize_conv(pvr_encoder *e, ConvOp &op) {
                         hf[co * K + ((size_t)a * k + b) * op.cin + ci] = w->data[(((size_t)co * cr + ci) * k + a) * k + b] * scale[co];
         if ((s = enc_upload(&op.d_wf, hf))) return s;
         if (op.split16) {
-            // the fp32 stage / head of the parity plan on the 16-bit matrix pipe: (hi, lo) f16 pairs of the same fp32 weights (conv_split16.hip); for a from32
+            // the fp32 stage / head of the parity plan (every convolution of a PVR_F32S plan) on the 16-bit matrix pipe: (hi, lo) f16 pairs of the same fp32 weights (conv_split16.hip); for a from32
             // convolution only the hi half is used: f16(w), the 16-bit plan's own weight.  (d_wf stays until prepare_weights has made the head's pair image)
             PVR_HIP_TRY(hipMalloc((void **)&op.d_wsp, (size_t)cout_pad * K * 4));
             if ((s = launch_split16_pack(op.d_wf, op.d_wsp, cout_pad, (int)K, nullptr))) return s;
@@ -277,6 +293,20 @@ static pvr_status finalize_stem(pvr_encoder *e, const std::string &conv_name = "
         if ((s = enc_upload(&e->d_stem_wf, hf))) return s;
         return enc_upload(&e->d_stem_b, shift);
     }
+    if (e->desc.dtype == PVR_F32S) {              // the same folded fp32 weights in the 16-bit stem's K order (a 8 + b) 4 + c, as the split image stem_split16.hip reads
+        std::vector<float> hf(64 * 224, 0.f);
+        for (int co = 0; co < 64; ++co)
+            for (int c = 0; c < 3; ++c)
+                for (int t = 0; t < 49; ++t) hf[(size_t)co * 224 + ((t / 7) * 8 + t % 7) * 4 + c] = (float)wat(co, c, t / 7, t % 7) * scale[co];
+        float *d_hf = nullptr;
+        if ((s = enc_upload(&d_hf, hf))) return s;
+        PVR_HIP_TRY(hipMalloc((void **)&e->d_stem_w, 64 * 224 * 4));
+        s = launch_split16_pack(d_hf, e->d_stem_w, 64, 224, nullptr);
+        PVR_HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(d_hf);
+        if (s) return s;
+        return enc_upload(&e->d_stem_b, shift);
+    }
     std::vector<u16> hw(64 * 224, 0);
     for (int co = 0; co < 64; ++co)
         for (int a = 0; a < 7; ++a)
@@ -338,13 +368,16 @@ static pvr_status ensure_smallk(pvr_encoder *enc) {
 // activation workspace of the current lane (ResNet50 family)
 static pvr_status alloc_workspace(pvr_encoder *enc) {
     const int C = enc->desc.chunk, crop = enc->desc.crop;
-    const bool f32 = enc->desc.dtype == PVR_F32;
+    const bool f32 = stores_f32(enc->desc.dtype);
     const size_t esz = f32 ? 4 : 2;                               // activation element size
     const size_t img = (size_t)C * (crop + 6) * (crop + 8) * 4;
     PVR_HIP_TRY(hipMalloc((void **)&enc->d_img, img * 2));
     PVR_HIP_TRY(hipMemset(enc->d_img, 0, img * 2));            // zero border = conv1 padding, written once
     PVR_HIP_TRY(hipMalloc((void **)&enc->d_stem, (size_t)C * 112 * 112 * 64 * esz));
-    if (f32) PVR_HIP_TRY(hipMalloc((void **)&enc->d_imgf, (size_t)C * crop * crop * 4 * sizeof(float)));
+    if (enc->desc.dtype == PVR_F32S) {                         // the normalised image in d_img's zero-bordered layout: border written once, here
+        PVR_HIP_TRY(hipMalloc((void **)&enc->d_imgf, img * sizeof(float)));
+        PVR_HIP_TRY(hipMemset(enc->d_imgf, 0, img * sizeof(float)));
+    } else if (f32) PVR_HIP_TRY(hipMalloc((void **)&enc->d_imgf, (size_t)C * crop * crop * 4 * sizeof(float)));
     for (int b = 0; b < B_COUNT; ++b) {
         size_t bytes = enc->buf_elems * esz;
         if (b == B_F32) bytes = (size_t)C * enc->final_hw * enc->final_c * 4;
@@ -399,8 +432,8 @@ extern "C" {
 pvr_status pvr_encoder_create(const pvr_encoder_desc *desc, pvr_encoder **out) {
     PVR_REQUIRE(desc && out, "pvr_encoder_create: null argument");
     PVR_REQUIRE(desc->arch >= PVR_ARCH_RESNET50 && desc->arch <= PVR_ARCH_RESNET34, "unknown arch %d", desc->arch);
-    PVR_REQUIRE(desc->dtype == PVR_BF16 || desc->dtype == PVR_F16 || (desc->dtype == PVR_F32 && (desc->arch <= PVR_ARCH_RESNET50_L3 || desc->arch == PVR_ARCH_RESNET18 || desc->arch == PVR_ARCH_RESNET34)),
-                "dtype must be PVR_BF16 or PVR_F16 (PVR_F32 is built for the ResNet50 family only)");
+    PVR_REQUIRE(desc->dtype == PVR_BF16 || desc->dtype == PVR_F16 || (stores_f32(desc->dtype) && (desc->arch <= PVR_ARCH_RESNET50_L3 || desc->arch == PVR_ARCH_RESNET18 || desc->arch == PVR_ARCH_RESNET34)),
+                "dtype must be PVR_BF16 or PVR_F16 (PVR_F32 and PVR_F32S are built for the torchvision ResNet family only: ResNet50, its _l3 / _l4 variants, ResNet18 / 34)");
     PVR_REQUIRE(desc->max_batch > 0, "max_batch must be positive");
     PVR_REQUIRE(desc->crop == 224, "crop must be 224 (reference embeddings.py:82; CLIP input_resolution 224)");
     PVR_REQUIRE(desc->resize >= desc->crop, "resize must be >= crop");
@@ -418,6 +451,13 @@ pvr_status pvr_encoder_create(const pvr_encoder_desc *desc, pvr_encoder **out) {
         if (s) { delete e; return s; }
     } else {
         plan_encoder(e);                                        // the whole launch plan (encoder_plan.hip): finalize only prepares weights and workspace
+        if (e->desc.dtype == PVR_F32S)                          // every convolution runs on conv_split16: a shape it cannot take fails here, not at launch
+            for (const ConvOp &op : e->ops)
+                if (op.kind != 0 || !conv_split16_supported(op.cin, op.cout, op.k)) {
+                    set_error("PVR_F32S: %s (cin %d, cout %d, k %d) is not a conv_split16 shape", op.conv.c_str(), op.cin, op.cout, op.k);
+                    delete e;
+                    return PVR_ERR_INVALID;
+                }
     }
     *out = e;
     return PVR_OK;
@@ -438,6 +478,7 @@ pvr_status pvr_encoder_load_weights(pvr_encoder *enc, const char *name, const fl
 pvr_status pvr_encoder_set_host_backend(pvr_encoder *enc, int32_t on) {
     PVR_REQUIRE(enc, "null encoder");
     PVR_REQUIRE(!enc->finalized, "pvr_encoder_set_host_backend: call between create and finalize");
+    PVR_REQUIRE(!on || enc->desc.dtype != PVR_F32S, "pvr_encoder_set_host_backend: the CPU plan is fp32; create the encoder with dtype PVR_F32, not PVR_F32S");
     enc->host = on != 0;
     return PVR_OK;
 }
@@ -540,23 +581,34 @@ static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t 
             return PVR_OK;
         };
         if ((s = mark())) return s;
-        if (dt == PVR_F32) {
-            // reference-precision plan: integer transforms (exact, via the bf16 image) -> fp32 /255, Normalize ->
-            // fp32 conv1 -> fp32 maxpool -> fp32 implicit-GEMM convs (f32 MFMA) -> fp32 pool / flatten
+        if (stores_f32(dt)) {
+            // reference-precision plans: integer transforms (exact, via the bf16 image) -> fp32 /255, Normalize ->
+            // fp32 conv1 -> fp32 maxpool -> fp32 implicit-GEMM convs -> fp32 pool / flatten.  PVR_F32: every product on the f32-input MFMA;
+            // PVR_F32S: the same launches with every product as the exact split product on the 16-bit MFMA (the normalised image zero-bordered for stem_split16)
             const int crop = enc->desc.crop;
+            const bool split = dt == PVR_F32S;
             if ((s = launch_preprocess(fr, nb, h, w, enc->desc.resize, crop, enc->d_img, PVR_BF16, st, enc->crop_pos))) return s;
-            if ((s = launch_normalize_nhwc4(enc->d_img, enc->d_imgf, nb, crop, enc->desc.mean, enc->desc.std_, PVR_BF16, st))) return s;
+            if ((s = launch_normalize_nhwc4(enc->d_img, enc->d_imgf, nb, crop, enc->desc.mean, enc->desc.std_, PVR_BF16, st, split))) return s;
             if ((s = mark())) return s;
-            if ((s = launch_stem_f32(enc->d_imgf, enc->d_stem_wf, enc->d_stem_b, (float *)enc->d_stem, nb, crop, st))) return s;
+            if (split) s = launch_stem_split16(enc->d_imgf, enc->d_stem_w, enc->d_stem_b, (float *)enc->d_stem, nb, crop, st);
+            else s = launch_stem_f32(enc->d_imgf, enc->d_stem_wf, enc->d_stem_b, (float *)enc->d_stem, nb, crop, st);
+            if (s) return s;
+            if (enc->range_flags) launch_range_flag_split(enc->d_stem, (size_t)nb * 112 * 112 * 64, enc->range_flags, (int)enc->sched_plain.size(), st);   // (check_range: PVR_F32S only)
             if ((s = mark())) return s;
             if ((s = launch_maxpool_f32((const float *)enc->d_stem, (float *)enc->d_buf[B_X0], nb, 112, 112, 64, st))) return s;
             if ((s = mark())) return s;
             enc->last_n = nb;
             for (auto &op : enc->ops) {
                 const float *res = op.res_buf == B_NONE ? nullptr : (const float *)enc->d_buf[op.res_buf];
-                if ((s = launch_conv_f32((const float *)enc->d_buf[op.in_buf], op.d_wf, op.d_b, res, (float *)enc->d_buf[op.out_buf], nb,
-                                         op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st)))
-                    return s;
+                if (split) s = launch_conv_split16((const float *)enc->d_buf[op.in_buf], op.d_wsp, op.d_b, res, (float *)enc->d_buf[op.out_buf], nb,
+                                                   op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
+                else s = launch_conv_f32((const float *)enc->d_buf[op.in_buf], op.d_wf, op.d_b, res, (float *)enc->d_buf[op.out_buf], nb,
+                                         op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
+                if (s) return s;
+                if (enc->range_flags) {                 // pvr_encoder_check_range: the launch's output, all of it
+                    const int ho_ = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo_ = (op.w + 2 * op.pad - op.k) / op.stride + 1;
+                    launch_range_flag_split(enc->d_buf[op.out_buf], (size_t)nb * ho_ * wo_ * op.cout, enc->range_flags, (int)(&op - enc->ops.data()), st);
+                }
                 if ((s = mark())) return s;
             }
             float *o32 = out + (size_t)f0 * out_stride;
@@ -878,7 +930,7 @@ pvr_status pvr_encoder_profile(pvr_encoder *enc, const uint8_t *frames, int32_t 
         }
         // stem: 118.0 MMAC/frame = 112*112*64*147
         if (nl > 1) op_flops[1] = 2.0 * n * 112.0 * 112.0 * 64.0 * 147.0;
-        if (nl > 1 && enc->fuse && enc->stem_c1 >= 0 && enc->desc.dtype != PVR_F32) op_flops[1] += 2.0 * n * 56.0 * 56.0 * 64.0 * 64.0;   // layer1.0.conv1 runs inside the stem
+        if (nl > 1 && enc->fuse && enc->stem_c1 >= 0 && !stores_f32(enc->desc.dtype)) op_flops[1] += 2.0 * n * 56.0 * 56.0 * 64.0 * 64.0;   // layer1.0.conv1 runs inside the stem
         int i = 3;
         auto flops = [&](int oi) {
             if (oi < 0) return 0.0;
@@ -886,7 +938,7 @@ pvr_status pvr_encoder_profile(pvr_encoder *enc, const uint8_t *frames, int32_t 
             const double ho = (op.h + 2 * op.pad - op.k) / op.stride + 1;
             return 2.0 * n * ho * ho * (double)op.cout_real * op.k * op.k * op.cin_real;
         };
-        const bool fused = enc->fuse && enc->desc.dtype != PVR_F32;
+        const bool fused = enc->fuse && !stores_f32(enc->desc.dtype);
         for (const Launch &l : (fused ? enc->sched_fused : enc->sched_plain)) {
             if (i >= nl) break;
             op_flops[i++] = flops(l.conv1) + flops(l.conv2) + flops(l.conv3) + flops(l.next1) + flops(l.ds) + flops(l.pair);
@@ -977,7 +1029,7 @@ pvr_status pvr_encoder_check_range(pvr_encoder *enc, const uint8_t *frames, int3
     PVR_REQUIRE(enc && frames && out && first_bad, "pvr_encoder_check_range: null argument");
     PVR_NO_HOST(enc, "pvr_encoder_check_range");
     PVR_REQUIRE(enc->finalized && !enc->vit && !enc->rnd && enc->desc.arch != PVR_ARCH_CLIP_RN50 && enc->desc.dtype != PVR_F32,
-                "pvr_encoder_check_range: built for the 16-bit plans of the torchvision ResNet family");
+                "pvr_encoder_check_range: built for the 16-bit and PVR_F32S plans of the torchvision ResNet family (PVR_F32 has the full fp32 range)");
     PVR_REQUIRE(n > 0 && n <= enc->desc.chunk, "pvr_encoder_check_range: n=%d must fit one chunk (%d)", n, enc->desc.chunk);
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t nl = enc->sched_plain.size();
@@ -1045,11 +1097,11 @@ pvr_status pvr_encoder_tap(pvr_encoder *enc, const char *name, float *out, int64
     PVR_REQUIRE((int64_t)elems <= cap, "tap %s needs %zu elements, cap %lld", name, elems, (long long)cap);
     *count = (int64_t)elems;
     const bool img16 = nm == "pre";                     // the transformed image stays 16-bit in every mode
-    if (f32 || (enc->desc.dtype == PVR_F32 && !img16)) {
+    if (f32 || (stores_f32(enc->desc.dtype) && !img16)) {
         PVR_HIP_TRY(hipMemcpyAsync(out, src, elems * 4, hipMemcpyDeviceToDevice, st));
         return PVR_OK;
     }
-    return launch_h_to_f32(src, out, elems, enc->desc.dtype == PVR_F32 ? PVR_BF16 : enc->desc.dtype, st);
+    return launch_h_to_f32(src, out, elems, stores_f32(enc->desc.dtype) ? PVR_BF16 : enc->desc.dtype, st);
 }
 
 void pvr_encoder_destroy(pvr_encoder *enc) {

@@ -120,6 +120,10 @@ struct HostTensor {
     std::vector<float> data;
 };
 
+// the two fp32-storage compute types: PVR_F32 multiplies on the f32-input MFMA, PVR_F32S on the 16-bit MFMA as exact (hi, lo) split products (conv_split16.hip,
+// stem_split16.hip).  Workspace, weights layout, schedule, taps and profiling are the same for both
+inline bool stores_f32(int dtype) { return dtype == PVR_F32 || dtype == PVR_F32S; }
+
 constexpr int PVR_MAX_LANES = 4;
 // B_Y0 / B_Y1: fp32 residual stream of the compressed PVRs' parity plan (allocated only for that plan); B_STEM: d_stem (112x112x64), not in d_buf
 enum BufId { B_NONE = -1, B_X0 = 0, B_X1, B_T1, B_T2, B_DS, B_F32, B_Y0, B_Y1, B_COUNT, B_STEM = B_COUNT };
@@ -133,14 +137,14 @@ struct ConvOp {
     bool from32 = false;           // a 16-bit convolution (16-bit weights, one MFMA per product) whose INPUT is the fp32 residual stream: conv_split16's single-term
                                    // form rounds the operand in its staging pass - the fp32 -> 16-bit copy launch of the stream is gone (round 6)
     // plan facts, set by the planner at create (encoder_plan.hip) - finalize makes the device images they call for
-    bool split16 = false;          // an f32op / from32 convolution of an f16 plan that runs on conv_split16.hip (d_wsp)
+    bool split16 = false;          // an f32op / from32 convolution of an f16 plan, or any convolution of a PVR_F32S plan: runs on conv_split16.hip (d_wsp)
     bool wfrag = false;            // a per-frame launch's member, or a stand-alone launch conv_wfrag.hip may take by the batch: reads d_wfb
     u16 *d_w = nullptr;
     u16 *d_wp = nullptr;           // row-permuted copy for the fused bottleneck chain (bottleneck_chain.hip)
     u16 *d_wfb = nullptr;          // fragment-blocked copy of d_w for the per-frame layer3 tail (bneck_frame.hip: launch_pack_frag_weights)
     u16 *d_wpb = nullptr;          // ... and that copy in the blocked layout [row >> 4][cin >> 3][row & 15][8] (chain_wave.hip reads W3 / Wd pieces from L2)
     std::vector<u16> h_w;          // host copy, kept until finalize has built the packed copies (prepare_weights)
-    float *d_wf = nullptr;         // fp32 weights (PVR_F32 mode)
+    float *d_wf = nullptr;         // fp32 weights (PVR_F32 mode; PVR_F32S: only until finalize has packed d_wsp from them)
     u16 *d_wpk = nullptr;          // conv2 of a layer2 wave-form tail: the launch's 17 weight units as LDS images (chain_wave128.hip: launch_chain_wave128_pack)
     u16 *d_wsp_pair = nullptr;     // compression head: [conv1 ; downsample] rows as ONE split weight image (both read the same fp32 input: one launch, round 6)
     float *d_b_pair = nullptr;
@@ -227,7 +231,8 @@ struct pvr_encoder {
     int final_hw = 0, final_c = 0, final_creal = 0;   // geometry of the last activation
     // device
     u16 *d_img = nullptr, *d_stem = nullptr, *d_pool = nullptr, *d_stem_w = nullptr, *d_zero = nullptr;
-    float *d_stem_b = nullptr, *d_stem_wf = nullptr, *d_imgf = nullptr;   // fp32 mode: [64][49][4] stem weights, normalised NHWC4 image
+    float *d_stem_b = nullptr, *d_stem_wf = nullptr, *d_imgf = nullptr;   // fp32 mode: [64][49][4] stem weights, normalised NHWC4 image (PVR_F32S: d_stem_w holds the
+                                                                          // split image of the [64][7][8][4] weights, d_imgf the zero-bordered (crop + 6, crop + 8) image)
     void *d_buf[B_COUNT] = {nullptr};
     size_t buf_elems = 0;
     // second activation workspace (pvr_encoder_forward_lane, lane 1): lets the caller keep two batches in flight on two
@@ -275,7 +280,11 @@ pvr_status enc_upload(T **dptr, const std::vector<T> &h) {
 pvr_status launch_conv_f32(const float *, const float *, const float *, const float *, float *, int, int, int, int, int, int, int, int, int, hipStream_t);
 pvr_status launch_stem_f32(const float *, const float *, const float *, float *, int, int, hipStream_t);
 pvr_status launch_maxpool_f32(const float *, float *, int, int, int, int, hipStream_t);
-pvr_status launch_normalize_nhwc4(const void *img_h, float *out, int n, int crop, const float *mean, const float *std_, int dtype, hipStream_t);
+// (padded: the output in the zero-bordered (n, crop + 6, crop + 8, 4) layout stem_split16.hip reads, border untouched)
+pvr_status launch_normalize_nhwc4(const void *img_h, float *out, int n, int crop, const float *mean, const float *std_, int dtype, hipStream_t, bool padded = false);
+// stem_split16.hip (PVR_F32S: conv1 as the exact split product on the 16-bit MFMA)
+pvr_status launch_stem_split16(const float *img_padded, const void *wsp, const float *bias, float *out, int n, int S, hipStream_t);
+long long stem_split16_launches();
 // random_pvr.hip
 pvr_status random5_create(pvr_encoder *e);
 pvr_status random5_finalize(pvr_encoder *e);

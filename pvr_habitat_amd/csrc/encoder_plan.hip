@@ -235,7 +235,7 @@ static void build_clip_rn50(pvr_encoder *e) {
 // measured) get 8 K ranges and, as scratch for the fp32 partial planes, a 16-bit ping-pong buffer that is
 // dead at that point of the plan (not read by this or any later op before it is overwritten).  PVR_SPLITK=0 turns it off.
 static void plan_splitk(pvr_encoder *e) {
-    if (!e->sw.splitk || e->desc.dtype == PVR_F32) return;
+    if (!e->sw.splitk || stores_f32(e->desc.dtype)) return;
     const int n = (int)e->ops.size();
     for (int i = 0; i < n; ++i) {
         ConvOp &op = e->ops[i];
@@ -530,7 +530,7 @@ static void plan_y_s2(pvr_encoder *e) {
 static void build_schedules(pvr_encoder *e) {
     const int n = (int)e->ops.size();
     for (int i = 0; i < n; ++i) { Launch l; l.conv2 = i; e->sched_plain.push_back(l); }
-    if (e->desc.dtype == PVR_F32 || e->desc.arch == PVR_ARCH_CLIP_RN50) { e->sched_fused = e->sched_plain; return; }   // (CLIP: pools between the convolutions)
+    if (stores_f32(e->desc.dtype) || e->desc.arch == PVR_ARCH_CLIP_RN50) { e->sched_fused = e->sched_plain; return; }   // (CLIP: pools between the convolutions)
     plan_blocks(e);
     plan_wave_forms(e);
     plan_wave128(e);
@@ -569,6 +569,7 @@ int small_batch_ksplit(const pvr_encoder *enc, const ConvOp &op, int nb) {
 uint8_t resolve_kind(const pvr_encoder *enc, const std::vector<Launch> &plan, size_t li, int nb, bool allow_pool) {
     const Launch &l = plan[li];
     const ConvOp &op = enc->ops[l.conv3 >= 0 ? l.conv3 : l.conv2];
+    if (enc->desc.dtype == PVR_F32S) return LK_SPLIT16;          // one launch per convolution, whatever the batch: no fused plan, no split-K, no frame kernels
     const bool ll = enc->low_latency && nb <= 4;                 // (the low-latency plan covers forwards of <= 4 frames: small_batch_ksplit)
     const bool autoalgo = enc->sw.conv_algo == -1;
     if (l.frame) {
@@ -606,8 +607,8 @@ void resolve_kinds(pvr_encoder *enc) {
     const std::vector<Launch> &plan = cur_plan(enc);
     const int chunk = enc->desc.chunk;
     enc->kinds_stride = plan.size();
-    enc->kinds.assign((size_t)chunk * plan.size(), LK_CONV);
-    if (enc->desc.dtype == PVR_F32 || enc->desc.arch == PVR_ARCH_CLIP_RN50 || enc->vit || enc->rnd || enc->host) return;
+    enc->kinds.assign((size_t)chunk * plan.size(), enc->desc.dtype == PVR_F32S ? LK_SPLIT16 : LK_CONV);
+    if (stores_f32(enc->desc.dtype) || enc->desc.arch == PVR_ARCH_CLIP_RN50 || enc->vit || enc->rnd || enc->host) return;
     for (int nb = 1; nb <= chunk; ++nb)
         for (size_t i = 0; i < plan.size(); ++i) enc->kinds[(size_t)(nb - 1) * plan.size() + i] = resolve_kind(enc, plan, i, nb);
     // a tail that stores y only at its stride-2 reader's pixels (Launch::y_s2): where that reader runs on conv_expand at stride 2 and would at stride 1
@@ -648,7 +649,8 @@ void plan_encoder(pvr_encoder *e) {
     else build_resnet50(e);
     e->buf_elems = (size_t)e->desc.chunk * 56 * 56 * 256;         // largest activation (layer1 output)
     for (ConvOp &op : e->ops)                                     // the fp32 stage / head of the parity plan and the readers of its fp32 stream, on the 16-bit MFMA
-        op.split16 = (op.f32op || op.from32) && e->desc.dtype == PVR_F16 && e->sw.split16 && conv_split16_supported(op.cin, op.cout, op.k);
+        op.split16 = e->desc.dtype == PVR_F32S ? op.kind == 0                   // the fp32-parity mode on the 16-bit MFMA: every convolution (pvr_encoder_create refuses a plan with a shape conv_split16 cannot take)
+                                               : (op.f32op || op.from32) && e->desc.dtype == PVR_F16 && e->sw.split16 && conv_split16_supported(op.cin, op.cout, op.k);
     plan_splitk(e);
     build_schedules(e);
     e->fuse = e->sw.fuse != 0;
@@ -683,7 +685,7 @@ int32_t pvr_encoder_launch_name(const pvr_encoder *enc, int32_t index, char *buf
     static const char *head[3] = {"preprocess", "stem", "maxpool"};
     if (index < 3) nm = head[index];
     else {
-        const bool fused = enc->fuse && enc->desc.dtype != PVR_F32;
+        const bool fused = enc->fuse && !stores_f32(enc->desc.dtype);
         const std::vector<Launch> &sc = fused ? enc->sched_fused : enc->sched_plain;
         const int i = index - 3;
         if (i < (int)sc.size()) {

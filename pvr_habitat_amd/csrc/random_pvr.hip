@@ -8,6 +8,9 @@
 namespace pvr {
 
 // uint8 NHWC frame -> Resize(256, bilinear, round to uint8) -> CenterCrop(224) -> /255 -> Normalize, as fp32 NHWC4
+// PAD: the output keeps the input's zero-bordered layout (n, crop + 6, crop + 8, 4), pixel (y, x) at [y + 3][x + 3] - the image stem_split16.hip reads (the
+// border is written once, at allocation); else dense (n, crop, crop, 4)
+template <bool PAD>
 __global__ __launch_bounds__(256) void normalize_nhwc4_kernel(const u16 *__restrict__ img_h, float *__restrict__ out, int n, int crop,
                                                               float m0, float m1, float m2, float s0, float s1, float s2, int f16) {
     // img_h is the stem input image written by preprocess_kernel: (n, crop+6, crop+8, 4) 16-bit holding x-128 exactly
@@ -20,17 +23,23 @@ __global__ __launch_bounds__(256) void normalize_nhwc4_kernel(const u16 *__restr
                     bl = (f16 ? from_h<true>(v.z) : from_h<false>(v.z)) + 128.f;
         f32x4 o;
         o[0] = (r / 255.0f - m0) / s0; o[1] = (g / 255.0f - m1) / s1; o[2] = (bl / 255.0f - m2) / s2; o[3] = 0.f;
-        reinterpret_cast<f32x4 *>(out)[i] = o;
+        if constexpr (PAD) reinterpret_cast<f32x4 *>(out)[((size_t)b * PH + y + 3) * PW + x + 3] = o;
+        else reinterpret_cast<f32x4 *>(out)[i] = o;
     }
 }
 
 }  // namespace pvr
 
 namespace pvr {
-pvr_status launch_normalize_nhwc4(const void *img_h, float *out, int n, int crop, const float *mean, const float *std_, int dtype, hipStream_t st) {
+pvr_status launch_normalize_nhwc4(const void *img_h, float *out, int n, int crop, const float *mean, const float *std_, int dtype, hipStream_t st, bool padded) {
     const size_t tot = (size_t)n * crop * crop;
-    hipLaunchKernelGGL(normalize_nhwc4_kernel, dim3((unsigned)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256)), dim3(256), 0, st,
-                       (const u16 *)img_h, out, n, crop, mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], dtype == PVR_F16 ? 1 : 0);
+    const dim3 grid((unsigned)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256));
+    if (padded)
+        hipLaunchKernelGGL(normalize_nhwc4_kernel<true>, grid, dim3(256), 0, st,
+                           (const u16 *)img_h, out, n, crop, mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], dtype == PVR_F16 ? 1 : 0);
+    else
+        hipLaunchKernelGGL(normalize_nhwc4_kernel<false>, grid, dim3(256), 0, st,
+                           (const u16 *)img_h, out, n, crop, mean[0], mean[1], mean[2], std_[0], std_[1], std_[2], dtype == PVR_F16 ? 1 : 0);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }
@@ -95,7 +104,7 @@ pvr_status random5_forward(pvr_encoder *e, const uint8_t *frames, int n, int h, 
         // the uint8 part of the transforms is shared with the ResNet path (bit-exact vs the oracle); x-128 is exact in 16 bits
         if ((s = launch_preprocess(frames + (size_t)f0 * h * w * 3, nb, h, w, e->desc.resize, crop, r->img_h, dt, st))) return s;
         const size_t tot = (size_t)nb * crop * crop;
-        hipLaunchKernelGGL(normalize_nhwc4_kernel, dim3((unsigned)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256)), dim3(256), 0, st,
+        hipLaunchKernelGGL(normalize_nhwc4_kernel<false>, dim3((unsigned)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256)), dim3(256), 0, st,
                            r->img_h, r->img, nb, crop, e->desc.mean[0], e->desc.mean[1], e->desc.mean[2], e->desc.std_[0], e->desc.std_[1],
                            e->desc.std_[2], dt == PVR_F16 ? 1 : 0);
         const void *in = r->img;

@@ -89,7 +89,11 @@ def _dtype_from_env(compute_dtype=None):
         return _lib.PVR_F16
     if d in ('f32', 'fp32', 'float32'):
         return _lib.PVR_F32                     # reference-precision mode (ResNet50 family only): f32 MFMA, ~1/8 the speed
-    raise ValueError('compute dtype must be bf16, f16 or f32, got %r' % d)
+    if d in ('f32s', 'f32_split'):
+        # fp32 storage as 'f32', every product on the 16-bit MFMA as an exact (hi, lo) f16 split product: ~1e-6 from 'f32' at several times its rate.  The
+        # high part is an f16, so activations must stay below 65504 (validate_range checks the first frames; 'f32' has the full range)
+        return _lib.PVR_F32S
+    raise ValueError('compute dtype must be bf16, f16, f32 or f32s, got %r' % d)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -312,7 +316,8 @@ class HipResNet50(_Node):
     def check_range(self, frames_u8):
         """Load-time validation of the 16-bit storage range on real frames (pvr_encoder_check_range): one forward of the UNFUSED plan with every launch's
         output checked for inf / NaN - an overflow inside the network can be turned into a finite, wrong embedding by the next ReLU, which the finite check of
-        the output cannot see.  Returns the name of the first convolution whose output is non-finite, or None.  ResNet family, 16-bit plans."""
+        the output cannot see.  Returns the name of the first convolution whose output is non-finite, or None.  ResNet family, 16-bit plans - and 'f32s' plans,
+        where an output above 65504 in magnitude counts as well: the next convolution rounds the high part of its operand to f16."""
         if self._handle is None:
             self._build()
         n = min(int(frames_u8.shape[0]), self._chunk or self._max_batch)
@@ -601,7 +606,7 @@ class EmbeddingNet(nn.Module):
         return self._forward(observation)
 
     def validate_range(self, observation_dev, max_frames=8):
-        """ONE-OFF, on the first frames this net embeds (PVR_RANGE_CHECK=0 skips it): every f16 ResNet member runs pvr_encoder_check_range on up to
+        """ONE-OFF, on the first frames this net embeds (PVR_RANGE_CHECK=0 skips it): every f16 or f32s ResNet member runs pvr_encoder_check_range on up to
         `max_frames` of them.  The reference is fp32 (src/embeddings.py:386-402); f16 storage has 5 exponent bits, and an activation that overflows inside the
         network can come out as a finite, wrong embedding (ReLU maps -inf and NaN to 0) - this names the convolution instead.  It validates THESE frames with
         THIS checkpoint, not every later batch; the per-batch finite check of the outputs stays."""
@@ -611,8 +616,11 @@ class EmbeddingNet(nn.Module):
         for m in [self.embedding] + [x for x in getattr(self.embedding, 'model', [])]:
             members += list(getattr(m, 'models', [m]))
         for m in members:
-            if isinstance(m, HipResNet50) and m._dtype == _lib.PVR_F16 and m.variant in ('conv5', 'conv4', 'conv3', 'r18', 'r34'):
+            if isinstance(m, HipResNet50) and m._dtype in (_lib.PVR_F16, _lib.PVR_F32S) and m.variant in ('conv5', 'conv4', 'conv3', 'r18', 'r34'):
                 bad = m.check_range(observation_dev[:max_frames])
+                if bad is not None and m._dtype == _lib.PVR_F32S:
+                    raise FloatingPointError("activations of '%s' leave the f16 range of the split product's high parts on these frames (first output above "
+                                             "65504: %s): use compute_dtype='f32' (full fp32 range) for this checkpoint" % (self.embedding_name, bad))
                 if bad is not None:
                     raise FloatingPointError("activations of '%s' leave the f16 range on these frames (first non-finite output: %s): "
                                              "use compute_dtype='bf16' (8 exponent bits) or 'f32' for this checkpoint" % (self.embedding_name, bad))
@@ -630,9 +638,13 @@ def _checked(host_out, model):
     """The embeddings are on the host anyway: a non-finite value means an activation left the 16-bit storage range (f16 has
     5 exponent bits; the reference computes in fp32).  Fail loudly instead of handing garbage to the BC stage."""
     if not np.isfinite(host_out).all():
+        dt = getattr(model, '_dtype', None)
+        if dt == _lib.PVR_F32S:
+            raise FloatingPointError("non-finite embedding: activations overflowed the f16 high parts of the split product (f32s); "
+                                     "use compute_dtype='f32' (full fp32 range) for this checkpoint")
         raise FloatingPointError('non-finite embedding: activations overflowed the encoder storage type (%s); '
                                  "use compute_dtype='bf16' (8 exponent bits) or 'f32' for this checkpoint"
-                                 % {_lib.PVR_F16: 'f16', _lib.PVR_BF16: 'bf16', _lib.PVR_F32: 'f32'}.get(getattr(model, '_dtype', None), 'mixed'))
+                                 % {_lib.PVR_F16: 'f16', _lib.PVR_BF16: 'bf16', _lib.PVR_F32: 'f32', _lib.PVR_F32S: 'f32s'}.get(dt, 'mixed'))
     return host_out
 
 
