@@ -353,36 +353,43 @@ static pvr_status finalize_attnpool(pvr_encoder *e) {
 
 }  // namespace pvr
 
-static void *bufp(pvr_encoder *enc, int id) { return id == B_STEM ? (void *)enc->d_stem : enc->d_buf[id]; }
+using Lane = pvr_encoder::Lane;
+
+static void *bufp(const Lane &L, int id) { return id == B_STEM ? (void *)L.d_stem : L.buf[id]; }
 
 // The low-latency plan's scratch, for every lane that has a workspace: allocated when the plan is switched on (pvr_encoder_set_low_latency), at
 // finalize when it was switched on before, and when a lane's workspace is first made - never inside a forward (no allocation on the
 // forward path after finalize).
+static pvr_status lane_smallk(pvr_encoder *enc, Lane &L) {
+    if (enc->low_latency && !L.d_smallk) PVR_HIP_TRY(hipMalloc((void **)&L.d_smallk, SMALLK_BYTES));
+    return PVR_OK;
+}
 static pvr_status ensure_smallk(pvr_encoder *enc) {
-    if (!enc->low_latency || enc->vit || enc->rnd || enc->host) return PVR_OK;
-    for (int l = 0; l < PVR_MAX_LANES; ++l)
-        if (enc->lane_ws[l].valid && !enc->d_smallk[l]) PVR_HIP_TRY(hipMalloc((void **)&enc->d_smallk[l], SMALLK_BYTES));
+    if (enc->vit || enc->rnd || enc->host) return PVR_OK;
+    pvr_status s;
+    for (Lane &L : enc->lanes)
+        if (L.valid && (s = lane_smallk(enc, L))) return s;
     return PVR_OK;
 }
 
-// activation workspace of the current lane (ResNet50 family)
-static pvr_status alloc_workspace(pvr_encoder *enc) {
+// activation workspace of one lane (ResNet50 family)
+static pvr_status alloc_workspace(pvr_encoder *enc, Lane &L) {
     const int C = enc->desc.chunk, crop = enc->desc.crop;
     const bool f32 = stores_f32(enc->desc.dtype);
     const size_t esz = f32 ? 4 : 2;                               // activation element size
     const size_t img = (size_t)C * (crop + 6) * (crop + 8) * 4;
-    PVR_HIP_TRY(hipMalloc((void **)&enc->d_img, img * 2));
-    PVR_HIP_TRY(hipMemset(enc->d_img, 0, img * 2));            // zero border = conv1 padding, written once
-    PVR_HIP_TRY(hipMalloc((void **)&enc->d_stem, (size_t)C * 112 * 112 * 64 * esz));
+    PVR_HIP_TRY(hipMalloc((void **)&L.d_img, img * 2));
+    PVR_HIP_TRY(hipMemset(L.d_img, 0, img * 2));            // zero border = conv1 padding, written once
+    PVR_HIP_TRY(hipMalloc((void **)&L.d_stem, (size_t)C * 112 * 112 * 64 * esz));
     if (enc->desc.dtype == PVR_F32S) {                         // the normalised image in d_img's zero-bordered layout: border written once, here
-        PVR_HIP_TRY(hipMalloc((void **)&enc->d_imgf, img * sizeof(float)));
-        PVR_HIP_TRY(hipMemset(enc->d_imgf, 0, img * sizeof(float)));
-    } else if (f32) PVR_HIP_TRY(hipMalloc((void **)&enc->d_imgf, (size_t)C * crop * crop * 4 * sizeof(float)));
+        PVR_HIP_TRY(hipMalloc((void **)&L.d_imgf, img * sizeof(float)));
+        PVR_HIP_TRY(hipMemset(L.d_imgf, 0, img * sizeof(float)));
+    } else if (f32) PVR_HIP_TRY(hipMalloc((void **)&L.d_imgf, (size_t)C * crop * crop * 4 * sizeof(float)));
     for (int b = 0; b < B_COUNT; ++b) {
         size_t bytes = enc->buf_elems * esz;
         if (b == B_F32) bytes = (size_t)C * enc->final_hw * enc->final_c * 4;
         if ((b == B_Y0 || b == B_Y1) && !enc->resid32) continue;             // fp32 residual stream: parity plan of the compressed PVRs only
-        PVR_HIP_TRY(hipMalloc(&enc->d_buf[b], bytes));
+        PVR_HIP_TRY(hipMalloc(&L.buf[b], bytes));
     }
     return PVR_OK;
 }
@@ -391,39 +398,28 @@ static pvr_status alloc_zero_page(pvr_encoder *enc) {          // padding rows, 
     PVR_HIP_TRY(hipMemset(enc->d_zero, 0, PVR_ZERO_BYTES));
     return PVR_OK;
 }
-static void save_lane(pvr_encoder *enc, int lane) {
-    auto &l = enc->lane_ws[lane];
-    l.d_img = enc->d_img; l.d_stem = enc->d_stem; l.d_imgf = enc->d_imgf;
-    for (int b = 0; b < B_COUNT; ++b) l.d_buf[b] = enc->d_buf[b];
-    l.valid = true; enc->cur_lane = lane;
+static void lane_free(Lane &L) {                               // whatever of the lane exists (a failed first use, pvr_encoder_destroy)
+    for (void *q : L.buf) if (q) (void)hipFree(q);
+    for (void *q : {(void *)L.d_img, (void *)L.d_stem, (void *)L.d_imgf, (void *)L.d_smallk}) if (q) (void)hipFree(q);
+    if (L.done) (void)hipEventDestroy(L.done);
+    L = Lane();
 }
-static pvr_status use_lane(pvr_encoder *enc, int lane) {
-    if (lane == enc->cur_lane) return PVR_OK;
-    if (!enc->lane_ws[lane].valid) {                            // first use: allocate, off the hot path
-        // allocate into the encoder's current-pointer slots, but keep the previous lane's pointers aside: if any hipMalloc fails
-        // (a ~3 GB workspace can), free what was allocated and put the previous lane back, so the encoder stays usable
-        const int prev = enc->cur_lane;
-        enc->d_img = nullptr; enc->d_stem = nullptr; enc->d_imgf = nullptr;
-        for (int b = 0; b < B_COUNT; ++b) enc->d_buf[b] = nullptr;
-        pvr_status s = alloc_workspace(enc);
-        if (!s && hipDeviceSynchronize() != hipSuccess) { set_error("use_lane: device sync failed"); s = PVR_ERR_HIP; }
-        if (s) {
-            for (int b = 0; b < B_COUNT; ++b) if (enc->d_buf[b]) (void)hipFree(enc->d_buf[b]);
-            if (enc->d_img) (void)hipFree(enc->d_img);
-            if (enc->d_stem) (void)hipFree(enc->d_stem);
-            if (enc->d_imgf) (void)hipFree(enc->d_imgf);
-            const auto &l = enc->lane_ws[prev];
-            enc->d_img = l.d_img; enc->d_stem = l.d_stem; enc->d_imgf = l.d_imgf;
-            for (int b = 0; b < B_COUNT; ++b) enc->d_buf[b] = l.d_buf[b];
-            return s;
-        }
-        save_lane(enc, lane);
-        return ensure_smallk(enc);
+// The lane a forward runs on.  First use (lane 0: finalize) allocates it off the hot path, into a local Lane that enters the array only when every
+// allocation succeeded (a ~3 GB workspace can fail): the other lanes are never touched, so the encoder stays usable.  The memsets run on the null
+// stream and forwards on the caller's (torch's current stream need not be ordered against it), so the device is drained once here.
+static pvr_status get_lane(pvr_encoder *enc, int lane, Lane **out) {
+    Lane &slot = enc->lanes[lane];
+    if (!slot.valid) {
+        Lane L;
+        pvr_status s = alloc_workspace(enc, L);
+        if (!s) s = lane_smallk(enc, L);
+        if (!s && hipDeviceSynchronize() != hipSuccess) { set_error("get_lane: device sync failed"); s = PVR_ERR_HIP; }
+        if (s) { lane_free(L); return s; }
+        if (enc->ap_out) L.ap_rows = enc->ap_out + (size_t)lane * enc->desc.chunk * 1024;
+        L.valid = true;
+        slot = L;
     }
-    const auto &l = enc->lane_ws[lane];
-    enc->d_img = l.d_img; enc->d_stem = l.d_stem; enc->d_imgf = l.d_imgf;
-    for (int b = 0; b < B_COUNT; ++b) enc->d_buf[b] = l.d_buf[b];
-    enc->cur_lane = lane;
+    *out = &slot;
     return PVR_OK;
 }
 
@@ -506,13 +502,10 @@ pvr_status pvr_encoder_finalize(pvr_encoder *enc) {
         op.h_w.clear(); op.h_w.shrink_to_fit(); op.h_b.clear(); op.h_b.shrink_to_fit();
         if (op.split16 && op.d_wf) { (void)hipFree(op.d_wf); op.d_wf = nullptr; }     // fp32 weights that were only the source of a split image
     }
-    if ((s = alloc_workspace(enc))) return s;
+    Lane *lane0;
+    if ((s = get_lane(enc, 0, &lane0))) return s;               // (with the low-latency scratch when the plan was switched on before)
     if ((s = alloc_zero_page(enc))) return s;
-    save_lane(enc, 0);
-    if ((s = ensure_smallk(enc))) return s;
-    // the memsets above run on the null stream; forwards run on the caller's stream (torch's current
-    // stream need not be ordered against it), so drain the device once here, off the hot path
-    PVR_HIP_TRY(hipDeviceSynchronize());
+    PVR_HIP_TRY(hipDeviceSynchronize());                        // (its memset runs on the null stream, forwards on the caller's: see get_lane)
     enc->weights.clear();                                       // host copies no longer needed
     enc->finalized = true;
     return PVR_OK;
@@ -525,349 +518,373 @@ int32_t pvr_encoder_out_size(const pvr_encoder *enc) { return enc ? enc->out_siz
 // One chunk of the CLIP RN50 tower: Resize(224, bicubic, antialias) + CenterCrop -> stem image -> conv1 (stem kernel) -> plan
 // (convolutions and 2x2 average pools) -> attention pool (tokens, fused q/k/v GEMM, attention core, c_proj of token 0).
 
-static pvr_status clip_rn50_chunk(pvr_encoder *enc, const uint8_t *fr, int nb, int h, int w, float *out, int64_t out_stride, hipStream_t st) {
+static pvr_status clip_rn50_chunk(pvr_encoder *enc, Lane &L, int lane, const uint8_t *fr, int nb, int h, int w, float *out, int64_t out_stride, hipStream_t st) {
     const int dt = enc->desc.dtype, crop = enc->desc.crop;
     pvr_status s;
     const uint8_t *u8; int oh, ow;
-    if ((s = resizer_run(enc, enc->cur_lane, fr, nb, h, w, st, &u8, &oh, &ow))) return s;
+    if ((s = resizer_run(enc, lane, fr, nb, h, w, st, &u8, &oh, &ow))) return s;
     // short side == crop here, so this only centre-crops and converts to the stem's centred 4-channel image
-    if ((s = launch_preprocess(u8, nb, oh, ow, enc->desc.resize, crop, enc->d_img, dt, st))) return s;
+    if ((s = launch_preprocess(u8, nb, oh, ow, enc->desc.resize, crop, L.d_img, dt, st))) return s;
     enc->last_n = nb;
     if (enc->stop_after == "pre") return PVR_OK;
-    if ((s = launch_stem(enc->d_img, enc->d_stem_w, enc->d_stem_b, enc->d_stem, nb, crop, dt, st))) return s;
+    if ((s = launch_stem(L.d_img, enc->d_stem_w, enc->d_stem_b, L.d_stem, nb, crop, dt, st))) return s;
     for (const ConvOp &op : enc->ops) {
-        if (op.kind == 1) s = launch_avgpool2(bufp(enc, op.in_buf), bufp(enc, op.out_buf), nb, op.h, op.w, op.cin, dt, st);
-        else s = launch_conv(enc->sw, bufp(enc, op.in_buf), op.d_w, op.d_b, op.res_buf == B_NONE ? nullptr : bufp(enc, op.res_buf), bufp(enc, op.out_buf),
+        if (op.kind == 1) s = launch_avgpool2(bufp(L, op.in_buf), bufp(L, op.out_buf), nb, op.h, op.w, op.cin, dt, st);
+        else s = launch_conv(enc->sw, bufp(L, op.in_buf), op.d_w, op.d_b, op.res_buf == B_NONE ? nullptr : bufp(L, op.res_buf), bufp(L, op.out_buf),
                              enc->d_zero, nb, op.h, op.w, op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
         if (s) return s;
         if (!enc->stop_after.empty() && op.tap == enc->stop_after) return PVR_OK;
     }
     // AttentionPool2d(7, 2048, 32 heads, 1024)
     const int C = 2048, T = 50;
-    if ((s = launch_attnpool_tokens((const float *)enc->d_buf[B_F32], enc->ap_pos, enc->d_buf[B_T1], nb, 49, C, dt, st))) return s;
-    if ((s = launch_conv(enc->sw, enc->d_buf[B_T1], enc->ap_wqkv, enc->ap_bqkv, nullptr, enc->d_buf[B_X0], enc->d_zero, nb * T, 1, 1, C, 3 * C, 1, 1, 1, 0, 0, 0, dt, st))) return s;
-    if ((s = launch_attention(enc->d_buf[B_X0], enc->d_buf[B_T2], T, C, 32, nb, dt, st))) return s;
+    if ((s = launch_attnpool_tokens((const float *)L.buf[B_F32], enc->ap_pos, L.buf[B_T1], nb, 49, C, dt, st))) return s;
+    if ((s = launch_conv(enc->sw, L.buf[B_T1], enc->ap_wqkv, enc->ap_bqkv, nullptr, L.buf[B_X0], enc->d_zero, nb * T, 1, 1, C, 3 * C, 1, 1, 1, 0, 0, 0, dt, st))) return s;
+    if ((s = launch_attention(L.buf[B_X0], L.buf[B_T2], T, C, 32, nb, dt, st))) return s;
     // c_proj of token 0 only: a 1x1 "convolution" over (n, T, 1) with stride T picks row 0 of every image; fp32 out
-    float *dense = enc->ap_out + (size_t)enc->cur_lane * enc->desc.chunk * 1024;
-    if ((s = launch_conv(enc->sw, enc->d_buf[B_T2], enc->ap_wc, enc->ap_bc, nullptr, dense, enc->d_zero, nb, T, 1, C, 1024, 1, 1, T, 0, 0, 1, dt, st))) return s;
+    float *dense = L.ap_rows;
+    if ((s = launch_conv(enc->sw, L.buf[B_T2], enc->ap_wc, enc->ap_bc, nullptr, dense, enc->d_zero, nb, T, 1, C, 1024, 1, 1, T, 0, 0, 1, dt, st))) return s;
     PVR_HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride * 4, dense, 1024 * 4, 1024 * 4, nb, hipMemcpyDeviceToDevice, st));
     return PVR_OK;
 }
 
-// ev != nullptr: record one event before the first launch and one after every launch of the FIRST chunk
-static pvr_status forward_impl(pvr_encoder *enc, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *out,
-                               int64_t out_stride, void *hip_stream, std::vector<hipEvent_t> *ev) {
+// Per-call inputs of a forward that only the instrumented entry points set
+struct ForwardArgs {
+    std::vector<hipEvent_t> *ev = nullptr;        // pvr_encoder_profile: one event before the first launch and one after every launch of the FIRST chunk
+    int rec_first = -1, rec_last = -1;            // pvr_encoder_profile_span: only these two marks are recorded, the others are placeholders
+    int *bad_flags = nullptr;                     // pvr_encoder_check_range: per-launch "output holds inf / NaN" flags of this forward
+};
+static pvr_status mark_launch(const ForwardArgs &fa, hipStream_t st) {
+    if (fa.ev) {
+        hipEvent_t e;
+        PVR_HIP_TRY(hipEventCreate(&e));
+        const int idx = (int)fa.ev->size();
+        if (fa.rec_first < 0 || idx == fa.rec_first || idx == fa.rec_last) PVR_HIP_TRY(hipEventRecord(e, st));
+        fa.ev->push_back(e);
+    }
+    return PVR_OK;
+}
+
+// One chunk of the reference-precision plans: integer transforms (exact, via the bf16 image) -> fp32 /255, Normalize ->
+// fp32 conv1 -> fp32 maxpool -> fp32 implicit-GEMM convs -> fp32 pool / flatten.  PVR_F32: every product on the f32-input MFMA;
+// PVR_F32S: the same launches with every product as the exact split product on the 16-bit MFMA (the normalised image zero-bordered for stem_split16)
+static pvr_status f32_chunk(pvr_encoder *enc, Lane &L, const uint8_t *fr, int nb, int h, int w, float *out, int64_t out_stride, hipStream_t st, const ForwardArgs &fa) {
+    const int dt = enc->desc.dtype;
+    pvr_status s;
+    auto mark = [&] { return mark_launch(fa, st); };
+    const int crop = enc->desc.crop;
+    const bool split = dt == PVR_F32S;
+    if ((s = launch_preprocess(fr, nb, h, w, enc->desc.resize, crop, L.d_img, PVR_BF16, st, enc->crop_pos))) return s;
+    if ((s = launch_normalize_nhwc4(L.d_img, L.d_imgf, nb, crop, enc->desc.mean, enc->desc.std_, PVR_BF16, st, split))) return s;
+    if ((s = mark())) return s;
+    if (split) s = launch_stem_split16(L.d_imgf, enc->d_stem_w, enc->d_stem_b, (float *)L.d_stem, nb, crop, st);
+    else s = launch_stem_f32(L.d_imgf, enc->d_stem_wf, enc->d_stem_b, (float *)L.d_stem, nb, crop, st);
+    if (s) return s;
+    if (fa.bad_flags) launch_range_flag_split(L.d_stem, (size_t)nb * 112 * 112 * 64, fa.bad_flags, (int)enc->sched_plain.size(), st);   // (check_range: PVR_F32S only)
+    if ((s = mark())) return s;
+    if ((s = launch_maxpool_f32((const float *)L.d_stem, (float *)L.buf[B_X0], nb, 112, 112, 64, st))) return s;
+    if ((s = mark())) return s;
+    enc->last_n = nb;
+    for (auto &op : enc->ops) {
+        const float *res = op.res_buf == B_NONE ? nullptr : (const float *)L.buf[op.res_buf];
+        if (split) s = launch_conv_split16((const float *)L.buf[op.in_buf], op.d_wsp, op.d_b, res, (float *)L.buf[op.out_buf], nb,
+                                           op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
+        else s = launch_conv_f32((const float *)L.buf[op.in_buf], op.d_wf, op.d_b, res, (float *)L.buf[op.out_buf], nb,
+                                 op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
+        if (s) return s;
+        if (fa.bad_flags) {                 // pvr_encoder_check_range: the launch's output, all of it
+            const int ho_ = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo_ = (op.w + 2 * op.pad - op.k) / op.stride + 1;
+            launch_range_flag_split(L.buf[op.out_buf], (size_t)nb * ho_ * wo_ * op.cout, fa.bad_flags, (int)(&op - enc->ops.data()), st);
+        }
+        if ((s = mark())) return s;
+    }
+    if (pooled_head(enc))
+        s = launch_avgpool(L.buf[B_F32], out, out_stride, nb, enc->final_hw, enc->final_c, 1, dt, st);
+    else
+        s = launch_nhwc_to_chw((const float *)L.buf[B_F32], out, out_stride, nb, enc->final_hw, enc->final_c,
+                               enc->final_creal, st);
+    if (s) return s;
+    return mark();
+}
+
+// One chunk of the 16-bit plans (ResNet50 family).  stopped: a debug stop (pvr_encoder_debug_stop_after) ended it - the forward ends there too
+static pvr_status h16_chunk(pvr_encoder *enc, Lane &L, const uint8_t *fr, int nb, int h, int w, float *out, int64_t out_stride, hipStream_t st, const ForwardArgs &fa,
+                            bool &stopped) {
+    const int dt = enc->desc.dtype;
+    pvr_status s;
+    auto mark = [&] { return mark_launch(fa, st); };
+    // frames that need no resize (the bench configuration: 256 x 256 frames, Resize(256) is the identity): the fused stem reads the
+    // uint8 frames itself - no preprocess launch, no padded 16-bit image in HBM
+    int fused_u8 = 0;
+    // layer1.0.conv1 has no launch in the fused schedule (encoder_plan.hip: plan_stem_c1): the stem's register-pooling form runs it
+    const bool c1_pending = enc->fuse && enc->stem_c1 >= 0;
+    const bool c1_in_stem = c1_pending && enc->stop_after.empty() && stem_conv1_capable(enc->sw);
+    if (enc->sw.stem_u8 && enc->sw.stem_lds && enc->stop_after.empty() && enc->desc.crop == 224 && enc->crop_pos >= 0 && enc->crop_pos <= 4) {
+        int rn = 1, top = 0, left = 0;
+        preprocess_geometry(h, w, enc->desc.resize, enc->desc.crop, enc->crop_pos, &rn, &top, &left);
+        if (!rn && stem_pool_u8_ok(fr, h, w, top, left)) {
+            if ((s = mark())) return s;                  // (launch index of the preprocess stays: pvr_encoder_profile)
+            if ((s = launch_stem_pool_u8(enc->sw, fr, nb, h, w, top, left, enc->d_stem_w, enc->d_stem_b, L.buf[B_X0], dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
+                                         c1_in_stem ? enc->ops[enc->stem_c1].d_b : nullptr, c1_in_stem ? L.buf[B_T1] : nullptr, enc->stem_c1_blk))) return s;
+            fused_u8 = 1;
+        }
+    }
+    if (!fused_u8) {
+        if ((s = launch_preprocess(fr, nb, h, w, enc->desc.resize, enc->desc.crop, L.d_img, dt, st, enc->crop_pos))) return s;
+        if ((s = mark())) return s;
+    }
+    enc->last_n = nb;
+    if (enc->stop_after == "pre") { stopped = true; return PVR_OK; }
+    if (enc->stop_after == "stem") {             // debug tap of the un-pooled conv1 output: unfused kernel
+        if ((s = launch_stem(L.d_img, enc->d_stem_w, enc->d_stem_b, L.d_stem, nb, enc->desc.crop, dt, st))) return s;
+        stopped = true;
+        return PVR_OK;
+    }
+    // conv1 + bn1 + relu + maxpool fused: the 112x112x64 activation stays in LDS
+    if (!fused_u8 && (s = launch_stem_pool(enc->sw, L.d_img, enc->d_stem_w, enc->d_stem_b, L.buf[B_X0], nb, enc->desc.crop, dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
+                                           c1_in_stem ? enc->ops[enc->stem_c1].d_b : nullptr, c1_in_stem ? L.buf[B_T1] : nullptr, enc->stem_c1_blk))) return s;
+    if (fa.bad_flags) {                      // pvr_encoder_check_range: the pooled stem output (flag slot behind the plan's launches)
+        const size_t n8 = (size_t)nb * 56 * 56 * 64 / 8;
+        hipLaunchKernelGGL(range_flag_kernel<false>, dim3(2048), dim3(256), 0, st, L.buf[B_X0], n8, dt, fa.bad_flags, (int)cur_plan(enc).size());
+    }
+    if ((s = mark())) return s;
+    if ((s = mark())) return s;                  // (keeps the launch indices of pvr_encoder_profile stable)
+    if (enc->stop_after == "pool") { stopped = true; return PVR_OK; }
+    bool t1_blocked = false;                     // t1_blocked: the conv1 launch in front of layer1's first tail wrote t1 in the blocked layout
+    if (c1_in_stem) t1_blocked = enc->stem_c1_blk != 0;
+    else if (c1_pending && enc->stop_after != "pool") {
+        // ... or, where that stem form did not run (debug stops, PVR_STEM_REGPOOL=0, PVR_STEM_LDS=0), as its own launch in front of the plan - blocked t1 when the tail wants it
+        const ConvOp &c1 = enc->ops[enc->stem_c1];
+        if (enc->stem_c1_blk && enc->sw.conv_algo == -1 && conv_expand_supported(enc->sw, (int64_t)nb * c1.h * c1.w, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, false)) {
+            s = launch_conv_expand(L.buf[c1.in_buf], c1.d_w, c1.d_b, nullptr, L.buf[c1.out_buf], nb, c1.h, c1.w, c1.cin, c1.cout, 1, c1.relu, dt, st, 1);
+            t1_blocked = true;
+        } else
+            s = launch_conv(enc->sw, L.buf[c1.in_buf], c1.d_w, c1.d_b, nullptr, L.buf[c1.out_buf], enc->d_zero, nb, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, dt, st);
+        if (s) return s;
+    }
+    bool pooled = false;                         // the plan's last convolution wrote the average pool itself (conv_wfrag's pooled form)
+    const std::vector<Launch> &plan_ = cur_plan(enc);
+    const uint8_t *kinds = enc->kinds.data() + (size_t)(nb - 1) * plan_.size();
+    float *smallk = L.d_smallk;
+    // the pooled epilogue stores 16-byte pieces of the caller's rows: a property of this call's arguments, not of the plan
+    const bool pool_args_ok = enc->stop_after.empty() && out_stride % 4 == 0 && ((size_t)out & 15) == 0;
+    int launch_idx = 0;                          // debug: stop_after = "#k" ends the forward after conv launch k of the plan
+    const bool run_ok = enc->stop_after.empty() && !fa.bad_flags;
+    const int stop_idx = enc->stop_after.size() > 1 && enc->stop_after[0] == '#' ? atoi(enc->stop_after.c_str() + 1) : -1;
+    // a member convolution of a launch that runs as its members (small forwards): split-K in the low-latency plan, else the shape's kernel
+    auto member = [&](const ConvOp &o, const void *in, const void *r_, void *out_) -> pvr_status {
+        if (const int ks = small_batch_ksplit(enc, o, nb)) {
+            if (!smallk) { set_error("low-latency plan without its scratch (pvr_encoder_set_low_latency allocates it)"); return PVR_ERR_STATE; }
+            return launch_conv_splitk(in, o.d_w, o.d_b, r_, out_, enc->d_zero, smallk, ks, nb, o.h, o.w, o.cin, o.cout, o.k, o.k, o.stride, o.pad, o.relu, o.out_f32, dt, st);
+        }
+        return launch_conv(enc->sw, in, o.d_w, o.d_b, r_, out_, enc->d_zero, nb, o.h, o.w, o.cin, o.cout, o.k, o.k, o.stride, o.pad, o.relu, o.out_f32, dt, st);
+    };
+    for (size_t li = 0; li < plan_.size(); ++li) {
+        const Launch &l = plan_[li];
+        const ConvOp &op = enc->ops[l.conv3 >= 0 ? l.conv3 : l.conv2];
+        const void *res = op.res_buf == B_NONE ? nullptr : L.buf[op.res_buf];
+        int kind = kinds[li];
+        if (kind == LK_WFRAG_POOL && !pool_args_ok) kind = resolve_kind(enc, plan_, li, nb, false);
+        if ((kind == LK_FRAME_RUN || kind == LK_FRAME_RUN_TAIL) && !run_ok) kind = LK_FRAME_FRONT1;     // (taps, debug stops, range validation: one launch per bottleneck)
+        if (kind == LK_CHAIN_YS2 && !run_ok) kind = LK_CHAIN;                                           // (... and all of y)
+        if (kind == LK_CONV_YS2 && !run_ok) kind = LK_CONV;
+        switch (kind) {
+        case LK_FRAME_RUN: {
+            BFBlk blks[6];
+            int nblk = 0;
+            for (size_t t = li; t < plan_.size() && nblk < 6 && (t == li || kinds[t] == LK_FRAME_RUN_TAIL); ++t, ++nblk) {
+                const Launch &lt = plan_[t];
+                const ConvOp &o3 = enc->ops[lt.conv3], &o2 = enc->ops[lt.conv2], &o1 = enc->ops[lt.conv1];
+                blks[nblk] = BFBlk{(const u16 *)o1.d_wfb, (const u16 *)o2.d_wfb, (const u16 *)o3.d_wfb, (const u16 *)L.buf[o3.res_buf], o1.d_b, o2.d_b, o3.d_b,
+                                   (u16 *)L.buf[o3.out_buf]};
+            }
+            s = launch_bneck_frame_run(blks, nblk, nb, dt, st, enc->sw.frame_stagger);
+            break;
+        }
+        case LK_FRAME_RUN_TAIL:
+            s = PVR_OK;                                   // (inside the run's launch)
+            break;
+        case LK_FRAME_FRONT1: {
+            const ConvOp &c2 = enc->ops[l.conv2], &cf = enc->ops[l.conv1];
+            s = launch_bneck_frame(enc->sw, nullptr, c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, L.buf[op.out_buf], nullptr, nb, 3 | 8, dt, st,
+                                   nullptr, nullptr, nullptr, nullptr, cf.d_wfb, cf.d_b);
+            break;
+        }
+        case LK_FRAME: {
+            const ConvOp &c2 = enc->ops[l.conv2];
+            const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
+            s = launch_bneck_frame(enc->sw, L.buf[l.t1_in], c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, L.buf[op.out_buf], nullptr, nb, c1 ? 7 : 3, dt, st,
+                                   nullptr, c1 ? c1->d_wfb : nullptr, c1 ? c1->d_b : nullptr, c1 ? L.buf[l.t1_out] : nullptr);
+            break;
+        }
+        case LK_FRAME_MEMBERS: {
+            // t2 goes to the t1 buffer this launch does not read
+            const ConvOp &c2 = enc->ops[l.conv2];
+            const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
+            const ConvOp *cf = l.conv1 >= 0 ? &enc->ops[l.conv1] : nullptr;
+            const int t2b = l.t1_in == B_T1 ? B_T2 : B_T1;
+            s = PVR_OK;
+            if (cf) s = member(*cf, L.buf[cf->in_buf], nullptr, L.buf[l.t1_in]);
+            if (!s) s = member(c2, L.buf[l.t1_in], nullptr, L.buf[t2b]);
+            if (!s) s = member(op, L.buf[t2b], res, L.buf[op.out_buf]);
+            if (!s && c1) s = member(*c1, L.buf[op.out_buf], nullptr, L.buf[l.t1_out]);
+            break;
+        }
+        case LK_DUAL: {
+            // conv3 & downsample as one two-operand launch (layer3.0 / layer4.0)
+            const ConvOp &cd = enc->ops[l.ds];
+            s = launch_conv_pp256(enc->sw, L.buf[op.in_buf], op.d_wcat, op.d_bsum, nullptr, L.buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0,
+                                  op.relu, 0, 0, dt, 224, st, L.buf[cd.in_buf], cd.h, cd.w, cd.cin, cd.stride);
+            break;
+        }
+        case LK_DUAL_MEMBERS: {
+            const ConvOp &cd = enc->ops[l.ds];
+            s = member(cd, L.buf[cd.in_buf], nullptr, L.buf[cd.out_buf]);
+            if (!s) s = member(op, L.buf[op.in_buf], res, L.buf[op.out_buf]);
+            break;
+        }
+        case LK_CHAIN:
+        case LK_CHAIN_YS2: {
+            const ConvOp &c2 = enc->ops[l.conv2];
+            const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
+            const ConvOp *cd = l.ds >= 0 ? &enc->ops[l.ds] : nullptr;
+            s = launch_bottleneck_chain(enc->sw, L.buf[l.t1_in], c2.d_w, c2.d_b, op.d_wp, cd ? op.d_bsum : op.d_b, res, L.buf[op.out_buf],
+                                        c1 ? c1->d_wp : nullptr, c1 ? c1->d_b : nullptr, c1 ? L.buf[l.t1_out] : nullptr, nb,
+                                        c2.h, c2.w, c2.cout, c1 ? c1->cout : 0, c2.stride, dt, st,
+                                        cd ? L.buf[cd->in_buf] : nullptr, cd ? cd->d_wp : nullptr, op.d_wpb, cd ? cd->d_wpb : nullptr,
+                                        l.wave, cd ? (l.in_blk && t1_blocked) : l.in_blk, l.out_blk, c2.d_wpk, kind == LK_CHAIN_YS2);
+            t1_blocked = false;
+            break;
+        }
+        case LK_CONV_YS2:
+            // the 1 x 1 stride-2 reader of a y_s2 tail: stride 1 over the (n, h / 2, w / 2, cin) tensor in the front of the same buffer
+            s = launch_conv_expand(L.buf[op.in_buf], op.d_w, op.d_b, nullptr, L.buf[op.out_buf], nb, op.h / 2, op.w / 2, op.cin, op.cout, 1, op.relu, dt, st);
+            break;
+        case LK_CAST:
+            s = launch_f32_to_h((const float *)L.buf[op.in_buf], L.buf[op.out_buf], (size_t)nb * op.h * op.w * op.cin, dt, st);
+            break;
+        case LK_F32:
+            s = launch_conv_f32((const float *)L.buf[op.in_buf], op.d_wf, op.d_b, (const float *)res, (float *)L.buf[op.out_buf], nb,
+                                op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
+            break;
+        case LK_SPLIT16:
+            s = launch_conv_split16((const float *)L.buf[op.in_buf], op.d_wsp, op.d_b, (const float *)res, (float *)L.buf[op.out_buf], nb,
+                                    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
+            break;
+        case LK_SPLIT16_PAIR: {
+            const ConvOp &od = enc->ops[l.pair];
+            s = launch_conv_split16((const float *)L.buf[op.in_buf], op.d_wsp_pair, op.d_b_pair, nullptr, (float *)L.buf[op.out_buf], nb, op.h, op.w, op.cin,
+                                    128, op.k, op.stride, op.pad, 1, st, (float *)L.buf[od.out_buf], 64);
+            break;
+        }
+        case LK_SPLIT16_IN32:
+            // a 16-bit convolution whose operand is the fp32 residual stream (rounded to f16 in the kernel's staging pass): t1 leaves 16-bit, a downsample fp32
+            s = launch_conv_split16((const float *)L.buf[op.in_buf], op.d_wsp, op.d_b, nullptr, (op.out_f32 & 1) ? (float *)L.buf[op.out_buf] : nullptr, nb,
+                                    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st, nullptr, 0, (op.out_f32 & 1) ? nullptr : L.buf[op.out_buf], 1);
+            break;
+        case LK_SPLITK_SMALL:
+            // low-latency plan: the few pixel tiles of a <= 4-frame forward share each K loop between `ks` blocks
+            s = member(op, L.buf[op.in_buf], res, L.buf[op.out_buf]);
+            break;
+        case LK_SPLITK:
+            s = launch_conv_splitk(L.buf[op.in_buf], op.d_w, op.d_b, res, L.buf[op.out_buf], enc->d_zero, (float *)L.buf[op.ks_buf],
+                                   op.ksplit, nb, op.h, op.w, op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
+            break;
+        case LK_EXPAND_BLOCKED:
+            // layer1.0.conv1 in front of a wave-form tail: t1 in the blocked layout
+            s = launch_conv_expand(L.buf[op.in_buf], op.d_w, op.d_b, nullptr, L.buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, 1, op.relu, dt, st, 1);
+            t1_blocked = true;
+            break;
+        case LK_WFRAG_POOL:
+            // the trunk's last conv3 + identity + ReLU with AdaptiveAvgPool2d(1) in its epilogue: the (n,7,7,2048) fp32 activation is never written
+            s = launch_conv_wfrag(enc->sw, L.buf[op.in_buf], op.d_wfb, op.d_b, res, nullptr, nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0, 1, 1, dt, st,
+                                  out, out_stride);
+            pooled = true;
+            break;
+        case LK_WFRAG:
+            // few pixels, deep K (layer4 at batch 256): 112 x 256 tiles, weights as L2 fragments
+            s = launch_conv_wfrag(enc->sw, L.buf[op.in_buf], op.d_wfb, op.d_b, res, L.buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, op.k, op.k,
+                                  op.stride, op.pad, op.relu, op.out_f32, dt, st);
+            break;
+        default:
+            s = launch_conv(enc->sw, L.buf[op.in_buf], op.d_w, op.d_b, res, L.buf[op.out_buf], enc->d_zero, nb, op.h, op.w,
+                            op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
+        }
+        if (s) return s;
+        if (fa.bad_flags && kind != LK_WFRAG_POOL) {         // pvr_encoder_check_range: the launch's output, all of it
+            const int ho_ = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo_ = (op.w + 2 * op.pad - op.k) / op.stride + 1;
+            const size_t n8 = (size_t)nb * ho_ * wo_ * op.cout / 8;
+            const int blocks = (int)((n8 + 255) / 256 < 2048 ? (n8 + 255) / 256 : 2048);
+            if ((op.out_f32 & 1) || op.f32op) hipLaunchKernelGGL(range_flag_kernel<true>, dim3(blocks), dim3(256), 0, st, L.buf[op.out_buf], n8, dt, fa.bad_flags, (int)li);
+            else hipLaunchKernelGGL(range_flag_kernel<false>, dim3(blocks), dim3(256), 0, st, L.buf[op.out_buf], n8, dt, fa.bad_flags, (int)li);
+        }
+        if ((s = mark())) return s;
+        if (!enc->stop_after.empty() && op.tap == enc->stop_after) { stopped = true; break; }
+        if (launch_idx++ == stop_idx) { stopped = true; break; }
+    }
+    enc->last_pooled = pooled;
+    if (stopped) return PVR_OK;
+    if (pooled)
+        s = PVR_OK;                               // (the last launch wrote the pooled rows)
+    else if (pooled_head(enc))
+        s = launch_avgpool(L.buf[B_F32], out, out_stride, nb, enc->final_hw, enc->final_c, 1, dt, st);
+    else
+        s = launch_nhwc_to_chw((const float *)L.buf[B_F32], out, out_stride, nb, enc->final_hw, enc->final_c,
+                               enc->final_creal, st);
+    if (s) return s;
+    return mark();
+}
+
+static pvr_status forward_impl(pvr_encoder *enc, int lane, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *out,
+                               int64_t out_stride, void *hip_stream, const ForwardArgs &fa) {
     PVR_REQUIRE(enc && frames && out, "pvr_encoder_forward: null argument");
     if (!enc->finalized) { set_error("encoder not finalized"); return PVR_ERR_STATE; }
     PVR_REQUIRE(n > 0 && n <= enc->desc.max_batch, "n=%d outside 1..max_batch=%d", n, enc->desc.max_batch);
     PVR_REQUIRE(out_stride >= enc->out_size, "out_stride %lld < out_size %d", (long long)out_stride, enc->out_size);
     hipStream_t st = (hipStream_t)hip_stream;
-    const int dt = enc->desc.dtype;
     pvr_status s;
-    if (enc->vit) return vit_forward(enc, frames, n, h, w, out, out_stride, st);
     if (enc->rnd) return random5_forward(enc, frames, n, h, w, out, out_stride, st);
-    for (int f0 = 0; f0 < n; f0 += enc->desc.chunk) {
+    enc->last_lane = lane;
+    if (enc->vit) return vit_forward(enc, lane, frames, n, h, w, out, out_stride, st);
+    Lane *L;
+    if ((s = get_lane(enc, lane, &L))) return s;
+    ForwardArgs ca = fa;                             // (events: the first chunk only)
+    for (int f0 = 0; f0 < n; f0 += enc->desc.chunk, ca.ev = nullptr) {
         const int nb = (n - f0 < enc->desc.chunk) ? n - f0 : enc->desc.chunk;
         const uint8_t *fr = frames + (size_t)f0 * h * w * 3;
-        auto mark = [&]() -> pvr_status {
-            if (ev && f0 == 0) {
-                hipEvent_t e;
-                PVR_HIP_TRY(hipEventCreate(&e));
-                // span mode (pvr_encoder_profile_span): only the two marks that bracket the span are recorded, the others are placeholders
-                const int idx = (int)ev->size();
-                if (enc->span_first < 0 || idx == enc->span_first || idx == enc->span_last) PVR_HIP_TRY(hipEventRecord(e, st));
-                ev->push_back(e);
-            }
-            return PVR_OK;
-        };
-        if ((s = mark())) return s;
-        if (stores_f32(dt)) {
-            // reference-precision plans: integer transforms (exact, via the bf16 image) -> fp32 /255, Normalize ->
-            // fp32 conv1 -> fp32 maxpool -> fp32 implicit-GEMM convs -> fp32 pool / flatten.  PVR_F32: every product on the f32-input MFMA;
-            // PVR_F32S: the same launches with every product as the exact split product on the 16-bit MFMA (the normalised image zero-bordered for stem_split16)
-            const int crop = enc->desc.crop;
-            const bool split = dt == PVR_F32S;
-            if ((s = launch_preprocess(fr, nb, h, w, enc->desc.resize, crop, enc->d_img, PVR_BF16, st, enc->crop_pos))) return s;
-            if ((s = launch_normalize_nhwc4(enc->d_img, enc->d_imgf, nb, crop, enc->desc.mean, enc->desc.std_, PVR_BF16, st, split))) return s;
-            if ((s = mark())) return s;
-            if (split) s = launch_stem_split16(enc->d_imgf, enc->d_stem_w, enc->d_stem_b, (float *)enc->d_stem, nb, crop, st);
-            else s = launch_stem_f32(enc->d_imgf, enc->d_stem_wf, enc->d_stem_b, (float *)enc->d_stem, nb, crop, st);
-            if (s) return s;
-            if (enc->range_flags) launch_range_flag_split(enc->d_stem, (size_t)nb * 112 * 112 * 64, enc->range_flags, (int)enc->sched_plain.size(), st);   // (check_range: PVR_F32S only)
-            if ((s = mark())) return s;
-            if ((s = launch_maxpool_f32((const float *)enc->d_stem, (float *)enc->d_buf[B_X0], nb, 112, 112, 64, st))) return s;
-            if ((s = mark())) return s;
-            enc->last_n = nb;
-            for (auto &op : enc->ops) {
-                const float *res = op.res_buf == B_NONE ? nullptr : (const float *)enc->d_buf[op.res_buf];
-                if (split) s = launch_conv_split16((const float *)enc->d_buf[op.in_buf], op.d_wsp, op.d_b, res, (float *)enc->d_buf[op.out_buf], nb,
-                                                   op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
-                else s = launch_conv_f32((const float *)enc->d_buf[op.in_buf], op.d_wf, op.d_b, res, (float *)enc->d_buf[op.out_buf], nb,
-                                         op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
-                if (s) return s;
-                if (enc->range_flags) {                 // pvr_encoder_check_range: the launch's output, all of it
-                    const int ho_ = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo_ = (op.w + 2 * op.pad - op.k) / op.stride + 1;
-                    launch_range_flag_split(enc->d_buf[op.out_buf], (size_t)nb * ho_ * wo_ * op.cout, enc->range_flags, (int)(&op - enc->ops.data()), st);
-                }
-                if ((s = mark())) return s;
-            }
-            float *o32 = out + (size_t)f0 * out_stride;
-            if (pooled_head(enc))
-                s = launch_avgpool(enc->d_buf[B_F32], o32, out_stride, nb, enc->final_hw, enc->final_c, 1, dt, st);
-            else
-                s = launch_nhwc_to_chw((const float *)enc->d_buf[B_F32], o32, out_stride, nb, enc->final_hw, enc->final_c,
-                                       enc->final_creal, st);
-            if (s) return s;
-            if ((s = mark())) return s;
-            continue;
-        }
-        if (enc->desc.arch == PVR_ARCH_CLIP_RN50) {
-            if ((s = clip_rn50_chunk(enc, fr, nb, h, w, out + (size_t)f0 * out_stride, out_stride, st))) return s;
-            continue;
-        }
-        // frames that need no resize (the bench configuration: 256 x 256 frames, Resize(256) is the identity): the fused stem reads the
-        // uint8 frames itself - no preprocess launch, no padded 16-bit image in HBM
-        int fused_u8 = 0;
-        // layer1.0.conv1 has no launch in the fused schedule (encoder_plan.hip: plan_stem_c1): the stem's register-pooling form runs it
-        const bool c1_pending = enc->fuse && enc->stem_c1 >= 0;
-        const bool c1_in_stem = c1_pending && enc->stop_after.empty() && stem_conv1_capable(enc->sw);
-        if (enc->sw.stem_u8 && enc->sw.stem_lds && enc->stop_after.empty() && enc->desc.crop == 224 && enc->crop_pos >= 0 && enc->crop_pos <= 4) {
-            int rn = 1, top = 0, left = 0;
-            preprocess_geometry(h, w, enc->desc.resize, enc->desc.crop, enc->crop_pos, &rn, &top, &left);
-            if (!rn && stem_pool_u8_ok(fr, h, w, top, left)) {
-                if ((s = mark())) return s;                  // (launch index of the preprocess stays: pvr_encoder_profile)
-                if ((s = launch_stem_pool_u8(enc->sw, fr, nb, h, w, top, left, enc->d_stem_w, enc->d_stem_b, enc->d_buf[B_X0], dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
-                                             c1_in_stem ? enc->ops[enc->stem_c1].d_b : nullptr, c1_in_stem ? enc->d_buf[B_T1] : nullptr, enc->stem_c1_blk))) return s;
-                fused_u8 = 1;
-            }
-        }
-        if (!fused_u8) {
-        if ((s = launch_preprocess(fr, nb, h, w, enc->desc.resize, enc->desc.crop, enc->d_img, dt, st, enc->crop_pos))) return s;
-        if ((s = mark())) return s;
-        }
-        enc->last_n = nb;
-        if (enc->stop_after == "pre") return PVR_OK;
-        if (enc->stop_after == "stem") {             // debug tap of the un-pooled conv1 output: unfused kernel
-            if ((s = launch_stem(enc->d_img, enc->d_stem_w, enc->d_stem_b, enc->d_stem, nb, enc->desc.crop, dt, st))) return s;
-            return PVR_OK;
-        }
-        // conv1 + bn1 + relu + maxpool fused: the 112x112x64 activation stays in LDS
-        if (!fused_u8 && (s = launch_stem_pool(enc->sw, enc->d_img, enc->d_stem_w, enc->d_stem_b, enc->d_buf[B_X0], nb, enc->desc.crop, dt, st, c1_in_stem ? enc->d_stem_c1w : nullptr,
-                                               c1_in_stem ? enc->ops[enc->stem_c1].d_b : nullptr, c1_in_stem ? enc->d_buf[B_T1] : nullptr, enc->stem_c1_blk))) return s;
-        if (enc->range_flags) {                      // pvr_encoder_check_range: the pooled stem output (flag slot behind the plan's launches)
-            const size_t n8 = (size_t)nb * 56 * 56 * 64 / 8;
-            hipLaunchKernelGGL(range_flag_kernel<false>, dim3(2048), dim3(256), 0, st, enc->d_buf[B_X0], n8, dt, enc->range_flags, (int)cur_plan(enc).size());
-        }
-        if ((s = mark())) return s;
-        if ((s = mark())) return s;                  // (keeps the launch indices of pvr_encoder_profile stable)
-        if (enc->stop_after == "pool") return PVR_OK;
-        bool stopped = false, t1_blocked = false;   // t1_blocked: the conv1 launch in front of layer1's first tail wrote t1 in the blocked layout
-        if (c1_in_stem) t1_blocked = enc->stem_c1_blk != 0;
-        else if (c1_pending && enc->stop_after != "pool") {
-            // ... or, where that stem form did not run (debug stops, PVR_STEM_REGPOOL=0, PVR_STEM_LDS=0), as its own launch in front of the plan - blocked t1 when the tail wants it
-            const ConvOp &c1 = enc->ops[enc->stem_c1];
-            if (enc->stem_c1_blk && enc->sw.conv_algo == -1 && conv_expand_supported(enc->sw, (int64_t)nb * c1.h * c1.w, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, false)) {
-                s = launch_conv_expand(enc->d_buf[c1.in_buf], c1.d_w, c1.d_b, nullptr, enc->d_buf[c1.out_buf], nb, c1.h, c1.w, c1.cin, c1.cout, 1, c1.relu, dt, st, 1);
-                t1_blocked = true;
-            } else
-                s = launch_conv(enc->sw, enc->d_buf[c1.in_buf], c1.d_w, c1.d_b, nullptr, enc->d_buf[c1.out_buf], enc->d_zero, nb, c1.h, c1.w, c1.cin, c1.cout, 1, 1, 1, 0, c1.relu, 0, dt, st);
-            if (s) return s;
-        }
-        bool pooled = false;                         // the plan's last convolution wrote the average pool itself (conv_wfrag's pooled form)
-        const std::vector<Launch> &plan_ = cur_plan(enc);
-        const uint8_t *kinds = enc->kinds.data() + (size_t)(nb - 1) * plan_.size();
-        float *smallk = enc->d_smallk[enc->cur_lane];
-        // the pooled epilogue stores 16-byte pieces of the caller's rows: a property of this call's arguments, not of the plan
-        const bool pool_args_ok = enc->stop_after.empty() && out_stride % 4 == 0 && (((size_t)(out + (size_t)f0 * out_stride)) & 15) == 0;
-        int launch_idx = 0;                          // debug: stop_after = "#k" ends the forward after conv launch k of the plan
-        const bool run_ok = enc->stop_after.empty() && !enc->range_flags;
-        const int stop_idx = enc->stop_after.size() > 1 && enc->stop_after[0] == '#' ? atoi(enc->stop_after.c_str() + 1) : -1;
-        // a member convolution of a launch that runs as its members (small forwards): split-K in the low-latency plan, else the shape's kernel
-        auto member = [&](const ConvOp &o, const void *in, const void *r_, void *out_) -> pvr_status {
-            if (const int ks = small_batch_ksplit(enc, o, nb)) {
-                if (!smallk) { set_error("low-latency plan without its scratch (pvr_encoder_set_low_latency allocates it)"); return PVR_ERR_STATE; }
-                return launch_conv_splitk(in, o.d_w, o.d_b, r_, out_, enc->d_zero, smallk, ks, nb, o.h, o.w, o.cin, o.cout, o.k, o.k, o.stride, o.pad, o.relu, o.out_f32, dt, st);
-            }
-            return launch_conv(enc->sw, in, o.d_w, o.d_b, r_, out_, enc->d_zero, nb, o.h, o.w, o.cin, o.cout, o.k, o.k, o.stride, o.pad, o.relu, o.out_f32, dt, st);
-        };
-        for (size_t li = 0; li < plan_.size(); ++li) {
-            const Launch &l = plan_[li];
-            const ConvOp &op = enc->ops[l.conv3 >= 0 ? l.conv3 : l.conv2];
-            const void *res = op.res_buf == B_NONE ? nullptr : enc->d_buf[op.res_buf];
-            int kind = kinds[li];
-            if (kind == LK_WFRAG_POOL && !pool_args_ok) kind = resolve_kind(enc, plan_, li, nb, false);
-            if ((kind == LK_FRAME_RUN || kind == LK_FRAME_RUN_TAIL) && !run_ok) kind = LK_FRAME_FRONT1;     // (taps, debug stops, range validation: one launch per bottleneck)
-            if (kind == LK_CHAIN_YS2 && !run_ok) kind = LK_CHAIN;                                           // (... and all of y)
-            if (kind == LK_CONV_YS2 && !run_ok) kind = LK_CONV;
-            switch (kind) {
-            case LK_FRAME_RUN: {
-                BFBlk blks[6];
-                int nblk = 0;
-                for (size_t t = li; t < plan_.size() && nblk < 6 && (t == li || kinds[t] == LK_FRAME_RUN_TAIL); ++t, ++nblk) {
-                    const Launch &lt = plan_[t];
-                    const ConvOp &o3 = enc->ops[lt.conv3], &o2 = enc->ops[lt.conv2], &o1 = enc->ops[lt.conv1];
-                    blks[nblk] = BFBlk{(const u16 *)o1.d_wfb, (const u16 *)o2.d_wfb, (const u16 *)o3.d_wfb, (const u16 *)enc->d_buf[o3.res_buf], o1.d_b, o2.d_b, o3.d_b,
-                                       (u16 *)enc->d_buf[o3.out_buf]};
-                }
-                s = launch_bneck_frame_run(blks, nblk, nb, dt, st, enc->sw.frame_stagger);
-                break;
-            }
-            case LK_FRAME_RUN_TAIL:
-                s = PVR_OK;                                   // (inside the run's launch)
-                break;
-            case LK_FRAME_FRONT1: {
-                const ConvOp &c2 = enc->ops[l.conv2], &cf = enc->ops[l.conv1];
-                s = launch_bneck_frame(enc->sw, nullptr, c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nullptr, nb, 3 | 8, dt, st,
-                                       nullptr, nullptr, nullptr, nullptr, cf.d_wfb, cf.d_b);
-                break;
-            }
-            case LK_FRAME: {
-                const ConvOp &c2 = enc->ops[l.conv2];
-                const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
-                s = launch_bneck_frame(enc->sw, enc->d_buf[l.t1_in], c2.d_wfb, c2.d_b, op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nullptr, nb, c1 ? 7 : 3, dt, st,
-                                       nullptr, c1 ? c1->d_wfb : nullptr, c1 ? c1->d_b : nullptr, c1 ? enc->d_buf[l.t1_out] : nullptr);
-                break;
-            }
-            case LK_FRAME_MEMBERS: {
-                // t2 goes to the t1 buffer this launch does not read
-                const ConvOp &c2 = enc->ops[l.conv2];
-                const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
-                const ConvOp *cf = l.conv1 >= 0 ? &enc->ops[l.conv1] : nullptr;
-                const int t2b = l.t1_in == B_T1 ? B_T2 : B_T1;
-                s = PVR_OK;
-                if (cf) s = member(*cf, enc->d_buf[cf->in_buf], nullptr, enc->d_buf[l.t1_in]);
-                if (!s) s = member(c2, enc->d_buf[l.t1_in], nullptr, enc->d_buf[t2b]);
-                if (!s) s = member(op, enc->d_buf[t2b], res, enc->d_buf[op.out_buf]);
-                if (!s && c1) s = member(*c1, enc->d_buf[op.out_buf], nullptr, enc->d_buf[l.t1_out]);
-                break;
-            }
-            case LK_DUAL: {
-                // conv3 & downsample as one two-operand launch (layer3.0 / layer4.0)
-                const ConvOp &cd = enc->ops[l.ds];
-                s = launch_conv_pp256(enc->sw, enc->d_buf[op.in_buf], op.d_wcat, op.d_bsum, nullptr, enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0,
-                                      op.relu, 0, 0, dt, 224, st, enc->d_buf[cd.in_buf], cd.h, cd.w, cd.cin, cd.stride);
-                break;
-            }
-            case LK_DUAL_MEMBERS: {
-                const ConvOp &cd = enc->ops[l.ds];
-                s = member(cd, enc->d_buf[cd.in_buf], nullptr, enc->d_buf[cd.out_buf]);
-                if (!s) s = member(op, enc->d_buf[op.in_buf], res, enc->d_buf[op.out_buf]);
-                break;
-            }
-            case LK_CHAIN:
-            case LK_CHAIN_YS2: {
-                const ConvOp &c2 = enc->ops[l.conv2];
-                const ConvOp *c1 = l.next1 >= 0 ? &enc->ops[l.next1] : nullptr;
-                const ConvOp *cd = l.ds >= 0 ? &enc->ops[l.ds] : nullptr;
-                s = launch_bottleneck_chain(enc->sw, enc->d_buf[l.t1_in], c2.d_w, c2.d_b, op.d_wp, cd ? op.d_bsum : op.d_b, res, enc->d_buf[op.out_buf],
-                                            c1 ? c1->d_wp : nullptr, c1 ? c1->d_b : nullptr, c1 ? enc->d_buf[l.t1_out] : nullptr, nb,
-                                            c2.h, c2.w, c2.cout, c1 ? c1->cout : 0, c2.stride, dt, st,
-                                            cd ? enc->d_buf[cd->in_buf] : nullptr, cd ? cd->d_wp : nullptr, op.d_wpb, cd ? cd->d_wpb : nullptr,
-                                            l.wave, cd ? (l.in_blk && t1_blocked) : l.in_blk, l.out_blk, c2.d_wpk, kind == LK_CHAIN_YS2);
-                t1_blocked = false;
-                break;
-            }
-            case LK_CONV_YS2:
-                // the 1 x 1 stride-2 reader of a y_s2 tail: stride 1 over the (n, h / 2, w / 2, cin) tensor in the front of the same buffer
-                s = launch_conv_expand(enc->d_buf[op.in_buf], op.d_w, op.d_b, nullptr, enc->d_buf[op.out_buf], nb, op.h / 2, op.w / 2, op.cin, op.cout, 1, op.relu, dt, st);
-                break;
-            case LK_CAST:
-                s = launch_f32_to_h((const float *)enc->d_buf[op.in_buf], enc->d_buf[op.out_buf], (size_t)nb * op.h * op.w * op.cin, dt, st);
-                break;
-            case LK_F32:
-                s = launch_conv_f32((const float *)enc->d_buf[op.in_buf], op.d_wf, op.d_b, (const float *)res, (float *)enc->d_buf[op.out_buf], nb,
-                                    op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
-                break;
-            case LK_SPLIT16:
-                s = launch_conv_split16((const float *)enc->d_buf[op.in_buf], op.d_wsp, op.d_b, (const float *)res, (float *)enc->d_buf[op.out_buf], nb,
-                                        op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
-                break;
-            case LK_SPLIT16_PAIR: {
-                const ConvOp &od = enc->ops[l.pair];
-                s = launch_conv_split16((const float *)enc->d_buf[op.in_buf], op.d_wsp_pair, op.d_b_pair, nullptr, (float *)enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin,
-                                        128, op.k, op.stride, op.pad, 1, st, (float *)enc->d_buf[od.out_buf], 64);
-                break;
-            }
-            case LK_SPLIT16_IN32:
-                // a 16-bit convolution whose operand is the fp32 residual stream (rounded to f16 in the kernel's staging pass): t1 leaves 16-bit, a downsample fp32
-                s = launch_conv_split16((const float *)enc->d_buf[op.in_buf], op.d_wsp, op.d_b, nullptr, (op.out_f32 & 1) ? (float *)enc->d_buf[op.out_buf] : nullptr, nb,
-                                        op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st, nullptr, 0, (op.out_f32 & 1) ? nullptr : enc->d_buf[op.out_buf], 1);
-                break;
-            case LK_SPLITK_SMALL:
-                // low-latency plan: the few pixel tiles of a <= 4-frame forward share each K loop between `ks` blocks
-                s = member(op, enc->d_buf[op.in_buf], res, enc->d_buf[op.out_buf]);
-                break;
-            case LK_SPLITK:
-                s = launch_conv_splitk(enc->d_buf[op.in_buf], op.d_w, op.d_b, res, enc->d_buf[op.out_buf], enc->d_zero, (float *)enc->d_buf[op.ks_buf],
-                                       op.ksplit, nb, op.h, op.w, op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
-                break;
-            case LK_EXPAND_BLOCKED:
-                // layer1.0.conv1 in front of a wave-form tail: t1 in the blocked layout
-                s = launch_conv_expand(enc->d_buf[op.in_buf], op.d_w, op.d_b, nullptr, enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, 1, op.relu, dt, st, 1);
-                t1_blocked = true;
-                break;
-            case LK_WFRAG_POOL:
-                // the trunk's last conv3 + identity + ReLU with AdaptiveAvgPool2d(1) in its epilogue: the (n,7,7,2048) fp32 activation is never written
-                s = launch_conv_wfrag(enc->sw, enc->d_buf[op.in_buf], op.d_wfb, op.d_b, res, nullptr, nb, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0, 1, 1, dt, st,
-                                      out + (size_t)f0 * out_stride, out_stride);
-                pooled = true;
-                break;
-            case LK_WFRAG:
-                // few pixels, deep K (layer4 at batch 256): 112 x 256 tiles, weights as L2 fragments
-                s = launch_conv_wfrag(enc->sw, enc->d_buf[op.in_buf], op.d_wfb, op.d_b, res, enc->d_buf[op.out_buf], nb, op.h, op.w, op.cin, op.cout, op.k, op.k,
-                                      op.stride, op.pad, op.relu, op.out_f32, dt, st);
-                break;
-            default:
-                s = launch_conv(enc->sw, enc->d_buf[op.in_buf], op.d_w, op.d_b, res, enc->d_buf[op.out_buf], enc->d_zero, nb, op.h, op.w,
-                                op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
-            }
-            if (s) return s;
-            if (enc->range_flags && kind != LK_WFRAG_POOL) {         // pvr_encoder_check_range: the launch's output, all of it
-                const int ho_ = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo_ = (op.w + 2 * op.pad - op.k) / op.stride + 1;
-                const size_t n8 = (size_t)nb * ho_ * wo_ * op.cout / 8;
-                const int blocks = (int)((n8 + 255) / 256 < 2048 ? (n8 + 255) / 256 : 2048);
-                if ((op.out_f32 & 1) || op.f32op) hipLaunchKernelGGL(range_flag_kernel<true>, dim3(blocks), dim3(256), 0, st, enc->d_buf[op.out_buf], n8, dt, enc->range_flags, (int)li);
-                else hipLaunchKernelGGL(range_flag_kernel<false>, dim3(blocks), dim3(256), 0, st, enc->d_buf[op.out_buf], n8, dt, enc->range_flags, (int)li);
-            }
-            if ((s = mark())) return s;
-            if (!enc->stop_after.empty() && op.tap == enc->stop_after) { stopped = true; break; }
-            if (launch_idx++ == stop_idx) { stopped = true; break; }
-        }
-        enc->last_pooled = pooled;
-        if (stopped) return PVR_OK;
         float *o = out + (size_t)f0 * out_stride;
-        if (pooled)
-            s = PVR_OK;                               // (the last launch wrote the pooled rows)
-        else if (pooled_head(enc))
-            s = launch_avgpool(enc->d_buf[B_F32], o, out_stride, nb, enc->final_hw, enc->final_c, 1, dt, st);
-        else
-            s = launch_nhwc_to_chw((const float *)enc->d_buf[B_F32], o, out_stride, nb, enc->final_hw, enc->final_c,
-                                   enc->final_creal, st);
-        if (s) return s;
-        if ((s = mark())) return s;
+        bool stopped = false;
+        if ((s = mark_launch(ca, st))) return s;
+        if (stores_f32(enc->desc.dtype)) s = f32_chunk(enc, *L, fr, nb, h, w, o, out_stride, st, ca);
+        else if (enc->desc.arch == PVR_ARCH_CLIP_RN50) s = clip_rn50_chunk(enc, *L, lane, fr, nb, h, w, o, out_stride, st);
+        else s = h16_chunk(enc, *L, fr, nb, h, w, o, out_stride, st, ca, stopped);
+        if (s || stopped) return s;
     }
     return PVR_OK;
 }
 
-// Same-lane forwards issued on DIFFERENT streams are ordered here, not by the caller: every forward records lane_done[lane] on its
+// Same-lane forwards issued on DIFFERENT streams are ordered here, not by the caller: every forward records the lane's event on its
 // stream and the next forward on that lane waits for it first (a device-side event wait, no host synchronisation), so a lane's
 // workspace is never shared by two forwards in flight.  Different lanes stay independent.
 static pvr_status lane_wait(pvr_encoder *enc, int lane, void *hip_stream) {
+    const Lane &L = enc->lanes[lane];
     hipStream_t st = (hipStream_t)hip_stream;
-    if (enc->lane_done[lane] && enc->lane_stream[lane] != st) PVR_HIP_TRY(hipStreamWaitEvent(st, enc->lane_done[lane], 0));
+    if (L.done && L.stream != st) PVR_HIP_TRY(hipStreamWaitEvent(st, L.done, 0));
     return PVR_OK;
 }
 static pvr_status lane_mark(pvr_encoder *enc, int lane, void *hip_stream) {
+    Lane &L = enc->lanes[lane];
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!enc->lane_done[lane]) PVR_HIP_TRY(hipEventCreateWithFlags(&enc->lane_done[lane], hipEventDisableTiming));
-    PVR_HIP_TRY(hipEventRecord(enc->lane_done[lane], st));
-    enc->lane_stream[lane] = st;
+    if (!L.done) PVR_HIP_TRY(hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+    PVR_HIP_TRY(hipEventRecord(L.done, st));
+    L.stream = st;
     return PVR_OK;
 }
 static pvr_status lane_forward(pvr_encoder *enc, int lane, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *out,
                                int64_t out_stride, void *hip_stream) {
+    if (!enc->finalized) { set_error("encoder not finalized"); return PVR_ERR_STATE; }
+    PVR_REQUIRE(lane == 0 || !enc->rnd, "pvr_encoder_forward_lane: the 'random' PVR plan has a single workspace");
     pvr_status s = lane_wait(enc, lane, hip_stream);
-    if (!s) s = forward_impl(enc, frames, n, h, w, out, out_stride, hip_stream, nullptr);
+    if (!s) s = forward_impl(enc, lane, frames, n, h, w, out, out_stride, hip_stream, ForwardArgs());
     if (!s) s = lane_mark(enc, lane, hip_stream);
     return s;
 }
@@ -885,9 +902,6 @@ pvr_status pvr_encoder_forward(pvr_encoder *enc, const uint8_t *frames, int32_t 
     }
     PVR_REQUIRE(enc, "pvr_encoder_forward: null encoder");
     TraceScope trace("pvr_encoder_forward");
-    if (enc->finalized && !enc->vit && !enc->rnd) { pvr_status s = use_lane(enc, 0); if (s) return s; }
-    if (enc->finalized && enc->vit) { pvr_status s = vit_use_lane(enc, 0); if (s) return s; }
-    if (!enc->finalized) { set_error("encoder not finalized"); return PVR_ERR_STATE; }
     return lane_forward(enc, 0, frames, n, h, w, out, out_stride, hip_stream);
 }
 
@@ -897,10 +911,6 @@ pvr_status pvr_encoder_forward_lane(pvr_encoder *enc, int32_t lane, const uint8_
     PVR_REQUIRE(enc, "pvr_encoder_forward_lane: null encoder");
     TraceScope trace(lane == 0 ? "pvr_encoder_forward_lane 0" : "pvr_encoder_forward_lane 1+");
     PVR_REQUIRE(lane >= 0 && lane < PVR_MAX_LANES, "pvr_encoder_forward_lane: lane must be 0..%d", PVR_MAX_LANES - 1);
-    if (!enc->finalized) { set_error("encoder not finalized"); return PVR_ERR_STATE; }
-    if (enc->vit) { pvr_status s = vit_use_lane(enc, lane); if (s) return s; }
-    else if (!enc->rnd) { pvr_status s = use_lane(enc, lane); if (s) return s; }            // (the 'random' plan has one workspace)
-    else PVR_REQUIRE(lane == 0, "pvr_encoder_forward_lane: the 'random' PVR plan has a single workspace");
     return lane_forward(enc, lane, frames, n, h, w, out, out_stride, hip_stream);
 }
 
@@ -914,10 +924,10 @@ pvr_status pvr_encoder_profile(pvr_encoder *enc, const uint8_t *frames, int32_t 
     PVR_NO_HOST(enc, "pvr_encoder_profile");
     PVR_REQUIRE(n <= enc->desc.chunk, "profile: n=%d must fit one chunk (%d)", n, enc->desc.chunk);
     std::vector<hipEvent_t> ev;
-    pvr_status s = (enc->finalized && !enc->vit && !enc->rnd) ? use_lane(enc, 0) : PVR_OK;
-    if (!s && enc->finalized && enc->vit) s = vit_use_lane(enc, 0);
-    if (!s) s = lane_wait(enc, 0, hip_stream);
-    if (!s) s = forward_impl(enc, frames, n, h, w, out, out_stride, hip_stream, &ev);
+    ForwardArgs fa;
+    fa.ev = &ev;
+    pvr_status s = lane_wait(enc, 0, hip_stream);
+    if (!s) s = forward_impl(enc, 0, frames, n, h, w, out, out_stride, hip_stream, fa);
     if (!s && hipStreamSynchronize((hipStream_t)hip_stream) != hipSuccess) { set_error("profile: sync failed"); s = PVR_ERR_HIP; }
     const int nl = (int)ev.size() - 1;
     if (!s && nl > cap) { set_error("profile: %d launches > cap %d", nl, cap); s = PVR_ERR_INVALID; }
@@ -959,12 +969,10 @@ pvr_status pvr_encoder_profile_span(pvr_encoder *enc, const uint8_t *frames, int
     PVR_REQUIRE(n <= enc->desc.chunk, "profile: n=%d must fit one chunk (%d)", n, enc->desc.chunk);
     PVR_REQUIRE(first_op >= 0 && last_op >= first_op, "pvr_encoder_profile_span: bad launch range %d..%d", first_op, last_op);
     std::vector<hipEvent_t> ev;
-    pvr_status s = (enc->finalized && !enc->vit && !enc->rnd) ? use_lane(enc, 0) : PVR_OK;
-    if (!s && enc->finalized && enc->vit) s = vit_use_lane(enc, 0);
-    if (!s) s = lane_wait(enc, 0, hip_stream);
-    enc->span_first = first_op; enc->span_last = last_op + 1;
-    if (!s) s = forward_impl(enc, frames, n, h, w, out, out_stride, hip_stream, &ev);
-    enc->span_first = enc->span_last = -1;
+    ForwardArgs fa;
+    fa.ev = &ev; fa.rec_first = first_op; fa.rec_last = last_op + 1;
+    pvr_status s = lane_wait(enc, 0, hip_stream);
+    if (!s) s = forward_impl(enc, 0, frames, n, h, w, out, out_stride, hip_stream, fa);
     if (!s && hipStreamSynchronize((hipStream_t)hip_stream) != hipSuccess) { set_error("profile: sync failed"); s = PVR_ERR_HIP; }
     if (!s && last_op + 1 >= (int)ev.size()) { set_error("profile_span: launch %d past the plan's %d launches", last_op, (int)ev.size() - 1); s = PVR_ERR_INVALID; }
     if (!s && hipEventElapsedTime(span_ms, ev[first_op], ev[last_op + 1]) != hipSuccess) { set_error("profile_span: elapsed time failed"); s = PVR_ERR_HIP; }
@@ -1033,17 +1041,16 @@ pvr_status pvr_encoder_check_range(pvr_encoder *enc, const uint8_t *frames, int3
     PVR_REQUIRE(n > 0 && n <= enc->desc.chunk, "pvr_encoder_check_range: n=%d must fit one chunk (%d)", n, enc->desc.chunk);
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t nl = enc->sched_plain.size();
-    pvr_status s = use_lane(enc, 0);
-    if (!s) s = lane_wait(enc, 0, hip_stream);
+    pvr_status s = lane_wait(enc, 0, hip_stream);
     if (s) return s;
     int *flags = nullptr;
     PVR_HIP_TRY(hipMalloc((void **)&flags, (nl + 1) * sizeof(int)));
     if (hipMemsetAsync(flags, 0, (nl + 1) * sizeof(int), st) != hipSuccess) { (void)hipFree(flags); set_error("check_range: memset failed"); return PVR_ERR_HIP; }
     const bool fuse0 = enc->fuse;
     enc->fuse = false; resolve_kinds(enc);
-    enc->range_flags = flags;
-    s = forward_impl(enc, frames, n, h, w, out, out_stride, hip_stream, nullptr);
-    enc->range_flags = nullptr;
+    ForwardArgs fa;
+    fa.bad_flags = flags;
+    s = forward_impl(enc, 0, frames, n, h, w, out, out_stride, hip_stream, fa);
     enc->fuse = fuse0; resolve_kinds(enc);
     std::vector<int> hf(nl + 1, 0);
     if (!s && hipMemcpyAsync(hf.data(), flags, (nl + 1) * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) { set_error("check_range: copy failed"); s = PVR_ERR_HIP; }
@@ -1068,17 +1075,18 @@ pvr_status pvr_encoder_tap(pvr_encoder *enc, const char *name, float *out, int64
     hipStream_t st = (hipStream_t)hip_stream;
     if (enc->vit) return vit_tap(enc, name, out, cap, count, st);
     const int n = enc->last_n, crop = enc->desc.crop;
+    const Lane &L = enc->lanes[enc->last_lane];
     const std::string nm = name;
     const void *src = nullptr;
     size_t elems = 0;
     int f32 = 0;
-    if (nm == "pre") { src = enc->d_img; elems = (size_t)n * (crop + 6) * (crop + 8) * 4; }
-    else if (nm == "stem") { src = enc->d_stem; elems = (size_t)n * 112 * 112 * 64; }
-    else if (nm == "pool") { src = enc->d_buf[B_X0]; elems = (size_t)n * 56 * 56 * 64; }
+    if (nm == "pre") { src = L.d_img; elems = (size_t)n * (crop + 6) * (crop + 8) * 4; }
+    else if (nm == "stem") { src = L.d_stem; elems = (size_t)n * 112 * 112 * 64; }
+    else if (nm == "pool") { src = L.buf[B_X0]; elems = (size_t)n * 56 * 56 * 64; }
     else if (nm.compare(0, 3, "buf") == 0 && nm.find(':') != std::string::npos) {   // debug: "buf<b>:<elems>" = raw workspace buffer b
         const int b = atoi(nm.c_str() + 3);
         PVR_REQUIRE(b >= 0 && b < B_F32, "tap %s: 16-bit workspace buffers are 0..%d", name, B_F32 - 1);
-        src = enc->d_buf[b]; elems = (size_t)atoll(nm.c_str() + nm.find(':') + 1);
+        src = L.buf[b]; elems = (size_t)atoll(nm.c_str() + nm.find(':') + 1);
     } else {
         auto it = enc->taps.find(nm);
         PVR_REQUIRE(it != enc->taps.end(), "unknown tap %s", name);
@@ -1090,7 +1098,7 @@ pvr_status pvr_encoder_tap(pvr_encoder *enc, const char *name, float *out, int64
                       "pvr_encoder_debug_stop_after(enc, \"%s\") or pvr_encoder_debug_set_switch(enc, \"pool_fuse\", 0) first", name, name);
             return PVR_ERR_STATE;
         }
-        src = enc->d_buf[it->second.first];
+        src = L.buf[it->second.first];
         elems = (size_t)n * g[0] * g[1] * g[2];
         f32 = g[3];
     }
@@ -1112,27 +1120,11 @@ void pvr_encoder_destroy(pvr_encoder *enc) {
     for (auto &op : enc->ops) { if (op.d_w) (void)hipFree(op.d_w); if (op.d_wp) (void)hipFree(op.d_wp); if (op.d_wpb) (void)hipFree(op.d_wpb); if (op.d_wfb) (void)hipFree(op.d_wfb); if (op.d_wcat) (void)hipFree(op.d_wcat); if (op.d_wf) (void)hipFree(op.d_wf); if (op.d_wsp) (void)hipFree(op.d_wsp); if (op.d_wsp_pair) (void)hipFree(op.d_wsp_pair); if (op.d_b_pair) (void)hipFree(op.d_b_pair); if (op.d_wpk) (void)hipFree(op.d_wpk); if (op.d_b) (void)hipFree(op.d_b); if (op.d_bsum) (void)hipFree(op.d_bsum); }
     if (enc->d_stem_wf) (void)hipFree(enc->d_stem_wf);
     if (enc->d_stem_c1w) (void)hipFree(enc->d_stem_c1w);
-    bool any_lane = false;
-    for (auto &l : enc->lane_ws) {
-        if (!l.valid) continue;
-        any_lane = true;
-        for (int b = 0; b < B_COUNT; ++b) if (l.d_buf[b]) (void)hipFree(l.d_buf[b]);
-        if (l.d_img) (void)hipFree(l.d_img);
-        if (l.d_stem) (void)hipFree(l.d_stem);
-        if (l.d_imgf) (void)hipFree(l.d_imgf);
-    }
-    if (!any_lane) {
-        for (int b = 0; b < B_COUNT; ++b) if (enc->d_buf[b]) (void)hipFree(enc->d_buf[b]);
-        if (enc->d_img) (void)hipFree(enc->d_img);
-        if (enc->d_stem) (void)hipFree(enc->d_stem);
-        if (enc->d_imgf) (void)hipFree(enc->d_imgf);
-    }
+    for (Lane &L : enc->lanes) lane_free(L);
     if (enc->d_stem_w) (void)hipFree(enc->d_stem_w);
     if (enc->d_stem_b) (void)hipFree(enc->d_stem_b);
     if (enc->d_zero) (void)hipFree(enc->d_zero);
     resizer_destroy(enc);
-    for (auto &ev : enc->lane_done) if (ev) (void)hipEventDestroy(ev);
-    for (float *q : enc->d_smallk) if (q) (void)hipFree(q);
     for (void *q : {(void *)enc->ap_wqkv, (void *)enc->ap_wc, (void *)enc->ap_bqkv, (void *)enc->ap_bc, (void *)enc->ap_pos, (void *)enc->ap_out}) if (q) (void)hipFree(q);
     delete enc;
 }

@@ -125,7 +125,7 @@ struct HostTensor {
 inline bool stores_f32(int dtype) { return dtype == PVR_F32 || dtype == PVR_F32S; }
 
 constexpr int PVR_MAX_LANES = 4;
-// B_Y0 / B_Y1: fp32 residual stream of the compressed PVRs' parity plan (allocated only for that plan); B_STEM: d_stem (112x112x64), not in d_buf
+// B_Y0 / B_Y1: fp32 residual stream of the compressed PVRs' parity plan (allocated only for that plan); B_STEM: the lane's d_stem (112x112x64), not in buf[]
 enum BufId { B_NONE = -1, B_X0 = 0, B_X1, B_T1, B_T2, B_DS, B_F32, B_Y0, B_Y1, B_COUNT, B_STEM = B_COUNT };
 
 struct ConvOp {
@@ -202,6 +202,16 @@ enum LaunchKind : uint8_t {
 const char *launch_kind_name(int k);
 
 
+// Resize(resize_to, bicubic) + CenterCrop(res) of uint8 frames (vit.hip): the resampling tables, the frame size they were built for and the per-lane
+// temporaries.  A ViT plan has one, a CLIP RN50 encoder has one.  aa_prepare rebuilds it when the frame size changes.
+struct Resizer {
+    int res = 224, resize_to = 224;
+    int h = 0, w = 0, rh = 0, rw = 0, maxk_h = 0, maxk_w = 0;   // frame size of the tables (0: none yet), size after Resize, taps per output index
+    int *xmin = nullptr, *xsize = nullptr, *ymin = nullptr, *ysize = nullptr;
+    float *wx = nullptr, *wy = nullptr;
+    struct Tmp { float *tmp = nullptr; uint8_t *u8 = nullptr; } lane[PVR_MAX_LANES];   // horizontal pass (fp32), resized crop (uint8)
+};
+
 }  // namespace pvr
 
 using namespace pvr;
@@ -221,39 +231,42 @@ struct pvr_encoder {
     u16 *d_stem_c1w = nullptr;                      // its weights as the stem's fragment image (stem_c1_pack)
     std::vector<uint8_t> kinds;                     // LaunchKind of launch i for a forward of nb frames: kinds[(nb - 1) * plan.size() + i] (resolve_kinds)
     size_t kinds_stride = 0;
-    int *range_flags = nullptr;                     // pvr_encoder_check_range: per-launch "output holds inf / NaN" flags of the forward in progress (else null)
     bool last_pooled = false;                       // the last forward wrote the pooled rows from the last convolution: the B_F32 tap does not exist
-    float *d_smallk[PVR_MAX_LANES] = {nullptr};     // the low-latency plan's fp32 partial planes, per lane (pvr_encoder_set_low_latency / first use of a lane: never in a forward)
     bool tail32 = false;                            // round 3: + the last trunk stage entirely in fp32 (conv_f32.hip), fp32 stream one stage earlier
     bool resid32 = false;                           // compressed PVRs, f16: fp32 residual stream from layer3 on + fp32 compression head
     bool finalized = false;
     int out_size = 0;
     int final_hw = 0, final_c = 0, final_creal = 0;   // geometry of the last activation
     // device
-    u16 *d_img = nullptr, *d_stem = nullptr, *d_pool = nullptr, *d_stem_w = nullptr, *d_zero = nullptr;
-    float *d_stem_b = nullptr, *d_stem_wf = nullptr, *d_imgf = nullptr;   // fp32 mode: [64][49][4] stem weights, normalised NHWC4 image (PVR_F32S: d_stem_w holds the
-                                                                          // split image of the [64][7][8][4] weights, d_imgf the zero-bordered (crop + 6, crop + 8) image)
-    void *d_buf[B_COUNT] = {nullptr};
+    u16 *d_stem_w = nullptr, *d_zero = nullptr;
+    float *d_stem_b = nullptr, *d_stem_wf = nullptr;   // fp32 mode: [64][49][4] stem weights (PVR_F32S: d_stem_w holds the split image of the [64][7][8][4] weights)
     size_t buf_elems = 0;
-    // second activation workspace (pvr_encoder_forward_lane, lane 1): lets the caller keep two batches in flight on two
-    // streams; allocated on first use.  The members above are the CURRENT lane's pointers (swapped by use_lane).
-    struct LaneWs { u16 *d_img = nullptr, *d_stem = nullptr; float *d_imgf = nullptr; void *d_buf[B_COUNT] = {nullptr}; bool valid = false; } lane_ws[PVR_MAX_LANES];
-    int cur_lane = 0;
-    hipEvent_t lane_done[PVR_MAX_LANES] = {nullptr};   // recorded after each forward on the lane; the next forward on it waits
-    hipStream_t lane_stream[PVR_MAX_LANES] = {nullptr};   // stream of that forward (no wait when the stream is the same)
+    // Everything that exists once per lane (pvr_encoder_forward_lane keeps up to PVR_MAX_LANES batches in flight, each on its own activation workspace).  A forward
+    // is given its lane (encoder.hip: get_lane); lane 0 is made at finalize, the others on first use.  The ViT plans keep their workspaces in vit.hip (pvr_vit::Ws)
+    // and the 'random' PVR has a single one: of a Lane they use the event and the stream only.
+    struct Lane {
+        u16 *d_img = nullptr, *d_stem = nullptr;       // zero-bordered 16-bit image (border = conv1 padding, written once at allocation); 112x112x64 stem output
+        float *d_imgf = nullptr;                       // fp32 modes: normalised NHWC4 image (PVR_F32S: zero-bordered (crop + 6, crop + 8), border written once at allocation)
+        void *buf[B_COUNT] = {nullptr};
+        float *d_smallk = nullptr;                     // the low-latency plan's fp32 partial planes (pvr_encoder_set_low_latency / finalize / first use of the lane: never in a forward)
+        float *ap_rows = nullptr;                      // CLIP RN50: this lane's rows of ap_out (not owned)
+        hipEvent_t done = nullptr;                     // recorded after each forward on the lane; the next forward on it waits
+        hipStream_t stream = nullptr;                  // stream of that forward (no wait when the stream is the same)
+        bool valid = false;                            // the workspace exists
+    } lanes[PVR_MAX_LANES];
+    int last_lane = 0;                               // the lane the last forward ran on: the taps read its workspace, with that forward's last_n
     int crop_pos = 0;                                // 0 centre (reference), 1..4 corner crops (pvr_encoder_set_crop_position)
-    int span_first = -1, span_last = -1;             // pvr_encoder_profile_span: the two marks of the forward that are recorded
     int last_n = 0;
     std::string stop_after;                                          // debug: end the forward after this tap
     std::map<std::string, std::pair<int, std::vector<int>>> taps;   // name -> (buf, {h,w,c,is_f32})
-    // CLIP RN50 (clip_rn50.hip): antialiased-bicubic resizer (a weight-less pvr_vit), attention-pool parameters
-    struct pvr_vit *resizer = nullptr;
+    // CLIP RN50 (clip_rn50.hip): antialiased-bicubic resizer, attention-pool parameters
+    Resizer resizer;
     u16 *ap_wqkv = nullptr, *ap_wc = nullptr;
     float *ap_bqkv = nullptr, *ap_bc = nullptr, *ap_pos = nullptr, *ap_out = nullptr;
-    struct pvr_vit *vit = nullptr;
+    struct pvr_vit *vit = nullptr;                                   // CLIP ViT plan (vit.hip) when arch >= PVR_ARCH_CLIP_VIT_B32
     bool host = false;                                               // pvr_encoder_set_host_backend: CPU plan (host_encoder.hip), host pointers in / out
     struct pvr::HostPlan *hplan = nullptr;
-    struct pvr_random5 *rnd = nullptr;                               // 'random' 5-conv PVR (random_pvr.hip)                                   // CLIP ViT plan (vit.hip) when arch >= PVR_ARCH_CLIP_VIT_B32
+    struct pvr_random5 *rnd = nullptr;                               // 'random' 5-conv PVR (random_pvr.hip)
 };
 
 
@@ -297,7 +310,6 @@ void host_destroy(pvr_encoder *e);
 // vit.hip
 pvr_status vit_create(pvr_encoder *e);
 pvr_status vit_finalize(pvr_encoder *e);
-pvr_status vit_use_lane(pvr_encoder *e, int lane);
 // vit.hip pieces shared with the CLIP RN50 plan: Resize(224, bicubic, antialias) + CenterCrop into a (res,res,3) uint8 image, attention core
 pvr_status resizer_create(pvr_encoder *e);
 pvr_status resizer_run(pvr_encoder *e, int lane, const uint8_t *frames, int nb, int h, int w, hipStream_t st, const uint8_t **u8, int *oh, int *ow);
@@ -312,7 +324,7 @@ pvr_status launch_cls_head(const float *x, const float *gamma, const float *beta
 pvr_status launch_avgpool2(const void *in, void *out, int n, int h, int w, int c, int dtype, hipStream_t st);
 pvr_status launch_attnpool_tokens(const float *x, const float *pos, void *tokens, int n, int hw, int c, int dtype, hipStream_t st);
 pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
-pvr_status vit_forward(pvr_encoder *e, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st);
+pvr_status vit_forward(pvr_encoder *e, int lane, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st);
 void vit_destroy(pvr_encoder *e);
 pvr_status vit_tap(pvr_encoder *e, const char *name, float *out, int64_t cap, int64_t *count, hipStream_t st);
 }  // namespace pvr

@@ -349,24 +349,16 @@ struct pvr_vit {
     int patch = 32, width = 768, layers = 12, heads = 12, out_dim = 512, res = 224, grid = 7, T = 50, TK = 64;
     bool mae = false;               // timm/MAE layout: patch bias, no ln_pre, LN eps 1e-6, erf GELU, CLS output without proj
     float eps = 1e-5f;
-    int act = 2, resize_to = 224;
+    int act = 2;
     std::vector<VitBlock> blocks;
     u16 *w_patch = nullptr;
     float *b_patch = nullptr, *cls = nullptr, *pos = nullptr, *lnpre_w = nullptr, *lnpre_b = nullptr, *lnpost_w = nullptr,
           *lnpost_b = nullptr, *proj = nullptr;
-    // workspace (chunk frames)
-    u16 *A = nullptr, *y = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *zero = nullptr;
-    float *pe = nullptr, *x0 = nullptr, *x1 = nullptr;
-    // antialiased-bicubic resize state, rebuilt when the frame size changes
-    int rs_h = 0, rs_w = 0, rs_rh = 0, rs_rw = 0, rs_maxk_h = 0, rs_maxk_w = 0;
-    int *rs_xmin = nullptr, *rs_xsize = nullptr, *rs_ymin = nullptr, *rs_ysize = nullptr;
-    float *rs_wx = nullptr, *rs_wy = nullptr, *rs_tmp = nullptr;
-    uint8_t *rs_u8 = nullptr;
-    // second workspace lane (pvr_encoder_forward_lane): the members above are the CURRENT lane's pointers
+    u16 *zero = nullptr;
+    // one activation workspace (chunk frames) per lane (pvr_encoder_forward_lane): lane 0 is made at finalize, the others on first use (vit_use_lane).
+    // A forward, a tap and the resize step are given the lane's Ws
     struct Ws { u16 *A = nullptr, *y = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr; float *pe = nullptr, *x0 = nullptr, *x1 = nullptr; bool valid = false; } ws[PVR_MAX_LANES];
-    float *rs_tmp_l[PVR_MAX_LANES] = {nullptr};
-    uint8_t *rs_u8_l[PVR_MAX_LANES] = {nullptr};
-    int cur = 0;
+    Resizer rs;                     // the transforms' Resize when the short side is not resize_to; a lane that exists has its temporaries
     std::vector<void *> owned;
 };
 
@@ -406,8 +398,8 @@ pvr_status vit_create(pvr_encoder *e) {
     if (e->desc.arch == PVR_ARCH_MAE_VIT_L16) { v->width = 1024; v->layers = 24; v->heads = 16; }   // mae.py:283-288
     if (e->desc.arch == PVR_ARCH_MAE_VIT_H14) { v->width = 1280; v->layers = 32; v->heads = 16; v->patch = 14; }   // mae.py:291-296
     if (v->mae) { v->eps = 1e-6f; v->act = 3; v->out_dim = v->width; }
-    v->res = e->desc.crop;
-    v->resize_to = e->desc.resize;
+    v->res = v->rs.res = e->desc.crop;
+    v->rs.resize_to = e->desc.resize;
     v->grid = v->res / v->patch;
     v->T = v->grid * v->grid + 1;
     v->TK = (v->T + 31) / 32 * 32;
@@ -419,24 +411,7 @@ pvr_status vit_create(pvr_encoder *e) {
     return PVR_OK;
 }
 
-static pvr_status vit_alloc_ws(pvr_encoder *e) {
-    pvr_vit *v = e->vit;
-    const size_t C = e->desc.chunk, rows = C * v->T, prow = C * v->grid * v->grid, W = v->width, K = ((size_t)v->patch * v->patch * 3 + 63) / 64 * 64;
-    auto alloc = [&](void **ptr, size_t bytes) -> pvr_status {
-        PVR_HIP_TRY(hipMalloc(ptr, bytes));
-        v->owned.push_back(*ptr);
-        return PVR_OK;
-    };
-    pvr_status s;
-    if ((s = alloc((void **)&v->A, prow * K * 2))) return s;
-    if ((s = alloc((void **)&v->pe, prow * W * 4))) return s;
-    if ((s = alloc((void **)&v->x0, rows * W * 4))) return s;
-    if ((s = alloc((void **)&v->x1, rows * W * 4))) return s;
-    if ((s = alloc((void **)&v->y, rows * W * 2))) return s;
-    if ((s = alloc((void **)&v->qkv, rows * 3 * W * 2))) return s;
-    if ((s = alloc((void **)&v->att, rows * W * 2))) return s;
-    return alloc((void **)&v->hid, rows * 4 * W * 2);
-}
+static pvr_status vit_use_lane(pvr_encoder *e, int lane, pvr_vit::Ws **out);
 
 pvr_status vit_finalize(pvr_encoder *e) {
     pvr_vit *v = e->vit;
@@ -493,42 +468,26 @@ pvr_status vit_finalize(pvr_encoder *e) {
         if ((s = up_f32(e, p + n_l2 + "weight", W, &b.ln2_w))) return s;
         if ((s = up_f32(e, p + n_l2 + "bias", W, &b.ln2_b))) return s;
     }
-    if ((s = vit_alloc_ws(e))) return s;
-    v->ws[0] = {v->A, v->y, v->qkv, v->att, v->hid, v->pe, v->x0, v->x1, true};
+    pvr_vit::Ws *ws0;
+    if ((s = vit_use_lane(e, 0, &ws0))) return s;
     PVR_HIP_TRY(hipMalloc((void **)&v->zero, 256));
     v->owned.push_back(v->zero);
     PVR_HIP_TRY(hipMemset(v->zero, 0, 256));
     return PVR_OK;
 }
 
-pvr_status vit_use_lane(pvr_encoder *e, int lane) {
-    pvr_vit *v = e->vit;
-    if (lane == v->cur) return PVR_OK;
-    if (!v->ws[lane].valid) {
-        pvr_status s = vit_alloc_ws(e);
-        if (s) return s;
-        PVR_HIP_TRY(hipDeviceSynchronize());
-        v->ws[lane] = {v->A, v->y, v->qkv, v->att, v->hid, v->pe, v->x0, v->x1, true};
-    }
-    if (v->rs_h != 0 && !v->rs_tmp_l[lane]) {                  // resize tables exist already: this lane's temporaries do not yet
-        PVR_HIP_TRY(hipMalloc((void **)&v->rs_tmp_l[lane], (size_t)e->desc.chunk * v->rs_h * v->res * 3 * sizeof(float)));
-        PVR_HIP_TRY(hipMalloc((void **)&v->rs_u8_l[lane], (size_t)e->desc.chunk * v->res * v->res * 3));
-        PVR_HIP_TRY(hipDeviceSynchronize());
-    }
-    const auto &w = v->ws[lane];
-    v->A = w.A; v->y = w.y; v->qkv = w.qkv; v->att = w.att; v->hid = w.hid; v->pe = w.pe; v->x0 = w.x0; v->x1 = w.x1;
-    v->rs_tmp = v->rs_tmp_l[lane]; v->rs_u8 = v->rs_u8_l[lane];
-    v->cur = lane;
-    return PVR_OK;
+static void resizer_free(Resizer &r) {
+    for (void *q : {(void *)r.xmin, (void *)r.xsize, (void *)r.ymin, (void *)r.ysize, (void *)r.wx, (void *)r.wy}) if (q) (void)hipFree(q);
+    for (auto &t : r.lane) { if (t.tmp) (void)hipFree(t.tmp); if (t.u8) (void)hipFree(t.u8); }
+    const int res = r.res, resize_to = r.resize_to;
+    r = Resizer();                                             // (no tables: h = w = 0)
+    r.res = res; r.resize_to = resize_to;
 }
 
 void vit_destroy(pvr_encoder *e) {
     if (!e->vit) return;
     for (void *p : e->vit->owned) (void)hipFree(p);
-    pvr_vit *v = e->vit;
-    std::vector<void *> rs = {v->rs_xmin, v->rs_xsize, v->rs_ymin, v->rs_ysize, v->rs_wx, v->rs_wy};
-    for (int l = 0; l < PVR_MAX_LANES; ++l) { rs.push_back(v->rs_tmp_l[l]); rs.push_back(v->rs_u8_l[l]); }
-    for (void *q : rs) if (q) (void)hipFree(q);
+    resizer_free(e->vit->rs);
     delete e->vit;
     e->vit = nullptr;
 }
@@ -588,36 +547,83 @@ static void cubic_tables(int in, int out, std::vector<int> &mn, std::vector<int>
     }
 }
 
-static pvr_status aa_prepare(pvr_encoder *e, int h, int w) {
-    pvr_vit *v = e->vit;
-    if (v->rs_h == h && v->rs_w == w) return PVR_OK;
-    const int sh = w <= h ? w : h, lg = w <= h ? h : w;
-    const int ns = v->resize_to, nl = (int)((double)v->resize_to * (double)lg / (double)sh);     // torchvision resize(int size)
-    v->rs_rw = w <= h ? ns : nl; v->rs_rh = w <= h ? nl : ns;
-    std::vector<int> xm, xs, ym, ys;
-    std::vector<float> wx, wy;
-    if (v->mae) {
-        cubic_tables(w, v->rs_rw, xm, xs, wx, v->rs_maxk_w);
-        cubic_tables(h, v->rs_rh, ym, ys, wy, v->rs_maxk_h);
-    } else {
-        aa_tables(w, v->rs_rw, xm, xs, wx, v->rs_maxk_w);
-        aa_tables(h, v->rs_rh, ym, ys, wy, v->rs_maxk_h);
+// The resizer's tables for (h, w) frames and the temporaries of the lanes in `lanes` (bit l: lane l).  A change of frame size rebuilds the tables (cubic: the
+// 'mae' names' plain bicubic, else antialiased) and drops every lane's temporaries.  Allocates and synchronises the device, so only then - or when a lane has no
+// temporaries of this size yet
+static pvr_status aa_prepare(Resizer &r, int chunk, int h, int w, bool cubic, unsigned lanes) {
+    bool changed = false;
+    if (r.h != h || r.w != w) {
+        const int sh = w <= h ? w : h, lg = w <= h ? h : w;
+        const int ns = r.resize_to, nl = (int)((double)r.resize_to * (double)lg / (double)sh);     // torchvision resize(int size)
+        std::vector<int> xm, xs, ym, ys;
+        std::vector<float> wx, wy;
+        PVR_HIP_TRY(hipDeviceSynchronize());
+        resizer_free(r);
+        r.rw = w <= h ? ns : nl; r.rh = w <= h ? nl : ns;
+        (cubic ? cubic_tables : aa_tables)(w, r.rw, xm, xs, wx, r.maxk_w);
+        (cubic ? cubic_tables : aa_tables)(h, r.rh, ym, ys, wy, r.maxk_h);
+        pvr_status s;
+        if ((s = enc_upload(&r.xmin, xm)) || (s = enc_upload(&r.xsize, xs)) || (s = enc_upload(&r.ymin, ym)) ||
+            (s = enc_upload(&r.ysize, ys)) || (s = enc_upload(&r.wx, wx)) || (s = enc_upload(&r.wy, wy))) return s;
+        r.h = h; r.w = w;
+        changed = true;
     }
-    std::vector<void *> old = {v->rs_xmin, v->rs_xsize, v->rs_ymin, v->rs_ysize, v->rs_wx, v->rs_wy};
-    for (int l = 0; l < PVR_MAX_LANES; ++l) { old.push_back(v->rs_tmp_l[l]); old.push_back(v->rs_u8_l[l]); }
-    PVR_HIP_TRY(hipDeviceSynchronize());
-    for (void *q : old) if (q) (void)hipFree(q);
-    pvr_status s;
-    if ((s = enc_upload(&v->rs_xmin, xm)) || (s = enc_upload(&v->rs_xsize, xs)) || (s = enc_upload(&v->rs_ymin, ym)) ||
-        (s = enc_upload(&v->rs_ysize, ys)) || (s = enc_upload(&v->rs_wx, wx)) || (s = enc_upload(&v->rs_wy, wy))) return s;
     for (int l = 0; l < PVR_MAX_LANES; ++l) {
-        if (l > 0 && !v->ws[l].valid) { v->rs_tmp_l[l] = nullptr; v->rs_u8_l[l] = nullptr; continue; }   // lanes never used need no buffers
-        PVR_HIP_TRY(hipMalloc((void **)&v->rs_tmp_l[l], (size_t)e->desc.chunk * h * v->res * 3 * sizeof(float)));
-        PVR_HIP_TRY(hipMalloc((void **)&v->rs_u8_l[l], (size_t)e->desc.chunk * v->res * v->res * 3));
+        Resizer::Tmp &t = r.lane[l];
+        if (!(lanes >> l & 1) || t.u8) continue;
+        if (!t.tmp) PVR_HIP_TRY(hipMalloc((void **)&t.tmp, (size_t)chunk * h * r.res * 3 * sizeof(float)));
+        PVR_HIP_TRY(hipMalloc((void **)&t.u8, (size_t)chunk * r.res * r.res * 3));
+        changed = true;
     }
-    v->rs_tmp = v->rs_tmp_l[v->cur]; v->rs_u8 = v->rs_u8_l[v->cur];
+    if (changed) PVR_HIP_TRY(hipDeviceSynchronize());
+    return PVR_OK;
+}
+
+// the two passes of the resize on the lane's temporaries: lane.u8 = the (res, res, 3) uint8 crop of every frame
+static void launch_aa_resize(const Resizer &r, int lane, const uint8_t *frames, int nb, int h, int w, hipStream_t st) {
+    const Resizer::Tmp &t = r.lane[lane];
+    const int top = (int)nearbyint((r.rh - r.res) / 2.0), left = (int)nearbyint((r.rw - r.res) / 2.0);
+    const size_t t1 = (size_t)nb * h * r.res * 3, t2 = (size_t)nb * r.res * r.res * 3;
+    hipLaunchKernelGGL(aa_resize_h_kernel, dim3((int)((t1 + 255) / 256 > 8192 ? 8192 : (t1 + 255) / 256)), dim3(256), 0, st, frames,
+                       t.tmp, r.xmin, r.xsize, r.wx, r.maxk_w, nb, h, w, left, r.res);
+    hipLaunchKernelGGL(aa_resize_v_kernel, dim3((int)((t2 + 255) / 256 > 8192 ? 8192 : (t2 + 255) / 256)), dim3(256), 0, st,
+                       t.tmp, t.u8, r.ymin, r.ysize, r.wy, r.maxk_h, nb, h, top, r.res);
+}
+
+static pvr_status vit_alloc_ws(pvr_encoder *e, pvr_vit::Ws &n) {
+    const pvr_vit *v = e->vit;
+    const size_t C = e->desc.chunk, rows = C * v->T, prow = C * v->grid * v->grid, W = v->width, K = ((size_t)v->patch * v->patch * 3 + 63) / 64 * 64;
+    PVR_HIP_TRY(hipMalloc((void **)&n.A, prow * K * 2));
+    PVR_HIP_TRY(hipMalloc((void **)&n.pe, prow * W * 4));
+    PVR_HIP_TRY(hipMalloc((void **)&n.x0, rows * W * 4));
+    PVR_HIP_TRY(hipMalloc((void **)&n.x1, rows * W * 4));
+    PVR_HIP_TRY(hipMalloc((void **)&n.y, rows * W * 2));
+    PVR_HIP_TRY(hipMalloc((void **)&n.qkv, rows * 3 * W * 2));
+    PVR_HIP_TRY(hipMalloc((void **)&n.att, rows * W * 2));
+    PVR_HIP_TRY(hipMalloc((void **)&n.hid, rows * 4 * W * 2));
     PVR_HIP_TRY(hipDeviceSynchronize());
-    v->rs_h = h; v->rs_w = w;
+    return PVR_OK;
+}
+
+// The lane a forward runs on.  First use (lane 0: finalize) allocates it off the hot path, into a local Ws that enters the array - and its buffers the free
+// list - only when every allocation succeeded, the lane's resize temporaries included when tables exist: a failure leaves the other lanes as they were
+static pvr_status vit_use_lane(pvr_encoder *e, int lane, pvr_vit::Ws **out) {
+    pvr_vit *v = e->vit;
+    pvr_vit::Ws &slot = v->ws[lane];
+    if (!slot.valid) {
+        pvr_vit::Ws n;
+        pvr_status s = vit_alloc_ws(e, n);
+        if (!s && v->rs.h != 0) s = aa_prepare(v->rs, e->desc.chunk, v->rs.h, v->rs.w, v->mae, 1u << lane);
+        const auto bufs = {(void *)n.A, (void *)n.pe, (void *)n.x0, (void *)n.x1, (void *)n.y, (void *)n.qkv, (void *)n.att, (void *)n.hid};
+        if (s) {
+            for (void *q : bufs) if (q) (void)hipFree(q);
+            return s;
+        }
+        v->owned.insert(v->owned.end(), bufs);
+        n.valid = true;
+        slot = n;
+    }
+    *out = &slot;
     return PVR_OK;
 }
 
@@ -686,16 +692,23 @@ pvr_status launch_cls_head(const float *x, const float *gamma, const float *beta
 }
 
 template <bool F16, int WD>
-static pvr_status vit_forward_t(pvr_encoder *e, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st) {
+static pvr_status vit_forward_t(pvr_encoder *e, int lane, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st) {
     pvr_vit *v = e->vit;
     const int W = v->width, P = v->patch, K = (P * P * 3 + 63) / 64 * 64, T = v->T, g2 = v->grid * v->grid, dt = e->desc.dtype;
     PVR_REQUIRE(W == WD, "vit: width %d does not match the instantiated plan", W);
     // transforms (embeddings.py:309-314): Resize(res, BICUBIC, antialias) is the identity when the short side is res
     const int sh = w <= h ? w : h;
-    const bool resize = sh != v->resize_to;
+    const bool resize = sh != v->rs.resize_to;
     pvr_status s;
-    if (resize && (s = aa_prepare(e, h, w))) return s;
-    const int eh = resize ? v->rs_rh : h, ew = resize ? v->rs_rw : w;              // size after Resize
+    pvr_vit::Ws *wsp;
+    if ((s = vit_use_lane(e, lane, &wsp))) return s;
+    const pvr_vit::Ws &ws = *wsp;
+    if (resize) {
+        unsigned lanes = 0;                                                        // every lane that exists has resize temporaries
+        for (int l = 0; l < PVR_MAX_LANES; ++l) lanes |= (unsigned)v->ws[l].valid << l;
+        if ((s = aa_prepare(v->rs, e->desc.chunk, h, w, v->mae, lanes))) return s;
+    }
+    const int eh = resize ? v->rs.rh : h, ew = resize ? v->rs.rw : w;              // size after Resize
     const int top = (int)nearbyint((eh - v->res) / 2.0), left = (int)nearbyint((ew - v->res) / 2.0);
     for (int f0 = 0; f0 < n; f0 += e->desc.chunk) {
         const int nb = (n - f0 < e->desc.chunk) ? n - f0 : e->desc.chunk;
@@ -703,41 +716,37 @@ static pvr_status vit_forward_t(pvr_encoder *e, const uint8_t *frames, int n, in
         const uint8_t *fr = frames + (size_t)f0 * h * w * 3;
         const size_t tot = (size_t)prow * (K / 8);
         if (resize) {
-            const size_t t1 = (size_t)nb * h * v->res * 3, t2 = (size_t)nb * v->res * v->res * 3;
-            hipLaunchKernelGGL(aa_resize_h_kernel, dim3((int)((t1 + 255) / 256 > 8192 ? 8192 : (t1 + 255) / 256)), dim3(256), 0, st, fr,
-                               v->rs_tmp, v->rs_xmin, v->rs_xsize, v->rs_wx, v->rs_maxk_w, nb, h, w, left, v->res);
-            hipLaunchKernelGGL(aa_resize_v_kernel, dim3((int)((t2 + 255) / 256 > 8192 ? 8192 : (t2 + 255) / 256)), dim3(256), 0, st,
-                               v->rs_tmp, v->rs_u8, v->rs_ymin, v->rs_ysize, v->rs_wy, v->rs_maxk_h, nb, h, top, v->res);
+            launch_aa_resize(v->rs, lane, fr, nb, h, w, st);
             hipLaunchKernelGGL(patchify_kernel<F16>, dim3((int)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256)), dim3(256), 0, st,
-                               v->rs_u8, v->A, nb, v->res, v->res, 0, 0, v->res, P);
+                               v->rs.lane[lane].u8, ws.A, nb, v->res, v->res, 0, 0, v->res, P);
         } else {
             hipLaunchKernelGGL(patchify_kernel<F16>, dim3((int)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256)), dim3(256), 0, st,
-                               fr, v->A, nb, h, w, top, left, v->res, P);
+                               fr, ws.A, nb, h, w, top, left, v->res, P);
         }
         PVR_LAUNCH_CHECK();
         // patch embedding GEMM -> fp32 [prow][W]
-        if ((s = launch_conv(e->sw, v->A, v->w_patch, v->b_patch, nullptr, v->pe, v->zero, prow, 1, 1, K, W, 1, 1, 1, 0, 0, 1, dt, st))) return s;
+        if ((s = launch_conv(e->sw, ws.A, v->w_patch, v->b_patch, nullptr, ws.pe, v->zero, prow, 1, 1, K, W, 1, 1, 1, 0, 0, 1, dt, st))) return s;
         // tokens + positional embedding + ln_pre -> residual stream x0 (fp32)
-        if ((s = launch_layernorm(nullptr, v->pe, v->cls, v->pos, v->lnpre_w, v->lnpre_b, v->x0, nullptr, rows, T, W, v->eps, v->mae ? 0 : 1, dt, st))) return s;
+        if ((s = launch_layernorm(nullptr, ws.pe, v->cls, v->pos, v->lnpre_w, v->lnpre_b, ws.x0, nullptr, rows, T, W, v->eps, v->mae ? 0 : 1, dt, st))) return s;
         e->last_n = nb;
         const std::string &stop = e->stop_after;
         if (stop == "pe" || stop == "ln_pre") return PVR_OK;
-        float *x = v->x0, *xn = v->x1;
+        float *x = ws.x0, *xn = ws.x1;
         int bi = 0;
         for (auto &b : v->blocks) {
-            if ((s = launch_layernorm(x, nullptr, nullptr, nullptr, b.ln1_w, b.ln1_b, nullptr, v->y, rows, T, W, v->eps, 1, dt, st))) return s;
-            if ((s = launch_conv(e->sw, v->y, b.w_qkv, b.b_qkv, nullptr, v->qkv, v->zero, rows, 1, 1, W, 3 * W, 1, 1, 1, 0, 0, 0, dt, st))) return s;
+            if ((s = launch_layernorm(x, nullptr, nullptr, nullptr, b.ln1_w, b.ln1_b, nullptr, ws.y, rows, T, W, v->eps, 1, dt, st))) return s;
+            if ((s = launch_conv(e->sw, ws.y, b.w_qkv, b.b_qkv, nullptr, ws.qkv, v->zero, rows, 1, 1, W, 3 * W, 1, 1, 1, 0, 0, 0, dt, st))) return s;
             if (bi == 0 && stop == "qkv0") return PVR_OK;
-            if ((s = launch_attention_any<F16>(v->qkv, v->att, T, v->TK, W, v->heads, nb, st))) return s;
+            if ((s = launch_attention_any<F16>(ws.qkv, ws.att, T, v->TK, W, v->heads, nb, st))) return s;
             PVR_LAUNCH_CHECK();
             if (bi == 0 && stop == "att0") return PVR_OK;
             // x' = x + out_proj(att): fp32 residual in (bit1), fp32 out (bit0)
-            if ((s = launch_conv(e->sw, v->att, b.w_out, b.b_out, x, xn, v->zero, rows, 1, 1, W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
+            if ((s = launch_conv(e->sw, ws.att, b.w_out, b.b_out, x, xn, v->zero, rows, 1, 1, W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
             if (bi == 0 && stop == "res0") return PVR_OK;
-            if ((s = launch_layernorm(xn, nullptr, nullptr, nullptr, b.ln2_w, b.ln2_b, nullptr, v->y, rows, T, W, v->eps, 1, dt, st))) return s;
-            if ((s = launch_conv(e->sw, v->y, b.w_fc, b.b_fc, nullptr, v->hid, v->zero, rows, 1, 1, W, 4 * W, 1, 1, 1, 0, v->act, 0, dt, st))) return s;   // QuickGELU / GELU
+            if ((s = launch_layernorm(xn, nullptr, nullptr, nullptr, b.ln2_w, b.ln2_b, nullptr, ws.y, rows, T, W, v->eps, 1, dt, st))) return s;
+            if ((s = launch_conv(e->sw, ws.y, b.w_fc, b.b_fc, nullptr, ws.hid, v->zero, rows, 1, 1, W, 4 * W, 1, 1, 1, 0, v->act, 0, dt, st))) return s;   // QuickGELU / GELU
             if (bi == 0 && stop == "fc0") return PVR_OK;
-            if ((s = launch_conv(e->sw, v->hid, b.w_proj, b.b_proj, xn, x, v->zero, rows, 1, 1, 4 * W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
+            if ((s = launch_conv(e->sw, ws.hid, b.w_proj, b.b_proj, xn, x, v->zero, rows, 1, 1, 4 * W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
             if (stop == "block" + std::to_string(bi)) return PVR_OK;
             ++bi;
         }
@@ -759,23 +768,25 @@ static pvr_status launch_u8_to_f32(const uint8_t *in, float *out, size_t n, hipS
 // parity taps (after a forward stopped with pvr_encoder_debug_stop_after): fp32 copies of plan buffers
 pvr_status vit_tap(pvr_encoder *e, const char *name, float *out, int64_t cap, int64_t *count, hipStream_t st) {
     pvr_vit *v = e->vit;
+    const pvr_vit::Ws &ws = v->ws[e->last_lane];                // the lane the last forward ran on
+    const uint8_t *rs_u8 = v->rs.lane[e->last_lane].u8;
     const std::string nm = name;
     const size_t rows = (size_t)e->last_n * v->T, W = v->width;
     const void *src = nullptr;
     size_t elems = 0;
     bool f32 = true;
-    if (nm == "pe") { src = v->pe; elems = (size_t)e->last_n * v->grid * v->grid * W; }
-    else if (nm == "ln_pre" || nm.rfind("block", 0) == 0) { src = v->x0; elems = rows * W; }
-    else if (nm == "qkv0") { src = v->qkv; elems = rows * 3 * W; f32 = false; }
-    else if (nm == "att0") { src = v->att; elems = rows * W; f32 = false; }
-    else if (nm == "res0") { src = v->x1; elems = rows * W; }
-    else if (nm == "fc0") { src = v->hid; elems = rows * 4 * W; f32 = false; }
+    if (nm == "pe") { src = ws.pe; elems = (size_t)e->last_n * v->grid * v->grid * W; }
+    else if (nm == "ln_pre" || nm.rfind("block", 0) == 0) { src = ws.x0; elems = rows * W; }
+    else if (nm == "qkv0") { src = ws.qkv; elems = rows * 3 * W; f32 = false; }
+    else if (nm == "att0") { src = ws.att; elems = rows * W; f32 = false; }
+    else if (nm == "res0") { src = ws.x1; elems = rows * W; }
+    else if (nm == "fc0") { src = ws.hid; elems = rows * 4 * W; f32 = false; }
     else if (nm == "resized") {                      // uint8 crop after the antialiased Resize, as fp32
-        PVR_REQUIRE(v->rs_u8 != nullptr, "no resize has run");
+        PVR_REQUIRE(rs_u8 != nullptr, "no resize has run");
         elems = (size_t)e->last_n * v->res * v->res * 3;
         PVR_REQUIRE((int64_t)elems <= cap, "tap resized needs %zu elements", elems);
         *count = (int64_t)elems;
-        return launch_u8_to_f32(v->rs_u8, out, elems, st);
+        return launch_u8_to_f32(rs_u8, out, elems, st);
     }
     else { set_error("unknown vit tap %s", name); return PVR_ERR_INVALID; }
     PVR_REQUIRE((int64_t)elems <= cap, "tap %s needs %zu elements", name, elems);
@@ -794,54 +805,36 @@ pvr_status launch_attention(const void *qkv, void *out, int T, int W, int heads,
                             : launch_attention_any<false>((const u16 *)qkv, (u16 *)out, T, TK, W, heads, nb, st);
 }
 
-// Resize(res, BICUBIC, antialias=True) + CenterCrop(res) as a stand-alone service (CLIP RN50 plan): a weight-less pvr_vit that
-// only owns the resampling tables and per-lane temporaries
+// Resize(res, BICUBIC, antialias=True) + CenterCrop(res) as a stand-alone service (CLIP RN50 plan): the encoder's own Resizer; a lane's temporaries are
+// made when that lane is first resized on
 pvr_status resizer_create(pvr_encoder *e) {
-    pvr_vit *v = new pvr_vit();
-    v->res = e->desc.crop; v->resize_to = e->desc.resize; v->mae = false;
-    for (auto &w : v->ws) w.valid = true;                       // every lane gets its resize temporaries
-    e->resizer = v;
+    e->resizer.res = e->desc.crop; e->resizer.resize_to = e->desc.resize;
     return PVR_OK;
 }
 
 pvr_status resizer_run(pvr_encoder *e, int lane, const uint8_t *frames, int nb, int h, int w, hipStream_t st, const uint8_t **u8, int *oh, int *ow) {
-    pvr_vit *v = e->resizer;
+    Resizer &r = e->resizer;
     const int sh = w <= h ? w : h;
-    if (sh == v->resize_to) { *u8 = frames; *oh = h; *ow = w; return PVR_OK; }      // Resize is the identity: the caller centre-crops
-    pvr_vit *saved = e->vit;
-    e->vit = v;
-    pvr_status s = aa_prepare(e, h, w);
-    e->vit = saved;
+    if (sh == r.resize_to) { *u8 = frames; *oh = h; *ow = w; return PVR_OK; }      // Resize is the identity: the caller centre-crops
+    pvr_status s = aa_prepare(r, e->desc.chunk, h, w, false, 1u << lane);
     if (s) return s;
-    const int top = (int)nearbyint((v->rs_rh - v->res) / 2.0), left = (int)nearbyint((v->rs_rw - v->res) / 2.0);
-    const size_t t1 = (size_t)nb * h * v->res * 3, t2 = (size_t)nb * v->res * v->res * 3;
-    hipLaunchKernelGGL(aa_resize_h_kernel, dim3((int)((t1 + 255) / 256 > 8192 ? 8192 : (t1 + 255) / 256)), dim3(256), 0, st, frames,
-                       v->rs_tmp_l[lane], v->rs_xmin, v->rs_xsize, v->rs_wx, v->rs_maxk_w, nb, h, w, left, v->res);
-    hipLaunchKernelGGL(aa_resize_v_kernel, dim3((int)((t2 + 255) / 256 > 8192 ? 8192 : (t2 + 255) / 256)), dim3(256), 0, st,
-                       v->rs_tmp_l[lane], v->rs_u8_l[lane], v->rs_ymin, v->rs_ysize, v->rs_wy, v->rs_maxk_h, nb, h, top, v->res);
+    launch_aa_resize(r, lane, frames, nb, h, w, st);
     PVR_LAUNCH_CHECK();
-    *u8 = v->rs_u8_l[lane]; *oh = v->res; *ow = v->res;
+    *u8 = r.lane[lane].u8; *oh = r.res; *ow = r.res;
     return PVR_OK;
 }
 
-void resizer_destroy(pvr_encoder *e) {
-    if (!e->resizer) return;
-    pvr_vit *saved = e->vit;
-    e->vit = e->resizer;
-    vit_destroy(e);
-    e->vit = saved;
-    e->resizer = nullptr;
-}
+void resizer_destroy(pvr_encoder *e) { resizer_free(e->resizer); }
 
-pvr_status vit_forward(pvr_encoder *e, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st) {
+pvr_status vit_forward(pvr_encoder *e, int lane, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st) {
     if (e->vit->width == 1024)
-        return e->desc.dtype == PVR_F16 ? vit_forward_t<true, 1024>(e, frames, n, h, w, out, out_stride, st)
-                                        : vit_forward_t<false, 1024>(e, frames, n, h, w, out, out_stride, st);
+        return e->desc.dtype == PVR_F16 ? vit_forward_t<true, 1024>(e, lane, frames, n, h, w, out, out_stride, st)
+                                        : vit_forward_t<false, 1024>(e, lane, frames, n, h, w, out, out_stride, st);
     if (e->vit->width == 1280)
-        return e->desc.dtype == PVR_F16 ? vit_forward_t<true, 1280>(e, frames, n, h, w, out, out_stride, st)
-                                        : vit_forward_t<false, 1280>(e, frames, n, h, w, out, out_stride, st);
-    return e->desc.dtype == PVR_F16 ? vit_forward_t<true, 768>(e, frames, n, h, w, out, out_stride, st)
-                                    : vit_forward_t<false, 768>(e, frames, n, h, w, out, out_stride, st);
+        return e->desc.dtype == PVR_F16 ? vit_forward_t<true, 1280>(e, lane, frames, n, h, w, out, out_stride, st)
+                                        : vit_forward_t<false, 1280>(e, lane, frames, n, h, w, out, out_stride, st);
+    return e->desc.dtype == PVR_F16 ? vit_forward_t<true, 768>(e, lane, frames, n, h, w, out, out_stride, st)
+                                    : vit_forward_t<false, 768>(e, lane, frames, n, h, w, out, out_stride, st);
 }
 
 }  // namespace pvr

@@ -813,6 +813,47 @@ def test_two_lanes_in_flight_match_sequential_forwards(variant):
     assert torch.equal(m(fb), ref_b)                                   # the default entry point still works afterwards (lane 0)
 
 
+def test_two_lanes_with_two_frame_sizes_resize_and_tap_per_lane():
+    """CLIP ViT-B/32 with a Resize in front, a different frame size on each lane: the resampling tables are rebuilt at every size change (a device
+    synchronise each time), both lanes keep giving the sequential results bit for bit, and the 'resized' tap reads the lane of the last forward."""
+    from pvr_habitat_amd.embeddings import HipResNet50
+    m = HipResNet50(synth.clip_vit_state_dict(1, patch=32), 'clip_b32', compute_dtype='bf16', max_batch=4)
+    fa = torch.from_numpy(synth.frames(13, 3, 64, 96)).cuda()
+    fb = torch.from_numpy(synth.frames(14, 2, 96, 128)).cuda()
+    ref_a = m(fa).clone()
+    ref_b = m(fb).clone()
+    rs_b = m.tap('resized', 2 * 224 * 224 * 3).clone()
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    oa, ob = torch.zeros_like(ref_a), torch.zeros_like(ref_b)
+    torch.cuda.synchronize()
+    for _ in range(2):
+        with torch.cuda.stream(sa):
+            m.forward_into(fa, oa, lane=0)
+        with torch.cuda.stream(sb):
+            m.forward_into(fb, ob, lane=1)
+    torch.cuda.synchronize()
+    assert torch.equal(oa, ref_a) and torch.equal(ob, ref_b)
+    assert torch.equal(m.tap('resized', 2 * 224 * 224 * 3), rs_b)
+
+
+def test_taps_follow_the_lane_of_the_last_forward():
+    """pvr_encoder_tap reads the workspace of the lane the last forward ran on, with that forward's frame count."""
+    from pvr_habitat_amd.embeddings import HipResNet50
+    m = HipResNet50(synth.resnet50_state_dict(1, 'conv5'), 'conv5', compute_dtype='bf16', max_batch=4)
+    m.set_switch('pool_fuse', 0)                                       # the layer4 activation is written: its tap exists
+    fa = torch.from_numpy(synth.frames(15, 3, 64, 64)).cuda()
+    fb = torch.from_numpy(synth.frames(16, 2, 64, 64)).cuda()
+    out = torch.empty((3, 2048), device='cuda')
+    m(fa); ta = m.tap('layer4', 3 * 49 * 2048).clone()
+    m(fb); tb = m.tap('layer4', 2 * 49 * 2048).clone()
+    assert ta.numel() == 3 * 49 * 2048 and tb.numel() == 2 * 49 * 2048 and not torch.equal(ta[:tb.numel()], tb)
+    m.forward_into(fa, out, lane=0)
+    m.forward_into(fb, out[:2], lane=1)
+    assert torch.equal(m.tap('layer4', 3 * 49 * 2048), tb)             # lane 1's two frames, not lane 0's three
+    m.forward_into(fa, out, lane=0)
+    assert torch.equal(m.tap('layer4', 3 * 49 * 2048), ta)
+
+
 @pytest.mark.parametrize('variant', ['conv5', 'clip_b16'])
 def test_same_lane_forwards_on_different_streams_are_ordered_by_the_library(variant):
     """A forward on the default stream followed AT ONCE (no host or stream synchronisation by the caller) by forwards on
@@ -1263,6 +1304,18 @@ def test_low_latency_plan_for_online_embedding(monkeypatch):
         assert _relerr(o_fast.cpu().numpy(), ref)[0] < tol
         assert torch.equal(fast(d[:1]), o_fast[:1]) and torch.equal(fast(d[1:2]), o_fast[1:2]) and torch.equal(fast(d[:4])[:2], o_fast)
         assert torch.equal(fast(d), base(d))                               # 8 frames: outside the plan, same launches as the default
+        # a second lane has the plan's scratch whichever came first, the lane or the plan
+        out1 = torch.zeros((2, 2048), device='cuda')
+        fast.forward_into(d[:2], out1, lane=1)                             # lane first used with the plan on
+        torch.cuda.synchronize()
+        assert torch.equal(out1, o_fast)
+        late = HipResNet50(sd, 'conv5', compute_dtype=dt, max_batch=8)
+        late.forward_into(d[:2], out1, lane=1)                             # lane made first, plan switched on afterwards
+        late.set_low_latency(True)
+        out1.zero_()
+        late.forward_into(d[:2], out1, lane=1)
+        torch.cuda.synchronize()
+        assert torch.equal(out1, o_fast)
         out = torch.empty((2, 2048), device='cuda')
         t = {}
         for name, m in (('default', base), ('low-latency', fast)):
