@@ -32,8 +32,9 @@ typedef int pvr_status;
 #define PVR_ERR_STATE 4
 
 /* storage / MFMA input type of the encoder ("throughput" = bf16, "parity" = f16); accumulation
- * is always fp32.  PVR_F32 (ResNet50 family only) stores and multiplies in fp32 on the f32-input MFMA: the
- * reference's own arithmetic type, ~1e-6 from the fp32 oracle, at the f32 MFMA rate.  PVR_F32S (same architectures) stores fp32 exactly as PVR_F32 and
+ * is always fp32.  PVR_F32 (torchvision ResNet family, CLIP ViT B/32 and B/16, MAE ViT B/16, L/16, H/14) stores and multiplies in fp32 on the f32-input
+ * MFMA: the reference's own arithmetic type, ~1e-6 from the fp32 oracle, at the f32 MFMA rate; in the ViT plans the attention scores, the softmax and its
+ * probabilities, the LayerNorm outputs and the GELU / QuickGELU epilogues are fp32 too.  PVR_F32S (ResNet family only) stores fp32 exactly as PVR_F32 and
  * multiplies on the 16-bit matrix pipe: every fp32 operand as an exact (hi, lo) pair of f16 values, three MFMAs per fragment pair (conv_split16.hip,
  * stem_split16.hip) - within ~1e-6 of PVR_F32 at several times its rate.  The high part is an f16: activations must stay below 65504 in magnitude
  * (pvr_encoder_check_range validates that); PVR_F32 has the full fp32 range */
@@ -79,7 +80,7 @@ typedef struct pvr_encoder pvr_encoder;
 
 typedef struct pvr_encoder_desc {
     int32_t arch;          /* PVR_ARCH_* */
-    int32_t dtype;         /* PVR_BF16, PVR_F16, or PVR_F32 / PVR_F32S (torchvision ResNet family) */
+    int32_t dtype;         /* PVR_BF16, PVR_F16, PVR_F32 (torchvision ResNet family, CLIP / MAE ViT) or PVR_F32S (torchvision ResNet family) */
     int32_t max_batch;     /* frames per forward call the workspace is sized for */
     int32_t chunk;         /* frames pushed through the layer stack at a time (0 = max_batch) */
     int32_t resize;        /* short-side target, 256 (embeddings.py:81) */
@@ -254,7 +255,9 @@ int64_t pvr_debug_conv_wfrag_launches(void);
 pvr_status pvr_op_split16_pack_weights(const float *w_dev, void *out_dev, int32_t rows, int32_t k, void *hip_stream);
 pvr_status pvr_op_conv2d_split16(const float *in_dev, const void *wgt_split_dev, const float *bias_dev, const float *residual_dev, float *out_dev, int32_t n,
                                  int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t relu, void *hip_stream);
-/* the same convolution on the f32-input MFMA (conv_f32.hip, the PVR_F32 reference-precision mode's kernel): wgt fp32 (cout_pad, k*k*cin) */
+/* the same convolution on the f32-input MFMA (conv_f32.hip, the PVR_F32 reference-precision mode's kernel): wgt fp32 (cout_pad, k*k*cin).  relu is the
+ * activation code of the epilogue: 0 none, 1 ReLU, 2 QuickGELU x * sigmoid(1.702 x), 3 GELU (erf form) - both evaluated to fp32 accuracy (the ViT plans'
+ * linear layers are this call with k = 1 over rows as pixels) */
 pvr_status pvr_op_conv2d_f32(const float *in_dev, const float *wgt_dev, const float *bias_dev, const float *residual_dev, float *out_dev, int32_t n,
                              int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t relu, void *hip_stream);
 int64_t pvr_debug_conv_split16_launches(void);
@@ -310,11 +313,12 @@ pvr_status pvr_op_nonfinite_flag(const float *x_dev, int64_t rows, int64_t cols,
 /* The ViT plans' kernels one at a time (test entry points; the encoder reaches the same launch dispatchers).  A shape that is not built returns a
  * status with a message and launches nothing.
  * Multi-head softmax attention: qkv (nb*T, 3W) 16-bit rows of [q | k | v], head h at columns h*HD.. of each third, HD = W / heads in {64, 80},
- * 1 <= T <= 288; out (nb*T, W) 16-bit.  Scores are scaled by 1/sqrt(HD). */
+ * 1 <= T <= 288; out (nb*T, W) 16-bit.  Scores are scaled by 1/sqrt(HD).  dtype PVR_F32: qkv and out are fp32, both products run on the f32-input MFMA and
+ * nothing in between is rounded to 16 bits (vit_f32.hip). */
 pvr_status pvr_op_attention(const void *qkv_dev, void *out_dev, int32_t T, int32_t W, int32_t heads, int32_t nb, int32_t dtype, void *hip_stream);
 /* LayerNorm over rows of W fp32 values (W in {768, 1024, 1280}).  Input: x (rows, W), or - when patch_emb is given - the assembled token sequence
  * row b*T + t = (t == 0 ? cls : patch_emb[b*(T-1) + t-1]) + pos[t] (rows a multiple of T).  normalize = 0 writes the (assembled) input unchanged.
- * Outputs: out_f32 (rows, W) and / or out_h (rows, W) in the 16-bit type `dtype`; either may be null, not both. */
+ * Outputs: out_f32 (rows, W) and / or out_h (rows, W) in the 16-bit type `dtype`; either may be null, not both.  dtype PVR_F32: out_f32 only. */
 pvr_status pvr_op_layernorm(const float *x_dev, const float *patch_emb_dev, const float *cls_dev, const float *pos_dev, const float *gamma_dev,
                             const float *beta_dev, float *out_f32_dev, void *out_h_dev, int32_t rows, int32_t T, int32_t W, float eps, int32_t normalize,
                             int32_t dtype, void *hip_stream);

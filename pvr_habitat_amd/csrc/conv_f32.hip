@@ -11,12 +11,16 @@ __device__ __forceinline__ f32x4 mfma_f32x(float a, float b, f32x4 c) { return _
 struct ConvF {
     const float *in, *wgt, *bias, *res;
     float *out;
-    int N, H, W, Cin, Ho, Wo, Cout, CoutPad, KH, KW, stride, pad, M, K, relu, n_tiles;
+    int N, H, W, Cin, Ho, Wo, Cout, CoutPad, KH, KW, stride, pad, M, K, act, n_tiles;     // act: 0 none, 1 relu, 2 QuickGELU x*sigmoid(1.702x), 3 GELU (erf)
     unsigned in_bytes, w_bytes;
 };
 
 // NHWC implicit GEMM, 64 pixels x 64 couts x 32 k per step, 2x2 waves, 2-stage LDS pipeline.
 // Cin % 32 == 0, so a 32-wide K slice is one filter tap and 128 contiguous bytes.
+// SETS = 1: one fma chain over the whole of K per output (every convolution of the ResNet plans).  SETS = 8, the linear-layer form (the ViT plans' GEMMs,
+// K up to 5120): k-step ks of every slice feeds accumulator set ks, so an output is eight chains of K / 8 products summed pairwise at the end - the
+// rounding error of a chain grows with its length, and one chain of 3072 products measured 5.8x the max-norm error of a blocked fp32 GEMM (with eight: 2x).
+template <int SETS>
 __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
     constexpr int BM = 64, BN = 64, BK = 32, LD = 36, TILE = 64 * 36;
     __shared__ __attribute__((aligned(16))) float sm[2][2][TILE];
@@ -71,11 +75,14 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
         }                                                                                                \
     }
     const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fq = lane >> 4;
-    f32x4 acc[2][2];
+    static_assert(SETS == 1 || SETS == BK / 4, "one accumulator set, or one per k-step of a slice");
+    f32x4 accs[SETS][2][2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int t = 0; t < SETS; ++t)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) accs[t][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     PVR_F_LOAD(0);
     PVR_F_STORE(0);
     __syncthreads();
@@ -95,7 +102,7 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = mfma_f32x(a[i], b[j], acc[i][j]);
+                for (int j = 0; j < 2; ++j) accs[SETS == 1 ? 0 : ks][i][j] = mfma_f32x(a[i], b[j], accs[SETS == 1 ? 0 : ks][i][j]);
         }
         if (more) PVR_F_STORE(cur ^ 1);
         __syncthreads();
@@ -103,6 +110,14 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
     }
 #undef PVR_F_LOAD
 #undef PVR_F_STORE
+    f32x4 (&acc)[2][2] = accs[0];
+    if constexpr (SETS == 8) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[i][j] = ((accs[0][i][j] + accs[1][i][j]) + (accs[2][i][j] + accs[3][i][j])) + ((accs[4][i][j] + accs[5][i][j]) + (accs[6][i][j] + accs[7][i][j]));
+    }
     // D: row = pixel (4*fq + r), col = cout (fr)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -117,7 +132,11 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
                 if (m >= p.M) continue;
                 float v = acc[i][j][r] + bv;
                 if (p.res) v += p.res[(size_t)m * p.Cout + co];
-                if (p.relu) v = fmaxf(v, 0.f);
+                if (p.act == 1) v = fmaxf(v, 0.f);
+                // fp32-accurate forms: the device library's expf / erff and a true division (the rcp / __expf / gelu_erf of the 16-bit epilogues are
+                // accurate to 16-bit rounding only)
+                else if (p.act == 2) v = v * (1.0f / (1.0f + expf(-1.702f * v)));
+                else if (p.act == 3) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
                 p.out[(size_t)m * p.Cout + co] = v;
             }
     }
@@ -186,7 +205,8 @@ __global__ __launch_bounds__(256) void maxpool_f32_kernel(const float *__restric
 }
 
 pvr_status launch_conv_f32(const float *in, const float *wgt, const float *bias, const float *res, float *out, int n, int h, int w,
-                           int cin, int cout, int k, int stride, int pad, int relu, hipStream_t stream) {
+                           int cin, int cout, int k, int stride, int pad, int act, hipStream_t stream) {
+    PVR_REQUIRE(act >= 0 && act <= 3, "conv_f32: activation code %d (0 none, 1 ReLU, 2 QuickGELU, 3 GELU)", act);
     PVR_REQUIRE(cin % 32 == 0 && k <= 3, "conv_f32: cin %d must be a multiple of 32 and k <= 3", cin);
     ConvF p;
     p.in = in; p.wgt = wgt; p.bias = bias; p.res = res; p.out = out;
@@ -194,10 +214,13 @@ pvr_status launch_conv_f32(const float *in, const float *wgt, const float *bias,
     p.stride = stride; p.pad = pad; p.Ho = (h + 2 * pad - k) / stride + 1; p.Wo = (w + 2 * pad - k) / stride + 1;
     const int64_t M = (int64_t)n * p.Ho * p.Wo, inb = (int64_t)n * h * w * cin * 4, wb = (int64_t)p.CoutPad * k * k * cin * 4;
     PVR_REQUIRE(M < (1ll << 31) && inb < 0x7ffffff0ll && wb < 0x7ffffff0ll, "conv_f32: operand larger than 2 GiB (use a smaller chunk)");
-    p.M = (int)M; p.K = k * k * cin; p.relu = relu; p.in_bytes = (unsigned)inb; p.w_bytes = (unsigned)wb;
+    p.M = (int)M; p.K = k * k * cin; p.act = act; p.in_bytes = (unsigned)inb; p.w_bytes = (unsigned)wb;
     p.n_tiles = (cout + 63) / 64;
     const int grid = ((p.M + 63) / 64) * p.n_tiles;
-    hipLaunchKernelGGL(conv_f32_kernel, dim3(grid), dim3(256), 0, stream, p);
+    // rows of features through a weight matrix (h = w = k = 1: how the ViT plans call it) take the eight-chain form; a convolution over an image keeps its
+    // single chain, bit for bit
+    if (h == 1 && w == 1 && k == 1) hipLaunchKernelGGL(conv_f32_kernel<8>, dim3(grid), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(conv_f32_kernel<1>, dim3(grid), dim3(256), 0, stream, p);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }

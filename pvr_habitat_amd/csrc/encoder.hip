@@ -428,8 +428,11 @@ extern "C" {
 pvr_status pvr_encoder_create(const pvr_encoder_desc *desc, pvr_encoder **out) {
     PVR_REQUIRE(desc && out, "pvr_encoder_create: null argument");
     PVR_REQUIRE(desc->arch >= PVR_ARCH_RESNET50 && desc->arch <= PVR_ARCH_RESNET34, "unknown arch %d", desc->arch);
-    PVR_REQUIRE(desc->dtype == PVR_BF16 || desc->dtype == PVR_F16 || (stores_f32(desc->dtype) && (desc->arch <= PVR_ARCH_RESNET50_L3 || desc->arch == PVR_ARCH_RESNET18 || desc->arch == PVR_ARCH_RESNET34)),
-                "dtype must be PVR_BF16 or PVR_F16 (PVR_F32 and PVR_F32S are built for the torchvision ResNet family only: ResNet50, its _l3 / _l4 variants, ResNet18 / 34)");
+    const bool resnet = desc->arch <= PVR_ARCH_RESNET50_L3 || desc->arch == PVR_ARCH_RESNET18 || desc->arch == PVR_ARCH_RESNET34;
+    const bool vit_arch = desc->arch >= PVR_ARCH_CLIP_VIT_B32 && desc->arch <= PVR_ARCH_MAE_VIT_H14 && desc->arch != PVR_ARCH_RANDOM5;
+    PVR_REQUIRE(desc->dtype == PVR_BF16 || desc->dtype == PVR_F16 || (stores_f32(desc->dtype) && resnet) || (desc->dtype == PVR_F32 && vit_arch),
+                "dtype must be PVR_BF16 or PVR_F16 (PVR_F32 is built for the torchvision ResNet family - ResNet50, its _l3 / _l4 variants, ResNet18 / 34 - and for the "
+                "CLIP ViT / MAE ViT encoders; PVR_F32S for the ResNet family only)");
     PVR_REQUIRE(desc->max_batch > 0, "max_batch must be positive");
     PVR_REQUIRE(desc->crop == 224, "crop must be 224 (reference embeddings.py:82; CLIP input_resolution 224)");
     PVR_REQUIRE(desc->resize >= desc->crop, "resize must be >= crop");

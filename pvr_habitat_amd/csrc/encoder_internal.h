@@ -314,8 +314,10 @@ pvr_status vit_finalize(pvr_encoder *e);
 pvr_status resizer_create(pvr_encoder *e);
 pvr_status resizer_run(pvr_encoder *e, int lane, const uint8_t *frames, int nb, int h, int w, hipStream_t st, const uint8_t **u8, int *oh, int *ow);
 void resizer_destroy(pvr_encoder *e);
-pvr_status launch_attention(const void *qkv, void *out, int T, int W, int heads, int nb, int dtype, hipStream_t st);
-// vit.hip launch dispatchers the ViT forward and the pvr_op_* test entry points share (width 768 / 1024 / 1280, f16 / bf16; anything else is refused)
+pvr_status launch_attention(const void *qkv, void *out, int T, int W, int heads, int nb, int dtype, hipStream_t st);   // dtype PVR_F32: vit_f32.hip
+// vit_f32.hip: the fp32 attention core (fp32 qkv rows [q | k | v] in, fp32 out, f32-input MFMA), head dim 64 / 80, 1..288 tokens
+pvr_status launch_attention_f32(const float *qkv, float *out, int T, int W, int heads, int nb, hipStream_t st);
+// vit.hip launch dispatchers the ViT forward and the pvr_op_* test entry points share (width 768 / 1024 / 1280, f16 / bf16 - and PVR_F32 with the fp32 output only; anything else is refused)
 pvr_status launch_layernorm(const float *x, const float *patch_emb, const float *cls, const float *pos, const float *gamma, const float *beta,
                             float *out_f32, void *out_h, int rows, int T, int W, float eps, int normalize, int dtype, hipStream_t st);
 pvr_status launch_cls_head(const float *x, const float *gamma, const float *beta, const float *proj, float *out, int64_t out_stride, int nb, int T, int W,

@@ -12,6 +12,8 @@
 // Attention: one workgroup per (image, head); scores are computed TRANSPOSED (S^T = K Q^T) so that the softmaxed
 // accumulator tile is already the B operand of the second product (O^T = V^T P^T) — no LDS round trip for P
 // (cdna_hip_programming.md, "An accumulator tile as the next MFMA's operand"); softmax reductions are wave shuffles.
+// dtype PVR_F32 (the reference-precision mode) runs the same launch list with fp32 storage and fp32 products: patchify_f32_kernel, conv_f32.hip's
+// GEMM (bias, residual, QuickGELU / GELU epilogues in fp32), the LayerNorm kernel's fp32 output as the GEMM operand, vit_f32.hip's attention.
 #include "encoder_internal.h"
 
 namespace pvr {
@@ -38,6 +40,26 @@ __global__ __launch_bounds__(256) void patchify_kernel(const uint8_t *__restrict
             oe[e] = k < Kr ? to_h<F16>((float)frames[(((size_t)b * h + y) * w + x) * 3 + c] - 128.f) : (u16)0;     // centred, exact
         }
         *reinterpret_cast<u32x4 *>(A + row * K + k8) = o;
+    }
+}
+
+// the same rows as fp32 (PVR_F32 plan): the centred values x - 128, exact
+__global__ __launch_bounds__(256) void patchify_f32_kernel(const uint8_t *__restrict__ frames, float *__restrict__ A, int n, int h, int w, int top, int left,
+                                                           int res, int P) {
+    const int g = res / P, Kr = P * P * 3, K = (Kr + 63) / 64 * 64;
+    const size_t total = (size_t)n * g * g * (K / 4);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int k4 = (int)(i % (K / 4)) * 4;
+        const size_t row = i / (K / 4);
+        const int gx = (int)(row % g), gy = (int)((row / g) % g), b = (int)(row / ((size_t)g * g));
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int k = k4 + e, c = k % 3, px = (k / 3) % P, py = k / (3 * P);
+            const int y = top + gy * P + py, x = left + gx * P + px;
+            o[e] = k < Kr ? (float)frames[(((size_t)b * h + y) * w + x) * 3 + c] - 128.f : 0.f;
+        }
+        *reinterpret_cast<f32x4 *>(A + row * K + k4) = o;
     }
 }
 
@@ -340,7 +362,7 @@ __global__ __launch_bounds__(256) void cls_head_kernel(const float *__restrict__
 using namespace pvr;
 
 struct VitBlock {
-    u16 *w_qkv = nullptr, *w_out = nullptr, *w_fc = nullptr, *w_proj = nullptr;
+    void *w_qkv = nullptr, *w_out = nullptr, *w_fc = nullptr, *w_proj = nullptr;     // 16-bit rows, or fp32 (PVR_F32)
     float *b_qkv = nullptr, *b_out = nullptr, *b_fc = nullptr, *b_proj = nullptr;
     float *ln1_w = nullptr, *ln1_b = nullptr, *ln2_w = nullptr, *ln2_b = nullptr;
 };
@@ -351,13 +373,13 @@ struct pvr_vit {
     float eps = 1e-5f;
     int act = 2;
     std::vector<VitBlock> blocks;
-    u16 *w_patch = nullptr;
+    void *w_patch = nullptr;
     float *b_patch = nullptr, *cls = nullptr, *pos = nullptr, *lnpre_w = nullptr, *lnpre_b = nullptr, *lnpost_w = nullptr,
           *lnpost_b = nullptr, *proj = nullptr;
     u16 *zero = nullptr;
     // one activation workspace (chunk frames) per lane (pvr_encoder_forward_lane): lane 0 is made at finalize, the others on first use (vit_use_lane).
     // A forward, a tap and the resize step are given the lane's Ws
-    struct Ws { u16 *A = nullptr, *y = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr; float *pe = nullptr, *x0 = nullptr, *x1 = nullptr; bool valid = false; } ws[PVR_MAX_LANES];
+    struct Ws { void *A = nullptr, *y = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr; float *pe = nullptr, *x0 = nullptr, *x1 = nullptr; bool valid = false; } ws[PVR_MAX_LANES];
     Resizer rs;                     // the transforms' Resize when the short side is not resize_to; a lane that exists has its temporaries
     std::vector<void *> owned;
 };
@@ -373,18 +395,24 @@ static pvr_status up_f32(pvr_encoder *e, const std::string &name, size_t numel, 
     return PVR_OK;
 }
 
-// nn.Linear weight [out][in] -> 16-bit rows (already K-major), rows padded to a multiple of 64
-static pvr_status up_linear(pvr_encoder *e, const std::string &wname, const std::string &bname, int out_f, int in_f, u16 **dw, float **db) {
+// nn.Linear weight [out][in] -> 16-bit rows (already K-major), rows padded to a multiple of 64; PVR_F32: the same rows as fp32, conv_f32's (cout_pad, K)
+static pvr_status up_linear(pvr_encoder *e, const std::string &wname, const std::string &bname, int out_f, int in_f, void **dw, float **db) {
     const HostTensor *w, *b;
     pvr_status s;
     if ((s = enc_need(e, wname, &w, (size_t)out_f * in_f))) return s;
     if ((s = enc_need(e, bname, &b, (size_t)out_f))) return s;
     const int pad = (out_f + 63) / 64 * 64;
-    std::vector<u16> hw((size_t)pad * in_f, 0);
-    for (size_t i = 0; i < (size_t)out_f * in_f; ++i) hw[i] = f32_to_h(w->data[i], e->desc.dtype);
     std::vector<float> hb(pad, 0.f);
     for (int i = 0; i < out_f; ++i) hb[i] = b->data[i];
-    if ((s = enc_upload(dw, hw))) return s;
+    if (e->desc.dtype == PVR_F32) {
+        std::vector<float> hw((size_t)pad * in_f, 0.f);
+        std::copy(w->data.begin(), w->data.begin() + (size_t)out_f * in_f, hw.begin());
+        if ((s = enc_upload((float **)dw, hw))) return s;
+    } else {
+        std::vector<u16> hw((size_t)pad * in_f, 0);
+        for (size_t i = 0; i < (size_t)out_f * in_f; ++i) hw[i] = f32_to_h(w->data[i], e->desc.dtype);
+        if ((s = enc_upload((u16 **)dw, hw))) return s;
+    }
     e->vit->owned.push_back(*dw);
     if ((s = enc_upload(db, hb))) return s;
     e->vit->owned.push_back(*db);
@@ -424,20 +452,23 @@ pvr_status vit_finalize(pvr_encoder *e) {
     const HostTensor *pb = nullptr;                              // timm PatchEmbed has a bias, CLIP conv1 does not
     if (v->mae && (s = enc_need(e, "patch_embed.proj.bias", &pb, (size_t)W))) return s;
     {
-        std::vector<u16> hw((size_t)W * K, 0);
-        std::vector<float> hb(W, 0.f);
+        const bool f32 = dt == PVR_F32;
+        std::vector<u16> hw(f32 ? 0 : (size_t)W * K, 0);
+        std::vector<float> hwf(f32 ? (size_t)W * K : 0, 0.f), hb(W, 0.f);
         for (int co = 0; co < W; ++co) {
             double bsum = 0.0;
             for (int c = 0; c < 3; ++c)
                 for (int py = 0; py < P; ++py)
                     for (int px = 0; px < P; ++px) {
                         const double wv = w->data[(((size_t)co * 3 + c) * P + py) * P + px];
-                        hw[(size_t)co * K + (py * P + px) * 3 + c] = f32_to_h((float)(wv / (255.0 * e->desc.std_[c])), dt);
+                        const float wf = (float)(wv / (255.0 * e->desc.std_[c]));
+                        if (f32) hwf[(size_t)co * K + (py * P + px) * 3 + c] = wf;
+                        else hw[(size_t)co * K + (py * P + px) * 3 + c] = f32_to_h(wf, dt);
                         bsum += wv * (128.0 - 255.0 * e->desc.mean[c]) / (255.0 * e->desc.std_[c]);   // x = xc + 128
                     }
             hb[co] = (float)bsum + (pb ? pb->data[co] : 0.f);
         }
-        if ((s = enc_upload(&v->w_patch, hw))) return s;
+        if ((s = f32 ? enc_upload((float **)&v->w_patch, hwf) : enc_upload((u16 **)&v->w_patch, hw))) return s;
         v->owned.push_back(v->w_patch);
         if ((s = enc_upload(&v->b_patch, hb))) return s;
         v->owned.push_back(v->b_patch);
@@ -593,14 +624,15 @@ static void launch_aa_resize(const Resizer &r, int lane, const uint8_t *frames, 
 static pvr_status vit_alloc_ws(pvr_encoder *e, pvr_vit::Ws &n) {
     const pvr_vit *v = e->vit;
     const size_t C = e->desc.chunk, rows = C * v->T, prow = C * v->grid * v->grid, W = v->width, K = ((size_t)v->patch * v->patch * 3 + 63) / 64 * 64;
-    PVR_HIP_TRY(hipMalloc((void **)&n.A, prow * K * 2));
+    const size_t es = e->desc.dtype == PVR_F32 ? 4 : 2;          // bytes per element of the GEMM operands
+    PVR_HIP_TRY(hipMalloc((void **)&n.A, prow * K * es));
     PVR_HIP_TRY(hipMalloc((void **)&n.pe, prow * W * 4));
     PVR_HIP_TRY(hipMalloc((void **)&n.x0, rows * W * 4));
     PVR_HIP_TRY(hipMalloc((void **)&n.x1, rows * W * 4));
-    PVR_HIP_TRY(hipMalloc((void **)&n.y, rows * W * 2));
-    PVR_HIP_TRY(hipMalloc((void **)&n.qkv, rows * 3 * W * 2));
-    PVR_HIP_TRY(hipMalloc((void **)&n.att, rows * W * 2));
-    PVR_HIP_TRY(hipMalloc((void **)&n.hid, rows * 4 * W * 2));
+    PVR_HIP_TRY(hipMalloc((void **)&n.y, rows * W * es));
+    PVR_HIP_TRY(hipMalloc((void **)&n.qkv, rows * 3 * W * es));
+    PVR_HIP_TRY(hipMalloc((void **)&n.att, rows * W * es));
+    PVR_HIP_TRY(hipMalloc((void **)&n.hid, rows * 4 * W * es));
     PVR_HIP_TRY(hipDeviceSynchronize());
     return PVR_OK;
 }
@@ -663,7 +695,7 @@ static void launch_layernorm_inst(const float *x, const float *patch_emb, const 
 pvr_status launch_layernorm(const float *x, const float *patch_emb, const float *cls, const float *pos, const float *gamma, const float *beta,
                             float *out_f32, void *out_h, int rows, int T, int W, float eps, int normalize, int dtype, hipStream_t st) {
     PVR_REQUIRE(W == 768 || W == 1024 || W == 1280, "layernorm: width %d not built (768 / 1024 / 1280)", W);
-    PVR_REQUIRE(dtype == PVR_F16 || dtype == PVR_BF16, "layernorm: 16-bit storage types only");
+    PVR_REQUIRE(dtype == PVR_F16 || dtype == PVR_BF16 || (dtype == PVR_F32 && !out_h), "layernorm: f16 / bf16, or PVR_F32 with the fp32 output only");
     PVR_REQUIRE(rows > 0 && T > 0 && eps > 0.f, "layernorm: %d rows of %d tokens, eps %g", rows, T, (double)eps);
     PVR_REQUIRE(out_f32 || out_h, "layernorm: no output");
     PVR_REQUIRE(patch_emb ? (cls && pos && rows % T == 0) : x != nullptr, "layernorm: needs x, or patch_emb with cls and pos and whole token sequences");
@@ -703,6 +735,19 @@ static pvr_status vit_forward_t(pvr_encoder *e, int lane, const uint8_t *frames,
     pvr_vit::Ws *wsp;
     if ((s = vit_use_lane(e, lane, &wsp))) return s;
     const pvr_vit::Ws &ws = *wsp;
+    // PVR_F32: the same launches on the fp32 kernels (F16 is unused then).  ln: the GEMM operand y, 16-bit or fp32
+    const bool f32 = dt == PVR_F32;
+    auto gemm = [&](const void *in, const void *wgt, const float *bias, const float *res, void *o, int m, int cin, int cout, int act, int of32) -> pvr_status {
+        if (f32) return launch_conv_f32((const float *)in, (const float *)wgt, bias, res, (float *)o, m, 1, 1, cin, cout, 1, 1, 0, act, st);
+        return launch_conv(e->sw, in, wgt, bias, res, o, v->zero, m, 1, 1, cin, cout, 1, 1, 1, 0, act, of32, dt, st);
+    };
+    auto ln = [&](const float *x, const float *gw, const float *gb, void *y, int rows) -> pvr_status {
+        return launch_layernorm(x, nullptr, nullptr, nullptr, gw, gb, f32 ? (float *)y : nullptr, f32 ? nullptr : y, rows, T, W, v->eps, 1, dt, st);
+    };
+    auto patchify = [&](const uint8_t *src, int nb, int sh_, int sw_, int top_, int left_, int blocks) {
+        if (f32) hipLaunchKernelGGL(patchify_f32_kernel, dim3(blocks), dim3(256), 0, st, src, (float *)ws.A, nb, sh_, sw_, top_, left_, v->res, P);
+        else hipLaunchKernelGGL(patchify_kernel<F16>, dim3(blocks), dim3(256), 0, st, src, (u16 *)ws.A, nb, sh_, sw_, top_, left_, v->res, P);
+    };
     if (resize) {
         unsigned lanes = 0;                                                        // every lane that exists has resize temporaries
         for (int l = 0; l < PVR_MAX_LANES; ++l) lanes |= (unsigned)v->ws[l].valid << l;
@@ -714,18 +759,17 @@ static pvr_status vit_forward_t(pvr_encoder *e, int lane, const uint8_t *frames,
         const int nb = (n - f0 < e->desc.chunk) ? n - f0 : e->desc.chunk;
         const int rows = nb * T, prow = nb * g2;
         const uint8_t *fr = frames + (size_t)f0 * h * w * 3;
-        const size_t tot = (size_t)prow * (K / 8);
+        const size_t tot = (size_t)prow * (K / (f32 ? 4 : 8));
+        const int pblocks = (int)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256);
         if (resize) {
             launch_aa_resize(v->rs, lane, fr, nb, h, w, st);
-            hipLaunchKernelGGL(patchify_kernel<F16>, dim3((int)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256)), dim3(256), 0, st,
-                               v->rs.lane[lane].u8, ws.A, nb, v->res, v->res, 0, 0, v->res, P);
+            patchify(v->rs.lane[lane].u8, nb, v->res, v->res, 0, 0, pblocks);
         } else {
-            hipLaunchKernelGGL(patchify_kernel<F16>, dim3((int)((tot + 255) / 256 > 8192 ? 8192 : (tot + 255) / 256)), dim3(256), 0, st,
-                               fr, ws.A, nb, h, w, top, left, v->res, P);
+            patchify(fr, nb, h, w, top, left, pblocks);
         }
         PVR_LAUNCH_CHECK();
         // patch embedding GEMM -> fp32 [prow][W]
-        if ((s = launch_conv(e->sw, ws.A, v->w_patch, v->b_patch, nullptr, ws.pe, v->zero, prow, 1, 1, K, W, 1, 1, 1, 0, 0, 1, dt, st))) return s;
+        if ((s = gemm(ws.A, v->w_patch, v->b_patch, nullptr, ws.pe, prow, K, W, 0, 1))) return s;
         // tokens + positional embedding + ln_pre -> residual stream x0 (fp32)
         if ((s = launch_layernorm(nullptr, ws.pe, v->cls, v->pos, v->lnpre_w, v->lnpre_b, ws.x0, nullptr, rows, T, W, v->eps, v->mae ? 0 : 1, dt, st))) return s;
         e->last_n = nb;
@@ -734,19 +778,20 @@ static pvr_status vit_forward_t(pvr_encoder *e, int lane, const uint8_t *frames,
         float *x = ws.x0, *xn = ws.x1;
         int bi = 0;
         for (auto &b : v->blocks) {
-            if ((s = launch_layernorm(x, nullptr, nullptr, nullptr, b.ln1_w, b.ln1_b, nullptr, ws.y, rows, T, W, v->eps, 1, dt, st))) return s;
-            if ((s = launch_conv(e->sw, ws.y, b.w_qkv, b.b_qkv, nullptr, ws.qkv, v->zero, rows, 1, 1, W, 3 * W, 1, 1, 1, 0, 0, 0, dt, st))) return s;
+            if ((s = ln(x, b.ln1_w, b.ln1_b, ws.y, rows))) return s;
+            if ((s = gemm(ws.y, b.w_qkv, b.b_qkv, nullptr, ws.qkv, rows, W, 3 * W, 0, 0))) return s;
             if (bi == 0 && stop == "qkv0") return PVR_OK;
-            if ((s = launch_attention_any<F16>(ws.qkv, ws.att, T, v->TK, W, v->heads, nb, st))) return s;
+            if ((s = f32 ? launch_attention_f32((const float *)ws.qkv, (float *)ws.att, T, W, v->heads, nb, st)
+                         : launch_attention_any<F16>((const u16 *)ws.qkv, (u16 *)ws.att, T, v->TK, W, v->heads, nb, st))) return s;
             PVR_LAUNCH_CHECK();
             if (bi == 0 && stop == "att0") return PVR_OK;
             // x' = x + out_proj(att): fp32 residual in (bit1), fp32 out (bit0)
-            if ((s = launch_conv(e->sw, ws.att, b.w_out, b.b_out, x, xn, v->zero, rows, 1, 1, W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
+            if ((s = gemm(ws.att, b.w_out, b.b_out, x, xn, rows, W, W, 0, 3))) return s;
             if (bi == 0 && stop == "res0") return PVR_OK;
-            if ((s = launch_layernorm(xn, nullptr, nullptr, nullptr, b.ln2_w, b.ln2_b, nullptr, ws.y, rows, T, W, v->eps, 1, dt, st))) return s;
-            if ((s = launch_conv(e->sw, ws.y, b.w_fc, b.b_fc, nullptr, ws.hid, v->zero, rows, 1, 1, W, 4 * W, 1, 1, 1, 0, v->act, 0, dt, st))) return s;   // QuickGELU / GELU
+            if ((s = ln(xn, b.ln2_w, b.ln2_b, ws.y, rows))) return s;
+            if ((s = gemm(ws.y, b.w_fc, b.b_fc, nullptr, ws.hid, rows, W, 4 * W, v->act, 0))) return s;   // QuickGELU / GELU
             if (bi == 0 && stop == "fc0") return PVR_OK;
-            if ((s = launch_conv(e->sw, ws.hid, b.w_proj, b.b_proj, xn, x, v->zero, rows, 1, 1, 4 * W, W, 1, 1, 1, 0, 0, 3, dt, st))) return s;
+            if ((s = gemm(ws.hid, b.w_proj, b.b_proj, xn, x, rows, 4 * W, W, 0, 3))) return s;
             if (stop == "block" + std::to_string(bi)) return PVR_OK;
             ++bi;
         }
@@ -775,12 +820,13 @@ pvr_status vit_tap(pvr_encoder *e, const char *name, float *out, int64_t cap, in
     const void *src = nullptr;
     size_t elems = 0;
     bool f32 = true;
+    const bool h16 = e->desc.dtype != PVR_F32;                  // the PVR_F32 plan's operand buffers are fp32 themselves
     if (nm == "pe") { src = ws.pe; elems = (size_t)e->last_n * v->grid * v->grid * W; }
     else if (nm == "ln_pre" || nm.rfind("block", 0) == 0) { src = ws.x0; elems = rows * W; }
-    else if (nm == "qkv0") { src = ws.qkv; elems = rows * 3 * W; f32 = false; }
-    else if (nm == "att0") { src = ws.att; elems = rows * W; f32 = false; }
+    else if (nm == "qkv0") { src = ws.qkv; elems = rows * 3 * W; f32 = !h16; }
+    else if (nm == "att0") { src = ws.att; elems = rows * W; f32 = !h16; }
     else if (nm == "res0") { src = ws.x1; elems = rows * W; }
-    else if (nm == "fc0") { src = ws.hid; elems = rows * 4 * W; f32 = false; }
+    else if (nm == "fc0") { src = ws.hid; elems = rows * 4 * W; f32 = !h16; }
     else if (nm == "resized") {                      // uint8 crop after the antialiased Resize, as fp32
         PVR_REQUIRE(rs_u8 != nullptr, "no resize has run");
         elems = (size_t)e->last_n * v->res * v->res * 3;
@@ -799,7 +845,8 @@ pvr_status vit_tap(pvr_encoder *e, const char *name, float *out, int64_t cap, in
 pvr_status launch_attention(const void *qkv, void *out, int T, int W, int heads, int nb, int dtype, hipStream_t st) {
     PVR_REQUIRE(qkv && out, "attention: null pointer");
     PVR_REQUIRE(T > 0 && T <= 288 && heads > 0 && nb > 0 && W > 0, "attention: %d tokens (1..288), %d heads, %d images not built", T, heads, nb);
-    PVR_REQUIRE(dtype == PVR_F16 || dtype == PVR_BF16, "attention: 16-bit storage types only");
+    if (dtype == PVR_F32) return launch_attention_f32((const float *)qkv, (float *)out, T, W, heads, nb, st);      // fp32 in and out (vit_f32.hip)
+    PVR_REQUIRE(dtype == PVR_F16 || dtype == PVR_BF16, "attention: f16, bf16 or PVR_F32");
     const int TK = (T + 31) / 32 * 32;
     return dtype == PVR_F16 ? launch_attention_any<true>((const u16 *)qkv, (u16 *)out, T, TK, W, heads, nb, st)
                             : launch_attention_any<false>((const u16 *)qkv, (u16 *)out, T, TK, W, heads, nb, st);

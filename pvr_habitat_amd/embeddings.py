@@ -88,7 +88,7 @@ def _dtype_from_env(compute_dtype=None):
     if d in ('f16', 'fp16', 'float16', 'half'):
         return _lib.PVR_F16
     if d in ('f32', 'fp32', 'float32'):
-        return _lib.PVR_F32                     # reference-precision mode (ResNet50 family only): f32 MFMA, ~1/8 the speed
+        return _lib.PVR_F32                     # reference-precision mode (ResNet family, CLIP / MAE ViT): fp32 storage, f32-input MFMA, a fraction of the 16-bit rate
     if d in ('f32s', 'f32_split'):
         # fp32 storage as 'f32', every product on the 16-bit MFMA as an exact (hi, lo) f16 split product: ~1e-6 from 'f32' at several times its rate.  The
         # high part is an f16, so activations must stay below 65504 (validate_range checks the first frames; 'f32' has the full range)
