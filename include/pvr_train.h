@@ -1,0 +1,104 @@
+/*
+ * pvr_train.h — C-ABI of the trainable ResNet encoder of libpvr_hip.so: EmbeddingNet(..., train=True)
+ * (reference src/embeddings.py:323-326 model.train() / requires_grad, :396-398 the forward that keeps its graph;
+ * exposed as --train_embedding, src/arguments.py:19).
+ *
+ * Scope: the torchvision trunks resnet18 / resnet34 / resnet50 (arch PVR_ARCH_RESNET18 / _RESNET34 / _RESNET50), fp32 storage,
+ * every product of a convolution, a data gradient or a weight gradient on the f32-input MFMA (the arithmetic of the PVR_F32
+ * plan), one GPU.  BatchNorm runs on the statistics of the WHOLE batch of a forward (they cannot be chunked).
+ *
+ * Buffers follow pvr_policy.h's convention: the caller owns ONE flat fp32 device buffer of parameters, every tensor in its
+ * state_dict shape (conv weights in torch's (cout, cin, kh, kw) layout - the library repacks them inside the forward), and
+ * steps it in place with any optimizer; the library reads it on the next forward.  A second flat buffer holds the BatchNorm
+ * buffers.  Status codes, error messages and stream handling as in pvr_hip.h.
+ */
+#ifndef PVR_TRAIN_H
+#define PVR_TRAIN_H
+
+#include "pvr_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct pvr_trainer pvr_trainer;
+
+/* desc as for pvr_encoder_create; arch RESNET50 / RESNET18 / RESNET34 with dtype PVR_F32, anything else is PVR_ERR_INVALID with a
+ * message that names what is trainable.  Host arithmetic only: the workspace (one saved pre-BN and one post-BN tensor per
+ * convolution, their gradients, the scratch of the split reductions - sized for max_batch frames) is made by the first forward. */
+pvr_status pvr_trainer_create(const pvr_encoder_desc *desc, pvr_trainer **out);
+void pvr_trainer_destroy(pvr_trainer *tr);
+int32_t pvr_trainer_out_size(const pvr_trainer *tr);
+
+/* the flat parameter buffer: its length in floats; name of tensor `index` in buffer order (returns the length, 0 past the end);
+ * offset of a tensor by its state_dict name ("layer2.0.downsample.0.weight"), -1 if there is none - *numel and shape[0..3]
+ * (unused dimensions 0) are filled when the pointers are given */
+int64_t pvr_trainer_param_count(const pvr_trainer *tr);
+int32_t pvr_trainer_param_name(const pvr_trainer *tr, int32_t index, char *buf, int32_t cap);
+int64_t pvr_trainer_param_offset(const pvr_trainer *tr, const char *name, int64_t *numel, int64_t *shape);
+/* the BatchNorm buffer block, counted in 4-byte slots: running_mean and running_var of every BatchNorm as fp32, then one int64
+ * num_batches_tracked per BatchNorm (two slots each, 8-byte aligned).  offset by name ("bn1.running_var",
+ * "layer1.0.bn2.num_batches_tracked"), -1 if there is none */
+int64_t pvr_trainer_buffer_count(const pvr_trainer *tr);
+int64_t pvr_trainer_buffer_offset(const pvr_trainer *tr, const char *name, int64_t *numel);
+
+/* Training-mode forward of n <= max_batch uint8 (n,h,w,3) frames: the integer transforms and fp32 Normalize of the PVR_F32 plan,
+ * then per convolution the raw-weight convolution, BatchNorm on batch statistics (biased variance, eps 1e-5) [+ residual] [ReLU],
+ * max pool, average pool; row i of the result at out_dev + i * out_stride.  Updates running_mean / running_var (momentum 0.1,
+ * unbiased variance) and num_batches_tracked in bn_buffers_dev, and keeps every activation for ONE pvr_trainer_backward. */
+pvr_status pvr_trainer_forward(pvr_trainer *tr, const float *params_dev, void *bn_buffers_dev, const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w,
+                               float *out_dev, int64_t out_stride, void *hip_stream);
+/* d(loss)/d(out) (row i at dout_dev + i * dout_stride) -> d(loss)/d(params) in grads_dev, laid out as params and fully
+ * overwritten.  One backward per forward: without a forward whose activations are still held it returns PVR_ERR_STATE.
+ * Bit-reproducible run to run (no float atomics: every split reduction is summed in a fixed order). */
+pvr_status pvr_trainer_backward(pvr_trainer *tr, const float *params_dev, const float *dout_dev, int64_t dout_stride, float *grads_dev, void *hip_stream);
+
+/* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
+ * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
+ * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */
+pvr_status pvr_trainer_debug_set_timing(pvr_trainer *tr, int32_t on);
+int32_t pvr_trainer_launch_time(const pvr_trainer *tr, int32_t index, char *name, int32_t cap, float *ms, double *flops);
+
+/* ---------------------------------------------------------------------------------------------
+ * The trainer's kernels one at a time (unit-parity entry points).  All tensors fp32 NHWC on the device; an unsupported shape
+ * returns a status with a message and launches nothing.  scratch_dev: fp32 device scratch of at least the matching
+ * *_scratch_floats() values.
+ * ------------------------------------------------------------------------------------------- */
+/* BatchNorm2d, training mode, over `rows` = n*h*w rows of c channels (c % 4 == 0, rows >= 2): two-pass batch mean and biased
+ * variance; y = (z - mean) * rstd * gamma + beta [+ residual] [ReLU]; mean_out / rstd_out (c floats each) are what the backward
+ * needs.  running_mean / running_var / num_batches_tracked (int64) are updated when given (all three or none). */
+int64_t pvr_op_bn_scratch_floats(int64_t rows, int32_t c);
+pvr_status pvr_op_bn_train_forward(const float *z_dev, const float *residual_dev, const float *gamma_dev, const float *beta_dev, float *running_mean_dev,
+                                   float *running_var_dev, int64_t *num_batches_tracked_dev, float *y_dev, float *mean_out_dev, float *rstd_out_dev,
+                                   int64_t rows, int32_t c, int32_t relu, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+/* its backward: g = dy where (relu == 0 or y > 0) else 0; dgamma = sum g * xhat, dbeta = sum g; dz = gamma * rstd * (g - dbeta / rows - xhat * dgamma / rows);
+ * dres (optional) = g, added to what it holds when dres_accumulate != 0 */
+pvr_status pvr_op_bn_train_backward(const float *z_dev, const float *y_dev, const float *dy_dev, const float *gamma_dev, const float *mean_dev,
+                                    const float *rstd_dev, float *dz_dev, float *dres_dev, int32_t dres_accumulate, float *dgamma_dev, float *dbeta_dev,
+                                    int64_t rows, int32_t c, int32_t relu, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+/* Weight gradient of a k x k convolution (k 1 or 3, stride 1 or 2, cin % 32 == 0, cout % 4 == 0) on the f32-input MFMA:
+ * dw[co][ci][kh][kw] = sum over (n, y, x) of dz[n,y,x,co] * x[n, y*stride + kh - pad, x*stride + kw - pad, ci]; x (n,h,w,cin),
+ * dz (n,ho,wo,cout), dw in torch's (cout, cin, k, k) layout.  The pixel range is split over workgroups and the partials are summed in a fixed order. */
+int64_t pvr_op_conv_wgrad_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad);
+pvr_status pvr_op_conv_wgrad(const float *x_dev, const float *dz_dev, float *dw_dev, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k,
+                             int32_t stride, int32_t pad, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+/* Data gradient of the same convolution: dx (n,h,w,cin) [+= when accumulate != 0] conv(dz written to the even pixels of a zeroed (h, w) grid when stride == 2,
+ * rot180(W) transposed, stride 1, pad k - 1 - pad) through pvr_op_conv2d_f32's kernel.  w: torch's (cout, cin, k, k).  (k, pad) = (3, 1) or (1, 0),
+ * cout % 32 == 0, cin % 4 == 0; stride 2 needs even h and w (an odd size is refused). */
+int64_t pvr_op_conv_dgrad_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad);
+pvr_status pvr_op_conv_dgrad(const float *dz_dev, const float *w_dev, float *dx_dev, int32_t accumulate, int32_t n, int32_t h, int32_t w, int32_t cin,
+                             int32_t cout, int32_t k, int32_t stride, int32_t pad, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+/* Weight gradient of conv1 (7x7 / 2, pad 3): img the normalised NHWC4 image (n,S,S,4), dz (n,S/2,S/2,64), dw torch's (64,3,7,7).  S even. */
+int64_t pvr_op_stem_wgrad_scratch_floats(int32_t n, int32_t S);
+pvr_status pvr_op_stem_wgrad(const float *img_dev, const float *dz_dev, float *dw_dev, int32_t n, int32_t S, float *scratch_dev, int64_t scratch_floats,
+                             void *hip_stream);
+/* MaxPool2d(3, 2, 1) backward as a gather: x (n,h,w,c) the pool's input, dy (n,ho,wo,c), dx (n,h,w,c) fully written; a tie goes to the first maximum of a
+ * window in scan order (torch's rule) */
+pvr_status pvr_op_maxpool_backward(const float *x_dev, const float *dy_dev, float *dx_dev, int32_t n, int32_t h, int32_t w, int32_t c, void *hip_stream);
+/* AdaptiveAvgPool2d(1) backward: dx[(i*hw + p)*c + ch] = dout[i*dout_stride + ch] / hw */
+pvr_status pvr_op_avgpool_backward(const float *dout_dev, int64_t dout_stride, float *dx_dev, int32_t n, int32_t hw, int32_t c, void *hip_stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* PVR_TRAIN_H */

@@ -79,6 +79,30 @@ _SIGS = {
     'pvr_op_layernorm': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     'pvr_op_cls_head': (C.c_int, [C.c_void_p] * 5 + [C.c_int64] + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),
     'pvr_op_nonfinite_flag': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    # include/pvr_train.h: the trainable ResNet encoder and its kernels
+    'pvr_trainer_create': (C.c_int, [C.POINTER(EncoderDesc), C.POINTER(C.c_void_p)]),
+    'pvr_trainer_destroy': (None, [C.c_void_p]),
+    'pvr_trainer_out_size': (C.c_int32, [C.c_void_p]),
+    'pvr_trainer_param_count': (C.c_int64, [C.c_void_p]),
+    'pvr_trainer_param_name': (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32]),
+    'pvr_trainer_param_offset': (C.c_int64, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    'pvr_trainer_buffer_count': (C.c_int64, [C.c_void_p]),
+    'pvr_trainer_buffer_offset': (C.c_int64, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
+    'pvr_trainer_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_trainer_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'pvr_trainer_debug_set_timing': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pvr_trainer_launch_time': (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
+    'pvr_op_bn_scratch_floats': (C.c_int64, [C.c_int64, C.c_int32]),
+    'pvr_op_bn_train_forward': (C.c_int, [C.c_void_p] * 10 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_bn_train_backward': (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_conv_wgrad_scratch_floats': (C.c_int64, [C.c_int32] * 8),
+    'pvr_op_conv_wgrad': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 8 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_conv_dgrad_scratch_floats': (C.c_int64, [C.c_int32] * 8),
+    'pvr_op_conv_dgrad': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_stem_wgrad_scratch_floats': (C.c_int64, [C.c_int32, C.c_int32]),
+    'pvr_op_stem_wgrad': (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_maxpool_backward': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
+    'pvr_op_avgpool_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 

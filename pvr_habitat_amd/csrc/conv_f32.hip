@@ -144,6 +144,8 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
 
 // conv1 7x7/2 pad 3 + folded BN + ReLU on the normalised fp32 NHWC4 image: wave = 16 output pixels x 64 channels,
 // k-slot = input channel (slot 3 is the zero pad), one MFMA per (tap, 16 couts).  wgt [64][49][4].
+// RAW: stops before bias and ReLU - the raw-weight convolution in front of a training-mode BatchNorm (encoder_train.hip); bias is not read.
+template <bool RAW>
 __global__ __launch_bounds__(256) void stem_f32_kernel(const float *__restrict__ img, const float *__restrict__ wgt,
                                                        const float *__restrict__ bias, float *__restrict__ out, int n, int S) {
     const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
@@ -170,11 +172,11 @@ __global__ __launch_bounds__(256) void stem_f32_kernel(const float *__restrict__
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float bv = bias[j * 16 + fr];
+        const float bv = RAW ? 0.f : bias[j * 16 + fr];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const long long q = tile * 16 + fq * 4 + r;
-            if (q < npix) out[(size_t)q * 64 + j * 16 + fr] = fmaxf(acc[j][r] + bv, 0.f);
+            if (q < npix) out[(size_t)q * 64 + j * 16 + fr] = RAW ? acc[j][r] : fmaxf(acc[j][r] + bv, 0.f);
         }
     }
 }
@@ -225,9 +227,10 @@ pvr_status launch_conv_f32(const float *in, const float *wgt, const float *bias,
     return PVR_OK;
 }
 
-pvr_status launch_stem_f32(const float *img, const float *wgt, const float *bias, float *out, int n, int S, hipStream_t stream) {
+pvr_status launch_stem_f32(const float *img, const float *wgt, const float *bias, float *out, int n, int S, hipStream_t stream, bool raw) {
     const long long tiles = ((long long)n * (S / 2) * (S / 2) + 15) / 16;
-    hipLaunchKernelGGL(stem_f32_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, img, wgt, bias, out, n, S);
+    if (raw) hipLaunchKernelGGL(stem_f32_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, img, wgt, bias, out, n, S);
+    else hipLaunchKernelGGL(stem_f32_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, img, wgt, bias, out, n, S);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }

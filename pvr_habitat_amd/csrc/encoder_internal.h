@@ -291,7 +291,8 @@ pvr_status enc_upload(T **dptr, const std::vector<T> &h) {
 }
 // conv_f32.hip (PVR_F32 reference-precision mode) and the fp32 normaliser of random_pvr.hip
 pvr_status launch_conv_f32(const float *, const float *, const float *, const float *, float *, int, int, int, int, int, int, int, int, int, hipStream_t);
-pvr_status launch_stem_f32(const float *, const float *, const float *, float *, int, int, hipStream_t);
+// (raw: the convolution alone, no bias and no ReLU - the trainable encoder's conv1, encoder_train.hip)
+pvr_status launch_stem_f32(const float *, const float *, const float *, float *, int, int, hipStream_t, bool raw = false);
 pvr_status launch_maxpool_f32(const float *, float *, int, int, int, int, hipStream_t);
 // (padded: the output in the zero-bordered (n, crop + 6, crop + 8, 4) layout stem_split16.hip reads, border untouched)
 pvr_status launch_normalize_nhwc4(const void *img_h, float *out, int n, int crop, const float *mean, const float *std_, int dtype, hipStream_t, bool padded = false);

@@ -1,0 +1,378 @@
+// Trainable ResNet encoder (include/pvr_train.h): EmbeddingNet(..., train=True) of the reference (src/embeddings.py:323-326, :396-398) for the torchvision
+// trunks resnet18 / 34 / 50 in fp32.  The executor walks plan_encoder's op list (convolution + BN [+ residual] [+ ReLU], the in_buf / out_buf / res_buf
+// dataflow f32_chunk walks) with ONE saved pre-BN and one post-BN tensor per op instead of the reused workspace buffers, and walks it backwards for the
+// gradients.  The device code of the backward pass is train_kernels.hip; every product of a convolution, data gradient or weight gradient runs on the
+// f32-input MFMA (conv_f32.hip / conv_wgrad_kernel), BatchNorm statistics are two-pass, and every split reduction is summed in a fixed order.
+#include "encoder_internal.h"
+#include "train_internal.h"
+#include "../../include/pvr_train.h"
+
+namespace {
+
+struct Slot {
+    std::string name;
+    int64_t off, numel, shape[4];
+};
+
+struct TrainOp {
+    std::string conv, bn;
+    int in_src = -3, res_src = -2;              // producer of the input / residual: op index, -1 the max pool's output, -2 none
+    int h, w, cin, cout, k, stride, pad, relu, ho, wo;
+    int64_t w_off, g_off, b_off, rm_off, rv_off, nbt_off;   // params (floats) / buffer block (4-byte slots)
+    float *z = nullptr, *y = nullptr, *dy = nullptr, *mean = nullptr, *rstd = nullptr;
+};
+
+struct Timed {
+    std::string name;
+    double flops;
+    float ms;
+};
+
+struct EventPair {
+    hipEvent_t e0, e1;
+};
+
+}  // namespace
+
+struct pvr_trainer {
+    pvr_encoder_desc desc;
+    int out_size = 0, final_hw = 0, final_c = 0;
+    TrainOp stem;                                // conv1 / bn1 (7x7 / 2 on the NHWC4 image; in_src unused)
+    std::vector<TrainOp> ops;
+    std::vector<Slot> params, buffers;
+    int64_t n_params = 0, n_buf_slots = 0;
+    // device (made by the first forward, sized for max_batch)
+    void *arena = nullptr;
+    u16 *d_img = nullptr;
+    float *d_imgf = nullptr, *pool = nullptr, *dpool = nullptr, *dz = nullptr, *dil = nullptr, *wpack = nullptr, *stem_wpack = nullptr, *wg_scratch = nullptr,
+          *bn_scratch = nullptr, *zero_bias = nullptr;
+    int64_t wg_floats = 0, bn_floats = 0;
+    int fwd_n = 0;                               // frames of the forward whose activations are held (0: none - a backward is PVR_ERR_STATE)
+    bool timing = false;
+    std::vector<Timed> times;                    // launch i of a step is bracketed by events[i]
+    std::vector<EventPair> events;               // made once each, on demand; destroyed with the trainer (no error path leaves one behind)
+};
+
+namespace {
+
+constexpr int S_IMG = 224;
+
+int64_t add_slot(std::vector<Slot> &v, int64_t &total, const std::string &name, std::initializer_list<int64_t> shape, int64_t slots_per_elem = 1) {
+    Slot s;
+    s.name = name; s.off = total; s.numel = 1;
+    int i = 0;
+    for (int64_t d : shape) { s.shape[i++] = d; s.numel *= d; }
+    for (; i < 4; ++i) s.shape[i] = 0;
+    total += s.numel * slots_per_elem;
+    v.push_back(s);
+    return s.off;
+}
+
+void add_params(pvr_trainer *t, TrainOp &op) {
+    op.w_off = add_slot(t->params, t->n_params, op.conv + ".weight", {op.cout, op.cin == 4 ? 3 : op.cin, op.k, op.k});
+    op.g_off = add_slot(t->params, t->n_params, op.bn + ".weight", {op.cout});
+    op.b_off = add_slot(t->params, t->n_params, op.bn + ".bias", {op.cout});
+    op.rm_off = add_slot(t->buffers, t->n_buf_slots, op.bn + ".running_mean", {op.cout});
+    op.rv_off = add_slot(t->buffers, t->n_buf_slots, op.bn + ".running_var", {op.cout});
+}
+
+size_t out_elems(const TrainOp &op, int n) { return (size_t)n * op.ho * op.wo * op.cout; }
+
+struct Carver {                                  // sizes, then pointers, of one arena (256-byte aligned pieces)
+    char *base = nullptr;
+    size_t used = 0;
+    template <typename T> void take(T **p, size_t count) {
+        if (base) *p = (T *)(base + used);
+        used += (count * sizeof(T) + 255) / 256 * 256;
+    }
+};
+
+void carve(pvr_trainer *t, Carver &c) {
+    const int B = t->desc.max_batch;
+    c.take(&t->d_img, (size_t)B * (S_IMG + 6) * (S_IMG + 8) * 4);
+    c.take(&t->d_imgf, (size_t)B * S_IMG * S_IMG * 4);
+    size_t dz_max = out_elems(t->stem, B), dil_max = 1, w_max = 1;
+    int64_t wg_max = pvr_op_stem_wgrad_scratch_floats(B, S_IMG), bn_max = pvr_op_bn_scratch_floats((int64_t)B * t->stem.ho * t->stem.wo, 64);
+    int c_max = 64;
+    auto take_op = [&](TrainOp &op) {
+        c.take(&op.z, out_elems(op, B));
+        c.take(&op.y, out_elems(op, B));
+        c.take(&op.dy, out_elems(op, B));
+        c.take(&op.mean, op.cout);
+        c.take(&op.rstd, op.cout);
+    };
+    take_op(t->stem);
+    c.take(&t->pool, (size_t)B * 56 * 56 * 64);
+    c.take(&t->dpool, (size_t)B * 56 * 56 * 64);
+    for (TrainOp &op : t->ops) {
+        take_op(op);
+        dz_max = std::max(dz_max, out_elems(op, B));
+        if (op.stride == 2) dil_max = std::max(dil_max, (size_t)B * op.h * op.w * op.cout);
+        w_max = std::max(w_max, (size_t)std::max((op.cout + 63) / 64 * 64 * op.cin, (op.cin + 63) / 64 * 64 * op.cout) * op.k * op.k);
+        for (int n = 1; n <= B; ++n)               // (the number of pixel ranges is not monotone in the batch: the range length is rounded to 32)
+            wg_max = std::max(wg_max, pvr_op_conv_wgrad_scratch_floats(n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad));
+        bn_max = std::max(bn_max, pvr_op_bn_scratch_floats((int64_t)B * op.ho * op.wo, op.cout));
+        c_max = std::max(c_max, std::max(op.cin, op.cout));
+    }
+    c.take(&t->dz, dz_max);
+    c.take(&t->dil, dil_max);
+    c.take(&t->wpack, w_max);
+    c.take(&t->stem_wpack, (size_t)64 * 49 * 4);
+    c.take(&t->wg_scratch, (size_t)wg_max);
+    c.take(&t->bn_scratch, (size_t)bn_max);
+    c.take(&t->zero_bias, (size_t)c_max);
+    t->wg_floats = wg_max; t->bn_floats = bn_max;
+}
+
+// first forward: the whole workspace as one allocation; the image's zero border and the zero bias are written once, here (null stream: drained before
+// the caller's stream goes on, as encoder.hip: get_lane)
+pvr_status ensure_workspace(pvr_trainer *t) {
+    if (t->arena) return PVR_OK;
+    Carver size;
+    carve(t, size);
+    void *a = nullptr;
+    PVR_HIP_TRY(hipMalloc(&a, size.used));
+    Carver c;
+    c.base = (char *)a;
+    carve(t, c);
+    const size_t img_bytes = (size_t)t->desc.max_batch * (S_IMG + 6) * (S_IMG + 8) * 4 * 2;
+    const size_t zero_bytes = (size_t)((char *)a + size.used - (char *)t->zero_bias);      // (the arena's last piece)
+    if (hipMemset(t->d_img, 0, img_bytes) != hipSuccess || hipMemset(t->zero_bias, 0, zero_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(a);
+        set_error("pvr_trainer: workspace initialisation failed");
+        return PVR_ERR_HIP;
+    }
+    t->arena = a;
+    return PVR_OK;
+}
+
+struct Tick {                                    // per-launch timing: an event pair around every launch when pvr_trainer_debug_set_timing is on
+    pvr_trainer *t;
+    hipStream_t st;
+    pvr_status begin(const std::string &name, double flops) {
+        if (!t->timing) return PVR_OK;
+        const size_t i = t->times.size();
+        if (i == t->events.size()) {
+            EventPair p;
+            PVR_HIP_TRY(hipEventCreate(&p.e0));
+            if (hipEventCreate(&p.e1) != hipSuccess) {
+                (void)hipEventDestroy(p.e0);
+                set_error("pvr_trainer: hipEventCreate failed");
+                return PVR_ERR_HIP;
+            }
+            t->events.push_back(p);
+        }
+        PVR_HIP_TRY(hipEventRecord(t->events[i].e0, st));
+        t->times.push_back(Timed{name, flops, 0.f});
+        return PVR_OK;
+    }
+    pvr_status end() {
+        if (!t->timing) return PVR_OK;
+        PVR_HIP_TRY(hipEventRecord(t->events[t->times.size() - 1].e1, st));
+        return PVR_OK;
+    }
+};
+pvr_status collect_times(pvr_trainer *t, size_t from, hipStream_t st) {
+    if (!t->timing) return PVR_OK;
+    PVR_HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = from; i < t->times.size(); ++i)
+        PVR_HIP_TRY(hipEventElapsedTime(&t->times[i].ms, t->events[i].e0, t->events[i].e1));
+    return PVR_OK;
+}
+
+#define TR_RUN(name_, flops_, call_)                \
+    do {                                            \
+        if ((s = tick.begin(name_, flops_))) return s; \
+        if ((s = (call_))) return s;                \
+        if ((s = tick.end())) return s;             \
+    } while (0)
+
+const float *tensor_of(const pvr_trainer *t, int src) { return src == -1 ? t->pool : t->ops[src].y; }
+float *grad_of(pvr_trainer *t, int src) { return src == -1 ? t->dpool : t->ops[src].dy; }
+
+}  // namespace
+
+extern "C" {
+
+pvr_status pvr_trainer_create(const pvr_encoder_desc *desc, pvr_trainer **out) {
+    PVR_REQUIRE(desc && out, "pvr_trainer_create: null argument");
+    const char *scope = "trainable encoders: the torchvision ResNet trunks resnet18 / resnet34 / resnet50 (arch PVR_ARCH_RESNET18 / _RESNET34 / _RESNET50) "
+                        "with dtype PVR_F32";
+    PVR_REQUIRE(desc->arch == PVR_ARCH_RESNET50 || desc->arch == PVR_ARCH_RESNET18 || desc->arch == PVR_ARCH_RESNET34,
+                "pvr_trainer_create: arch %d is not trainable (%s; the compressed *_l3 / *_l4 variants, CLIP, MAE and 'random' run frozen)", desc->arch, scope);
+    PVR_REQUIRE(desc->dtype == PVR_F32, "pvr_trainer_create: dtype %d is not trainable (%s: fp32 storage, every product on the f32-input MFMA)", desc->dtype, scope);
+    PVR_REQUIRE(desc->crop == S_IMG, "pvr_trainer_create: crop %d: the trainer's stem, workspace and pools are built for the %d-pixel crop of the reference's "
+                "transforms", desc->crop, S_IMG);
+    pvr_encoder_desc d = *desc;
+    d.chunk = 0;                                  // batch statistics cannot be chunked: a forward is one pass over all its frames
+    pvr_encoder *enc = nullptr;
+    pvr_status s = pvr_encoder_create(&d, &enc);  // plans the op list from the desc alone (encoder_plan.hip); no weights, no device
+    if (s) return s;
+    pvr_trainer *t = new pvr_trainer();
+    t->desc = d;
+    t->out_size = enc->out_size; t->final_hw = enc->final_hw; t->final_c = enc->final_c;
+    TrainOp &st = t->stem;
+    st.conv = "conv1"; st.bn = "bn1";
+    st.h = st.w = S_IMG; st.cin = 4; st.cout = 64; st.k = 7; st.stride = 2; st.pad = 3; st.relu = 1; st.ho = st.wo = S_IMG / 2;
+    add_params(t, st);
+    int writer[B_COUNT + 1];
+    for (int &x : writer) x = -3;
+    writer[B_X0] = -1;                            // the max pool's output
+    bool ok = true;
+    for (const ConvOp &op : enc->ops) {
+        TrainOp o;
+        o.conv = op.conv; o.bn = op.bn;
+        o.h = op.h; o.w = op.w; o.cin = op.cin; o.cout = op.cout; o.k = op.k; o.stride = op.stride; o.pad = op.pad; o.relu = op.relu;
+        o.ho = (op.h + 2 * op.pad - op.k) / op.stride + 1; o.wo = (op.w + 2 * op.pad - op.k) / op.stride + 1;
+        o.in_src = writer[op.in_buf];
+        o.res_src = op.res_buf == B_NONE ? -2 : writer[op.res_buf];
+        ok = ok && op.kind == 0 && o.in_src >= -1 && o.res_src >= -2 && op.cin % 32 == 0 && op.cout % 64 == 0 && (op.k == 1 || op.k == 3) &&
+             (op.stride == 1 || (op.stride == 2 && op.h % 2 == 0 && op.w % 2 == 0)) && op.pad == op.k / 2 && op.cin == op.cin_real && op.cout == op.cout_real;
+        writer[op.out_buf] = (int)t->ops.size();
+        add_params(t, o);
+        t->ops.push_back(o);
+    }
+    pvr_encoder_destroy(enc);
+    if (!ok || t->ops.empty()) {
+        delete t;
+        set_error("pvr_trainer_create: the plan of arch %d holds an operation the trainer has no backward for", desc->arch);
+        return PVR_ERR_INVALID;
+    }
+    if (t->n_buf_slots & 1) ++t->n_buf_slots;     // (never: every BatchNorm adds 2 c slots) the int64 counters are 8-byte aligned
+    st.nbt_off = add_slot(t->buffers, t->n_buf_slots, st.bn + ".num_batches_tracked", {1}, 2);
+    for (TrainOp &o : t->ops) o.nbt_off = add_slot(t->buffers, t->n_buf_slots, o.bn + ".num_batches_tracked", {1}, 2);
+    *out = t;
+    return PVR_OK;
+}
+
+void pvr_trainer_destroy(pvr_trainer *t) {
+    if (!t) return;
+    if (t->arena) (void)hipFree(t->arena);
+    for (EventPair &p : t->events) {
+        (void)hipEventDestroy(p.e0);
+        (void)hipEventDestroy(p.e1);
+    }
+    delete t;
+}
+
+int32_t pvr_trainer_out_size(const pvr_trainer *t) { return t ? t->out_size : 0; }
+int64_t pvr_trainer_param_count(const pvr_trainer *t) { return t ? t->n_params : 0; }
+int64_t pvr_trainer_buffer_count(const pvr_trainer *t) { return t ? t->n_buf_slots : 0; }
+
+int32_t pvr_trainer_param_name(const pvr_trainer *t, int32_t index, char *buf, int32_t cap) {
+    if (!t || index < 0 || index >= (int32_t)t->params.size() || !buf || cap <= 0) return 0;
+    snprintf(buf, (size_t)cap, "%s", t->params[index].name.c_str());
+    return (int32_t)t->params[index].name.size();
+}
+
+static int64_t slot_offset(const std::vector<Slot> &v, const char *name, int64_t *numel, int64_t *shape) {
+    if (!name) return -1;
+    for (const Slot &s : v)
+        if (s.name == name) {
+            if (numel) *numel = s.numel;
+            if (shape) for (int i = 0; i < 4; ++i) shape[i] = s.shape[i];
+            return s.off;
+        }
+    return -1;
+}
+int64_t pvr_trainer_param_offset(const pvr_trainer *t, const char *name, int64_t *numel, int64_t *shape) {
+    return t ? slot_offset(t->params, name, numel, shape) : -1;
+}
+int64_t pvr_trainer_buffer_offset(const pvr_trainer *t, const char *name, int64_t *numel) { return t ? slot_offset(t->buffers, name, numel, nullptr) : -1; }
+
+pvr_status pvr_trainer_debug_set_timing(pvr_trainer *t, int32_t on) {
+    PVR_REQUIRE(t, "null trainer");
+    t->timing = on != 0;
+    t->times.clear();
+    return PVR_OK;
+}
+int32_t pvr_trainer_launch_time(const pvr_trainer *t, int32_t index, char *name, int32_t cap, float *ms, double *flops) {
+    if (!t || index < 0 || index >= (int32_t)t->times.size()) return 0;
+    const Timed &x = t->times[index];
+    if (name && cap > 0) snprintf(name, (size_t)cap, "%s", x.name.c_str());
+    if (ms) *ms = x.ms;
+    if (flops) *flops = x.flops;
+    return (int32_t)x.name.size();
+}
+
+pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *out,
+                               int64_t out_stride, void *stream) {
+    PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward: null argument");
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward: %d frames, the workspace holds max_batch = %d (BatchNorm takes the whole batch of a forward "
+                "together: it is not chunked)", n, t->desc.max_batch);
+    TraceScope ts("pvr_trainer_forward");
+    hipStream_t st = (hipStream_t)stream;
+    pvr_status s;
+    if ((s = ensure_workspace(t))) return s;
+    t->fwd_n = 0;                                 // the held activations are being overwritten
+    if (t->timing) t->times.clear();
+    Tick tick{t, st};
+    float *bufs = (float *)bn_buffers;
+    auto bn = [&](TrainOp &op, const float *res, int64_t rows) {
+        return pvr_op_bn_train_forward(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, (int64_t *)(bufs + op.nbt_off), op.y,
+                                       op.mean, op.rstd, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st);
+    };
+    TR_RUN("preprocess", 0, launch_preprocess(frames, n, h, w, t->desc.resize, t->desc.crop, t->d_img, PVR_BF16, st, 0));
+    TR_RUN("normalize", 0, launch_normalize_nhwc4(t->d_img, t->d_imgf, n, t->desc.crop, t->desc.mean, t->desc.std_, PVR_BF16, st, false));
+    TrainOp &sm = t->stem;
+    TR_RUN("conv1 pack", 0, launch_pack_stem_weights(params + sm.w_off, t->stem_wpack, st));
+    TR_RUN("conv1", 2.0 * n * 112 * 112 * 64 * 147, launch_stem_f32(t->d_imgf, t->stem_wpack, nullptr, sm.z, n, S_IMG, st, true));
+    TR_RUN("bn1", 0, bn(sm, nullptr, (int64_t)n * 112 * 112));
+    TR_RUN("maxpool", 0, launch_maxpool_f32(sm.y, t->pool, n, 112, 112, 64, st));
+    for (TrainOp &op : t->ops) {
+        const int64_t rows = (int64_t)n * op.ho * op.wo;
+        TR_RUN(op.conv + " pack", 0, launch_pack_conv_weights(params + op.w_off, t->wpack, op.cout, op.cin, op.k, false, st));
+        TR_RUN(op.conv, 2.0 * rows * op.cout * op.cin * op.k * op.k,
+               launch_conv_f32(tensor_of(t, op.in_src), t->wpack, t->zero_bias, nullptr, op.z, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, 0, st));
+        TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows));
+    }
+    TR_RUN("avgpool", 0, launch_avgpool(t->ops.back().y, out, out_stride, n, t->final_hw, t->final_c, 1, PVR_F32, st));
+    t->fwd_n = n;
+    return collect_times(t, 0, st);
+}
+
+pvr_status pvr_trainer_backward(pvr_trainer *t, const float *params, const float *dout, int64_t dout_stride, float *grads, void *stream) {
+    PVR_REQUIRE(t && params && dout && grads, "pvr_trainer_backward: null argument");
+    if (t->fwd_n <= 0) {
+        set_error("pvr_trainer_backward: no forward's activations are held (one backward per pvr_trainer_forward, right after it)");
+        return PVR_ERR_STATE;
+    }
+    TraceScope ts("pvr_trainer_backward");
+    hipStream_t st = (hipStream_t)stream;
+    const int n = t->fwd_n;
+    t->fwd_n = 0;
+    pvr_status s;
+    Tick tick{t, st};
+    const size_t first_time = t->times.size();
+    std::vector<char> have(t->ops.size() + 1, 0);  // gradient of tensor src (index src + 1) holds a value already: the next contribution accumulates
+    const int last = (int)t->ops.size() - 1;
+    TR_RUN("avgpool bwd", 0, pvr_op_avgpool_backward(dout, dout_stride, t->ops[last].dy, n, t->final_hw, t->final_c, st));
+    have[last + 1] = 1;
+    for (int i = last; i >= 0; --i) {
+        TrainOp &op = t->ops[i];
+        PVR_REQUIRE(have[i + 1], "pvr_trainer_backward: %s has no consumer", op.conv.c_str());
+        const int64_t rows = (int64_t)n * op.ho * op.wo;
+        float *dres = op.res_src == -2 ? nullptr : grad_of(t, op.res_src);
+        TR_RUN(op.bn + " bwd", 0,
+               pvr_op_bn_train_backward(op.z, op.y, op.dy, params + op.g_off, op.mean, op.rstd, t->dz, dres, dres ? have[op.res_src + 1] : 0, grads + op.g_off,
+                                        grads + op.b_off, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st));
+        if (dres) have[op.res_src + 1] = 1;
+        const double fl = 2.0 * rows * op.cout * op.cin * op.k * op.k;
+        TR_RUN(op.conv + " wgrad", fl,
+               pvr_op_conv_wgrad(tensor_of(t, op.in_src), t->dz, grads + op.w_off, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, t->wg_scratch, t->wg_floats, st));
+        TR_RUN(op.conv + " dgrad", fl,
+               launch_conv_dgrad(t->dz, params + op.w_off, grad_of(t, op.in_src), have[op.in_src + 1], n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad,
+                                 t->wpack, t->dil, t->zero_bias, st));
+        have[op.in_src + 1] = 1;
+    }
+    PVR_REQUIRE(have[0], "pvr_trainer_backward: the max pool's output has no consumer");
+    TrainOp &sm = t->stem;
+    TR_RUN("maxpool bwd", 0, pvr_op_maxpool_backward(sm.y, t->dpool, sm.dy, n, 112, 112, 64, st));
+    TR_RUN("bn1 bwd", 0,
+           pvr_op_bn_train_backward(sm.z, sm.y, sm.dy, params + sm.g_off, sm.mean, sm.rstd, t->dz, nullptr, 0, grads + sm.g_off, grads + sm.b_off,
+                                    (int64_t)n * 112 * 112, 64, 1, t->bn_scratch, t->bn_floats, st));
+    TR_RUN("conv1 wgrad", 2.0 * n * 112 * 112 * 64 * 147, pvr_op_stem_wgrad(t->d_imgf, t->dz, grads + sm.w_off, n, S_IMG, t->wg_scratch, t->wg_floats, st));
+    return collect_times(t, first_time, st);
+}
+
+}  // extern "C"

@@ -376,6 +376,183 @@ class HipResNet50(_Node):
         return out
 
 
+_TRAINABLE = ('r18', 'r34', 'conv5')
+_TRAINABLE_MSG = ("trainable (train=True) are the torchvision ResNet trunks: 'resnet18', 'resnet34', 'resnet50' and the conv5 checkpoints of the "
+                  "registry (resnet50_places, demy, moco_*), in fp32 on one GPU")
+
+
+class _EncoderFunction(torch.autograd.Function):
+    """Training-mode forward of the whole encoder as one autograd node (the pattern of models._PolicyFunction).  Inputs: the module, the uint8
+    frames, then every parameter, so autograd routes a gradient to each of them.  The library keeps the activations of ONE forward: a backward
+    after a later training forward of the same module raises."""
+
+    @staticmethod
+    def forward(ctx, model, frames_u8, *params):
+        out = model._forward_raw(frames_u8)
+        model._fwd_gen += 1
+        ctx.model, ctx.gen = model, model._fwd_gen
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        m = ctx.model
+        if ctx.gen != m._fwd_gen:
+            raise RuntimeError('trainable encoder backward: the activations of this forward are gone - a later training-mode forward of the same '
+                               'encoder overwrote them (one backward per forward, right after it)')
+        dout = dout.contiguous().float()
+        g = torch.empty_like(m._flat)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().pvr_trainer_backward(m._handle, vp(m._flat), vp(dout), dout.stride(0), vp(g), _lib.stream_ptr()))
+        return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._slots)
+
+
+class HipTrainableResNet(_Node):
+    """One trainable encoder (reference src/embeddings.py:323-326, :396-398): resnet18 / resnet34 / resnet50 in fp32 on the library's pvr_trainer
+    (include/pvr_train.h).  Parameters are nn.Parameter CUDA views of ONE flat fp32 buffer the library reads on every forward, so any torch
+    optimizer steps them in place; the BatchNorm buffers are views of a second block the training forward updates.  The tensors sit in the same
+    _Node tree as HipResNet50's: state_dict() keys and shapes equal the frozen model's and the reference's.  In eval mode the module runs the
+    frozen 'f32' plan (HipResNet50) built from the CURRENT parameters and running statistics.
+
+    max_batch is the largest training batch: the workspace keeps the pre-BN, post-BN and gradient tensor of EVERY convolution for that many frames
+    (about 0.03 GB per frame for resnet18 and 0.14 GB per frame for resnet50), so it defaults to 32, not to the frozen encoder's 256 - size it to
+    the training batch."""
+
+    def __init__(self, state_dict, variant='conv5', max_batch=None):
+        super().__init__()
+        assert variant in _TRAINABLE, variant
+        _lib.require_gpu()
+        self.variant = variant
+        self.out_size = OUT_SIZE[variant]
+        self._dtype = _lib.PVR_F32
+        self._max_batch = int(max_batch or 32)
+        self._fwd_gen = 0
+        self._frozen = []                        # the eval-mode plan, in a plain list: not a sub-module (its tensors are no part of state_dict())
+        L = _lib.lib()
+        tr = transforms_for('')
+        desc = _lib.EncoderDesc(arch=_ARCH[variant], dtype=_lib.PVR_F32, max_batch=self._max_batch, chunk=0, resize=tr.resize, crop=tr.crop)
+        desc.mean[:] = tr.mean
+        desc.std_[:] = tr.std
+        h = C.c_void_p()
+        _lib.check(L.pvr_trainer_create(C.byref(desc), C.byref(h)))
+        self._handle = h
+        dev = torch.device('cuda')
+        self._flat = torch.zeros(L.pvr_trainer_param_count(h), dtype=torch.float32, device=dev)
+        self._bufs = torch.zeros(L.pvr_trainer_buffer_count(h), dtype=torch.float32, device=dev)
+        self._slots = []                         # (offset, numel, shape) of every parameter, in the order they are handed to autograd
+        self._plist = []
+        numel, shape = C.c_int64(), (C.c_int64 * 4)()
+        for k, v in state_dict.items():
+            t = (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))).detach()
+            if k.endswith(('running_mean', 'running_var', 'num_batches_tracked')):
+                o = L.pvr_trainer_buffer_offset(h, k.encode(), C.byref(numel))
+                if o < 0:
+                    raise KeyError("trainable '%s' encoder: unexpected state_dict key %r" % (variant, k))
+                if k.endswith('num_batches_tracked'):
+                    view = self._bufs[o:o + 2].view(torch.int64).view(())
+                else:
+                    view = self._bufs[o:o + numel.value]
+                view.copy_(t.to(device=dev, dtype=view.dtype).reshape(view.shape))
+                _install(self, k, view)
+            else:
+                o = L.pvr_trainer_param_offset(h, k.encode(), C.byref(numel), shape)
+                if o < 0:
+                    raise KeyError("trainable '%s' encoder: unexpected state_dict key %r" % (variant, k))
+                shp = tuple(int(x) for x in shape if x > 0)
+                assert tuple(t.shape) == shp, (k, tuple(t.shape), shp)
+                view = self._flat[o:o + numel.value].view(shp)
+                view.copy_(t.to(device=dev, dtype=torch.float32))
+                _install(self, k, view)
+                self._slots.append((o, numel.value, shp))
+                self._plist.append(self.get_parameter(k))
+        missing = sum(n for _, n, _ in self._slots) != self._flat.numel()
+        if missing:                               # (the reference asserts missing_keys == [], moco.py:24)
+            raise KeyError("trainable '%s' encoder: the state_dict does not hold every parameter" % variant)
+
+    # -- lifetime ------------------------------------------------------------------------------
+    def close(self):
+        """free the frozen eval-mode plan now; the trainer handle lives as long as the module (its parameters are views the library reads)"""
+        for m in self._frozen:
+            m.close()
+        del self._frozen[:]
+
+    def __del__(self):
+        try:
+            self.close()
+            if self._handle is not None:
+                _lib.lib().pvr_trainer_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    def train(self, mode=True):
+        self.close()                              # the frozen plan folds the parameters of the moment it is built
+        return super().train(mode)
+
+    def load_state_dict(self, *a, **k):
+        self.close()
+        return super().load_state_dict(*a, **k)
+
+    @property
+    def max_batch(self):
+        return self._max_batch
+
+    @property
+    def lanes(self):
+        return 4
+
+    def set_low_latency(self, on=True):
+        self._low_latency = bool(on)
+
+    def _eval_model(self):
+        if not self._frozen:
+            self._frozen.append(HipResNet50({k: v.detach().cpu() for k, v in self.state_dict().items()}, self.variant, compute_dtype='f32',
+                                            max_batch=self._max_batch))
+            if getattr(self, '_low_latency', False):
+                self._frozen[0].set_low_latency(True)
+        return self._frozen[0]
+
+    def forward_into(self, frames_u8, out, lane=0):
+        """eval mode only (the streaming embedders): the frozen 'f32' plan of the current parameters"""
+        if self.training:
+            raise RuntimeError('forward_into is the frozen encoder\'s entry point: call .eval() first (a training-mode forward returns a tensor with a graph)')
+        self._eval_model().forward_into(frames_u8, out, lane=lane)
+
+    def _forward_raw(self, frames_u8):
+        n, h, w, c = frames_u8.shape
+        assert c == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and frames_u8.is_contiguous()
+        if n > self._max_batch:
+            raise ValueError('training forward of %d frames: the workspace was made for max_batch = %d (BatchNorm takes the whole batch together, '
+                             'it cannot be chunked)' % (n, self._max_batch))
+        out = torch.empty((n, self.out_size), dtype=torch.float32, device=frames_u8.device)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().pvr_trainer_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8), n, h, w, vp(out), out.stride(0),
+                                                  _lib.stream_ptr()))
+        return out
+
+    def forward(self, frames_u8):
+        if self.training:
+            self.close()
+            return _EncoderFunction.apply(self, frames_u8.contiguous(), *self._plist)
+        with torch.no_grad():
+            return self._eval_model()(frames_u8)
+
+
+def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False):
+    """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
+    if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
+            and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
+        raise NotImplementedError("Requested model not available.")                 # embeddings.py:321
+    if embedding_name not in _SINGLE or _SINGLE[embedding_name][1] not in _TRAINABLE:
+        raise NotImplementedError("training the embedding '%s' is not built: %s (the compressed *_l3 / *_l4 variants, Uber models, CLIP, MAE and "
+                                  "'random' run frozen)" % (embedding_name, _TRAINABLE_MSG))
+    if host:
+        raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
+    if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
+        raise ValueError("train=True computes in fp32 (compute_dtype None or 'f32'), got %r" % (compute_dtype,))
+    sd, variant = _load_named_state_dict(embedding_name, pretrained)
+    return HipTrainableResNet(sd, variant, max_batch=max_batch)
+
+
 class UberModel(nn.Module):
     """reference src/embeddings.py:44-57.  `models` stays a plain list as in the reference (so, as there,
     its weights are not part of state_dict()); each member writes its columns of one output buffer."""
@@ -504,6 +681,12 @@ def _get_embedding(embedding_name='random', in_channels=3, pretrained=True, trai
     assert in_channels == 3, 'Current models accept 3-channel inputs only.'          # embeddings.py:87
     if embedding_name == 'true_state':
         return nn.Sequential(nn.Identity()), nn.Sequential(nn.Identity())
+    if train:                                                                        # embeddings.py:323-326
+        model = _get_trainable(embedding_name, pretrained, **hip_kw)
+        model.train()
+        for p in model.parameters():
+            p.requires_grad = True
+        return model, transforms_for(embedding_name)
     if embedding_name in _SINGLE:
         sd, variant = _load_named_state_dict(embedding_name, pretrained)
         model = HipResNet50(sd, variant, **hip_kw)
@@ -549,9 +732,6 @@ def _get_embedding(embedding_name='random', in_channels=3, pretrained=True, trai
                                   "family is not built in pvr_habitat_amd yet)" % embedding_name)
     else:
         raise NotImplementedError("Requested model not available.")                 # embeddings.py:321
-    if train:
-        raise NotImplementedError('pvr_habitat_amd runs the encoder frozen (the reference scripts hard-code '
-                                  'train=False, main_bc_2.py:68-72); training the embedding is not built')
     model.eval()
     for p in model.parameters():
         p.requires_grad = False
@@ -575,6 +755,8 @@ class EmbeddingNet(nn.Module):
         # (csrc/host_encoder.hip: plain C++ loops behind the same pvr_encoder_* ABI, fp32) - the ResNet family only.
         # It is selected EXPLICITLY (the reference's own flag); a box whose GPU is missing or invisible still fails loudly (no silent fallback).
         self._host = bool(disable_cuda)
+        if crops == 5 and train:
+            raise NotImplementedError('train=True with crops=5: the 5-crop extension wraps the frozen encoder only')
         self.embedding, self.transforms = _get_embedding(embedding_name, in_channels, pretrained, train,
                                                          compute_dtype=compute_dtype, max_batch=max_batch, chunk=chunk, host=self._host)
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
@@ -629,6 +811,11 @@ class EmbeddingNet(nn.Module):
         if self.embedding_name == 'true_state':
             return observation.squeeze().cpu().numpy()
         # observation.shape -> (N, H, W, 3); transposes + transforms + model are one HIP plan
+        # embeddings.py:396-398: a device tensor that keeps its graph.  Only the trainable module has a training mode: a frozen encoder on which
+        # .train() was called (by a parent module, say) keeps returning checked numpy rows
+        if isinstance(self.embedding, HipTrainableResNet) and self.embedding.training:
+            out = self.embed_device(observation)
+            return out.view(-1, self.out_size).squeeze()
         with torch.no_grad():
             out = self.embed_device(observation)
             return _checked(out.view(-1, self.out_size).squeeze().cpu().numpy(), self.embedding)

@@ -485,6 +485,9 @@ def _block_rows(flags, row_bytes, batch):
 
 
 def run(flags):
+    if flags.train_embedding:
+        raise NotImplementedError('save_embedded_obs writes embedding rows: that needs the frozen encoder (a trainable EmbeddingNet(train=True) '
+                                  'is for end-to-end training); run without --train_embedding')
     save_name = os.path.join(flags.data_path, flags.env + '_' + flags.embedding_name + '.pickle')
     if os.path.isfile(save_name):
         return                                                  # idempotent skip (:97-101)
