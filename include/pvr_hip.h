@@ -191,6 +191,18 @@ pvr_status pvr_op_preprocess(const uint8_t *frames_dev, int32_t n, int32_t h, in
  * out: (n,112,112,64) NHWC 16-bit */
 pvr_status pvr_op_stem(const void *img_dev, const void *wgt_dev, const float *bias_dev, void *out_dev,
                        int32_t n, int32_t dtype, void *hip_stream);
+/* The fused forms of the stem one at a time (test entry points; the encoder reaches the same launchers): conv1 7x7/2 + folded BN + ReLU + maxpool 3x3/2 pad 1
+ * (torchvision ResNet conv1 / bn1 / relu / maxpool, reference src/embeddings.py:118-120) -> out (n,56,56,64) NHWC 16-bit.  form: 0 stem_pool_kernel (padded
+ * image only), 1 the LDS-tile form, 2 the register-pooling form.  c1_w / c1_b / c1_t1 (all three or none; form 2 only): layer1.0.conv1 inside the launch -
+ * c1_w the (64, 64) 1x1 weights as the fragment image the stem reads, t1 (n,56,56,64) = relu(conv1x1(out) + c1_b).  The _u8 call reads uint8 (n,h,w,3) frames
+ * with the 224 x 224 window at (top, left) (pvr_debug_stem_u8_geometry_ok) instead of the padded image.  A form or geometry that is not built returns a
+ * status with a message and launches nothing. */
+pvr_status pvr_op_stem_pool(const void *img_padded_dev, const void *wgt_dev, const float *bias_dev, void *out_dev, int32_t n, int32_t form, const void *c1_w_dev,
+                            const float *c1_b_dev, void *c1_t1_dev, int32_t dtype, void *hip_stream);
+pvr_status pvr_op_stem_pool_u8(const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, int32_t top, int32_t left, const void *wgt_dev, const float *bias_dev,
+                               void *out_dev, int32_t form, const void *c1_w_dev, const float *c1_b_dev, void *c1_t1_dev, int32_t dtype, void *hip_stream);
+/* host-only: (64, 64) 16-bit 1x1 weights in pvr_op_conv2d's layout -> the 8 KB fragment image pvr_op_stem_pool's c1_w is (4096 values each) */
+pvr_status pvr_debug_stem_c1_pack(const uint16_t *w, uint16_t *image);
 /* maxpool 3x3/2 pad 1 on NHWC 16-bit */
 pvr_status pvr_op_maxpool(const void *in_dev, void *out_dev, int32_t n, int32_t h, int32_t w, int32_t c,
                           int32_t dtype, void *hip_stream);
@@ -201,6 +213,12 @@ pvr_status pvr_op_conv2d(const void *in_dev, const void *wgt_dev, const float *b
                          const void *residual_dev, void *out_dev, int32_t n, int32_t h, int32_t w,
                          int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
                          int32_t relu, int32_t out_f32, int32_t dtype, void *hip_stream);
+/* pvr_op_conv2d split over K (conv_igemm.hip; the *_l4 compression head and the low-latency plan): `ksplit` > 1 blocks per tile write fp32 partial planes to
+ * scratch (ksplit * M * cout floats, M = n*ho*wo), one elementwise launch adds them in plane order, then bias, the 16-bit residual and ReLU.  relu 0 / 1,
+ * out_f32 0 / 1. */
+pvr_status pvr_op_conv2d_splitk(const void *in_dev, const void *wgt_dev, const float *bias_dev, const void *residual_dev, void *out_dev, float *scratch_dev,
+                                int32_t ksplit, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride,
+                                int32_t pad, int32_t relu, int32_t out_f32, int32_t dtype, void *hip_stream);
 /* Per-frame fused layer3 bottleneck (torchvision Bottleneck, reference src/embeddings.py:118-120; bneck_frame.hip), one workgroup per 14 x 14 frame:
  * [x (n,14,14,1024) -> the block's own conv1 1x1 (+ b1f, ReLU) ->] t1 (n,14,14,256) -> conv2 3x3 pad 1 (+ b2, ReLU, rounded to the storage type) -> conv3 1x1
  * to 1024 channels (+ b3 + residual (n,14,14,1024), ReLU) -> y (n,14,14,1024) [-> the NEXT block's conv1 1x1 (+ b1n, ReLU) -> t1n (n,14,14,256)].
@@ -305,6 +323,17 @@ int64_t pvr_debug_pp_persistent_launches(void);
 /* global average pool of NHWC (16-bit or fp32) -> fp32 rows at out + i*out_stride */
 pvr_status pvr_op_avgpool(const void *in_dev, float *out_dev, int64_t out_stride, int32_t n, int32_t hw,
                           int32_t c, int32_t in_f32, int32_t dtype, void *hip_stream);
+/* The layout and format kernels one at a time (test entry points; the encoder reaches the same launchers).
+ * AvgPool2d(2) on NHWC 16-bit (CLIP ModifiedResNet): (n,h,w,c) -> (n,h/2,w/2,c); h, w even, c % 8 == 0 */
+pvr_status pvr_op_avgpool2(const void *in_dev, void *out_dev, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype, void *hip_stream);
+/* AttentionPool2d token assembly (CLIP ModifiedResNet): x fp32 (n,hw,c), pos fp32 (hw+1,c) -> tokens 16-bit (n,hw+1,c): token 0 = mean_p x[p] + pos[0],
+ * token 1+p = x[p] + pos[1+p] */
+pvr_status pvr_op_attnpool_tokens(const float *x_dev, const float *pos_dev, void *tokens_dev, int32_t n, int32_t hw, int32_t c, int32_t dtype, void *hip_stream);
+/* the compression heads' C-major flatten: fp32 NHWC (n,hw,cpad) -> out[b*out_stride + ch*hw + i], ch < creal <= cpad */
+pvr_status pvr_op_nhwc_to_chw(const float *in_dev, float *out_dev, int64_t out_stride, int32_t n, int32_t hw, int32_t cpad, int32_t creal, void *hip_stream);
+/* fp32 -> 16-bit (round to nearest even; count % 8 == 0) and 16-bit -> fp32 (exact) copies */
+pvr_status pvr_op_f32_to_h(const float *in_dev, void *out_dev, int64_t count, int32_t dtype, void *hip_stream);
+pvr_status pvr_op_h_to_f32(const void *in_dev, float *out_dev, int64_t count, int32_t dtype, void *hip_stream);
 /* Finite check of fp32 results on the device: rows x cols values with row stride `stride` (elements); sets *flag_dev (a device int32 the caller
  * zeroed) to 1 if any value is inf or NaN.  Enqueued on `stream`, no synchronisation.  The streaming embedder checks every batch this way and
  * reads the flag once per call (the reference has no such check: its fp32 path cannot overflow a 16-bit storage type). */

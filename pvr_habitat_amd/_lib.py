@@ -50,6 +50,15 @@ _SIGS = {
                                            C.POINTER(C.c_float)]),
     'pvr_op_preprocess': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     'pvr_op_stem': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    'pvr_op_stem_pool': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p]),
+    'pvr_op_stem_pool_u8': (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p]),
+    'pvr_debug_stem_c1_pack': (C.c_int, [C.c_void_p, C.c_void_p]),
+    'pvr_op_conv2d_splitk': (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 13 + [C.c_void_p]),
+    'pvr_op_avgpool2': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p]),
+    'pvr_op_attnpool_tokens': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
+    'pvr_op_nhwc_to_chw': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p]),
+    'pvr_op_f32_to_h': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    'pvr_op_h_to_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     'pvr_op_maxpool': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'pvr_op_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 12 + [C.c_void_p]),
     'pvr_op_avgpool': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),

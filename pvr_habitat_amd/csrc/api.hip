@@ -57,8 +57,8 @@ pvr_status launch_conv_split16(const float *in, const void *wsp, const float *bi
 static void *g_zero = nullptr;
 static pvr_status zero_page(void **out) {
     if (!g_zero) {
-        PVR_HIP_TRY(hipMalloc(&g_zero, 256));
-        PVR_HIP_TRY(hipMemset(g_zero, 0, 256));
+        PVR_HIP_TRY(hipMalloc(&g_zero, PVR_ZERO_BYTES));       // (the split-K launch reads an all-zero bias of cout floats from it)
+        PVR_HIP_TRY(hipMemset(g_zero, 0, PVR_ZERO_BYTES));
         PVR_HIP_TRY(hipDeviceSynchronize());
     }
     *out = g_zero;
@@ -214,6 +214,69 @@ pvr_status pvr_op_avgpool(const void *in, float *out, int64_t out_stride, int32_
                           int32_t dtype, void *stream) {
     PVR_REQUIRE(in && out, "pvr_op_avgpool: null pointer");
     return launch_avgpool(in, out, out_stride, n, hw, c, in_f32, dtype, (hipStream_t)stream);
+}
+
+// The fused forms of the stem one at a time (tests/test_gpu_resnet_kernels.py): the form is chosen on a copy of op_switches()
+static pvr_status stem_form_switches(int form, PlanSwitches &sw) {
+    PVR_REQUIRE(form >= 0 && form <= 2, "pvr_op_stem_pool: form must be 0 (stem_pool_kernel), 1 (LDS tile) or 2 (register pooling), got %d", form);
+    sw = op_switches();
+    sw.stem_lds = form >= 1;
+    sw.stem_regpool = form == 2;
+    return PVR_OK;
+}
+pvr_status pvr_op_stem_pool(const void *img_padded, const void *wgt, const float *bias, void *out, int32_t n, int32_t form, const void *c1_w, const float *c1_b,
+                            void *c1_t1, int32_t dtype, void *stream) {
+    PVR_REQUIRE(img_padded && wgt && bias && out && n > 0, "pvr_op_stem_pool: null pointer or empty batch");
+    PVR_REQUIRE(dtype == PVR_BF16 || dtype == PVR_F16, "pvr_op_stem_pool: 16-bit storage types only");
+    PlanSwitches sw;
+    if (pvr_status s = stem_form_switches(form, sw)) return s;
+    return launch_stem_pool(sw, img_padded, wgt, bias, out, n, 224, dtype, (hipStream_t)stream, c1_w, c1_b, c1_t1, 0);
+}
+pvr_status pvr_op_stem_pool_u8(const uint8_t *frames, int32_t n, int32_t h, int32_t w, int32_t top, int32_t left, const void *wgt, const float *bias, void *out,
+                               int32_t form, const void *c1_w, const float *c1_b, void *c1_t1, int32_t dtype, void *stream) {
+    PVR_REQUIRE(frames && wgt && bias && out && n > 0, "pvr_op_stem_pool_u8: null pointer or empty batch");
+    PVR_REQUIRE(dtype == PVR_BF16 || dtype == PVR_F16, "pvr_op_stem_pool_u8: 16-bit storage types only");
+    PlanSwitches sw;
+    if (pvr_status s = stem_form_switches(form, sw)) return s;
+    PVR_REQUIRE(form != 0, "pvr_op_stem_pool_u8: stem_pool_kernel (form 0) has no uint8 form");
+    return launch_stem_pool_u8(sw, frames, n, h, w, top, left, wgt, bias, out, dtype, (hipStream_t)stream, c1_w, c1_b, c1_t1, 0);
+}
+pvr_status pvr_debug_stem_c1_pack(const uint16_t *w, uint16_t *image) {
+    PVR_REQUIRE(w && image, "pvr_debug_stem_c1_pack: null pointer");
+    stem_c1_pack(w, image);
+    return PVR_OK;
+}
+
+pvr_status pvr_op_conv2d_splitk(const void *in, const void *wgt, const float *bias, const void *residual, void *out, float *scratch, int32_t ksplit, int32_t n,
+                                int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t relu,
+                                int32_t out_f32, int32_t dtype, void *stream) {
+    PVR_REQUIRE(in && wgt && bias && out && n > 0 && h > 0 && w > 0, "pvr_op_conv2d_splitk: null pointer or empty input");
+    PVR_REQUIRE(dtype == PVR_BF16 || dtype == PVR_F16, "pvr_op_conv2d_splitk: 16-bit storage types only");
+    void *z;
+    if (pvr_status s = zero_page(&z)) return s;
+    return launch_conv_splitk(in, wgt, bias, residual, out, z, scratch, ksplit, n, h, w, cin, cout, kh, kw, stride, pad, relu, out_f32, dtype, (hipStream_t)stream);
+}
+
+// the layout and format kernels one at a time
+pvr_status pvr_op_avgpool2(const void *in, void *out, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype, void *stream) {
+    PVR_REQUIRE(in && out && n > 0 && (dtype == PVR_BF16 || dtype == PVR_F16), "pvr_op_avgpool2: null pointer, empty batch or not a 16-bit type");
+    return launch_avgpool2(in, out, n, h, w, c, dtype, (hipStream_t)stream);
+}
+pvr_status pvr_op_attnpool_tokens(const float *x, const float *pos, void *tokens, int32_t n, int32_t hw, int32_t c, int32_t dtype, void *stream) {
+    PVR_REQUIRE(x && pos && tokens && n > 0 && hw > 0 && c > 0 && (dtype == PVR_BF16 || dtype == PVR_F16), "pvr_op_attnpool_tokens: null pointer, empty input or not a 16-bit type");
+    return launch_attnpool_tokens(x, pos, tokens, n, hw, c, dtype, (hipStream_t)stream);
+}
+pvr_status pvr_op_nhwc_to_chw(const float *in, float *out, int64_t out_stride, int32_t n, int32_t hw, int32_t cpad, int32_t creal, void *stream) {
+    PVR_REQUIRE(in && out && n > 0 && hw > 0 && creal > 0 && creal <= cpad && out_stride >= (int64_t)hw * creal, "pvr_op_nhwc_to_chw: bad argument");
+    return launch_nhwc_to_chw(in, out, out_stride, n, hw, cpad, creal, (hipStream_t)stream);
+}
+pvr_status pvr_op_f32_to_h(const float *in, void *out, int64_t count, int32_t dtype, void *stream) {
+    PVR_REQUIRE(in && out && count > 0 && (dtype == PVR_BF16 || dtype == PVR_F16), "pvr_op_f32_to_h: null pointer, empty input or not a 16-bit type");
+    return launch_f32_to_h(in, out, (size_t)count, dtype, (hipStream_t)stream);
+}
+pvr_status pvr_op_h_to_f32(const void *in, float *out, int64_t count, int32_t dtype, void *stream) {
+    PVR_REQUIRE(in && out && count > 0 && (dtype == PVR_BF16 || dtype == PVR_F16), "pvr_op_h_to_f32: null pointer, empty input or not a 16-bit type");
+    return launch_h_to_f32(in, out, (size_t)count, dtype, (hipStream_t)stream);
 }
 
 // Finite check of an embedding block ON THE DEVICE: rows x cols fp32 with row stride `stride`; *flag (a device int32 the caller zeroed) is

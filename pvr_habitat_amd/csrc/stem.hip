@@ -881,11 +881,11 @@ pvr_status launch_stem_pool(const PlanSwitches &sw, const void *img, const void 
     }
     if (use_lds) {
         const size_t lds = 5 * 112 * 128 + 2 * 32768;
-        static bool attr2_done = false;
-        if (!attr2_done) {
+        static DeviceOnce attr2_done;         // per device: a second GPU of the process needs the attribute too
+        if (attr2_done.needed()) {
             PVR_HIP_TRY(hipFuncSetAttribute((const void *)stem_pool_lds_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             PVR_HIP_TRY(hipFuncSetAttribute((const void *)stem_pool_lds_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr2_done = true;
+            attr2_done.mark();
         }
         if (dtype == PVR_F16)
             hipLaunchKernelGGL(stem_pool_lds_kernel<true>, grid, dim3(512), lds, stream, (const u16 *)img, (const u16 *)wgt, bias, (u16 *)out, n, ipb);
