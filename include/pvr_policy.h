@@ -138,6 +138,30 @@ pvr_status pvr_policy_apply(pvr_policy *pol, float *params, float *square_avg, c
 pvr_status pvr_policy_backward_dlogits(pvr_policy *pol, const float *params, const void *obs, const float *dlogits, int32_t T,
                                        int32_t B, float *grads, void *hip_stream);
 
+/* End-to-end BC (the observations are the output of a trainable encoder, pvr_train.h): the two backward entry points above with one more output.
+ * dobs (device, (T,B,obs_size) contiguous fp32, 16-byte aligned, caller-owned) is fully overwritten with d(loss)/d(obs) - of the mean NLL for
+ * pvr_policy_backward_dobs, of whatever dlogits encodes for pvr_policy_backward_dlogits_dobs:
+ *     without BatchNorm   dobs = dz1 W_fc1
+ *     with BatchNorm1d    dobs = gamma invstd (da0 - sum(da0) / N - xhat sum(da0 xhat) / N),  da0 = dz1 W_fc1, N = T B  (torch's training-mode rule)
+ * dobs == NULL is the entry point above: the same launches.  Asking for dobs does not change a bit of `grads`: its launches follow the ones that
+ * finish the parameter gradient.  PVR_ERR_INVALID (message names the cause) for conv_frames > 0 (uint8 observations have no gradient), a host
+ * handle, and an installed data-parallel collective (encoder training is single-GPU). */
+pvr_status pvr_policy_backward_dobs(pvr_policy *pol, const float *params, const pvr_policy_bn *bn, const void *obs, const uint8_t *done,
+                                    const int64_t *actions, int32_t T, int32_t B, float *grads, float *stats_out, float *logits_out,
+                                    float *dobs, void *hip_stream);
+pvr_status pvr_policy_backward_dlogits_dobs(pvr_policy *pol, const float *params, const void *obs, const float *dlogits, int32_t T,
+                                            int32_t B, float *grads, float *dobs, void *hip_stream);
+
+/* clip_grad_norm_ + RMSprop(momentum 0) over SEVERAL flat buffers with ONE norm (end-to-end BC: the policy's trainable prefix and the encoder's
+ * parameters; the reference clips over all parameters together).  Semantics of pvr_policy_apply: coef = min(1, max_norm / (norm + 1e-6)),
+ * v = alpha v + (1 - alpha) g^2, p -= lr g / (sqrt(v) + eps) with g the clipped gradient.  n_groups <= 8, counts[i] % 4 == 0, every buffer
+ * 16-byte aligned; the arrays of pointers and counts are host memory, the buffers device memory.  The norm is summed in a fixed order (256
+ * partials per group, then in group order; no float atomics): two runs give the same bits.  stats_out (device, 1 float, may be NULL) = the
+ * pre-clip norm over all groups.  No handle; calls on one stream are ordered. */
+pvr_status pvr_joint_apply_rmsprop(int32_t n_groups, float *const *params, float *const *square_avg, const float *const *grads,
+                                   const int64_t *counts, float lr, float alpha, float eps, float max_grad_norm, float *stats_out,
+                                   void *hip_stream);
+
 /* Other update rules on the same flat buffers (grad norm + clip as in pvr_policy_apply; stats_out[1] = pre-clip norm):
  * torch.optim.RMSprop with momentum != 0 (src/arguments.py:63 exposes --momentum; the reference default 0 is pvr_policy_apply) and
  * torch.optim.Adam(betas, eps; amsgrad off, no weight decay) - an extension, BASELINE.json's north_star names Adam.  step = 1, 2, ...
@@ -160,6 +184,12 @@ pvr_status pvr_bc_gather(const void *obs_dev, const int64_t *action_dev, const u
 
 /* parity/debug: copy the flat gradient of the last pvr_policy_step (pre-clip) to grads_out (device, trainable_count) */
 pvr_status pvr_policy_last_grads(pvr_policy *pol, float *grads_out, void *hip_stream);
+
+/* parity/debug: d(loss)/d(policy_logits) of the last backward of T x B rows, (T,B,A) contiguous, as the backward read it - the loss kernel's
+ * (softmax - onehot) / (T B) after pvr_policy_backward / _backward_dobs / _step, the caller's own after pvr_policy_backward_dlogits[_dobs].  Handing
+ * it to pvr_policy_backward_dlogits_dobs after a forward of the same inputs reproduces that backward bit for bit (tests/test_gpu_e2e_bc.py: torch's
+ * log_softmax rounds differently from the loss kernel, so the two forms of an iteration agree in every bit only on the same upstream gradient). */
+pvr_status pvr_policy_last_dlogits(pvr_policy *pol, float *dlogits_out, int32_t T, int32_t B, void *hip_stream);
 
 /* fp32-in / fp32-out GEMM as the policy runs it: C[M,N] = op(A) op(B)^T-style contraction over K.
  * a_km != 0: A stored [K][M] else [M][K];  b_kn != 0: B stored [K][N] else [N][K].  Optional bias[N], relu.

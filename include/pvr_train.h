@@ -24,11 +24,16 @@ extern "C" {
 typedef struct pvr_trainer pvr_trainer;
 
 /* desc as for pvr_encoder_create; arch RESNET50 / RESNET18 / RESNET34 with dtype PVR_F32, anything else is PVR_ERR_INVALID with a
- * message that names what is trainable.  Host arithmetic only: the workspace (one saved pre-BN and one post-BN tensor per
+ * message that names what is trainable; so is a max_batch at which one tensor of the workspace would pass 2 GiB (the launches address an operand
+ * with 32-bit byte offsets: 668 frames for resnet18 / 34, 334 for resnet50; the message names the number).  Host arithmetic only: the workspace (one saved pre-BN and one post-BN tensor per
  * convolution, their gradients, the scratch of the split reductions - sized for max_batch frames) is made by the first forward. */
 pvr_status pvr_trainer_create(const pvr_encoder_desc *desc, pvr_trainer **out);
 void pvr_trainer_destroy(pvr_trainer *tr);
 int32_t pvr_trainer_out_size(const pvr_trainer *tr);
+
+/* bytes of the device workspace the first forward will allocate for this handle's max_batch (host arithmetic only): what a caller compares
+ * with the free device memory before it trains */
+int64_t pvr_trainer_workspace_bytes(const pvr_trainer *tr);
 
 /* the flat parameter buffer: its length in floats; name of tensor `index` in buffer order (returns the length, 0 past the end);
  * offset of a tensor by its state_dict name ("layer2.0.downsample.0.weight"), -1 if there is none - *numel and shape[0..3]

@@ -93,6 +93,7 @@ _SIGS = {
     'pvr_trainer_destroy': (None, [C.c_void_p]),
     'pvr_trainer_out_size': (C.c_int32, [C.c_void_p]),
     'pvr_trainer_param_count': (C.c_int64, [C.c_void_p]),
+    'pvr_trainer_workspace_bytes': (C.c_int64, [C.c_void_p]),
     'pvr_trainer_param_name': (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32]),
     'pvr_trainer_param_offset': (C.c_int64, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     'pvr_trainer_buffer_count': (C.c_int64, [C.c_void_p]),

@@ -21,7 +21,10 @@ def make_parser():
     parser.add_argument('--embedding_name', type=str, default='resnet50')
     parser.add_argument('--train_embedding', action='store_true',
                         help='EmbeddingNet(train=True): a trainable fp32 encoder on one GPU - resnet18 / resnet34 / resnet50 and the conv5 checkpoints; '
-                             'every other name, and save_embedded_obs (embedding rows need the frozen encoder), refuse it')
+                             'every other name, and save_embedded_obs (embedding rows need the frozen encoder), refuse it.  main_bc_finetune: '
+                             'end-to-end BC - the encoder named by --embedding_name in front of PolicyNet on the raw frames, one clip and RMSprop '
+                             'update over both (fused, or the reference lines with --autograd_step); the training workspace grows with '
+                             'unroll_length x batch_size x frames and is checked against the free device memory before the first step')
     parser.add_argument('--disable_pretrained_embedding', action='store_false', dest='pretrained_embedding')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop

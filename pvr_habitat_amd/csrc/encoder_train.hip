@@ -238,6 +238,19 @@ pvr_status pvr_trainer_create(const pvr_encoder_desc *desc, pvr_trainer **out) {
         set_error("pvr_trainer_create: the plan of arch %d holds an operation the trainer has no backward for", desc->arch);
         return PVR_ERR_INVALID;
     }
+    // the convolution launches address an operand with 32-bit byte offsets (conv_f32: "operand larger than 2 GiB"), and no kernel of the trainer has run
+    // on a larger tensor: refuse, here and by name, a max_batch at which a tensor of the workspace (an activation, its gradient, the zero-filled grid
+    // of a stride-2 data gradient) would pass 2 GiB, instead of failing inside the first forward or backward
+    int64_t per_frame = std::max((int64_t)S_IMG * S_IMG * 4, (int64_t)st.ho * st.wo * st.cout);
+    for (const TrainOp &o : t->ops)
+        per_frame = std::max(per_frame, std::max((int64_t)o.h * o.w * std::max(o.cin, o.stride == 2 ? o.cout : 0), (int64_t)o.ho * o.wo * o.cout));
+    const int64_t frames_max = (0x7ffffff0ll - 1) / (per_frame * 4);
+    if (d.max_batch > frames_max) {
+        delete t;
+        set_error("pvr_trainer_create: max_batch %d: the largest tensor of this trunk's training workspace takes %.1f MB per frame and a launch addresses at "
+                  "most 2 GiB of one: the largest max_batch is %lld frames", d.max_batch, per_frame * 4 / 1048576.0, (long long)frames_max);
+        return PVR_ERR_INVALID;
+    }
     if (t->n_buf_slots & 1) ++t->n_buf_slots;     // (never: every BatchNorm adds 2 c slots) the int64 counters are 8-byte aligned
     st.nbt_off = add_slot(t->buffers, t->n_buf_slots, st.bn + ".num_batches_tracked", {1}, 2);
     for (TrainOp &o : t->ops) o.nbt_off = add_slot(t->buffers, t->n_buf_slots, o.bn + ".num_batches_tracked", {1}, 2);
@@ -258,6 +271,15 @@ void pvr_trainer_destroy(pvr_trainer *t) {
 int32_t pvr_trainer_out_size(const pvr_trainer *t) { return t ? t->out_size : 0; }
 int64_t pvr_trainer_param_count(const pvr_trainer *t) { return t ? t->n_params : 0; }
 int64_t pvr_trainer_buffer_count(const pvr_trainer *t) { return t ? t->n_buf_slots : 0; }
+
+int64_t pvr_trainer_workspace_bytes(const pvr_trainer *t) {
+    if (!t) return 0;
+    pvr_trainer sizing = *t;                      // (carve also notes the scratch sizes on its handle: size a copy, never its device pointers)
+    sizing.arena = nullptr;
+    Carver c;
+    carve(&sizing, c);
+    return (int64_t)c.used;
+}
 
 int32_t pvr_trainer_param_name(const pvr_trainer *t, int32_t index, char *buf, int32_t cap) {
     if (!t || index < 0 || index >= (int32_t)t->params.size() || !buf || cap <= 0) return 0;

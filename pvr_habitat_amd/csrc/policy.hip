@@ -521,7 +521,9 @@ pvr_status forward_core(pvr_policy *pol, const float *P, const pvr_policy_bn *bn
 }  // namespace
 
 // backward of everything after the forward in the workspace; leaves the unclipped gradient in Gd
-static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs_in, int T, int B, float *Gd, hipStream_t st) {
+// dobs (optional, vector policy only): d(loss)/d(obs) [N][O], written after the parameter gradient is final - the launches in front of it are
+// the ones a call without it enqueues, so asking for it does not move a bit of Gd
+static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs_in, int T, int B, float *Gd, hipStream_t st, float *dobs = nullptr) {
     const auto &d = pol->d;
     const int N = T * B, H = d.hidden, O = d.obs_size, A = d.num_actions;
     const float *obs = d.conv_frames > 0 ? pol->feat : (const float *)obs_in;
@@ -828,6 +830,23 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
             PVR_LAUNCH_CHECK();
         }
     }
+    if (dobs) {
+        // ---- d(loss)/d(obs) of the vector policy (the encoder's upstream gradient in end-to-end BC) ----------------------
+        if (!d.batch_norm) {
+            TRY(gemm(dz1, P + pol->o_fc1w, nullptr, nullptr, dobs, N, O, H, false, true, 0, st));           // dobs = dz1 W1
+        } else if (bn_fold) {
+            // the fold path never formed da0 = dz1 W1: form it in the caller's buffer, then apply torch's training-mode BatchNorm input
+            // gradient in place, with xhat as bn_xhat_kernel left it (pol->da0) and dgamma / dbeta from the finished gradient
+            TRY(gemm(dz1, P + pol->o_fc1w, nullptr, nullptr, dobs, N, O, H, false, true, 0, st));
+            hipLaunchKernelGGL(bn_dx_xhat_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, dobs, pol->da0, pol->bn_invstd, P + pol->o_bnw,
+                               Gd + pol->o_bnw, Gd + pol->o_bnb, (size_t)N * O / 4, O, N);
+            PVR_LAUNCH_CHECK();
+        } else {
+            hipLaunchKernelGGL(bn_dx_kernel, dim3(blocks_for((size_t)N * O)), dim3(256), 0, st, obs, pol->da0, pol->bn_mean, pol->bn_invstd, P + pol->o_bnw,
+                               Gd + pol->o_bnw, Gd + pol->o_bnb, dobs, N, O, N);
+            PVR_LAUNCH_CHECK();
+        }
+    }
     if (dp_active(pol)) {
         TRY(dp_bucket(pol, Gd, 0, b_fc, 3, st));                 // conv stack + BatchNorm affine (everything in front of fc.1)
         // the loss of the global batch: mean of the per-rank means (equal rows per rank)
@@ -862,11 +881,11 @@ static pvr_status set_lr(pvr_policy *pol, float lr, hipStream_t st) {
 
 // forward (training mode, zero initial state: main_bc_2.py:207-209) + loss + backward into `grads`
 static pvr_status loss_backward(pvr_policy *pol, const float *params, const pvr_policy_bn *bn, const void *obs, const uint8_t *done,
-                                const long long *actions, int T, int B, float *grads, hipStream_t st) {
+                                const long long *actions, int T, int B, float *grads, hipStream_t st, float *dobs = nullptr) {
     const int N = T * B;
     TRY(forward_core(pol, params, bn, obs, done, pol->zeros, pol->zeros, T, B, 1, actions, st));
     hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, st, pol->loss_row, N, 1.0f / (float)N, pol->stats);
-    return backward_core(pol, params, obs, T, B, grads, st);
+    return backward_core(pol, params, obs, T, B, grads, st, dobs);
 }
 
 static void drop_graph(pvr_policy *pol) {
@@ -1129,21 +1148,45 @@ pvr_status pvr_policy_forward(pvr_policy *pol, const float *params, const pvr_po
     return PVR_OK;
 }
 
-pvr_status pvr_policy_backward(pvr_policy *pol, const float *params, const pvr_policy_bn *bn, const void *obs, const uint8_t *done,
-                               const int64_t *actions, int32_t T, int32_t B, float *grads, float *stats_out, float *logits_out,
-                               void *hip_stream) {
-    PVR_REQUIRE(pol && params && obs && done && actions && grads, "pvr_policy_backward: null argument");
-    PVR_REQUIRE(!pol->hostp, "pvr_policy_backward: not part of the host (CPU) plan - it carries pvr_policy_forward and pvr_policy_step");
-    TraceScope trace("pvr_policy_backward");
+// the reasons a call cannot return d(loss)/d(obs); fn names the entry point
+static pvr_status dobs_check(const pvr_policy *pol, const float *dobs, const char *fn) {
+    if (!dobs) return PVR_OK;
+    PVR_REQUIRE(pol->d.conv_frames == 0, "%s: dobs with conv_frames = %d: the observations of PolicyNetWithConv are uint8 frames, they have no gradient", fn,
+                pol->d.conv_frames);
+    PVR_REQUIRE(!dp_active(pol), "%s: dobs with a data-parallel collective installed (world size %d): encoder training is single-GPU, and the gradient "
+                "buckets are still in flight where d(loss)/d(obs) is formed", fn, pol->dp_world);
+    PVR_REQUIRE(((uintptr_t)dobs & 15) == 0, "%s: dobs must be 16-byte aligned", fn);
+    return PVR_OK;
+}
+
+static pvr_status policy_backward_impl(pvr_policy *pol, const float *params, const pvr_policy_bn *bn, const void *obs, const uint8_t *done,
+                                       const int64_t *actions, int32_t T, int32_t B, float *grads, float *stats_out, float *logits_out, float *dobs,
+                                       void *hip_stream, const char *fn) {
+    PVR_REQUIRE(pol && params && obs && done && actions && grads, "%s: null argument", fn);
+    PVR_REQUIRE(!pol->hostp, "%s: not part of the host (CPU) plan - it carries pvr_policy_forward and pvr_policy_step", fn);
+    TRY(dobs_check(pol, dobs, fn));
+    TraceScope trace(fn);
     ScratchScope scratch_scope(pol);
     TRY(pvr_policy_status(pol));                                 // (sticky: a time-out of an earlier launch surfaces here)
     PVR_REQUIRE(T > 0 && T <= pol->d.max_t && B > 0 && B <= pol->d.max_b, "T=%d B=%d outside the workspace (%d,%d)", T, B, pol->d.max_t, pol->d.max_b);
     hipStream_t st = (hipStream_t)hip_stream;
     const int N = T * B, A = pol->d.num_actions;
-    TRY(loss_backward(pol, params, bn, obs, done, (const long long *)actions, T, B, grads, st));
+    TRY(loss_backward(pol, params, bn, obs, done, (const long long *)actions, T, B, grads, st, dobs));
     if (logits_out) PVR_HIP_TRY(hipMemcpyAsync(logits_out, pol->logits, (size_t)N * A * 4, hipMemcpyDeviceToDevice, st));
     if (stats_out) PVR_HIP_TRY(hipMemcpyAsync(stats_out, pol->stats, sizeof(float), hipMemcpyDeviceToDevice, st));
     return PVR_OK;
+}
+
+pvr_status pvr_policy_backward(pvr_policy *pol, const float *params, const pvr_policy_bn *bn, const void *obs, const uint8_t *done,
+                               const int64_t *actions, int32_t T, int32_t B, float *grads, float *stats_out, float *logits_out,
+                               void *hip_stream) {
+    return policy_backward_impl(pol, params, bn, obs, done, actions, T, B, grads, stats_out, logits_out, nullptr, hip_stream, "pvr_policy_backward");
+}
+
+pvr_status pvr_policy_backward_dobs(pvr_policy *pol, const float *params, const pvr_policy_bn *bn, const void *obs, const uint8_t *done,
+                                    const int64_t *actions, int32_t T, int32_t B, float *grads, float *stats_out, float *logits_out,
+                                    float *dobs, void *hip_stream) {
+    return policy_backward_impl(pol, params, bn, obs, done, actions, T, B, grads, stats_out, logits_out, dobs, hip_stream, "pvr_policy_backward_dobs");
 }
 
 pvr_status pvr_policy_apply(pvr_policy *pol, float *params, float *square_avg, const float *grads, float lr, float alpha, float eps,
@@ -1159,15 +1202,15 @@ pvr_status pvr_policy_apply(pvr_policy *pol, float *params, float *square_avg, c
     return PVR_OK;
 }
 
-pvr_status pvr_policy_backward_dlogits(pvr_policy *pol, const float *params, const void *obs, const float *dlogits, int32_t T, int32_t B,
-                                       float *grads, void *hip_stream) {
-    PVR_REQUIRE(pol && params && obs && dlogits && grads, "pvr_policy_backward_dlogits: null argument");
-    PVR_REQUIRE(!pol->hostp, "pvr_policy_backward_dlogits: not part of the host (CPU) plan - it carries pvr_policy_forward and pvr_policy_step");
+static pvr_status policy_backward_dlogits_impl(pvr_policy *pol, const float *params, const void *obs, const float *dlogits, int32_t T, int32_t B,
+                                               float *grads, float *dobs, void *hip_stream, const char *fn) {
+    PVR_REQUIRE(pol && params && obs && dlogits && grads, "%s: null argument", fn);
+    PVR_REQUIRE(!pol->hostp, "%s: not part of the host (CPU) plan - it carries pvr_policy_forward and pvr_policy_step", fn);
+    TRY(dobs_check(pol, dobs, fn));
     ScratchScope scratch_scope(pol);
     TRY(pvr_policy_status(pol));
     if (pol->fwd_T != T || pol->fwd_B != B) {
-        set_error("pvr_policy_backward_dlogits: needs the activations of a training-mode pvr_policy_forward with T=%d, B=%d (last: %d, %d)", T, B,
-                  pol->fwd_T, pol->fwd_B);
+        set_error("%s: needs the activations of a training-mode pvr_policy_forward with T=%d, B=%d (last: %d, %d)", fn, T, B, pol->fwd_T, pol->fwd_B);
         return PVR_ERR_STATE;
     }
     hipStream_t st = (hipStream_t)hip_stream;
@@ -1175,7 +1218,17 @@ pvr_status pvr_policy_backward_dlogits(pvr_policy *pol, const float *params, con
     hipLaunchKernelGGL(dlogits_pad_kernel, dim3((N * 16 + 255) / 256), dim3(256), 0, st, dlogits, pol->dlogits, N, pol->d.num_actions);
     PVR_LAUNCH_CHECK();
     pol->fwd_T = pol->fwd_B = 0;                                  // (backward reuses activation buffers as scratch: one backward per forward)
-    return backward_core(pol, params, obs, T, B, grads, st);
+    return backward_core(pol, params, obs, T, B, grads, st, dobs);
+}
+
+pvr_status pvr_policy_backward_dlogits(pvr_policy *pol, const float *params, const void *obs, const float *dlogits, int32_t T, int32_t B,
+                                       float *grads, void *hip_stream) {
+    return policy_backward_dlogits_impl(pol, params, obs, dlogits, T, B, grads, nullptr, hip_stream, "pvr_policy_backward_dlogits");
+}
+
+pvr_status pvr_policy_backward_dlogits_dobs(pvr_policy *pol, const float *params, const void *obs, const float *dlogits, int32_t T, int32_t B,
+                                            float *grads, float *dobs, void *hip_stream) {
+    return policy_backward_dlogits_impl(pol, params, obs, dlogits, T, B, grads, dobs, hip_stream, "pvr_policy_backward_dlogits_dobs");
 }
 
 pvr_status pvr_policy_apply_momentum(pvr_policy *pol, float *params, float *square_avg, float *momentum_buf, const float *grads, float lr,
@@ -1269,11 +1322,63 @@ pvr_status pvr_policy_step(pvr_policy *pol, float *params, float *square_avg, co
     return PVR_OK;
 }
 
+pvr_status pvr_joint_apply_rmsprop(int32_t n_groups, float *const *params, float *const *square_avg, const float *const *grads, const int64_t *counts,
+                                   float lr, float alpha, float eps, float max_grad_norm, float *stats_out, void *hip_stream) {
+    constexpr int MAX_GROUPS = 8, PART = 256;                     // partial sums per group
+    PVR_REQUIRE(n_groups >= 1 && n_groups <= MAX_GROUPS && params && square_avg && grads && counts, "pvr_joint_apply_rmsprop: null argument or n_groups = %d "
+                "outside 1..%d", n_groups, MAX_GROUPS);
+    for (int i = 0; i < n_groups; ++i) {
+        PVR_REQUIRE(params[i] && square_avg[i] && grads[i] && counts[i] > 0 && counts[i] % 4 == 0, "pvr_joint_apply_rmsprop: group %d: null buffer, or a count "
+                    "(%lld) that is no positive multiple of 4", i, (long long)counts[i]);
+        PVR_REQUIRE((((uintptr_t)params[i] | (uintptr_t)square_avg[i] | (uintptr_t)grads[i]) & 15) == 0, "pvr_joint_apply_rmsprop: group %d: buffers must be "
+                    "16-byte aligned (the kernels read float4s)", i);
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    // [MAX_GROUPS * PART] partial sums, then the stats block of norm_final_kernel / rmsprop_kernel (0 unused, 1 norm, 2 clip coefficient, 3 lr); one per
+    // (device, stream), made once and kept: the launches of successive calls on one stream are ordered, as those on a policy handle's own block are
+    static std::mutex mu;
+    static std::map<std::pair<int, void *>, float *> blocks;
+    int dev = 0;
+    PVR_HIP_TRY(hipGetDevice(&dev));
+    float *blk = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        const std::pair<int, void *> key(dev, hip_stream);
+        auto it = blocks.find(key);
+        if (it == blocks.end()) {
+            TRY(dalloc(&blk, (size_t)MAX_GROUPS * PART + 4));
+            blocks[key] = blk;
+        } else blk = it->second;
+    }
+    float *stats = blk + MAX_GROUPS * PART;
+    hipLaunchKernelGGL(set_scalar_kernel, dim3(1), dim3(1), 0, st, stats + 3, lr);
+    // per-group partials first (each group cut the same way whatever the other groups are), then one fixed-order sum over them in group order
+    for (int i = 0; i < n_groups; ++i)
+        hipLaunchKernelGGL(sumsq_partial_kernel, dim3(PART), dim3(256), 0, st, grads[i], (size_t)counts[i], blk + (size_t)i * PART);
+    hipLaunchKernelGGL(norm_final_kernel, dim3(1), dim3(256), 0, st, blk, n_groups * PART, max_grad_norm, stats);
+    for (int i = 0; i < n_groups; ++i)
+        hipLaunchKernelGGL(rmsprop_kernel, dim3(blocks_for((size_t)counts[i] / 4, 8192)), dim3(256), 0, st, params[i], square_avg[i], grads[i], stats,
+                           (size_t)counts[i] / 4, alpha, eps);
+    PVR_LAUNCH_CHECK();
+    if (stats_out) PVR_HIP_TRY(hipMemcpyAsync(stats_out, stats + 1, sizeof(float), hipMemcpyDeviceToDevice, st));
+    return PVR_OK;
+}
+
 pvr_status pvr_policy_last_grads(pvr_policy *pol, float *grads_out, void *hip_stream) {
     PVR_REQUIRE(pol && grads_out, "pvr_policy_last_grads: null argument");
     if (pol->hostp) return pvr::host_policy_last_grads(pol->hostp, grads_out);
     if (!pol->have_grads) { set_error("no training step has run"); return PVR_ERR_STATE; }
     PVR_HIP_TRY(hipMemcpyAsync(grads_out, pol->grads, (size_t)pol->n_train * 4, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
+    return PVR_OK;
+}
+
+pvr_status pvr_policy_last_dlogits(pvr_policy *pol, float *dlogits_out, int32_t T, int32_t B, void *hip_stream) {
+    PVR_REQUIRE(pol && dlogits_out, "pvr_policy_last_dlogits: null argument");
+    PVR_REQUIRE(!pol->hostp, "pvr_policy_last_dlogits: not part of the host (CPU) plan");
+    PVR_REQUIRE(T > 0 && T <= pol->d.max_t && B > 0 && B <= pol->d.max_b, "T=%d B=%d outside the workspace (%d,%d)", T, B, pol->d.max_t, pol->d.max_b);
+    if (!pol->have_grads) { set_error("no backward has run"); return PVR_ERR_STATE; }
+    const size_t A = (size_t)pol->d.num_actions;
+    PVR_HIP_TRY(hipMemcpy2DAsync(dlogits_out, A * 4, pol->dlogits, 16 * 4, A * 4, (size_t)T * B, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
     return PVR_OK;
 }
 

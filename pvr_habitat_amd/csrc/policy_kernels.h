@@ -518,6 +518,22 @@ static __global__ __launch_bounds__(256) void bn_fold_grads_kernel(float *__rest
     }
 }
 
+// d(loss)/d(obs) behind the fold path (end-to-end BC: the observations are a trainable encoder's output).  In place on dx, which holds
+// da0 = dz1 W1 on entry: dx = gamma * invstd * (da0 - dbeta / n - xhat * dgamma / n), torch's training-mode BatchNorm input gradient, with xhat as
+// bn_xhat_kernel wrote it and dgamma / dbeta the finished affine gradients (dgamma = sum_r da0 xhat, dbeta = sum_r da0).  C % 4 == 0.
+static __global__ __launch_bounds__(256) void bn_dx_xhat_kernel(float *__restrict__ dx, const float *__restrict__ xhat, const float *__restrict__ invstd,
+                                                         const float *__restrict__ gamma, const float *__restrict__ dgamma,
+                                                         const float *__restrict__ dbeta, size_t total4, int C, int n_stat) {
+    const float inv_n = 1.0f / (float)n_stat;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
+        const int c = (int)((i * 4) % (size_t)C);
+        const f32x4 dy = reinterpret_cast<const f32x4 *>(dx)[i], xh = reinterpret_cast<const f32x4 *>(xhat)[i];
+        const f32x4 is = *reinterpret_cast<const f32x4 *>(invstd + c), ga = *reinterpret_cast<const f32x4 *>(gamma + c);
+        const f32x4 dg = *reinterpret_cast<const f32x4 *>(dgamma + c), db = *reinterpret_cast<const f32x4 *>(dbeta + c);
+        reinterpret_cast<f32x4 *>(dx)[i] = ga * is * (dy - db * inv_n - xh * dg * inv_n);
+    }
+}
+
 // y = (x - mean) * invstd * gamma + beta  (training: batch stats; eval: running stats, invstd computed here)
 static __global__ __launch_bounds__(256) void bn_apply_kernel(const float *__restrict__ x, const float *__restrict__ mean,
                                                        const float *__restrict__ invstd_or_var, const float *__restrict__ gamma,

@@ -496,6 +496,10 @@ class HipTrainableResNet(_Node):
     def max_batch(self):
         return self._max_batch
 
+    def workspace_bytes(self):
+        """device bytes of the training workspace the first forward allocates for max_batch frames (pvr_trainer_workspace_bytes)"""
+        return int(_lib.lib().pvr_trainer_workspace_bytes(self._handle))
+
     @property
     def lanes(self):
         return 4
@@ -537,14 +541,40 @@ class HipTrainableResNet(_Node):
             return self._eval_model()(frames_u8)
 
 
+def require_trainable(embedding_name):
+    """raise NotImplementedError unless `embedding_name` is one EmbeddingNet(..., train=True) is built for; returns its variant"""
+    if embedding_name not in _SINGLE or _SINGLE[embedding_name][1] not in _TRAINABLE:
+        raise NotImplementedError("training the embedding '%s' is not built: %s (the compressed *_l3 / *_l4 variants, Uber models, CLIP, MAE and "
+                                  "'random' run frozen)" % (embedding_name, _TRAINABLE_MSG))
+    return _SINGLE[embedding_name][1]
+
+
+def trainer_workspace_bytes(embedding_name, max_batch):
+    """bytes of device memory the training workspace of `embedding_name` takes for max_batch frames (pvr_trainer_workspace_bytes on a handle made
+    for the question: host arithmetic, no GPU needed); None when the trainer refuses that max_batch (a tensor of the workspace would pass 2 GiB)"""
+    variant = require_trainable(embedding_name)
+    L = _lib.lib()
+    tr = transforms_for('')
+    desc = _lib.EncoderDesc(arch=_ARCH[variant], dtype=_lib.PVR_F32, max_batch=int(max_batch), chunk=0, resize=tr.resize, crop=tr.crop)
+    desc.mean[:] = tr.mean
+    desc.std_[:] = tr.std
+    h = C.c_void_p()
+    if L.pvr_trainer_create(C.byref(desc), C.byref(h)) != 0:
+        if 'largest max_batch' in _lib.last_error():
+            return None
+        _lib.check(1)
+    try:
+        return int(L.pvr_trainer_workspace_bytes(h))
+    finally:
+        L.pvr_trainer_destroy(h)
+
+
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
         raise NotImplementedError("Requested model not available.")                 # embeddings.py:321
-    if embedding_name not in _SINGLE or _SINGLE[embedding_name][1] not in _TRAINABLE:
-        raise NotImplementedError("training the embedding '%s' is not built: %s (the compressed *_l3 / *_l4 variants, Uber models, CLIP, MAE and "
-                                  "'random' run frozen)" % (embedding_name, _TRAINABLE_MSG))
+    require_trainable(embedding_name)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:

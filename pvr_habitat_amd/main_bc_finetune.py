@@ -9,7 +9,8 @@ running (HipRMSprop.step_data_parallel / pvr_policy_set_data_parallel) before th
 identical on every rank.  Launch:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m pvr_habitat_amd.main_bc_finetune ...
 (`__main__` reads RANK / LOCAL_RANK / WORLD_SIZE, picks the GPU and creates the process group before the first GPU call).
-Interrupted runs resume, completed runs return early (main_bc_finetune.py:47-56,84-89,135-143).  Habitat evaluation needs the
+`--train_embedding` with a trainable `--embedding_name` selects end-to-end BC instead (`run_end_to_end`: EmbeddingNet(train=True) in front of
+PolicyNet, one GPU).  Interrupted runs resume, completed runs return early (main_bc_finetune.py:47-56,84-89,135-143).  Habitat evaluation needs the
 simulator: pass `make_env` as in main_bc_2.run."""
 import os
 import pickle
@@ -42,7 +43,171 @@ def load_raw(flags, from_env):
     return obs, action, reward, done
 
 
+def largest_fitting_frames(embedding_name, frames_wanted, free_bytes):
+    """the largest frame count <= frames_wanted whose training workspace fits free_bytes (0: not even one frame)"""
+    from .embeddings import trainer_workspace_bytes
+    lo, hi = 0, int(frames_wanted)                              # invariant: lo fits (or is 0), hi + 1 does not
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        need = trainer_workspace_bytes(embedding_name, mid)     # (None: more frames than the trainer's launches can address)
+        if need is not None and need <= free_bytes:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def check_workspace_fits(flags, n_frames_per_obs):
+    """The trainer keeps every activation of a step: its workspace grows with unroll_length x batch_size x frames (about 0.03 GB per frame for
+    resnet18, 0.14 GB for resnet50: the reference's default T=100, B=32 does not fit an MI355X), and the trainer refuses a frame count at which one of
+    its tensors would pass 2 GiB (668 frames for resnet18, 334 for resnet50).  Compared with that limit and the free device memory BEFORE anything
+    is allocated, so that the error names a size that fits instead of an allocation failing inside the first step."""
+    from .embeddings import trainer_workspace_bytes
+    want = flags.unroll_length * flags.batch_size * n_frames_per_obs
+    need = trainer_workspace_bytes(flags.embedding_name, want)
+    free = int(torch.cuda.mem_get_info()[0])
+    if need is None or need > free:
+        fit = largest_fitting_frames(flags.embedding_name, want, free)
+        why = 'is more than the trainer\'s launches can address (one tensor of its workspace would pass 2 GiB)' if need is None \
+            else 'takes %.2f GB, %.2f GB of device memory are free' % (need / 2 ** 30, free / 2 ** 30)
+        raise RuntimeError("--train_embedding: the training workspace of '%s' for unroll_length %d x batch_size %d x %d frames = %d frames %s; "
+                           "the largest unroll_length x batch_size x frames that fits is %d (unroll_length <= %d at this batch_size)"
+                           % (flags.embedding_name, flags.unroll_length, flags.batch_size, n_frames_per_obs, want, why, fit,
+                              fit // (flags.batch_size * n_frames_per_obs)))
+    return need
+
+
+def run_end_to_end(flags, make_env=None):
+    """`--train_embedding`: BASELINE configs[3], the reference's main_bc_finetune with EmbeddingNet(embedding_name, train=True) in front of PolicyNet.
+    Same loader, sampler, device gather, stats pickle, resume and early return as `run`; the model is models.PolicyNetWithEncoder and the update is
+    models.HipJointRMSprop (four library calls per iteration) or, with --autograd_step, the reference's own lines over both parameter sets."""
+    from torch import nn
+    from torch.nn import functional as F
+    from . import embeddings as E
+    from .models import PolicyNetWithEncoder, HipJointRMSprop
+    E.require_trainable(flags.embedding_name)                   # NotImplementedError names what is trainable
+    world = max(rank_world()[1], int(os.environ.get('WORLD_SIZE', '1')))
+    if world > 1:
+        raise NotImplementedError('--train_embedding with a world size of %d: data-parallel encoder training is not built (the trainable encoder and its '
+                                  'BatchNorm statistics are single-GPU); run one process' % world)
+    fused = not getattr(flags, 'autograd_step', False)
+    if fused and (getattr(flags, 'optimizer', 'rmsprop') == 'adam' or flags.momentum != 0):
+        raise NotImplementedError('--train_embedding: the fused joint update is clip + RMSprop with momentum 0 (pvr_joint_apply_rmsprop); '
+                                  '--optimizer adam and --momentum != 0 are not built for it (--autograd_step runs torch.optim.RMSprop with momentum)')
+    if getattr(flags, 'optimizer', 'rmsprop') == 'adam':
+        raise NotImplementedError('--train_embedding --autograd_step runs the reference lines with torch.optim.RMSprop; --optimizer adam is not built here')
+    torch.manual_seed(flags.run_id)
+    np.random.seed(flags.run_id)
+    random.seed(flags.run_id)
+    from_env, to_env = flags.env, flags.to_env
+    os.makedirs(flags.save_path, exist_ok=True)
+    save_path = os.path.join(flags.save_path, from_env + '_em' + flags.embedding_name + '_finetuned_s' + str(flags.run_id) + '_' + to_env)
+    resume = False
+    if os.path.isfile(save_path + '.pickle'):
+        stats = pickle.load(open(save_path + '.pickle', 'rb'))
+        if stats[to_env]['frames'][-1] >= flags.max_frames:
+            print('   WARNING! This run was already completed. Stopping now.')
+            return stats
+        resume = os.path.isfile(save_path + '.tar')
+    if flags.disable_cuda or not torch.cuda.is_available():
+        raise NotImplementedError('--train_embedding needs the GPU: training the embedding on the host backend (disable_cuda) is not built')
+    flags.device = torch.device('cuda')
+    print('=== Loading trajectories ===')
+    obs, action, reward, done = load_raw(flags, from_env)
+    n_samples = len(reward)
+    print('  ', 'total number of samples', n_samples)
+    assert obs.dtype == np.uint8 and obs.ndim == 4 and obs.shape[3] % 3 == 0, 'raw (n, H, W, 3F) uint8 frames expected, got %s %s' % (obs.dtype, obs.shape)
+    n_f = obs.shape[3] // 3
+    env = None
+    n_actions = int(getattr(flags, 'num_actions', 3))
+    if make_env is not None:
+        flags.env = to_env
+        env = make_env(flags, None)
+        n_actions = env.gym_env.action_space.n
+    assert int(np.min(action)) >= 0 and int(np.max(action)) < n_actions, \
+        'actions in the data (%d..%d) do not fit num_actions=%d' % (int(np.min(action)), int(np.max(action)), n_actions)
+    T, B = flags.unroll_length, flags.batch_size
+    check_workspace_fits(flags, n_f)
+    net = E.EmbeddingNet(flags.embedding_name, pretrained=flags.pretrained_embedding, train=True, max_batch=T * B * n_f)
+    model = PolicyNetWithEncoder(net, n_actions, flags.batch_norm, num_frames=n_f, max_unroll=T, max_batch=B)
+    max_epochs = flags.max_frames // (T * B) + 1
+    if fused:
+        optimizer = HipJointRMSprop(model, lr=flags.learning_rate, eps=flags.epsilon, alpha=flags.alpha, max_grad_norm=flags.max_grad_norm,
+                                    max_epochs=max_epochs)
+    else:                                                       # main_bc_2.py:80-90 over both parameter sets
+        optimizer = torch.optim.RMSprop(model.parameters(), lr=flags.learning_rate, momentum=flags.momentum, eps=flags.epsilon, alpha=flags.alpha)
+        scheduler = torch.optim.lr_scheduler.LambdaLR(optimizer, lambda epoch: 1 - epoch / max_epochs)
+    stat_keys = ['episode_return', 'episode_success']
+    init_frames = 0
+    if resume:
+        print('=== Resuming previous run ===')
+        checkpoint = torch.load(save_path + '.tar', weights_only=False, map_location='cpu')
+        model.load_state_dict(checkpoint['actor_model_state_dict'])
+        optimizer.load_state_dict(checkpoint['actor_model_optimizer_state_dict'])
+        if fused:
+            optimizer.last_epoch = checkpoint['scheduler_state_dict']['last_epoch']
+        else:
+            scheduler.load_state_dict(checkpoint['scheduler_state_dict'])
+        init_frames = stats[to_env]['frames'][-1]
+    else:
+        stats = {to_env: {**{k: [np.nan] for k in stat_keys}, 'frames': [0], 'training_loss': [np.nan], 'gradient_norm': [np.nan]}}
+    print('=== Training policy and embedding ===')
+    model.train()
+    from .bc_data import DeviceDataset
+    dataset = DeviceDataset(obs, action, done, flags.device)
+    for frames in range(init_frames, flags.max_frames, B * T):
+        epoch = frames // (B * T)
+        starting_i = sample_with_minimum_distance(n=n_samples, k=B, d=T)
+        o, a, d = dataset.gather(starting_i, T)                 # (T, B, H, W, 3F) uint8
+        if fused:
+            optimizer.scheduler_step()
+            loss, gradient_norm = optimizer.step(o, d, a)
+        else:                                                   # main_bc_2.py:206-227, as written there
+            output, _ = model(dict(obs=o, done=d), model.initial_state(batch_size=B))
+            loss = F.nll_loss(F.log_softmax(torch.flatten(output['policy_logits'], 0, 1), dim=-1), target=torch.flatten(a, 0, 1).long())
+            scheduler.step()
+            optimizer.zero_grad()
+            loss.backward()
+            gradient_norm = 0.
+            for p in model.parameters():
+                if p.grad is not None and p.requires_grad:
+                    gradient_norm += p.grad.detach().data.norm(2).item() ** 2
+            gradient_norm = gradient_norm ** 0.5
+            nn.utils.clip_grad_norm_(model.parameters(), flags.max_grad_norm)
+            optimizer.step()
+        if (epoch + 1) % flags.eval_frequency == 0:
+            ev = {k: np.nan for k in stat_keys}
+            if env is not None and ((flags.essential_save_only and is_essential_save(epoch, max_epochs, flags.eval_frequency))
+                                    or not flags.essential_save_only):
+                model.eval()                                    # the frozen 'f32' plan of the current encoder parameters + the eval policy
+                ep = test(model, env, stat_keys, flags.n_episodes_test)
+                model.train()
+                ev = {k: float(np.mean(ep[k])) for k in stat_keys}
+            for k in stat_keys:
+                stats[to_env][k].append(ev[k])
+            stats[to_env]['frames'].append(frames)
+            stats[to_env]['training_loss'].append(float(loss))              # (synchronises)
+            stats[to_env]['gradient_norm'].append(float(gradient_norm))
+            model.check_status()
+            print('  ', 'frames', frames, 'training loss', float(loss), 'gradient norm', float(gradient_norm))
+            if not flags.disable_save:
+                pickle.dump(stats, open(save_path + '.pickle', 'wb'), protocol=pickle.HIGHEST_PROTOCOL)
+                # (host copies: the encoder's int64 BatchNorm counters are views of its fp32 buffer block, which torch.save refuses as they are)
+                torch.save({'actor_model_state_dict': {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
+                            'actor_model_optimizer_state_dict': optimizer.state_dict(),
+                            'scheduler_state_dict': {'last_epoch': optimizer.last_epoch} if fused else scheduler.state_dict(),
+                            'flags': {k: v for k, v in vars(flags).items() if k != 'device'}}, save_path + '.tar')
+    torch.cuda.synchronize()
+    model.check_status()
+    model.close()
+    if env is not None:
+        env.close()
+    return stats
+
+
 def run(flags, make_env=None):
+    if getattr(flags, 'train_embedding', False):
+        return run_end_to_end(flags, make_env)
     rank, world = rank_world()
     torch.manual_seed(flags.run_id)
     np.random.seed(flags.run_id)

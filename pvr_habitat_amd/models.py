@@ -68,12 +68,20 @@ def _plib():
         L.pvr_policy_set_data_parallel.argtypes = [vp, i32, i32, ALLREDUCE_FN, vp]
         L.pvr_policy_backward_dlogits.restype = C.c_int
         L.pvr_policy_backward_dlogits.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+        L.pvr_policy_backward_dobs.restype = C.c_int
+        L.pvr_policy_backward_dobs.argtypes = [vp, vp, C.POINTER(PolicyBN), vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+        L.pvr_policy_backward_dlogits_dobs.restype = C.c_int
+        L.pvr_policy_backward_dlogits_dobs.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
+        L.pvr_joint_apply_rmsprop.restype = C.c_int
+        L.pvr_joint_apply_rmsprop.argtypes = [i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), f32, f32, f32, f32, vp, vp]
         L.pvr_policy_apply_momentum.restype = C.c_int
         L.pvr_policy_apply_momentum.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, vp, vp]
         L.pvr_policy_apply_adam.restype = C.c_int
         L.pvr_policy_apply_adam.argtypes = [vp, vp, vp, vp, vp, f32, f32, f32, f32, i64, f32, vp, vp]
         L.pvr_policy_last_grads.restype = C.c_int
         L.pvr_policy_last_grads.argtypes = [vp, vp, vp]
+        L.pvr_policy_last_dlogits.restype = C.c_int
+        L.pvr_policy_last_dlogits.argtypes = [vp, vp, i32, i32, vp]
         L.pvr_policy_set_action_sampling.restype = C.c_int
         L.pvr_policy_set_action_sampling.argtypes = [vp, C.c_int32, C.c_uint64]
         L.pvr_policy_action_sampling_call.restype = C.c_uint64
@@ -132,7 +140,7 @@ def _reference_init(obs_size, num_actions, batch_norm, hidden, conv=False):
 
 class _PolicyFunction(torch.autograd.Function):
     """Training-mode forward of the whole policy as one autograd node.  Inputs: the model, the prepared device tensors, then every
-    trainable parameter (so autograd routes a gradient to each of them); outputs: logits (differentiable), baseline / action /
+    trainable parameter (so autograd routes a gradient to each of them; the observations get theirs when they carry a graph); outputs: logits (differentiable), baseline / action /
     final state (not differentiable: the BC loss reads only the logits, main_bc_2.py:211-214)."""
 
     @staticmethod
@@ -151,15 +159,22 @@ class _PolicyFunction(torch.autograd.Function):
                                'of the same policy overwrote its workspace (one backward per forward, right after it, as in the BC loop)')
         g = torch.empty(m._n_train, dtype=torch.float32, device=m.device)
         vp = lambda t: C.c_void_p(t.data_ptr())
-        status = _plib().pvr_policy_backward_dlogits(m._handle, vp(m._flat), vp(ctx.x), vp(dlogits.contiguous().float()), ctx.T, ctx.B,
-                                                     vp(g), _lib.stream_ptr())
+        dx = None
+        if ctx.needs_input_grad[1]:
+            # the observations carry a graph (a trainable encoder's output): the same backward, plus d(loss)/d(obs) for whatever produced them
+            dx = torch.empty_like(ctx.x)
+            status = _plib().pvr_policy_backward_dlogits_dobs(m._handle, vp(m._flat), vp(ctx.x), vp(dlogits.contiguous().float()), ctx.T, ctx.B,
+                                                              vp(g), vp(dx), _lib.stream_ptr())
+        else:
+            status = _plib().pvr_policy_backward_dlogits(m._handle, vp(m._flat), vp(ctx.x), vp(dlogits.contiguous().float()), ctx.T, ctx.B,
+                                                         vp(g), _lib.stream_ptr())
         m._checked(status)
         m._last_flat_grad = g
         grads = []
         for k in m._order:
             o, shp = m._slots[k]
             grads.append(g[o:o + int(np.prod(shp))].view(shp) if o < m._n_train else None)     # baseline head: no gradient
-        return (None,) * 7 + tuple(grads)
+        return (None, dx) + (None,) * 5 + tuple(grads)
 
 
 class PolicyNet(nn.Module):
@@ -436,7 +451,14 @@ class PolicyNet(nn.Module):
         if self._conv_frames:
             assert x.dtype == torch.uint8 and tuple(x.shape[2:]) == (64, 64, 3 * self._conv_frames), x.shape
             return torch.flatten(x, 0, 1).to(device=dev).contiguous()     # raw uint8 frames; /255 happens in the kernel
+        # (differentiable torch ops only: a CUDA fp32 obs that requires grad - the output of a trainable encoder - keeps its graph)
         return torch.flatten(x, 0, 1).float().to(device=dev).contiguous()
+
+    def last_dlogits(self, T, B):
+        """d(loss)/d(policy_logits) (T, B, A) the last backward of T x B rows read (parity tests: pvr_policy_last_dlogits)"""
+        out = torch.empty((T, B, self.num_actions), dtype=torch.float32, device=self.device)
+        _lib.check(_plib().pvr_policy_last_dlogits(self._handle, C.c_void_p(out.data_ptr()), T, B, self._stream()))
+        return out
 
     def last_grads(self):
         """Flat pre-clip gradient of the last fused step as {state_dict key: tensor} (parity tests)."""
@@ -669,6 +691,138 @@ class HipAdam(_HipOptimizer):
         _lib.check(_plib().pvr_policy_apply_adam(m._handle, vp(m._flat), vp(self.exp_avg), vp(self.exp_avg_sq), vp(self._grads), self.current_lr(),
                                                  self.betas[0], self.betas[1], self.eps, self.steps + 1, self.max_grad_norm, vp(stats),
                                                  _lib.stream_ptr()))
+
+
+class PolicyNetWithEncoder(nn.Module):
+    """End-to-end BC model (reference main_bc_finetune.py with `--train_embedding`: EmbeddingNet(train=True) in front of PolicyNet): raw uint8
+    (T, B, H, W, 3F) observations -> the trainable encoder on every frame -> the F embeddings of an observation side by side -> PolicyNet.
+    Output as PolicyNet.forward.  `embedding_net` is an EmbeddingNet(..., train=True, max_batch >= T*B*F) (or its HipTrainableResNet).
+
+    The frames are split on the device into (T*B*F, H, W, 3) in (observation, frame) order, so the trainer's contiguous (T*B*F, D) output IS the
+    (T*B, F*D) observation matrix: the layout of the reference's np.split / np.concatenate(..., -1) (save_embedded_obs.py:153-155).  BatchNorm2d
+    batch statistics do not depend on the order of the frames.  state_dict() has `embedding.*` and `policy.*` keys; eval() runs the frozen 'f32'
+    plan of the current encoder parameters and the eval policy.  Train it with the reference's own lines (loss.backward() reaches every encoder
+    parameter through PolicyNet's d(loss)/d(obs)) or with HipJointRMSprop."""
+
+    def __init__(self, embedding_net, num_actions, batch_norm=False, num_frames=2, max_unroll=100, max_batch=32):
+        super().__init__()
+        enc = getattr(embedding_net, 'embedding', embedding_net)
+        if not (hasattr(enc, '_forward_raw') and hasattr(enc, '_flat')):
+            raise NotImplementedError('PolicyNetWithEncoder needs a trainable encoder: EmbeddingNet(name, train=True) of resnet18 / resnet34 / resnet50 '
+                                      '(a frozen encoder has no gradient; embed the data once with save_embedded_obs instead)')
+        self.embedding = enc
+        self.num_frames = int(num_frames)
+        self.policy = PolicyNet((self.num_frames * int(enc.out_size),), num_actions, batch_norm, max_unroll=max_unroll, max_batch=max_batch)
+        self.policy.to(device=enc._flat.device)
+
+    @property
+    def device(self):
+        return self.policy.device
+
+    def initial_state(self, batch_size):
+        return self.policy.initial_state(batch_size)
+
+    def check_status(self):
+        self.policy.check_status()
+
+    def close(self):
+        self.policy.close()
+        self.embedding.close()
+
+    def split_frames(self, obs_u8):
+        """(T, B, H, W, 3F) uint8 -> (T*B*F, H, W, 3) contiguous on the device, (observation, frame) order"""
+        assert obs_u8.dtype == torch.uint8 and obs_u8.dim() == 5 and obs_u8.shape[4] == 3 * self.num_frames, tuple(obs_u8.shape)
+        T, B, H, W, _ = obs_u8.shape
+        x = obs_u8.to(device=self.device).reshape(T * B, H, W, self.num_frames, 3).permute(0, 3, 1, 2, 4)
+        return x.contiguous().view(T * B * self.num_frames, H, W, 3)
+
+    def forward(self, inputs, core_state=()):
+        obs = inputs['obs']
+        T, B = obs.shape[0], obs.shape[1]
+        emb = self.embedding(self.split_frames(obs))                          # (T*B*F, D); with its graph in training mode
+        x = emb.reshape(T, B, self.num_frames * int(self.embedding.out_size))
+        return self.policy(dict(obs=x, done=inputs['done']), core_state)
+
+
+class HipJointRMSprop(object):
+    """clip_grad_norm_ over ALL parameters + torch.optim.RMSprop(momentum 0) + LambdaLR(1 - epoch/max_epochs) for a PolicyNetWithEncoder, fused with
+    the forward / backward of the BC loss: `step` is four library calls and no autograd graph - the trainer's forward, pvr_policy_backward_dobs
+    (policy forward, loss, BPTT, d(loss)/d(obs)), pvr_trainer_backward on that gradient, and pvr_joint_apply_rmsprop over (the policy's trainable
+    prefix, the encoder's flat buffer) with ONE norm.  Eager launches (not captured in a graph).  `scheduler_step()` as HipRMSprop."""
+
+    def __init__(self, model, lr=1e-4, alpha=0.99, eps=1e-5, momentum=0, max_grad_norm=40.0, max_epochs=None):
+        if float(momentum) != 0:
+            raise NotImplementedError('HipJointRMSprop: momentum != 0 is not built for the joint (encoder + policy) update; use momentum 0 or the '
+                                      'autograd path with torch.optim.RMSprop')
+        self.model, self.lr0, self.alpha, self.eps = model, float(lr), float(alpha), float(eps)
+        self.max_grad_norm, self.max_epochs = float(max_grad_norm), max_epochs
+        self.last_epoch = 0
+        self.steps = 0
+        pol, enc = model.policy, model.embedding
+        if enc._flat.numel() % 4 or pol._n_train % 4:
+            raise ValueError('HipJointRMSprop: parameter counts must be multiples of 4 (float4 kernels)')
+        self.square_avg = {'policy': torch.zeros_like(pol._flat), 'embedding': torch.zeros_like(enc._flat)}
+        self._grads = None
+
+    def scheduler_step(self):
+        self.last_epoch += 1
+
+    def current_lr(self):
+        if self.max_epochs is None:
+            return self.lr0
+        return self.lr0 * (1 - self.last_epoch / self.max_epochs)
+
+    def grads(self):
+        """the flat pre-clip gradients of the last step: {'policy': trainable prefix, 'embedding': the encoder's flat layout}"""
+        return self._grads
+
+    def step(self, obs_u8, done, actions):
+        """obs (T,B,H,W,3F) uint8, done (T,B) bool, actions (T,B) int -> (loss, grad_norm) device scalars (norm over both parameter sets, pre-clip)"""
+        m = self.model
+        pol, enc = m.policy, m.embedding
+        if not (m.training and enc.training and pol.training):
+            raise RuntimeError('HipJointRMSprop.step: the model is in eval mode; call model.train() first')
+        T, B = obs_u8.shape[0], obs_u8.shape[1]
+        dev = pol.device
+        pol._ensure(T, B)
+        if self._grads is None or self._grads['policy'].device != dev:
+            self._grads = {'policy': torch.zeros(pol._n_train, dtype=torch.float32, device=dev), 'embedding': torch.zeros_like(enc._flat)}
+            self.square_avg = {k: v.to(dev) for k, v in self.square_avg.items()}
+        frames = m.split_frames(obs_u8)
+        d = done.to(device=dev).to(torch.uint8).contiguous()
+        a = actions.to(device=dev).long().contiguous()
+        L = _plib()
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.no_grad():
+            enc.close()                                                       # (a frozen eval plan folds parameters that are about to move)
+            emb = enc._forward_raw(frames)                                    # (T*B*F, D) contiguous = the (T*B, F*D) observation matrix
+            enc._fwd_gen += 1                                                 # an autograd forward still waiting for its backward has lost its activations
+            pol._fwd_gen = getattr(pol, '_fwd_gen', 0) + 1
+            dobs = torch.empty_like(emb)
+            stats = torch.zeros(2, dtype=torch.float32, device=dev)
+            bn = pol._bn_struct()
+            g = self._grads
+            pol._checked(L.pvr_policy_backward_dobs(pol._handle, vp(pol._flat), C.byref(bn) if bn else None, vp(emb), vp(d), vp(a), T, B,
+                                                    vp(g['policy']), vp(stats), None, vp(dobs), _lib.stream_ptr()))
+            _lib.check(L.pvr_trainer_backward(enc._handle, vp(enc._flat), vp(dobs), dobs.stride(0), vp(g['embedding']), _lib.stream_ptr()))
+            arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
+            counts = (C.c_int64 * 2)(pol._n_train, enc._flat.numel())
+            _lib.check(L.pvr_joint_apply_rmsprop(2, arr((pol._flat, enc._flat)), arr((self.square_avg['policy'], self.square_avg['embedding'])),
+                                                 arr((g['policy'], g['embedding'])), counts, self.current_lr(), self.alpha, self.eps,
+                                                 self.max_grad_norm, C.c_void_p(stats.data_ptr() + 4), _lib.stream_ptr()))
+        self.steps += 1
+        return stats[0], stats[1]
+
+    def state_dict(self):
+        return {'square_avg': {k: v.detach().cpu().clone() for k, v in self.square_avg.items()}, 'steps': self.steps, 'last_epoch': self.last_epoch,
+                'param_groups': [{'lr': self.current_lr(), 'initial_lr': self.lr0, 'momentum': 0, 'alpha': self.alpha, 'eps': self.eps,
+                                  'centered': False, 'weight_decay': 0}]}
+
+    def load_state_dict(self, sd):
+        for k in self.square_avg:
+            self.square_avg[k].copy_(sd['square_avg'][k].to(self.square_avg[k].device))
+        self.steps = int(sd['steps'])
+        self.last_epoch = int(sd.get('last_epoch', self.last_epoch))
 
 
 def make_optimizer(flags, model, max_epochs):
