@@ -5,7 +5,8 @@
  *
  * Scope: the torchvision trunks resnet18 / resnet34 / resnet50 (arch PVR_ARCH_RESNET18 / _RESNET34 / _RESNET50), fp32 storage,
  * every product of a convolution, a data gradient or a weight gradient on the f32-input MFMA (the arithmetic of the PVR_F32
- * plan), one GPU.  BatchNorm runs on the statistics of the WHOLE batch of a forward (they cannot be chunked).
+ * plan), one GPU.  BatchNorm runs on the statistics of the WHOLE batch of a forward (they cannot be chunked) or, after
+ * pvr_trainer_set_bn_frozen, on its running statistics (frames independent: a step is a sum over passes).
  *
  * Buffers follow pvr_policy.h's convention: the caller owns ONE flat fp32 device buffer of parameters, every tensor in its
  * state_dict shape (conv weights in torch's (cout, cin, kh, kw) layout - the library repacks them inside the forward), and
@@ -58,6 +59,21 @@ pvr_status pvr_trainer_forward(pvr_trainer *tr, const float *params_dev, void *b
  * Bit-reproducible run to run (no float atomics: every split reduction is summed in a fixed order). */
 pvr_status pvr_trainer_backward(pvr_trainer *tr, const float *params_dev, const float *dout_dev, int64_t dout_stride, float *grads_dev, void *hip_stream);
 
+/* BatchNorm mode of the handle.  on == 0 (the default): batch statistics, everything above.  on != 0: FROZEN BatchNorm - the fine-tuning mode of a
+ * pre-trained trunk (torch: model.train() followed by .eval() on every BatchNorm module): the convolutions and the BatchNorm affine parameters train,
+ * BatchNorm normalises with running_mean / running_var (eps 1e-5) and pvr_trainer_forward leaves running_mean, running_var and
+ * num_batches_tracked untouched.  Every frame is then independent of the others: a step over N frames is a sum over passes of <= max_batch frames
+ * (pvr_trainer_backward_acc), the workspace is sized by the pass, and a pass of one frame is legal.  Switching drops a held forward (a following
+ * backward is PVR_ERR_STATE). */
+pvr_status pvr_trainer_set_bn_frozen(pvr_trainer *tr, int32_t on);
+/* pvr_trainer_backward that can add to grads_dev.  accumulate == 0: pvr_trainer_backward (scratch unused).  accumulate != 0: this pass's gradient is
+ * written to the caller's scratch_dev (scratch_floats >= pvr_trainer_param_count) and ONE launch adds it onto grads_dev, one fp32 addition per
+ * element - the result of a step depends on the order of its passes and on nothing else.  Allowed in both BatchNorm modes; only with frozen
+ * BatchNorm is the sum over passes the gradient of the whole batch.  The scratch is the caller's so that pvr_trainer_workspace_bytes does not
+ * depend on how a caller steps. */
+pvr_status pvr_trainer_backward_acc(pvr_trainer *tr, const float *params_dev, const float *dout_dev, int64_t dout_stride, float *grads_dev,
+                                    int32_t accumulate, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
  * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */
@@ -81,6 +97,19 @@ pvr_status pvr_op_bn_train_forward(const float *z_dev, const float *residual_dev
 pvr_status pvr_op_bn_train_backward(const float *z_dev, const float *y_dev, const float *dy_dev, const float *gamma_dev, const float *mean_dev,
                                     const float *rstd_dev, float *dz_dev, float *dres_dev, int32_t dres_accumulate, float *dgamma_dev, float *dbeta_dev,
                                     int64_t rows, int32_t c, int32_t relu, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+/* BatchNorm2d on its RUNNING statistics (frozen BatchNorm), rows >= 1, c % 4 == 0: y = (z - running_mean) * rstd * gamma + beta [+ residual] [ReLU] with
+ * rstd = 1 / sqrt(running_var + 1e-5), one pass over z, no scratch; mean_out / rstd_out (c floats each) receive running_mean and rstd for the backward.
+ * running_mean / running_var are read only. */
+pvr_status pvr_op_bn_frozen_forward(const float *z_dev, const float *residual_dev, const float *gamma_dev, const float *beta_dev,
+                                    const float *running_mean_dev, const float *running_var_dev, float *y_dev, float *mean_out_dev, float *rstd_out_dev,
+                                    int64_t rows, int32_t c, int32_t relu, void *hip_stream);
+/* its backward (arguments as pvr_op_bn_train_backward, scratch of pvr_op_bn_scratch_floats): g = dy where (relu == 0 or y > 0) else 0;
+ * dbeta = sum g; dgamma = sum g * xhat, xhat = (z - mean) * rstd; dz = gamma * rstd * g (the statistics are constants: no mean terms);
+ * dres (optional) = g, added to what it holds when dres_accumulate != 0.  One kernel streams z, y, dy -> dz, dres and writes per-block partial
+ * sums, a second sums them in double in block order: no float atomics, two runs give the same bits. */
+pvr_status pvr_op_bn_frozen_backward(const float *z_dev, const float *y_dev, const float *dy_dev, const float *gamma_dev, const float *mean_dev,
+                                     const float *rstd_dev, float *dz_dev, float *dres_dev, int32_t dres_accumulate, float *dgamma_dev, float *dbeta_dev,
+                                     int64_t rows, int32_t c, int32_t relu, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
 /* Weight gradient of a k x k convolution (k 1 or 3, stride 1 or 2, cin % 32 == 0, cout % 4 == 0) on the f32-input MFMA:
  * dw[co][ci][kh][kw] = sum over (n, y, x) of dz[n,y,x,co] * x[n, y*stride + kh - pad, x*stride + kw - pad, ci]; x (n,h,w,cin),
  * dz (n,ho,wo,cout), dw in torch's (cout, cin, k, k) layout.  The pixel range is split over workgroups and the partials are summed in a fixed order. */

@@ -100,11 +100,15 @@ _SIGS = {
     'pvr_trainer_buffer_offset': (C.c_int64, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]),
     'pvr_trainer_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_trainer_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'pvr_trainer_set_bn_frozen': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pvr_trainer_backward_acc': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_trainer_debug_set_timing': (C.c_int, [C.c_void_p, C.c_int32]),
     'pvr_trainer_launch_time': (C.c_int32, [C.c_void_p, C.c_int32, C.c_char_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_double)]),
     'pvr_op_bn_scratch_floats': (C.c_int64, [C.c_int64, C.c_int32]),
     'pvr_op_bn_train_forward': (C.c_int, [C.c_void_p] * 10 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_bn_train_backward': (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_bn_frozen_forward': (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    'pvr_op_bn_frozen_backward': (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_conv_wgrad_scratch_floats': (C.c_int64, [C.c_int32] * 8),
     'pvr_op_conv_wgrad': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 8 + [C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_conv_dgrad_scratch_floats': (C.c_int64, [C.c_int32] * 8),

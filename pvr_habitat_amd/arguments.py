@@ -26,6 +26,16 @@ def make_parser():
                              'update over both (fused, or the reference lines with --autograd_step); the training workspace grows with '
                              'unroll_length x batch_size x frames and is checked against the free device memory before the first step')
     parser.add_argument('--disable_pretrained_embedding', action='store_false', dest='pretrained_embedding')
+    # not in the reference: fine-tuning with frozen BatchNorm, which lifts the frame limit of --train_embedding
+    parser.add_argument('--freeze_embedding_bn', action='store_true',
+                        help='with --train_embedding: frozen BatchNorm (torch: model.train() then .eval() on every BatchNorm) - the convolutions and the '
+                             'BatchNorm affine parameters train, BatchNorm normalises with the running statistics of the checkpoint and leaves them '
+                             'unchanged.  Frames are then independent, a step runs as passes of --embedding_chunk frames and the training workspace is '
+                             'sized by the chunk: any unroll_length x batch_size trains')
+    parser.add_argument('--embedding_chunk', type=int, default=None,
+                        help='with --freeze_embedding_bn: frames per trainer pass (default: the largest count within the trainer\'s own limit - 668 frames '
+                             'for resnet18 / 34, 334 for resnet50 - whose workspace fits the free device memory, never above unroll_length x batch_size x '
+                             'frames)')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

@@ -48,6 +48,7 @@ struct pvr_trainer {
           *bn_scratch = nullptr, *zero_bias = nullptr;
     int64_t wg_floats = 0, bn_floats = 0;
     int fwd_n = 0;                               // frames of the forward whose activations are held (0: none - a backward is PVR_ERR_STATE)
+    bool bn_frozen = false;                      // BatchNorm normalises with its running statistics (pvr_trainer_set_bn_frozen)
     bool timing = false;
     std::vector<Timed> times;                    // launch i of a step is bracketed by events[i]
     std::vector<EventPair> events;               // made once each, on demand; destroyed with the trainer (no error path leaves one behind)
@@ -320,6 +321,9 @@ int32_t pvr_trainer_launch_time(const pvr_trainer *t, int32_t index, char *name,
 pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *out,
                                int64_t out_stride, void *stream) {
     PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward: null argument");
+    if (t->bn_frozen)
+        PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward: %d frames, the workspace holds max_batch = %d (with frozen BatchNorm the frames are "
+                    "independent: run them as passes of at most max_batch and accumulate with pvr_trainer_backward_acc)", n, t->desc.max_batch);
     PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward: %d frames, the workspace holds max_batch = %d (BatchNorm takes the whole batch of a forward "
                 "together: it is not chunked)", n, t->desc.max_batch);
     TraceScope ts("pvr_trainer_forward");
@@ -331,6 +335,9 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
     Tick tick{t, st};
     float *bufs = (float *)bn_buffers;
     auto bn = [&](TrainOp &op, const float *res, int64_t rows) {
+        if (t->bn_frozen)                         // running statistics, read only: neither they nor num_batches_tracked are touched
+            return pvr_op_bn_frozen_forward(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, op.y, op.mean, op.rstd, rows,
+                                            op.cout, op.relu, st);
         return pvr_op_bn_train_forward(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, (int64_t *)(bufs + op.nbt_off), op.y,
                                        op.mean, op.rstd, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st);
     };
@@ -353,19 +360,18 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
     return collect_times(t, 0, st);
 }
 
-pvr_status pvr_trainer_backward(pvr_trainer *t, const float *params, const float *dout, int64_t dout_stride, float *grads, void *stream) {
-    PVR_REQUIRE(t && params && dout && grads, "pvr_trainer_backward: null argument");
-    if (t->fwd_n <= 0) {
-        set_error("pvr_trainer_backward: no forward's activations are held (one backward per pvr_trainer_forward, right after it)");
-        return PVR_ERR_STATE;
-    }
-    TraceScope ts("pvr_trainer_backward");
-    hipStream_t st = (hipStream_t)stream;
+}  // extern "C"
+
+namespace {
+
+// the backward of the held forward into `grads` (fully overwritten); the caller has checked that a forward is held
+pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout, int64_t dout_stride, float *grads, hipStream_t st) {
     const int n = t->fwd_n;
     t->fwd_n = 0;
     pvr_status s;
     Tick tick{t, st};
     const size_t first_time = t->times.size();
+    const auto bn_bwd = t->bn_frozen ? pvr_op_bn_frozen_backward : pvr_op_bn_train_backward;      // (the same arguments: mean / rstd are the slots the forward wrote)
     std::vector<char> have(t->ops.size() + 1, 0);  // gradient of tensor src (index src + 1) holds a value already: the next contribution accumulates
     const int last = (int)t->ops.size() - 1;
     TR_RUN("avgpool bwd", 0, pvr_op_avgpool_backward(dout, dout_stride, t->ops[last].dy, n, t->final_hw, t->final_c, st));
@@ -376,8 +382,8 @@ pvr_status pvr_trainer_backward(pvr_trainer *t, const float *params, const float
         const int64_t rows = (int64_t)n * op.ho * op.wo;
         float *dres = op.res_src == -2 ? nullptr : grad_of(t, op.res_src);
         TR_RUN(op.bn + " bwd", 0,
-               pvr_op_bn_train_backward(op.z, op.y, op.dy, params + op.g_off, op.mean, op.rstd, t->dz, dres, dres ? have[op.res_src + 1] : 0, grads + op.g_off,
-                                        grads + op.b_off, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st));
+               bn_bwd(op.z, op.y, op.dy, params + op.g_off, op.mean, op.rstd, t->dz, dres, dres ? have[op.res_src + 1] : 0, grads + op.g_off, grads + op.b_off,
+                      rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st));
         if (dres) have[op.res_src + 1] = 1;
         const double fl = 2.0 * rows * op.cout * op.cin * op.k * op.k;
         TR_RUN(op.conv + " wgrad", fl,
@@ -391,10 +397,48 @@ pvr_status pvr_trainer_backward(pvr_trainer *t, const float *params, const float
     TrainOp &sm = t->stem;
     TR_RUN("maxpool bwd", 0, pvr_op_maxpool_backward(sm.y, t->dpool, sm.dy, n, 112, 112, 64, st));
     TR_RUN("bn1 bwd", 0,
-           pvr_op_bn_train_backward(sm.z, sm.y, sm.dy, params + sm.g_off, sm.mean, sm.rstd, t->dz, nullptr, 0, grads + sm.g_off, grads + sm.b_off,
-                                    (int64_t)n * 112 * 112, 64, 1, t->bn_scratch, t->bn_floats, st));
+           bn_bwd(sm.z, sm.y, sm.dy, params + sm.g_off, sm.mean, sm.rstd, t->dz, nullptr, 0, grads + sm.g_off, grads + sm.b_off, (int64_t)n * 112 * 112, 64, 1,
+                  t->bn_scratch, t->bn_floats, st));
     TR_RUN("conv1 wgrad", 2.0 * n * 112 * 112 * 64 * 147, pvr_op_stem_wgrad(t->d_imgf, t->dz, grads + sm.w_off, n, S_IMG, t->wg_scratch, t->wg_floats, st));
     return collect_times(t, first_time, st);
+}
+
+pvr_status no_forward_held(const char *what) {
+    set_error("%s: no forward's activations are held (one backward per pvr_trainer_forward, right after it)", what);
+    return PVR_ERR_STATE;
+}
+
+}  // namespace
+
+extern "C" {
+
+pvr_status pvr_trainer_backward(pvr_trainer *t, const float *params, const float *dout, int64_t dout_stride, float *grads, void *stream) {
+    PVR_REQUIRE(t && params && dout && grads, "pvr_trainer_backward: null argument");
+    if (t->fwd_n <= 0) return no_forward_held("pvr_trainer_backward");
+    TraceScope ts("pvr_trainer_backward");
+    return backward_into(t, params, dout, dout_stride, grads, (hipStream_t)stream);
+}
+
+pvr_status pvr_trainer_backward_acc(pvr_trainer *t, const float *params, const float *dout, int64_t dout_stride, float *grads, int32_t accumulate,
+                                    float *scratch, int64_t scratch_floats, void *stream) {
+    PVR_REQUIRE(t && params && dout && grads, "pvr_trainer_backward_acc: null argument");
+    if (t->fwd_n <= 0) return no_forward_held("pvr_trainer_backward_acc");
+    TraceScope ts("pvr_trainer_backward_acc");
+    hipStream_t st = (hipStream_t)stream;
+    if (!accumulate) return backward_into(t, params, dout, dout_stride, grads, st);
+    // (checked before the held forward is spent: a refused call leaves it in place)
+    PVR_REQUIRE(scratch && scratch_floats >= t->n_params, "pvr_trainer_backward_acc: accumulate needs a scratch of pvr_trainer_param_count = %lld floats, got %lld",
+                (long long)t->n_params, (long long)(scratch ? scratch_floats : 0));
+    pvr_status s;
+    if ((s = backward_into(t, params, dout, dout_stride, scratch, st))) return s;
+    return launch_grad_add(grads, scratch, t->n_params, st);
+}
+
+pvr_status pvr_trainer_set_bn_frozen(pvr_trainer *t, int32_t on) {
+    PVR_REQUIRE(t, "pvr_trainer_set_bn_frozen: null trainer");
+    t->bn_frozen = on != 0;
+    t->fwd_n = 0;                                 // a held forward was made in the other mode: its mean / rstd slots mean something else
+    return PVR_OK;
 }
 
 }  // extern "C"

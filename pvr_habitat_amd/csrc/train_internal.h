@@ -11,4 +11,6 @@ pvr_status launch_pack_stem_weights(const float *w, float *out, hipStream_t st);
 // pvr_op_conv_dgrad with its scratch as separate pieces: wflip (cin_pad * k*k * cout floats), dil (n*h*w*cout floats, stride 2 only), zero_bias (>= cin zeros)
 pvr_status launch_conv_dgrad(const float *dz, const float *w, float *dx, int accumulate, int n, int h, int wd, int cin, int cout, int k, int stride, int pad,
                              float *wflip, float *dil, const float *zero_bias, hipStream_t st);
+// grads[i] += pass[i] over n floats: one fp32 addition per element (gradient accumulation over the passes of a chunked step)
+pvr_status launch_grad_add(float *grads, const float *pass, int64_t n, hipStream_t st);
 }  // namespace pvr

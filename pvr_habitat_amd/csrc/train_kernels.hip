@@ -134,6 +134,117 @@ static int ew_blocks(size_t work) {
 static int bn_splits(int64_t rows) { return (int)((rows + BN_CHUNK - 1) / BN_CHUNK); }
 
 // ------------------------------------------------------------------------------------------------------------------------------------------------
+// BatchNorm2d in training mode on its RUNNING statistics (model.train() with every BatchNorm in eval(): the fine-tuning mode of a pre-trained trunk).
+// Every row is independent of the others, so a step over N frames is a sum over chunks of frames.
+// Forward: one pass over z, no reduction, no scratch; the mean / rstd slots the backward reads receive the running mean and 1 / sqrt(running_var + eps)
+// (the same fp32 expression a thread evaluates for itself); the running buffers are read only.  FIXED: the grid stride is a multiple of the channel
+// groups of a row, so a thread's four channels - and their scale and shift - are the same in every iteration.
+// Backward: dz = gamma * rstd * g has no mean terms, so ONE kernel streams z, y, dy -> dz [, dres] and reduces sum g and sum g * xhat on the way: a block
+// is 64 channels (16 threads of 4) x 16 row lanes over BN_CHUNK rows - a thread's fp32 chain is at most 128 terms, the lanes are summed as a 4-step tree
+// (fewer roundings than bn_reduce_kernel's 256 + 3) - and writes partials in bn_reduce_kernel<2>'s layout, which bn_finalize_kernel<2> sums in double.
+// ------------------------------------------------------------------------------------------------------------------------------------------------
+template <bool FIXED>
+__global__ __launch_bounds__(256) void bn_frozen_apply_kernel(const float *__restrict__ z, const float *res, const float *__restrict__ gamma,
+                                                              const float *__restrict__ beta, const float *__restrict__ run_mean,
+                                                              const float *__restrict__ run_var, float *y, float *mean_out, float *rstd_out, size_t total4, int C,
+                                                              int relu) {
+    if (blockIdx.x == 0 && mean_out)
+        for (int c = threadIdx.x; c < C; c += 256) {
+            mean_out[c] = run_mean[c];
+            rstd_out[c] = 1.f / sqrtf(run_var[c] + BN_EPS);
+        }
+    const size_t c4n = (size_t)(C / 4);
+    float m[4], rs[4], ga[4], be[4];
+    auto load = [&](int c) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            m[e] = run_mean[c + e]; rs[e] = 1.f / sqrtf(run_var[c + e] + BN_EPS);
+            ga[e] = gamma[c + e]; be[e] = beta[c + e];
+        }
+    };
+    const size_t first = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (FIXED && first < total4) load((int)(first % c4n) * 4);
+    for (size_t i = first; i < total4; i += (size_t)gridDim.x * 256) {
+        if (!FIXED) load((int)(i % c4n) * 4);
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(z + i * 4);
+        f32x4 r = f32x4{0.f, 0.f, 0.f, 0.f}, o;
+        if (res) r = *reinterpret_cast<const f32x4 *>(res + i * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float t = (v[e] - m[e]) * rs[e] * ga[e] + be[e];
+            if (res) t += r[e];
+            o[e] = relu ? fmaxf(t, 0.f) : t;
+        }
+        *reinterpret_cast<f32x4 *>(y + i * 4) = o;
+    }
+}
+
+constexpr int BF_C4 = 16, BF_RL = 16;             // 16 threads of 4 channels x 16 row lanes
+struct BnFrozenBwd {
+    const float *z, *y, *dy, *gamma, *mean, *rstd;
+    float *dz, *dres, *part;                      // part: [split][2][C]
+    int64_t rows;
+    int C, relu, accumulate;
+};
+
+__global__ __launch_bounds__(256) void bn_frozen_backward_kernel(BnFrozenBwd p) {
+    __shared__ f32x4 sm[2][BF_RL][BF_C4];
+    const int cl = threadIdx.x & (BF_C4 - 1), rl = threadIdx.x >> 4;
+    const int c = (blockIdx.x * BF_C4 + cl) * 4;
+    const int64_t r0 = (int64_t)blockIdx.y * BN_CHUNK, r1 = min(r0 + BN_CHUNK, p.rows);
+    f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
+    if (c < p.C) {                                // (C % 4 == 0: channels c .. c + 3 exist together)
+        float m[4], rs[4], k[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { m[e] = p.mean[c + e]; rs[e] = p.rstd[c + e]; k[e] = p.gamma[c + e] * rs[e]; }
+#pragma unroll 2
+        for (int64_t r = r0 + rl; r < r1; r += BF_RL) {
+            const size_t i = (size_t)r * p.C + c;
+            const f32x4 zv = *reinterpret_cast<const f32x4 *>(p.z + i), gv = *reinterpret_cast<const f32x4 *>(p.dy + i);
+            f32x4 yv = f32x4{1.f, 1.f, 1.f, 1.f}, rv = f32x4{0.f, 0.f, 0.f, 0.f}, o;
+            if (p.relu) yv = *reinterpret_cast<const f32x4 *>(p.y + i);
+            if (p.dres && p.accumulate) rv = *reinterpret_cast<const f32x4 *>(p.dres + i);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float g = yv[e] > 0.f ? gv[e] : 0.f;
+                s0[e] += g;
+                s1[e] += g * ((zv[e] - m[e]) * rs[e]);
+                o[e] = k[e] * g;
+                rv[e] += g;
+            }
+            *reinterpret_cast<f32x4 *>(p.dz + i) = o;
+            if (p.dres) *reinterpret_cast<f32x4 *>(p.dres + i) = rv;
+        }
+    }
+    sm[0][rl][cl] = s0; sm[1][rl][cl] = s1;
+    __syncthreads();
+    if (rl < 2 && c < p.C) {
+        const f32x4 (*a)[BF_C4] = sm[rl];
+        const f32x4 v = (((a[0][cl] + a[1][cl]) + (a[2][cl] + a[3][cl])) + ((a[4][cl] + a[5][cl]) + (a[6][cl] + a[7][cl]))) +
+                        (((a[8][cl] + a[9][cl]) + (a[10][cl] + a[11][cl])) + ((a[12][cl] + a[13][cl]) + (a[14][cl] + a[15][cl])));
+        float *out = p.part + ((size_t)blockIdx.y * 2 + rl) * p.C + c;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[e] = v[e];
+    }
+}
+
+// grads += pass: one fp32 addition per element (the gradient accumulation of pvr_trainer_backward_acc)
+__global__ __launch_bounds__(256) void grad_add_kernel(float *__restrict__ g, const float *__restrict__ s, size_t n) {
+    const size_t n4 = n / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+        const f32x4 a = *reinterpret_cast<const f32x4 *>(g + i * 4), b = *reinterpret_cast<const f32x4 *>(s + i * 4);
+        *reinterpret_cast<f32x4 *>(g + i * 4) = a + b;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) g[n4 * 4 + threadIdx.x] += s[n4 * 4 + threadIdx.x];
+}
+
+pvr_status launch_grad_add(float *grads, const float *pass, int64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(grad_add_kernel, dim3(ew_blocks((size_t)(n + 3) / 4)), dim3(256), 0, st, grads, pass, (size_t)n);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------------------
 // weight layouts
 // ------------------------------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pack_conv_weights_kernel(const float *__restrict__ w, float *__restrict__ out, int cout, int cin, int k, int rows_pad, int flip) {
@@ -457,6 +568,54 @@ pvr_status pvr_op_bn_train_backward(const float *z, const float *y, const float 
     const size_t total4 = (size_t)rows * c / 4;
     hipLaunchKernelGGL(bn_backward_apply_kernel, dim3(ew_blocks(total4)), dim3(256), 0, st, z, y, dy, gamma, mean, rstd, sums, dz, dres, dres_accumulate, total4, c,
                        relu, 1.0f / (float)rows);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status bn_frozen_check(const char *what, int64_t rows, int c) {
+    PVR_REQUIRE(rows >= 1 && c > 0 && c % 4 == 0, "%s: %lld rows of %d channels (rows >= 1 and c %% 4 == 0)", what, (long long)rows, c);
+    PVR_REQUIRE(rows * c < (1ll << 40) && rows / BN_CHUNK < 65535, "%s: %lld rows are more than one launch takes", what, (long long)rows);
+    return PVR_OK;
+}
+
+pvr_status pvr_op_bn_frozen_forward(const float *z, const float *res, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                    float *y, float *mean_out, float *rstd_out, int64_t rows, int32_t c, int32_t relu, void *stream) {
+    PVR_REQUIRE(z && gamma && beta && run_mean && run_var && y && mean_out && rstd_out, "pvr_op_bn_frozen_forward: null argument");
+    pvr_status s;
+    if ((s = bn_frozen_check("pvr_op_bn_frozen_forward", rows, c))) return s;
+    const size_t total4 = (size_t)rows * c / 4;
+    // a grid whose stride (blocks * 256 float4s) is a multiple of the c / 4 channel groups of a row keeps a thread on the same four channels
+    int blocks = ew_blocks(total4);
+    int per = c / 4, a = per, b = 256;
+    while (b) { const int t = a % b; a = b; b = t; }
+    per /= a;                                     // blocks must be a multiple of (c / 4) / gcd(c / 4, 256)
+    const bool fixed = blocks >= per;
+    if (fixed) blocks -= blocks % per;
+    if (fixed)
+        hipLaunchKernelGGL(bn_frozen_apply_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, res, gamma, beta, run_mean, run_var, y, mean_out,
+                           rstd_out, total4, c, relu);
+    else
+        hipLaunchKernelGGL(bn_frozen_apply_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, res, gamma, beta, run_mean, run_var, y, mean_out,
+                           rstd_out, total4, c, relu);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+pvr_status pvr_op_bn_frozen_backward(const float *z, const float *y, const float *dy, const float *gamma, const float *mean, const float *rstd, float *dz,
+                                     float *dres, int32_t dres_accumulate, float *dgamma, float *dbeta, int64_t rows, int32_t c, int32_t relu, float *scratch,
+                                     int64_t scratch_floats, void *stream) {
+    PVR_REQUIRE(z && dy && gamma && mean && rstd && dz && dgamma && dbeta && (y || !relu), "pvr_op_bn_frozen_backward: null argument");
+    pvr_status s;
+    if ((s = bn_frozen_check("pvr_op_bn_frozen_backward", rows, c))) return s;
+    PVR_REQUIRE(scratch && scratch_floats >= pvr_op_bn_scratch_floats(rows, c), "pvr_op_bn_frozen_backward: scratch of %lld floats, pvr_op_bn_scratch_floats asks for %lld",
+                (long long)scratch_floats, (long long)pvr_op_bn_scratch_floats(rows, c));
+    hipStream_t st = (hipStream_t)stream;
+    const int nsplit = bn_splits(rows);
+    float *sums = scratch + (size_t)nsplit * 2 * c;
+    BnFrozenBwd r{z, y, dy, gamma, mean, rstd, dz, dres, scratch, rows, c, relu, dres_accumulate};
+    BnFin f{scratch, nsplit, c, rows, nullptr, nullptr, nullptr, nullptr, sums, dgamma, dbeta, nullptr};
+    hipLaunchKernelGGL(bn_frozen_backward_kernel, dim3((c / 4 + BF_C4 - 1) / BF_C4, nsplit), dim3(256), 0, st, r);
+    hipLaunchKernelGGL(bn_finalize_kernel<2>, dim3((c + 255) / 256), dim3(256), 0, st, f);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }

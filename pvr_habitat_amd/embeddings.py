@@ -384,13 +384,14 @@ _TRAINABLE_MSG = ("trainable (train=True) are the torchvision ResNet trunks: 're
 class _EncoderFunction(torch.autograd.Function):
     """Training-mode forward of the whole encoder as one autograd node (the pattern of models._PolicyFunction).  Inputs: the module, the uint8
     frames, then every parameter, so autograd routes a gradient to each of them.  The library keeps the activations of ONE forward: a backward
-    after a later training forward of the same module raises."""
+    after a later training forward of the same module raises.  The node keeps the uint8 frames (tiny next to an activation): with frozen BatchNorm
+    a forward of more than max_batch frames ran as several passes, and the backward recomputes every pass but the last."""
 
     @staticmethod
     def forward(ctx, model, frames_u8, *params):
         out = model._forward_raw(frames_u8)
         model._fwd_gen += 1
-        ctx.model, ctx.gen = model, model._fwd_gen
+        ctx.model, ctx.gen, ctx.frames = model, model._fwd_gen, frames_u8
         return out
 
     @staticmethod
@@ -401,8 +402,8 @@ class _EncoderFunction(torch.autograd.Function):
                                'encoder overwrote them (one backward per forward, right after it)')
         dout = dout.contiguous().float()
         g = torch.empty_like(m._flat)
-        vp = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(_lib.lib().pvr_trainer_backward(m._handle, vp(m._flat), vp(dout), dout.stride(0), vp(g), _lib.stream_ptr()))
+        m._backward_raw(ctx.frames, dout, g)
+        ctx.frames = None
         return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._slots)
 
 
@@ -415,9 +416,16 @@ class HipTrainableResNet(_Node):
 
     max_batch is the largest training batch: the workspace keeps the pre-BN, post-BN and gradient tensor of EVERY convolution for that many frames
     (about 0.03 GB per frame for resnet18 and 0.14 GB per frame for resnet50), so it defaults to 32, not to the frozen encoder's 256 - size it to
-    the training batch."""
+    the training batch.
 
-    def __init__(self, state_dict, variant='conv5', max_batch=None):
+    freeze_bn: frozen BatchNorm, the usual way to fine-tune a pre-trained trunk (torch: model.train() followed by .eval() on every BatchNorm
+    module) - the convolutions and the BatchNorm affine parameters train, BatchNorm normalises with its running statistics and leaves them and
+    num_batches_tracked untouched (pvr_trainer_set_bn_frozen).  Every frame is then independent of the others and max_batch is the CHUNK: a
+    training-mode forward of n > max_batch frames runs as ceil(n / max_batch) passes in frame order, its backward recomputes each pass but the
+    last (whose activations are still held) and accumulates the gradients (pvr_trainer_backward_acc: the last pass first, then the others in frame
+    order), so the workspace is sized by the chunk and not by n.  n <= max_batch stays one forward and one backward."""
+
+    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False):
         super().__init__()
         assert variant in _TRAINABLE, variant
         _lib.require_gpu()
@@ -426,6 +434,8 @@ class HipTrainableResNet(_Node):
         self._dtype = _lib.PVR_F32
         self._max_batch = int(max_batch or 32)
         self._fwd_gen = 0
+        self._freeze_bn = False
+        self._acc_scratch = None                 # one pass's gradient (a chunked backward only), made on first use
         self._frozen = []                        # the eval-mode plan, in a plain list: not a sub-module (its tensors are no part of state_dict())
         L = _lib.lib()
         tr = transforms_for('')
@@ -467,6 +477,8 @@ class HipTrainableResNet(_Node):
         missing = sum(n for _, n, _ in self._slots) != self._flat.numel()
         if missing:                               # (the reference asserts missing_keys == [], moco.py:24)
             raise KeyError("trainable '%s' encoder: the state_dict does not hold every parameter" % variant)
+        if freeze_bn:
+            self.set_bn_frozen(True)
 
     # -- lifetime ------------------------------------------------------------------------------
     def close(self):
@@ -496,6 +508,20 @@ class HipTrainableResNet(_Node):
     def max_batch(self):
         return self._max_batch
 
+    @property
+    def freeze_bn(self):
+        return self._freeze_bn
+
+    def set_bn_frozen(self, on=True):
+        """frozen BatchNorm on / off (see the class docstring); a training forward still waiting for its backward loses its activations"""
+        _lib.check(_lib.lib().pvr_trainer_set_bn_frozen(self._handle, 1 if on else 0))
+        self._freeze_bn = bool(on)
+        self._fwd_gen += 1
+
+    def _passes(self, n):
+        """[(lo, hi)] of the passes of a training forward of n frames, in frame order"""
+        return [(lo, min(lo + self._max_batch, n)) for lo in range(0, n, self._max_batch)]
+
     def workspace_bytes(self):
         """device bytes of the training workspace the first forward allocates for max_batch frames (pvr_trainer_workspace_bytes)"""
         return int(_lib.lib().pvr_trainer_workspace_bytes(self._handle))
@@ -524,14 +550,39 @@ class HipTrainableResNet(_Node):
     def _forward_raw(self, frames_u8):
         n, h, w, c = frames_u8.shape
         assert c == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and frames_u8.is_contiguous()
-        if n > self._max_batch:
+        if n > self._max_batch and not self._freeze_bn:
             raise ValueError('training forward of %d frames: the workspace was made for max_batch = %d (BatchNorm takes the whole batch together, '
                              'it cannot be chunked)' % (n, self._max_batch))
         out = torch.empty((n, self.out_size), dtype=torch.float32, device=frames_u8.device)
-        vp = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(_lib.lib().pvr_trainer_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8), n, h, w, vp(out), out.stride(0),
-                                                  _lib.stream_ptr()))
+        for lo, hi in self._passes(n):            # (one pass unless BatchNorm is frozen; the last pass's activations stay held)
+            self._forward_pass(frames_u8, lo, hi, out[lo:hi])
         return out
+
+    def _forward_pass(self, frames_u8, lo, hi, out):
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().pvr_trainer_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8[lo:hi]), hi - lo, frames_u8.shape[1],
+                                                  frames_u8.shape[2], vp(out), out.stride(0), _lib.stream_ptr()))
+
+    def _backward_raw(self, frames_u8, dout, grads):
+        """d(loss)/d(embeddings) of the training forward that just ran on frames_u8 -> the flat gradient `grads` (fully written).  One pass: one
+        pvr_trainer_backward.  Several (frozen BatchNorm): the last pass first - its activations are still held - then every other pass in frame
+        order, each recomputed and added by pvr_trainer_backward_acc."""
+        L = _lib.lib()
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        passes = self._passes(frames_u8.shape[0])
+        assert dout.shape[0] == frames_u8.shape[0] and dout.stride(1) == 1
+        if len(passes) == 1:
+            _lib.check(L.pvr_trainer_backward(self._handle, vp(self._flat), vp(dout), dout.stride(0), vp(grads), _lib.stream_ptr()))
+            return
+        if self._acc_scratch is None:
+            self._acc_scratch = torch.empty_like(self._flat)
+        sc = self._acc_scratch
+        again = torch.empty((self._max_batch, self.out_size), dtype=torch.float32, device=dout.device)       # the recomputed embeddings are not used
+        for i, (lo, hi) in enumerate(passes[-1:] + passes[:-1]):
+            if i:
+                self._forward_pass(frames_u8, lo, hi, again[:hi - lo])
+            _lib.check(L.pvr_trainer_backward_acc(self._handle, vp(self._flat), vp(dout[lo:hi]), dout.stride(0), vp(grads), 1 if i else 0, vp(sc), sc.numel(),
+                                                  _lib.stream_ptr()))
 
     def forward(self, frames_u8):
         if self.training:
@@ -569,7 +620,7 @@ def trainer_workspace_bytes(embedding_name, max_batch):
         L.pvr_trainer_destroy(h)
 
 
-def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False):
+def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -580,7 +631,7 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
         raise ValueError("train=True computes in fp32 (compute_dtype None or 'f32'), got %r" % (compute_dtype,))
     sd, variant = _load_named_state_dict(embedding_name, pretrained)
-    return HipTrainableResNet(sd, variant, max_batch=max_batch)
+    return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn)
 
 
 class UberModel(nn.Module):
@@ -775,7 +826,7 @@ class EmbeddingNet(nn.Module):
     """
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
-                 compute_dtype=None, max_batch=None, chunk=None, crops=1):
+                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -787,8 +838,11 @@ class EmbeddingNet(nn.Module):
         self._host = bool(disable_cuda)
         if crops == 5 and train:
             raise NotImplementedError('train=True with crops=5: the 5-crop extension wraps the frozen encoder only')
-        self.embedding, self.transforms = _get_embedding(embedding_name, in_channels, pretrained, train,
-                                                         compute_dtype=compute_dtype, max_batch=max_batch, chunk=chunk, host=self._host)
+        if freeze_bn and not train:
+            raise ValueError('freeze_bn is a mode of the trainable encoder (train=True): a frozen encoder already runs on the running statistics')
+        # freeze_bn (train=True only): frozen BatchNorm, max_batch is then the chunk of a training forward (HipTrainableResNet)
+        self.embedding, self.transforms = _get_embedding(embedding_name, in_channels, pretrained, train, compute_dtype=compute_dtype, max_batch=max_batch,
+                                                         chunk=chunk, host=self._host, **({'freeze_bn': True} if freeze_bn else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)
@@ -800,6 +854,12 @@ class EmbeddingNet(nn.Module):
 
     def _forward(self, observation_u8):
         return self.embedding(observation_u8)
+
+    def set_bn_frozen(self, on=True):
+        """frozen BatchNorm of the trainable encoder on / off (HipTrainableResNet.set_bn_frozen)"""
+        if not isinstance(self.embedding, HipTrainableResNet):
+            raise NotImplementedError('set_bn_frozen: only the trainable encoder (train=True) has a BatchNorm mode; %s' % _TRAINABLE_MSG)
+        self.embedding.set_bn_frozen(on)
 
     def close(self):
         """free every library handle under this embedding now (HipResNet50.close); the module stays usable"""

@@ -10,7 +10,7 @@ identical on every rank.  Launch:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 -m pvr_habitat_amd.main_bc_finetune ...
 (`__main__` reads RANK / LOCAL_RANK / WORLD_SIZE, picks the GPU and creates the process group before the first GPU call).
 `--train_embedding` with a trainable `--embedding_name` selects end-to-end BC instead (`run_end_to_end`: EmbeddingNet(train=True) in front of
-PolicyNet, one GPU).  Interrupted runs resume, completed runs return early (main_bc_finetune.py:47-56,84-89,135-143).  Habitat evaluation needs the
+PolicyNet, one GPU; `--freeze_embedding_bn [--embedding_chunk N]` trains on the running BatchNorm statistics in passes of N frames, at any T x B).  Interrupted runs resume, completed runs return early (main_bc_finetune.py:47-56,84-89,135-143).  Habitat evaluation needs the
 simulator: pass `make_env` as in main_bc_2.run."""
 import os
 import pickle
@@ -64,6 +64,8 @@ def check_workspace_fits(flags, n_frames_per_obs):
     is allocated, so that the error names a size that fits instead of an allocation failing inside the first step."""
     from .embeddings import trainer_workspace_bytes
     want = flags.unroll_length * flags.batch_size * n_frames_per_obs
+    if getattr(flags, 'freeze_embedding_bn', False):
+        return check_chunk_fits(flags, want)
     need = trainer_workspace_bytes(flags.embedding_name, want)
     free = int(torch.cuda.mem_get_info()[0])
     if need is None or need > free:
@@ -74,6 +76,34 @@ def check_workspace_fits(flags, n_frames_per_obs):
                            "the largest unroll_length x batch_size x frames that fits is %d (unroll_length <= %d at this batch_size)"
                            % (flags.embedding_name, flags.unroll_length, flags.batch_size, n_frames_per_obs, want, why, fit,
                               fit // (flags.batch_size * n_frames_per_obs)))
+    return need
+
+
+def check_chunk_fits(flags, want):
+    """--freeze_embedding_bn: frames are independent and a step of `want` frames runs as passes of --embedding_chunk frames, so it is the CHUNK's
+    workspace that has to fit.  Without --embedding_chunk the chunk is the largest frame count <= want that the trainer admits and whose workspace
+    fits nine tenths of the free device memory (the policy's workspace, the batch, the embeddings and one pass's gradient live next to it).  A given
+    chunk is compared with the free memory and the trainer's limit as it is, and the error names the largest chunk that fits.  The resolved chunk
+    is written back to flags.embedding_chunk (a checkpoint's flags carry it); returns the chunk's workspace bytes."""
+    from .embeddings import trainer_workspace_bytes
+    free = int(torch.cuda.mem_get_info()[0])
+    chunk = getattr(flags, 'embedding_chunk', None)
+    if chunk is None:
+        chunk = largest_fitting_frames(flags.embedding_name, want, free // 10 * 9)
+        if chunk < 1:
+            raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for a chunk of one frame takes %.2f GB, %.2f GB "
+                               "of device memory are free" % (flags.embedding_name, trainer_workspace_bytes(flags.embedding_name, 1) / 2 ** 30, free / 2 ** 30))
+    if chunk < 1:
+        raise ValueError('--embedding_chunk %d: a pass takes at least one frame' % chunk)
+    chunk = min(int(chunk), want)
+    need = trainer_workspace_bytes(flags.embedding_name, chunk)
+    if need is None or need > free:
+        fit = largest_fitting_frames(flags.embedding_name, chunk, free)
+        why = 'is more than the trainer\'s launches can address (one tensor of its workspace would pass 2 GiB)' if need is None \
+            else 'takes %.2f GB, %.2f GB of device memory are free' % (need / 2 ** 30, free / 2 ** 30)
+        raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for --embedding_chunk %d frames %s; the largest "
+                           "--embedding_chunk that fits is %d" % (flags.embedding_name, chunk, why, fit))
+    flags.embedding_chunk = chunk
     return need
 
 
@@ -128,7 +158,13 @@ def run_end_to_end(flags, make_env=None):
         'actions in the data (%d..%d) do not fit num_actions=%d' % (int(np.min(action)), int(np.max(action)), n_actions)
     T, B = flags.unroll_length, flags.batch_size
     check_workspace_fits(flags, n_f)
-    net = E.EmbeddingNet(flags.embedding_name, pretrained=flags.pretrained_embedding, train=True, max_batch=T * B * n_f)
+    if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
+        if not flags.pretrained_embedding:
+            print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')
+        print('  ', 'frozen BatchNorm:', T * B * n_f, 'frames per step in passes of', flags.embedding_chunk)
+        net = E.EmbeddingNet(flags.embedding_name, pretrained=flags.pretrained_embedding, train=True, freeze_bn=True, max_batch=flags.embedding_chunk)
+    else:
+        net = E.EmbeddingNet(flags.embedding_name, pretrained=flags.pretrained_embedding, train=True, max_batch=T * B * n_f)
     model = PolicyNetWithEncoder(net, n_actions, flags.batch_norm, num_frames=n_f, max_unroll=T, max_batch=B)
     max_epochs = flags.max_frames // (T * B) + 1
     if fused:

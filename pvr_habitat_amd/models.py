@@ -696,7 +696,8 @@ class HipAdam(_HipOptimizer):
 class PolicyNetWithEncoder(nn.Module):
     """End-to-end BC model (reference main_bc_finetune.py with `--train_embedding`: EmbeddingNet(train=True) in front of PolicyNet): raw uint8
     (T, B, H, W, 3F) observations -> the trainable encoder on every frame -> the F embeddings of an observation side by side -> PolicyNet.
-    Output as PolicyNet.forward.  `embedding_net` is an EmbeddingNet(..., train=True, max_batch >= T*B*F) (or its HipTrainableResNet).
+    Output as PolicyNet.forward.  `embedding_net` is an EmbeddingNet(..., train=True, max_batch >= T*B*F) (or its HipTrainableResNet); with
+    freeze_bn=True its max_batch is the chunk and may be smaller than T*B*F.
 
     The frames are split on the device into (T*B*F, H, W, 3) in (observation, frame) order, so the trainer's contiguous (T*B*F, D) output IS the
     (T*B, F*D) observation matrix: the layout of the reference's np.split / np.concatenate(..., -1) (save_embedded_obs.py:153-155).  BatchNorm2d
@@ -748,7 +749,11 @@ class HipJointRMSprop(object):
     """clip_grad_norm_ over ALL parameters + torch.optim.RMSprop(momentum 0) + LambdaLR(1 - epoch/max_epochs) for a PolicyNetWithEncoder, fused with
     the forward / backward of the BC loss: `step` is four library calls and no autograd graph - the trainer's forward, pvr_policy_backward_dobs
     (policy forward, loss, BPTT, d(loss)/d(obs)), pvr_trainer_backward on that gradient, and pvr_joint_apply_rmsprop over (the policy's trainable
-    prefix, the encoder's flat buffer) with ONE norm.  Eager launches (not captured in a graph).  `scheduler_step()` as HipRMSprop."""
+    prefix, the encoder's flat buffer) with ONE norm.  Eager launches (not captured in a graph).  `scheduler_step()` as HipRMSprop.
+
+    With a frozen-BatchNorm encoder (EmbeddingNet(..., train=True, freeze_bn=True, max_batch=chunk)) of fewer than T*B*F frames per pass the same
+    flow is chunked: the trainer's forward in passes to the (T*B*F, D) matrix, one pvr_policy_backward_dobs, the recompute + pvr_trainer_backward_acc
+    of every pass into the encoder's gradient (HipTrainableResNet._backward_raw), one pvr_joint_apply_rmsprop."""
 
     def __init__(self, model, lr=1e-4, alpha=0.99, eps=1e-5, momentum=0, max_grad_norm=40.0, max_epochs=None):
         if float(momentum) != 0:
@@ -804,7 +809,7 @@ class HipJointRMSprop(object):
             g = self._grads
             pol._checked(L.pvr_policy_backward_dobs(pol._handle, vp(pol._flat), C.byref(bn) if bn else None, vp(emb), vp(d), vp(a), T, B,
                                                     vp(g['policy']), vp(stats), None, vp(dobs), _lib.stream_ptr()))
-            _lib.check(L.pvr_trainer_backward(enc._handle, vp(enc._flat), vp(dobs), dobs.stride(0), vp(g['embedding']), _lib.stream_ptr()))
+            enc._backward_raw(frames, dobs, g['embedding'])                   # one pvr_trainer_backward, or the chunk walk of a frozen-BatchNorm encoder
             arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
             counts = (C.c_int64 * 2)(pol._n_train, enc._flat.numel())
             _lib.check(L.pvr_joint_apply_rmsprop(2, arr((pol._flat, enc._flat)), arr((self.square_avg['policy'], self.square_avg['embedding'])),
