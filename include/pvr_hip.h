@@ -166,13 +166,12 @@ pvr_status pvr_encoder_check_range(pvr_encoder *enc, const uint8_t *frames_dev, 
                                    void *hip_stream, int32_t *first_bad);
 /* Debug / A-B: the run-time switches of a finalized encoder - "pool_fuse" (the trunk's last convolution writes the average pool itself), "stem_u8" (the
  * fused stem reads uint8 frames that need no resize), "frame_min_n" (frames per forward from which layer3 runs one workgroup per frame), "frame_run" /
- * "frame_stagger" (layer3.1 .. 3.5 as one launch), "conv_algo" (the kernel of the shape-dispatched convolutions, as pvr_debug_set_conv_algo), "frame64"
- * (the tiling of the whole-bottleneck frame launches, as pvr_debug_set_frame64), "stem_regpool" (1 the fused stem's max pool in registers, 0 the LDS-tile
- * pooling of rounds 3-5; same bits).  Every other PVR_* switch shapes the plan and is read from the environment ONCE, in pvr_encoder_create; nothing
+ * "frame_stagger" (layer3.1 .. 3.5 as one launch), "conv_algo" (the kernel of the shape-dispatched convolutions, as pvr_debug_set_conv_algo), "stem_regpool" (1 the fused stem's max pool in registers,
+ * 0 the LDS-tile pooling of rounds 3-5; same bits).  Every other PVR_* switch shapes the plan and is read from the environment ONCE, in pvr_encoder_create; nothing
  * reads the environment on the forward path. */
 pvr_status pvr_encoder_debug_set_switch(pvr_encoder *enc, const char *name, int32_t value);
 /* Which kernel family launch `index` (pvr_encoder_launch_name's indices) runs as in a forward of n frames, e.g. "bneck_frame(front1)", "conv_wfrag(pool)",
- * "conv_pp256(dual)", "chain_wave" / "chain_wave128" / "bottleneck_chain" (the three forms of the fused bottleneck tail), "conv_split16", "conv" (the shape-dispatched implicit GEMMs).  The plan and this choice,
+ * "conv_pp256(dual)", "chain_wave" / "bottleneck_chain" (the two forms of the fused bottleneck tail), "conv_split16", "conv" (the shape-dispatched implicit GEMMs).  The plan and this choice,
  * tabulated per batch size, are made in pvr_encoder_create from the desc and the PVR_* switches alone (no weights, no device), so the handle need not be
  * finalized; returns the name's length, 0 past the end of the plan. */
 int32_t pvr_encoder_launch_kernel(const pvr_encoder *enc, int32_t n, int32_t index, char *buf, int32_t cap);
@@ -237,15 +236,6 @@ pvr_status pvr_debug_bneck_frame_stamps(const void *t1_dev, const void *w2_dev, 
                                         const void *w1f_dev, const float *b1f_dev, int32_t n, int32_t dtype, uint64_t *stamps_dev, void *hip_stream);
 /* launches of that kernel so far (tests: the layer3 plan really took it) */
 int64_t pvr_debug_bneck_frame_launches(void);
-/* round 6: which kernel runs the whole-bottleneck form (w1f given; torchvision Bottleneck conv1 -> conv2 -> conv3 + identity reached from reference
- * src/embeddings.py:118-120): 1 bneck_frame64.hip (one wave per SIMD, 64 output channels x 13 pixel tiles per wave: half the LDS reads per MFMA), 0 the
- * 32-channel tiling of round 5, -1 back to the environment (PVR_FRAME64, default 0: bit-identical, measured slower).  Both give the same bits.  Sets the
- * pvr_op_* calls' choice only (process-wide); an encoder handle reads PVR_FRAME64 at create and changes it with pvr_encoder_debug_set_switch("frame64"). */
-pvr_status pvr_debug_set_frame64(int32_t mode);
-int64_t pvr_debug_bneck_frame64_launches(void);
-/* the 64-channel tiling with s_memtime stamps of workgroup 8, wave 0 (8 x uint64 on the device) - diagnostics only */
-pvr_status pvr_debug_bneck_frame64_stamps(const void *w1f_dev, const float *b1f_dev, const void *w2_dev, const float *b2_dev, const void *w3_dev, const float *b3_dev,
-                                          const void *x_dev, void *y_dev, int32_t n, int32_t dtype, uint64_t *stamps_dev, void *hip_stream);
 /* pvr_op_conv2d's convolution for small pixel counts and deep K (layer4 at batch 256; conv_wfrag.hip): 112-pixel x 256-cout tiles, the weight operand read
  * from L2 as whole MFMA fragments.  wgt_packed: pvr_op_pack_frag_weights of the (cout, kh*kw*cin) matrix; cin % 64 == 0, cout % 256 == 0, kh == kw <= 3,
  * relu 0 / 1, residual 16-bit or NULL, out_f32 0 / 1.  Bit-identical to pvr_op_conv2d. */
@@ -287,10 +277,6 @@ pvr_status pvr_op_stem_split16(const float *img_padded_dev, const void *wgt_spli
                                void *hip_stream);
 /* launches of that kernel so far (tests: one per chunk of a PVR_F32S forward) */
 int64_t pvr_debug_stem_split16_launches(void);
-/* launches of the layer2 wave-form tail (chain_wave128.hip: torchvision Bottleneck conv2 -> conv3 + identity -> the next conv1 at Cm = 128, reference
- * src/embeddings.py:118-120) so far (tests: the layer2 plan really took it).  The form is opt-in: PVR_CHAIN_WAVE_L2=1 at pvr_encoder_create selects it,
- * the default (0) keeps the block form. */
-int64_t pvr_debug_chain_wave128_launches(void);
 /* debug / A-B: which implicit-GEMM kernel pvr_op_conv2d uses.  -1 = automatic choice by shape (default), 0 = conv_igemm (128x128 tiles) only,
  * 1 / 2 / 3 = conv_pp256 (ping-pong kernel, 256x256 / 128x256 / 224x256 tiles) whenever it accepts the shape.  All kernels accumulate every output in
  * the same K order and give bit-identical results.  Sets the pvr_op_* calls' choice only (process-wide); an encoder handle reads PVR_CONV_ALGO at create

@@ -65,9 +65,6 @@ _SIGS = {
     'pvr_debug_convert': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]),
     'pvr_op_bneck_frame': (C.c_int, [C.c_void_p] * 13 + [C.c_int32] * 3 + [C.c_void_p]),
     'pvr_debug_bneck_frame_launches': (C.c_int64, []),
-    'pvr_debug_set_frame64': (C.c_int, [C.c_int32]),
-    'pvr_debug_bneck_frame64_launches': (C.c_int64, []),
-    'pvr_debug_bneck_frame64_stamps': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 2 + [C.c_void_p] * 2),
     'pvr_op_conv_wfrag': (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 12 + [C.c_void_p]),
     'pvr_debug_conv_wfrag_launches': (C.c_int64, []),
     'pvr_op_conv_wfrag_pool': (C.c_int, [C.c_void_p] * 5 + [C.c_int64] + [C.c_int32] * 4 + [C.c_void_p]),
@@ -83,7 +80,6 @@ _SIGS = {
     'pvr_debug_conv_split16_launches': (C.c_int64, []),
     'pvr_op_stem_split16': (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 2 + [C.c_void_p]),
     'pvr_debug_stem_split16_launches': (C.c_int64, []),
-    'pvr_debug_chain_wave128_launches': (C.c_int64, []),
     'pvr_op_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     'pvr_op_layernorm': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     'pvr_op_cls_head': (C.c_int, [C.c_void_p] * 5 + [C.c_int64] + [C.c_int32] * 4 + [C.c_float, C.c_void_p]),

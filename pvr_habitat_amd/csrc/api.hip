@@ -48,7 +48,6 @@ long long bneck_frame_launches();
 long long pp_persistent_launches();
 long long conv_wfrag_launches();
 long long conv_split16_launches();
-long long chain_wave128_launches();
 pvr_status launch_split16_pack(const float *w, void *out, int rows, int K, hipStream_t stream);
 pvr_status launch_conv_split16(const float *in, const void *wsp, const float *bias, const float *res, float *out, int n, int h, int w, int cin,
                                int cout, int k, int stride, int pad, int relu, hipStream_t stream, float *out2 = nullptr, int n1 = 0, void *out16 = nullptr,
@@ -95,23 +94,6 @@ pvr_status pvr_debug_bneck_frame_stamps(const void *t1, const void *w2, const fl
     return launch_bneck_frame(op_switches(), t1, w2, b2, w3, b3, residual, y, nullptr, n, (w1n ? 7 : 3) | (w1f ? 8 : 0), dtype, (hipStream_t)stream, (unsigned long long *)stamps_dev,
                               w1n, b1n, t1n, w1f, b1f);
 }
-// round 6: which kernel runs pvr_op_bneck_frame's whole-bottleneck launches (w1f given): 1 the 64-channel tiling (bneck_frame64.hip), 0 bneck_frame_kernel<..,
-// FRONT1>, -1 back to the environment (PVR_FRAME64, default 0: bit-identical, measured slower).  Same bits either way.  The pvr_op_* calls only (op_switches);
-// an encoder handle has its own switch (pvr_encoder_debug_set_switch "frame64").
-pvr_status pvr_debug_set_frame64(int32_t mode) {
-    PVR_REQUIRE(mode >= -1 && mode <= 1, "pvr_debug_set_frame64: -1 (environment: PVR_FRAME64, default off), 0 or 1");
-    if (mode < 0) { PlanSwitches env; read_switches(env); mode = env.frame64; }
-    op_switches().frame64 = mode;
-    return PVR_OK;
-}
-int64_t pvr_debug_bneck_frame64_launches(void) { return (int64_t)bneck_frame64_launches(); }
-// the 64-channel tiling with s_memtime stamps of workgroup 8, wave 0 (8 x uint64: start, front conv1 done, conv2 loop done, t2 written, chunk 0 K loop, chunk 0
-// epilogue, all issued, stores drained) - diagnostics only
-pvr_status pvr_debug_bneck_frame64_stamps(const void *w1f, const float *b1f, const void *w2, const float *b2, const void *w3, const float *b3, const void *x, void *y,
-                                          int32_t n, int32_t dtype, uint64_t *stamps_dev, void *stream) {
-    PVR_REQUIRE(stamps_dev && n > 8, "pvr_debug_bneck_frame64_stamps: needs a stamp buffer and more than 8 frames");
-    return launch_bneck_frame64(w1f, b1f, w2, b2, w3, b3, x, y, n, dtype, (hipStream_t)stream, (unsigned long long *)stamps_dev);
-}
 // single-operator entry point of the small-M implicit-GEMM kernel with weights as L2 fragments (conv_wfrag.hip), for the op-level parity tests
 pvr_status pvr_op_conv_wfrag(const void *in, const void *wgt_packed, const float *bias, const void *residual, void *out, int32_t n, int32_t h, int32_t w,
                              int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t relu, int32_t out_f32, int32_t dtype,
@@ -156,7 +138,6 @@ pvr_status pvr_op_stem_split16(const float *img_padded, const void *wgt_split, c
     return launch_stem_split16(img_padded, wgt_split, bias, out, n, S, (hipStream_t)stream);
 }
 int64_t pvr_debug_stem_split16_launches(void) { return (int64_t)stem_split16_launches(); }
-int64_t pvr_debug_chain_wave128_launches(void) { return (int64_t)chain_wave128_launches(); }
 int64_t pvr_debug_pp_persistent_launches(void) { return (int64_t)pp_persistent_launches(); }
 
 size_t pvr_last_error(char *buf, size_t cap) {

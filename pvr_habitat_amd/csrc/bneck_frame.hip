@@ -640,11 +640,6 @@ pvr_status launch_bneck_frame(const PlanSwitches &sw, const void *t1, const void
                               void *t2_out, int n, int phases, int dtype, hipStream_t stream, unsigned long long *stamps, const void *w1np,
                               const float *b1n, void *t1n, const void *w1fp, const float *b1f) {
     const int ph = phases & 7, front = (phases & 8) != 0;
-    // the whole bottleneck (own conv1 in front) in the 64-channel tiling (bneck_frame64.hip, round 6) when sw.frame64 asks for it and no diagnostic form is
-    if (front && ph == 3 && !(phases & ~15) && !t2_out && !stamps && !w1np && w1fp && b1f && w2p && b2 && w3p && b3 && res && y && sw.frame64) {
-        ++g_bneck_frame_launches;                                 // (a per-frame bottleneck launch either way; bneck_frame64_launches() counts this tiling)
-        return launch_bneck_frame64(w1fp, b1f, w2p, b2, w3p, b3, res, y, n, dtype, stream, nullptr);
-    }
     PVR_REQUIRE(ph == 1 || ph == 3 || ph == 7, "bneck_frame: phases must be 1, 3 or 7 (+ 8: own conv1 in front; + 16 / 32: timing knock-outs of the y stores / identity loads)");
     PVR_REQUIRE((t1 || front) && w2p && b2 && (ph <= 1 || (w3p && b3 && res && y)) && (ph > 1 || t2_out) && (ph < 7 || (w1np && b1n && t1n)) &&
                 (!front || (w1fp && b1f && res && ph == 3)), "bneck_frame: null argument (the front conv1 comes with phases 3 only)");

@@ -31,7 +31,6 @@ void read_switches(PlanSwitches &sw) {
     sw.frame_front1 = get("PVR_FRAME_FRONT1", 1);
     sw.frame_next1 = get("PVR_FRAME_NEXT1", 0);
     sw.frame_bneck = get("PVR_FRAME_BNECK", 1);
-    sw.frame64 = get("PVR_FRAME64", 0);           // (measured slower: opt-in, profiles/experiments/r06_bneck_frame64.txt)
     sw.bneck_stagger = get("PVR_FRAME_STAGGER", 0);
     sw.dual_ds = get("PVR_DUAL_DS", 1);
     sw.chain_ds = get("PVR_CHAIN_DS", 1);
@@ -44,7 +43,6 @@ void read_switches(PlanSwitches &sw) {
     sw.chain_wave_halo = get("PVR_CHAIN_WAVE_HALO", 1);
     sw.chain_wave_128 = get("PVR_CHAIN_WAVE_128", 1);
     sw.strided_y = get("PVR_STRIDED_Y", 1);
-    sw.chain_wave_l2 = get("PVR_CHAIN_WAVE_L2", 0);   // (measured no faster than the block form: opt-in, profiles/experiments/r06_chain_wave128.txt)
     sw.splitk = get("PVR_SPLITK", 1);
     sw.smallk_div = get("PVR_SMALLK_DIV", 4);
     if (sw.smallk_div < 1) sw.smallk_div = 1;
@@ -224,11 +222,6 @@ static pvr_status prepare_weights(pvr_encoder *e) {
                         for (size_t c = 0; c < K; ++c) hb[(((size_t)(r >> 4) * (K / 8) + (c >> 3)) * 16 + (r & 15)) * 8 + (c & 7)] = hp[(size_t)r * K + c];
                     if ((s = enc_upload(&o.d_wpb, hb))) return s;
                 }
-            }
-            ConvOp &c2 = e->ops[l.conv2];
-            if (l.wave == 2 && !c2.d_wpk) {              // layer2 wave form: the launch's 17 weight units as LDS images
-                PVR_HIP_TRY(hipMalloc((void **)&c2.d_wpk, chain_wave128_pack_bytes()));
-                if ((s = launch_chain_wave128_pack(c2.d_w, o3.d_wp, l.next1 >= 0 ? e->ops[l.next1].d_wp : nullptr, c2.d_wpk, nullptr))) return s;
             }
         } else if (l.conv3 < 0 && l.ds >= 0) {
             // the two-operand launch: [W3 | W_downsample] rows, b3 + b_downsample
@@ -754,7 +747,7 @@ static pvr_status h16_chunk(pvr_encoder *enc, Lane &L, const uint8_t *fr, int nb
                                         c1 ? c1->d_wp : nullptr, c1 ? c1->d_b : nullptr, c1 ? L.buf[l.t1_out] : nullptr, nb,
                                         c2.h, c2.w, c2.cout, c1 ? c1->cout : 0, c2.stride, dt, st,
                                         cd ? L.buf[cd->in_buf] : nullptr, cd ? cd->d_wp : nullptr, op.d_wpb, cd ? cd->d_wpb : nullptr,
-                                        l.wave, cd ? (l.in_blk && t1_blocked) : l.in_blk, l.out_blk, c2.d_wpk, kind == LK_CHAIN_YS2);
+                                        l.wave, cd ? (l.in_blk && t1_blocked) : l.in_blk, l.out_blk, kind == LK_CHAIN_YS2);
             t1_blocked = false;
             break;
         }
@@ -1008,7 +1001,7 @@ pvr_status pvr_encoder_debug_set_fusion(pvr_encoder *enc, int32_t on) {
 }
 
 // The switches of a finalized encoder that do not shape its plan (PlanSwitches, "live"): pool_fuse, stem_u8, frame_min_n, frame_run, frame_stagger,
-// conv_algo, frame64, stem_regpool.  The A/B tests flip them between two forwards of ONE handle; everything else is fixed by the environment at
+// conv_algo, stem_regpool.  The A/B tests flip them between two forwards of ONE handle; everything else is fixed by the environment at
 // pvr_encoder_create.
 pvr_status pvr_encoder_debug_set_switch(pvr_encoder *enc, const char *name, int32_t value) {
     PVR_REQUIRE(enc && name, "pvr_encoder_debug_set_switch: null argument");
@@ -1019,10 +1012,9 @@ pvr_status pvr_encoder_debug_set_switch(pvr_encoder *enc, const char *name, int3
     else if (nm == "frame_run") enc->sw.frame_run = value;
     else if (nm == "frame_stagger") enc->sw.frame_stagger = value;
     else if (nm == "conv_algo") enc->sw.conv_algo = value;
-    else if (nm == "frame64") enc->sw.frame64 = value;
     else if (nm == "stem_regpool") enc->sw.stem_regpool = value;
     else {
-        set_error("pvr_encoder_debug_set_switch: '%s' is not a live switch (pool_fuse, stem_u8, frame_min_n, frame_run, frame_stagger, conv_algo, frame64, "
+        set_error("pvr_encoder_debug_set_switch: '%s' is not a live switch (pool_fuse, stem_u8, frame_min_n, frame_run, frame_stagger, conv_algo, "
                   "stem_regpool); plan switches are read from the environment at create", name);
         return PVR_ERR_INVALID;
     }
@@ -1120,7 +1112,7 @@ void pvr_encoder_destroy(pvr_encoder *enc) {
     if (enc->hplan) host_destroy(enc);
     if (enc->vit) vit_destroy(enc);
     if (enc->rnd) random5_destroy(enc);
-    for (auto &op : enc->ops) { if (op.d_w) (void)hipFree(op.d_w); if (op.d_wp) (void)hipFree(op.d_wp); if (op.d_wpb) (void)hipFree(op.d_wpb); if (op.d_wfb) (void)hipFree(op.d_wfb); if (op.d_wcat) (void)hipFree(op.d_wcat); if (op.d_wf) (void)hipFree(op.d_wf); if (op.d_wsp) (void)hipFree(op.d_wsp); if (op.d_wsp_pair) (void)hipFree(op.d_wsp_pair); if (op.d_b_pair) (void)hipFree(op.d_b_pair); if (op.d_wpk) (void)hipFree(op.d_wpk); if (op.d_b) (void)hipFree(op.d_b); if (op.d_bsum) (void)hipFree(op.d_bsum); }
+    for (auto &op : enc->ops) { if (op.d_w) (void)hipFree(op.d_w); if (op.d_wp) (void)hipFree(op.d_wp); if (op.d_wpb) (void)hipFree(op.d_wpb); if (op.d_wfb) (void)hipFree(op.d_wfb); if (op.d_wcat) (void)hipFree(op.d_wcat); if (op.d_wf) (void)hipFree(op.d_wf); if (op.d_wsp) (void)hipFree(op.d_wsp); if (op.d_wsp_pair) (void)hipFree(op.d_wsp_pair); if (op.d_b_pair) (void)hipFree(op.d_b_pair); if (op.d_b) (void)hipFree(op.d_b); if (op.d_bsum) (void)hipFree(op.d_bsum); }
     if (enc->d_stem_wf) (void)hipFree(enc->d_stem_wf);
     if (enc->d_stem_c1w) (void)hipFree(enc->d_stem_c1w);
     for (Lane &L : enc->lanes) lane_free(L);

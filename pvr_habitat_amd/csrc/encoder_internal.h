@@ -21,7 +21,6 @@ struct PlanSwitches {
     int frame_front1 = 1;     // PVR_FRAME_FRONT1: layer3's per-frame launches carry their own conv1
     int frame_next1 = 0;      // PVR_FRAME_NEXT1: ... carry the NEXT block's conv1 instead (measured slower)
     int frame_bneck = 1;      // PVR_FRAME_BNECK: layer3's per-frame launches (bneck_frame.hip) at all
-    int frame64 = 0;          // PVR_FRAME64 (live, opt-in: measured slower): the whole-bottleneck frame launches in the 64-channel tiling (bneck_frame64.hip)
     int bneck_stagger = 0;    // PVR_FRAME_STAGGER (EXPERIMENTS=1 builds only): odd workgroups of a single bottleneck's frame launch start late
     int dual_ds = 1;          // PVR_DUAL_DS: conv3 & downsample of layer3.0 / layer4.0 as one two-operand launch
     int chain_ds = 1;         // PVR_CHAIN_DS: layer1.0's downsample inside the chain
@@ -33,7 +32,6 @@ struct PlanSwitches {
     int chain_wave = 1;       // PVR_CHAIN_WAVE: the wave forms of the tails at all (0: every tail on the block form; bit-identical)
     int chain_wave_halo = 1;  // PVR_CHAIN_WAVE_HALO: the wave form reads blocked inputs through the halo registers (0: the per-K-step load ring)
     int chain_wave_128 = 1;   // PVR_CHAIN_WAVE_128: the wave form for layer1's last tail (next conv1 128 wide)
-    int chain_wave_l2 = 0;    // PVR_CHAIN_WAVE_L2 (opt-in: measured no faster): layer2's stride-1 tails on their wave form (chain_wave128.hip)
     int strided_y = 1;        // PVR_STRIDED_Y: a tail whose y is read only by a 1x1 stride-2 downsample stores just those pixels (layer1.2 -> layer2.0; bit-identical)
     int splitk = 1;           // PVR_SPLITK: planned split-K of the *_l4 head
     int smallk_div = 4;       // PVR_SMALLK_DIV: K slices per block of the low-latency plan
@@ -56,7 +54,7 @@ struct PlanSwitches {
     int pp_persist = 384;     // PVR_PP_PERSIST: tiles per launch from which conv_pp256 runs persistent (0 never)
 };
 void read_switches(PlanSwitches &sw);
-PlanSwitches &op_switches();   // the pvr_op_* entry points' instance: read_switches on first use; pvr_debug_set_conv_algo / _frame64 change it
+PlanSwitches &op_switches();   // the pvr_op_* entry points' instance: read_switches on first use; pvr_debug_set_conv_algo changes it
 
 pvr_status launch_preprocess(const uint8_t *, int, int, int, int, int, void *, int, hipStream_t, int crop_pos = 0);
 pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
@@ -103,10 +101,6 @@ struct BFBlk {
     unsigned short *y;
 };
 pvr_status launch_bneck_frame_run(const BFBlk *blocks, int nblk, int n, int dtype, hipStream_t stream, int stagger);
-// bneck_frame64.hip (round 6): the whole bottleneck per frame with ONE wave per SIMD, 64 output channels x 13 pixel tiles per wave (half the LDS reads per MFMA)
-pvr_status launch_bneck_frame64(const void *w1p, const float *b1, const void *w2p, const float *b2, const void *w3p, const float *b3, const void *x, void *y, int n,
-                                int dtype, hipStream_t stream, unsigned long long *stamps);
-long long bneck_frame64_launches();
 
 // conv_wfrag.hip: implicit GEMM in 112-pixel x 256-cout tiles with the weights read from L2 as MFMA fragments (layer4 at batch 256)
 bool conv_wfrag_supported(int64_t M, int64_t in_bytes, int cin, int cout, int kh, int kw, int pad, int act, int out_f32);
@@ -145,7 +139,6 @@ struct ConvOp {
     u16 *d_wpb = nullptr;          // ... and that copy in the blocked layout [row >> 4][cin >> 3][row & 15][8] (chain_wave.hip reads W3 / Wd pieces from L2)
     std::vector<u16> h_w;          // host copy, kept until finalize has built the packed copies (prepare_weights)
     float *d_wf = nullptr;         // fp32 weights (PVR_F32 mode; PVR_F32S: only until finalize has packed d_wsp from them)
-    u16 *d_wpk = nullptr;          // conv2 of a layer2 wave-form tail: the launch's 17 weight units as LDS images (chain_wave128.hip: launch_chain_wave128_pack)
     u16 *d_wsp_pair = nullptr;     // compression head: [conv1 ; downsample] rows as ONE split weight image (both read the same fp32 input: one launch, round 6)
     float *d_b_pair = nullptr;
     u16 *d_wsp = nullptr;          // fp32 weights as (hi, lo) f16 fragment pairs (conv_split16.hip: the f32op convolutions of an f16 plan)
@@ -164,12 +157,12 @@ struct Launch {
     int ds = -1;                              // chain: the block's downsample convolution, accumulated inside conv3 (no launch of its own);
                                               // with conv3 < 0: ops[conv2] is a conv3 that runs as conv_pp256's two-operand launch with ops[ds] (layer3.0 / layer4.0)
     int t1_in = B_NONE, t1_out = B_NONE;      // chain: buffer holding conv2's input / receiving the next block's conv1 output
-    int wave = 0;                             // chain: 1 the wave form runs it (chain_wave.hip), 2 the layer2 wave form (chain_wave128.hip)
+    int wave = 0;                             // chain: 1 the wave form runs it (chain_wave.hip), 0 the block form
     int conv1 = -1;                           // per-frame form: the block's own conv1 runs in front, inside the launch (the launch reads the block input)
     int frame = 0;                            // per-frame form (bneck_frame.hip, layer3): conv2 -> conv3 + residual [-> next1] of one 14 x 14 image per workgroup
     int pair = -1;                            // conv_split16 pair form: ops[conv2] and ops[pair] read the same fp32 input and run as one launch (the compression head)
     int in_blk = 0, out_blk = 0;              // chain, wave form: t1 + residual / y + t1' travel in the blocked layout between two such launches (chain_wave.hip);
-                                              // block form: out_blk 1 = y blocked, 3 = y and t1' blocked (a layer2 wave-form launch follows)
+                                              // block form: out_blk 1 = y blocked (t1' stays NHWC)
     int y_s2 = -1;                            // chain, wave form: index of the plan's only other reader of y, a 1 x 1 stride-2 convolution - plain forwards store
                                               // just the (even row, even column) pixels of y, compacted to (n, h / 2, w / 2, c), and that launch reads them at stride 1
 };

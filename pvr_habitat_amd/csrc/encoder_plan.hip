@@ -414,33 +414,7 @@ static void plan_wave_forms(pvr_encoder *e) {
         }
 }
 
-// Pass 3: layer2's stride-1 tails on their wave form (chain_wave128.hip, round 6).  That kernel reads t1 and the residual blocked and writes t1' blocked, so a
-// launch can take it only if (i) the launch in front is a chain that carries this block's conv1 and hands y and t1' over untapped - the block form (it can
-// write both blocked: out_blk 1 | 2) or another launch of this form - and (ii) the launch behind it, if it carries the next conv1 here, takes this form too.
-static void plan_wave128(pvr_encoder *e) {
-    std::vector<Launch> &sc = e->sched_fused;
-    const int ns = (int)sc.size();
-    auto linked = [&](int a, int b) {               // sc[a] hands y (as the residual) and t1' straight to sc[b]
-        if (a < 0 || b >= ns) return false;
-        const Launch &A = sc[a], &B = sc[b];
-        if (A.conv3 < 0 || B.conv3 < 0 || A.next1 < 0 || A.frame || B.frame || B.ds >= 0) return false;
-        const ConvOp &a2 = e->ops[A.conv2], &a3 = e->ops[A.conv3], &b2 = e->ops[B.conv2], &b3 = e->ops[B.conv3];
-        return B.t1_in == A.t1_out && b3.res_buf == a3.out_buf && a3.tap.empty() && b2.h == a2.h / a2.stride && b2.w == a2.w / a2.stride && A.next1 + 1 == B.conv2;
-    };
-    auto eligible = [&](int b) {
-        const Launch &B = sc[b];
-        if (B.conv3 < 0 || B.frame || B.ds >= 0 || B.wave) return false;
-        const ConvOp &b2 = e->ops[B.conv2];
-        return (b2.h * b2.w) % 16 == 0 && e->sw.chain_blocked && chain_uses_wave128(e->sw, b2.cout, B.next1 >= 0 ? e->ops[B.next1].cout : 0, b2.stride, (int64_t)b2.h * b2.w);
-    };
-    std::vector<char> can(ns, 0);
-    for (int b = ns - 1; b >= 1; --b)
-        can[b] = eligible(b) && linked(b - 1, b) && (sc[b].next1 < 0 || (b + 1 < ns && can[b + 1] && linked(b, b + 1)));
-    for (int b = 1; b < ns; ++b)
-        if (can[b] && (sc[b - 1].wave == 0 || sc[b - 1].wave == 2)) sc[b].wave = 2;
-}
-
-// Pass 4: two consecutive wave-form tails hand y (the second one's residual) and t1' (its conv2 input) over in the blocked layout
+// Pass 3: two consecutive wave-form tails hand y (the second one's residual) and t1' (its conv2 input) over in the blocked layout
 // (chain_wave.hip): only when nothing else reads those two buffers in between - no tap, no other launch - and the geometry allows it.
 static void plan_blocked_handoffs(pvr_encoder *e) {
     for (size_t a = 0; a + 1 < e->sched_fused.size(); ++a) {
@@ -450,10 +424,6 @@ static void plan_blocked_handoffs(pvr_encoder *e) {
         const int a_cmn = e->ops[A.next1].cout;
         if (!e->sw.chain_blocked) continue;
         if (B.t1_in != A.t1_out || b3.res_buf != a3.out_buf || !a3.tap.empty() || b2.h != a2.h / a2.stride || b2.w != a2.w / a2.stride || b2.stride != 1) continue;
-        if (B.wave == 2) {                            // a layer2 wave-form tail: everything it reads arrives blocked (its producer: block form or this form)
-            A.out_blk = A.wave == 2 ? 1 : 3; B.in_blk = 1;
-            continue;
-        }
         if (!A.wave && !B.wave) {
             // two block-form tails (layer2): y = the next residual travels blocked (16-byte accesses of a lane land in 512-byte runs);
             // t1' stays NHWC (the halo DMA wants contiguous pixel rows)
@@ -476,7 +446,7 @@ static void plan_blocked_handoffs(pvr_encoder *e) {
     }
 }
 
-// Pass 5: layer1.0.conv1 (1 x 1, 64 -> 64 on the pooled stem output) inside the fused stem (stem.hip, StemC1; round 6): the launch leaves the fused schedule; the
+// Pass 4: layer1.0.conv1 (1 x 1, 64 -> 64 on the pooled stem output) inside the fused stem (stem.hip, StemC1; round 6): the launch leaves the fused schedule; the
 // forward hands the stem its weights, or - where the stem's register-pooling form does not run - launches the convolution itself in front of the plan
 static void plan_stem_c1(pvr_encoder *e) {
     if (!e->sw.stem_conv1 || e->sched_fused.empty() || !(e->desc.arch == PVR_ARCH_RESNET50 || e->desc.arch == PVR_ARCH_RESNET50_L3 || e->desc.arch == PVR_ARCH_RESNET50_L4)) return;
@@ -490,7 +460,7 @@ static void plan_stem_c1(pvr_encoder *e) {
     }
 }
 
-// Pass 6: a wave-form tail that carries the next block's conv1 and whose y has ONE other reader, a 1 x 1 stride-2 convolution (layer1.2 -> layer2.0's
+// Pass 5: a wave-form tail that carries the next block's conv1 and whose y has ONE other reader, a 1 x 1 stride-2 convolution (layer1.2 -> layer2.0's
 // downsample): three quarters of y are never read.  The tail may store only the (even row, even column) pixels, compacted into the front of
 // the same buffer, and the reader then runs at stride 1 over them (y_s2).  Whether a forward does so is decided per batch size (resolve_kinds:
 // the reader must be conv_expand at both strides - the same K order, bit-identical) and per call (taps, debug stops and range checks see full y).
@@ -533,7 +503,6 @@ static void build_schedules(pvr_encoder *e) {
     if (stores_f32(e->desc.dtype) || e->desc.arch == PVR_ARCH_CLIP_RN50) { e->sched_fused = e->sched_plain; return; }   // (CLIP: pools between the convolutions)
     plan_blocks(e);
     plan_wave_forms(e);
-    plan_wave128(e);
     plan_blocked_handoffs(e);
     plan_stem_c1(e);
     plan_y_s2(e);
@@ -673,7 +642,7 @@ int32_t pvr_encoder_launch_kernel(const pvr_encoder *enc, int32_t n, int32_t ind
     const bool tab = enc->kinds_stride == plan.size() && enc->kinds.size() == (size_t)enc->desc.chunk * plan.size();
     const int kind = tab ? enc->kinds[(size_t)(nb - 1) * plan.size() + i] : resolve_kind(enc, plan, (size_t)i, nb);
     const char *nm = enc->desc.dtype == PVR_F32 ? "conv_f32" : launch_kind_name(kind);
-    if (enc->desc.dtype != PVR_F32 && (kind == LK_CHAIN || kind == LK_CHAIN_YS2)) nm = plan[i].wave == 2 ? "chain_wave128" : plan[i].wave == 1 ? "chain_wave" : "bottleneck_chain";
+    if (enc->desc.dtype != PVR_F32 && (kind == LK_CHAIN || kind == LK_CHAIN_YS2)) nm = plan[i].wave ? "chain_wave" : "bottleneck_chain";
     snprintf(buf, (size_t)cap, "%s", nm);
     return (int32_t)strlen(nm);
 }

@@ -307,7 +307,7 @@ class HipResNet50(_Node):
         return names
 
     def set_switch(self, name, value):
-        """run-time A/B switches of the built plan: 'pool_fuse', 'stem_u8', 'frame_min_n', 'frame_run', 'frame_stagger', 'conv_algo', 'frame64',
+        """run-time A/B switches of the built plan: 'pool_fuse', 'stem_u8', 'frame_min_n', 'frame_run', 'frame_stagger', 'conv_algo',
         'stem_regpool' (pvr_encoder_debug_set_switch); every other PVR_* switch is read from the environment when the handle is created"""
         if self._handle is None:
             self._build()

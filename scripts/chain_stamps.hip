@@ -8,10 +8,8 @@
 namespace pvr {
 // (the wave form lives in chain_wave.hip; this harness times the block form only)
 bool chain_wave_supported(const PlanSwitches &, int, int, int, bool) { return false; }
-bool chain_wave128_supported(const PlanSwitches &, int, int, int, int64_t) { return false; }
 bool chain_wave_blocked_ok(int, int, int) { return false; }
 pvr_status launch_chain_wave(ChainP &, int, int, int, hipStream_t) { return PVR_ERR_INVALID; }
-pvr_status launch_chain_wave128(ChainP &, int, int, hipStream_t) { return PVR_ERR_INVALID; }
 void set_error(const char *fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); fputc('\n', stderr); }
 const std::string &last_error() { static std::string s; return s; }
 }

@@ -183,18 +183,11 @@ def test_frame_bottleneck_op_is_bit_identical(dt, n):
     torch.cuda.synchronize()
     assert same(t2b, t2f_ref), diff(t2b, t2f_ref)
     assert torch.isfinite(y.float()).all() and same(y, yf_ref), diff(y, yf_ref)
-    # the same launch in both tilings (round 6: bneck_frame64.hip, one wave per SIMD x 64 output channels; it has no t2 tap)
-    try:
-        for mode in (0, 1):
-            _lib.check(L.pvr_debug_set_frame64(mode))
-            c64 = L.pvr_debug_bneck_frame64_launches()
-            y2 = torch.full((n, 14, 14, 1024), float('nan'), dtype=tdt, device='cuda')
-            _lib.check(L.pvr_op_bneck_frame(None, vp(w2), vp(b2), vp(w3), vp(b3), vp(r), vp(y2), None, None, None, None, vp(w1), vp(b1), n, 3 | 8, cdt, _lib.stream_ptr()))
-            torch.cuda.synchronize()
-            assert L.pvr_debug_bneck_frame64_launches() - c64 == mode
-            assert torch.isfinite(y2.float()).all() and same(y2, yf_ref), (mode, diff(y2, yf_ref))
-    finally:
-        _lib.check(L.pvr_debug_set_frame64(-1))
+    # the same launch without the t2 tap (what the encoder's plan runs)
+    y2 = torch.full((n, 14, 14, 1024), float('nan'), dtype=tdt, device='cuda')
+    _lib.check(L.pvr_op_bneck_frame(None, vp(w2), vp(b2), vp(w3), vp(b3), vp(r), vp(y2), None, None, None, None, vp(w1), vp(b1), n, 3 | 8, cdt, _lib.stream_ptr()))
+    torch.cuda.synchronize()
+    assert torch.isfinite(y2.float()).all() and same(y2, yf_ref), diff(y2, yf_ref)
 
 
 WF_CASES = [
@@ -1089,36 +1082,6 @@ def test_frame_bottleneck_plan_is_bit_identical(variant, dtype, n, monkeypatch):
 
 
 @pytest.mark.parametrize('dtype', ['f16', 'bf16'])
-def test_frame64_tiling_is_bit_identical(dtype):
-    """Round 6: the whole layer3 bottleneck per frame in the 64-channel tiling (bneck_frame64.hip: ONE wave per SIMD, each 64 output channels x 13 pixel tiles,
-    accumulators in the AGPR half of the register file, MFMAs as inline asm with in-place accumulators) against round 5's 32-channel tiling and against the
-    separate launches: the plan's embedding at the bench batch and a ragged one, every element, bit for bit, three times in a row; the launch counters say
-    which kernel ran."""
-    from pvr_habitat_amd.embeddings import HipResNet50
-    L = _lib.lib()
-    sd = synth.resnet50_state_dict(12)
-    for n in (256, 133):
-        fr = torch.from_numpy(synth.smooth_frames(90 + n, n, 64, 64)).cuda()
-        m = HipResNet50(sd, 'conv5', compute_dtype=dtype, max_batch=256)
-        m.set_switch('frame64', 0)
-        c32 = L.pvr_debug_bneck_frame_launches(); c64 = L.pvr_debug_bneck_frame64_launches()
-        ref = m(fr).clone()
-        assert L.pvr_debug_bneck_frame_launches() - c32 == 5 and L.pvr_debug_bneck_frame64_launches() == c64
-        m.set_switch('frame_min_n', 100000)                      # separate launches (member convolutions)
-        sep = m(fr).clone()
-        m.set_switch('frame_min_n', 128)
-        assert torch.equal(ref, sep)
-        m.set_switch('frame64', 1)
-        c64 = L.pvr_debug_bneck_frame64_launches()
-        for _ in range(3):
-            out = m(fr)
-            nd = int((out != ref).sum())
-            assert nd == 0, (n, nd, float((out - ref).abs().max()))
-        assert L.pvr_debug_bneck_frame64_launches() - c64 == 15
-        m.close()
-
-
-@pytest.mark.parametrize('dtype', ['f16', 'bf16'])
 def test_frame_run_is_bit_identical_at_the_bench_batch(dtype):
     """Round 6 (opt-in, PVR_FRAME_RUN=1: measured equal to the default): layer3.1 .. 3.5 as ONE launch that takes every frame through the five bottlenecks (bneck_frame.hip RUN: the workgroup that wrote a frame's y
     reads it back as the next x and identity; between two bottlenecks: stores retired + a workgroup barrier) against one launch per
@@ -1452,44 +1415,6 @@ def test_default_plan_at_the_bench_batch_against_the_oracle():
     assert 'bneck_frame(front1)' not in m.kernel_names(3) and 'bneck_frame(run)' not in m.kernel_names(3)
     assert np.array_equal(small, out[idx[:3]])
     m.close()
-
-
-@pytest.mark.parametrize('dtype,n', [('f16', 1), ('bf16', 3), ('f16', 6), ('bf16', 40), ('f16', 41)])
-def test_layer2_wave_form_equals_block_form(dtype, n, monkeypatch):
-    """chain_wave128.hip (round 6): layer2's stride-1 tails with wave-owned pixels and the 544 KB of weights streamed through a two-slot LDS ring,
-    against the block form (bottleneck_chain.hip) - same rounding points, same K order per accumulator: layer2's output and the embedding bit for
-    bit.  (Opt-in since the end of round 6: measured no faster than the block form, profiles/experiments/r06_chain_wave128.txt; PVR_CHAIN_WAVE_L2=1 selects it.)  Odd n: the last 32-pixel tile holds a single 16-pixel block; n = 40 / 41: several rounds per workgroup and workgroups with idle waves in
-    the last round.  The plan's launch list is unchanged (the form is a property of the launch); the launch counter says which form ran."""
-    from pvr_habitat_amd.embeddings import HipResNet50
-    L = _lib.lib()
-    L.pvr_debug_chain_wave128_launches.restype = C.c_int64
-    sd = synth.resnet50_state_dict(8, 'conv5')
-    fr = torch.from_numpy(synth.smooth_frames(170 + n, n, 160, 200)).cuda()
-    got = {}
-    for key, on in (('block', '0'), ('wave', '1')):
-        monkeypatch.setenv('PVR_CHAIN_WAVE_L2', on)
-        m = HipResNet50(sd, 'conv5', compute_dtype=dtype, max_batch=max(8, n))
-        names = m.op_names()
-        before = L.pvr_debug_chain_wave128_launches()
-        m.debug_stop_after('layer2')
-        m(fr)
-        t2 = m.tap('layer2', n * 28 * 28 * 512).clone()
-        m.debug_stop_after('')
-        emb = m(fr).clone()
-        assert torch.equal(emb, m(fr))
-        ran = L.pvr_debug_chain_wave128_launches() - before
-        assert ran == (9 if on == '1' else 0), ran                  # layer2.1 / 2.2 / 2.3, three forwards
-        if on == '1':                                               # the handle keeps the form it was built with (read once, at create)
-            monkeypatch.delenv('PVR_CHAIN_WAVE_L2')
-            before = L.pvr_debug_chain_wave128_launches()
-            assert torch.equal(m(fr), emb)
-            assert L.pvr_debug_chain_wave128_launches() > before
-        m.close()
-        got[key] = (t2, emb, names)
-    assert got['wave'][2] == got['block'][2]
-    assert torch.isfinite(got['block'][0]).all() and float(got['block'][0].abs().max()) > 0
-    for a, b, what in ((got['wave'][0], got['block'][0], 'layer2'), (got['wave'][1], got['block'][1], 'embedding')):
-        assert torch.equal(a, b), (what, int((a != b).sum()), float((a - b).abs().max()))
 
 
 @pytest.mark.parametrize('dt,n', [('f16', 3), ('bf16', 9), ('f16', 33)])

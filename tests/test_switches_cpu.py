@@ -53,3 +53,20 @@ def test_the_planner_is_host_code_and_owns_the_name_matching():
     assert not re.findall(r'\blaunch_(?!kind_name)\w+\(', plan)
     assert 'ends_with(' not in _src('encoder.hip')
 
+
+def test_every_plan_switch_is_read_by_the_code_it_switches():
+    """a PlanSwitches member that only read_switches and pvr_encoder_debug_set_switch touch switches nothing: every member is read (not merely assigned)
+    somewhere else in csrc/"""
+    decl = _body(_src('encoder_internal.h'), 'struct PlanSwitches')
+    members = re.findall(r'^\s*int (\w+) = ', decl, re.M)
+    assert len(members) > 20
+    text = ''
+    for name in sorted(os.listdir(CSRC)):
+        if name.endswith(('.hip', '.h')):
+            src = _src(name)
+            if name == 'encoder.hip':
+                for head in ('void read_switches(PlanSwitches &sw)', 'pvr_status pvr_encoder_debug_set_switch('):
+                    src = src.replace(_body(src, head), '{}')
+            text += re.sub(r'/\*.*?\*/', '', re.sub(r'//[^\n]*', '', src), flags=re.S)
+    dead = [m for m in members if not re.search(r'\bsw\.%s\b(?!\s*=[^=])' % m, text)]
+    assert not dead, dead
