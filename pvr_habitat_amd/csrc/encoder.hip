@@ -199,7 +199,7 @@ static pvr_status prepare_weights(pvr_encoder *e) {
     for (ConvOp &op : e->ops)                    // frame members and the stand-alone launches conv_wfrag may take (either schedule)
         if (op.wfrag && (s = pack_wfb(op))) return s;
     for (const Launch &l : e->sched_fused) {
-        if (l.conv3 >= 0 && !l.frame) {
+        if (l.form == LF_CHAIN) {
             // a chain: b3 + b_downsample when the downsample runs inside, row-permuted copies of its 1x1 weights
             ConvOp &o3 = e->ops[l.conv3];
             if (l.ds >= 0) {
@@ -223,7 +223,7 @@ static pvr_status prepare_weights(pvr_encoder *e) {
                     if ((s = enc_upload(&o.d_wpb, hb))) return s;
                 }
             }
-        } else if (l.conv3 < 0 && l.ds >= 0) {
+        } else if (l.form == LF_DUAL) {
             // the two-operand launch: [W3 | W_downsample] rows, b3 + b_downsample
             ConvOp &o3 = e->ops[l.conv2];
             const ConvOp &od = e->ops[l.ds];
@@ -236,7 +236,7 @@ static pvr_status prepare_weights(pvr_encoder *e) {
             std::vector<float> bs(cp, 0.f);
             for (int c = 0; c < o3.cout; ++c) bs[c] = o3.h_b[c] + od.h_b[c];
             if ((s = enc_upload(&o3.d_wcat, wc)) || (s = enc_upload(&o3.d_bsum, bs))) return s;
-        } else if (l.pair >= 0) {
+        } else if (l.form == LF_PAIR) {
             // the conv_split16 pair: [W1 ; Wd] (128 couts) as one split weight image, both biases
             ConvOp &op = e->ops[l.conv2];
             const ConvOp &od = e->ops[l.pair];
@@ -445,7 +445,7 @@ pvr_status pvr_encoder_create(const pvr_encoder_desc *desc, pvr_encoder **out) {
         plan_encoder(e);                                        // the whole launch plan (encoder_plan.hip): finalize only prepares weights and workspace
         if (e->desc.dtype == PVR_F32S)                          // every convolution runs on conv_split16: a shape it cannot take fails here, not at launch
             for (const ConvOp &op : e->ops)
-                if (op.kind != 0 || !conv_split16_supported(op.cin, op.cout, op.k)) {
+                if (!op.is_conv() || !conv_split16_supported(op.cin, op.cout, op.k)) {
                     set_error("PVR_F32S: %s (cin %d, cout %d, k %d) is not a conv_split16 shape", op.conv.c_str(), op.cin, op.cout, op.k);
                     delete e;
                     return PVR_ERR_INVALID;
@@ -472,6 +472,7 @@ pvr_status pvr_encoder_set_host_backend(pvr_encoder *enc, int32_t on) {
     PVR_REQUIRE(!enc->finalized, "pvr_encoder_set_host_backend: call between create and finalize");
     PVR_REQUIRE(!on || enc->desc.dtype != PVR_F32S, "pvr_encoder_set_host_backend: the CPU plan is fp32; create the encoder with dtype PVR_F32, not PVR_F32S");
     enc->host = on != 0;
+    if (!enc->vit && !enc->rnd) resolve_kinds(enc);             // (the switches of a host handle skip it)
     return PVR_OK;
 }
 
@@ -491,7 +492,7 @@ pvr_status pvr_encoder_finalize(pvr_encoder *enc) {
     if ((s = rn50c ? finalize_stem(enc, "visual.conv1.weight", "visual.bn1", 32, 3) : finalize_stem(enc))) return s;
     if (rn50c && (s = finalize_attnpool(enc))) return s;
     for (auto &op : enc->ops)
-        if (op.kind == 0 && (s = finalize_conv(enc, op))) return s;
+        if (op.is_conv() && (s = finalize_conv(enc, op))) return s;
     if ((s = prepare_weights(enc))) return s;
     PVR_HIP_TRY(hipDeviceSynchronize());                        // (the weight-packing launches above)
     for (auto &op : enc->ops) {
@@ -525,7 +526,7 @@ static pvr_status clip_rn50_chunk(pvr_encoder *enc, Lane &L, int lane, const uin
     if (enc->stop_after == "pre") return PVR_OK;
     if ((s = launch_stem(L.d_img, enc->d_stem_w, enc->d_stem_b, L.d_stem, nb, crop, dt, st))) return s;
     for (const ConvOp &op : enc->ops) {
-        if (op.kind == 1) s = launch_avgpool2(bufp(L, op.in_buf), bufp(L, op.out_buf), nb, op.h, op.w, op.cin, dt, st);
+        if (op.role == R_AVGPOOL2) s = launch_avgpool2(bufp(L, op.in_buf), bufp(L, op.out_buf), nb, op.h, op.w, op.cin, dt, st);
         else s = launch_conv(enc->sw, bufp(L, op.in_buf), op.d_w, op.d_b, op.res_buf == B_NONE ? nullptr : bufp(L, op.res_buf), bufp(L, op.out_buf),
                              enc->d_zero, nb, op.h, op.w, op.cin, op.cout, op.k, op.k, op.stride, op.pad, op.relu, op.out_f32, dt, st);
         if (s) return s;
@@ -587,10 +588,8 @@ static pvr_status f32_chunk(pvr_encoder *enc, Lane &L, const uint8_t *fr, int nb
         else s = launch_conv_f32((const float *)L.buf[op.in_buf], op.d_wf, op.d_b, res, (float *)L.buf[op.out_buf], nb,
                                  op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, op.relu, st);
         if (s) return s;
-        if (fa.bad_flags) {                 // pvr_encoder_check_range: the launch's output, all of it
-            const int ho_ = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo_ = (op.w + 2 * op.pad - op.k) / op.stride + 1;
-            launch_range_flag_split(L.buf[op.out_buf], (size_t)nb * ho_ * wo_ * op.cout, fa.bad_flags, (int)(&op - enc->ops.data()), st);
-        }
+        if (fa.bad_flags)                   // pvr_encoder_check_range: the launch's output, all of it
+            launch_range_flag_split(L.buf[op.out_buf], (size_t)nb * op.ho() * op.wo() * op.cout, fa.bad_flags, (int)(&op - enc->ops.data()), st);
         if ((s = mark())) return s;
     }
     if (pooled_head(enc))
@@ -676,7 +675,7 @@ static pvr_status h16_chunk(pvr_encoder *enc, Lane &L, const uint8_t *fr, int nb
     };
     for (size_t li = 0; li < plan_.size(); ++li) {
         const Launch &l = plan_[li];
-        const ConvOp &op = enc->ops[l.conv3 >= 0 ? l.conv3 : l.conv2];
+        const ConvOp &op = enc->ops[l.out_op()];
         const void *res = op.res_buf == B_NONE ? nullptr : L.buf[op.res_buf];
         int kind = kinds[li];
         if (kind == LK_WFRAG_POOL && !pool_args_ok) kind = resolve_kind(enc, plan_, li, nb, false);
@@ -807,8 +806,7 @@ static pvr_status h16_chunk(pvr_encoder *enc, Lane &L, const uint8_t *fr, int nb
         }
         if (s) return s;
         if (fa.bad_flags && kind != LK_WFRAG_POOL) {         // pvr_encoder_check_range: the launch's output, all of it
-            const int ho_ = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo_ = (op.w + 2 * op.pad - op.k) / op.stride + 1;
-            const size_t n8 = (size_t)nb * ho_ * wo_ * op.cout / 8;
+            const size_t n8 = (size_t)nb * op.ho() * op.wo() * op.cout / 8;
             const int blocks = (int)((n8 + 255) / 256 < 2048 ? (n8 + 255) / 256 : 2048);
             if ((op.out_f32 & 1) || op.f32op) hipLaunchKernelGGL(range_flag_kernel<true>, dim3(blocks), dim3(256), 0, st, L.buf[op.out_buf], n8, dt, fa.bad_flags, (int)li);
             else hipLaunchKernelGGL(range_flag_kernel<false>, dim3(blocks), dim3(256), 0, st, L.buf[op.out_buf], n8, dt, fa.bad_flags, (int)li);
@@ -941,11 +939,9 @@ pvr_status pvr_encoder_profile(pvr_encoder *enc, const uint8_t *frames, int32_t 
         auto flops = [&](int oi) {
             if (oi < 0) return 0.0;
             const ConvOp &op = enc->ops[oi];
-            const double ho = (op.h + 2 * op.pad - op.k) / op.stride + 1;
-            return 2.0 * n * ho * ho * (double)op.cout_real * op.k * op.k * op.cin_real;
+            return 2.0 * n * op.ho() * op.ho() * (double)op.cout_real * op.k * op.k * op.cin_real;
         };
-        const bool fused = enc->fuse && !stores_f32(enc->desc.dtype);
-        for (const Launch &l : (fused ? enc->sched_fused : enc->sched_plain)) {
+        for (const Launch &l : cur_plan(enc)) {
             if (i >= nl) break;
             op_flops[i++] = flops(l.conv1) + flops(l.conv2) + flops(l.conv3) + flops(l.next1) + flops(l.ds) + flops(l.pair);
         }

@@ -122,11 +122,25 @@ constexpr int PVR_MAX_LANES = 4;
 // B_Y0 / B_Y1: fp32 residual stream of the compressed PVRs' parity plan (allocated only for that plan); B_STEM: the lane's d_stem (112x112x64), not in buf[]
 enum BufId { B_NONE = -1, B_X0 = 0, B_X1, B_T1, B_T2, B_DS, B_F32, B_Y0, B_Y1, B_COUNT, B_STEM = B_COUNT };
 
+// What an op of the plan is: set by the builder that emits it (encoder_plan.hip).  The convolutions come first (ConvOp::is_conv).
+enum OpRole : uint8_t {
+    R_CONV1, R_CONV2, R_CONV3, R_DOWNSAMPLE,        // of a bottleneck or a basic block
+    R_HEAD_CONV1, R_HEAD_DOWNSAMPLE, R_HEAD_CONV2,  // of the compression head (*_l3 / *_l4)
+    R_STEM_CONV2, R_STEM_CONV3,                     // CLIP ModifiedResNet's second and third stem convolution
+    R_AVGPOOL2,                                     // AvgPool2d(2) on NHWC 16-bit (CLIP ModifiedResNet; cin = channels)
+    R_CAST,                                         // fp32 -> 16-bit copy
+};
+
+inline int conv_out_size(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
+
 struct ConvOp {
-    std::string conv, bn;          // state_dict prefixes
+    std::string conv, bn;          // state_dict prefixes (weights, launch names): the plan never parses them
+    OpRole role = R_CONV1;
     int in_buf, out_buf, res_buf;
     int h, w, cin, cin_real, cout, cout_real, k, stride, pad, relu, out_f32;
-    int kind = 0;                  // 0 convolution, 1 AvgPool2d(2) on NHWC 16-bit (CLIP ModifiedResNet; cin = channels), 2 fp32 -> 16-bit copy
+    bool is_conv() const { return role < R_AVGPOOL2; }
+    int ho() const { return conv_out_size(h, k, stride, pad); }
+    int wo() const { return conv_out_size(w, k, stride, pad); }
     bool f32op = false;            // convolution on fp32 buffers with fp32 weights on the f32-input MFMA (conv_f32.hip) inside a 16-bit plan
     bool from32 = false;           // a 16-bit convolution (16-bit weights, one MFMA per product) whose INPUT is the fp32 residual stream: conv_split16's single-term
                                    // form rounds the operand in its staging pass - the fp32 -> 16-bit copy launch of the stream is gone (round 6)
@@ -150,21 +164,36 @@ struct ConvOp {
     int ksplit = 0, ks_buf = B_NONE;   // split-K launch (conv_igemm.hip): number of K ranges, workspace buffer that is dead at this op
 };
 
-// one launch of the forward plan: a single convolution, or a fused bottleneck tail
-// (conv2 3x3 -> conv3 1x1 + residual -> the next block's conv1 1x1; bottleneck_chain.hip)
+// A residual block as its builder emitted it: indices into ops, -1 where the block has no such op.  The planner schedules blocks (encoder_plan.hip: plan_blocks).
+enum BlockType : uint8_t { BK_BOTTLENECK, BK_BASIC, BK_HEAD };   // conv1 1x1 -> conv2 3x3 -> conv3 1x1; conv1 3x3 -> conv2 3x3; the compression head
+struct Block {
+    BlockType type;
+    int stage, index;                           // layer`stage + 1`.`index`
+    int conv1 = -1, conv2 = -1, ds = -1, conv3 = -1;
+    int cast = -1;                              // the fp32 -> 16-bit copy of the block's output, when one follows it
+};
+
+// one launch of the forward plan
+enum LaunchForm : uint8_t {
+    LF_SINGLE,   // ops[conv2] alone, whatever its role
+    LF_CHAIN,    // fused bottleneck tail: conv2 3x3 -> conv3 1x1 + residual [-> the next block's conv1 1x1] (bottleneck_chain.hip, chain_wave.hip)
+    LF_FRAME,    // per-frame form (bneck_frame.hip, layer3): [conv1 ->] conv2 -> conv3 + residual [-> next1] of one 14 x 14 image per workgroup
+    LF_DUAL,     // ops[conv2] is a conv3 that runs as conv_pp256's two-operand launch with the block's downsample ops[ds] (layer3.0 / layer4.0)
+    LF_PAIR,     // conv_split16 pair: ops[conv2] and ops[pair] read the same fp32 input and run as one launch (the compression head)
+};
 struct Launch {
-    int conv2 = -1, conv3 = -1, next1 = -1;   // chain members (indices into ops); conv3 < 0: single launch of ops[conv2]
-    int ds = -1;                              // chain: the block's downsample convolution, accumulated inside conv3 (no launch of its own);
-                                              // with conv3 < 0: ops[conv2] is a conv3 that runs as conv_pp256's two-operand launch with ops[ds] (layer3.0 / layer4.0)
-    int t1_in = B_NONE, t1_out = B_NONE;      // chain: buffer holding conv2's input / receiving the next block's conv1 output
+    LaunchForm form = LF_SINGLE;
+    int conv2 = -1, conv3 = -1, next1 = -1;   // indices into ops; conv3 / next1: chain and frame members
+    int ds = -1;                              // chain: the block's downsample convolution, accumulated inside conv3 (no launch of its own); dual: see LF_DUAL
+    int t1_in = B_NONE, t1_out = B_NONE;      // chain, frame: buffer holding conv2's input / receiving the next block's conv1 output
     int wave = 0;                             // chain: 1 the wave form runs it (chain_wave.hip), 0 the block form
-    int conv1 = -1;                           // per-frame form: the block's own conv1 runs in front, inside the launch (the launch reads the block input)
-    int frame = 0;                            // per-frame form (bneck_frame.hip, layer3): conv2 -> conv3 + residual [-> next1] of one 14 x 14 image per workgroup
-    int pair = -1;                            // conv_split16 pair form: ops[conv2] and ops[pair] read the same fp32 input and run as one launch (the compression head)
+    int conv1 = -1;                           // frame: the block's own conv1 runs in front, inside the launch (the launch reads the block input)
+    int pair = -1;                            // pair: the second convolution
     int in_blk = 0, out_blk = 0;              // chain, wave form: t1 + residual / y + t1' travel in the blocked layout between two such launches (chain_wave.hip);
                                               // block form: out_blk 1 = y blocked (t1' stays NHWC)
     int y_s2 = -1;                            // chain, wave form: index of the plan's only other reader of y, a 1 x 1 stride-2 convolution - plain forwards store
                                               // just the (even row, even column) pixels of y, compacted to (n, h / 2, w / 2, c), and that launch reads them at stride 1
+    int out_op() const { return form == LF_CHAIN || form == LF_FRAME ? conv3 : conv2; }   // the op whose output (and residual) the launch writes
 };
 
 // What one launch of the plan runs as for a forward of nb frames: resolved off the hot path (resolve_kinds: create, set_low_latency,
@@ -191,6 +220,7 @@ enum LaunchKind : uint8_t {
     LK_WFRAG,             // conv_wfrag
     LK_CHAIN_YS2,         // LK_CHAIN storing y only at the pixels its stride-2 reader takes (Launch::y_s2; plain forwards: no tap, stop or range check)
     LK_CONV_YS2,          // ... and that reader: conv_expand at stride 1 over the compacted y
+    LK_COUNT
 };
 const char *launch_kind_name(int k);
 
@@ -215,6 +245,7 @@ struct pvr_encoder {
     pvr_encoder_desc desc;
     std::map<std::string, HostTensor> weights;
     std::vector<ConvOp> ops;
+    std::vector<Block> blocks;                      // the residual blocks of ops, in order (the ops outside them: CLIP's stem convolutions and pools)
     std::vector<Launch> sched_plain, sched_fused;   // one launch per op / with the layer1-layer2 bottleneck tails fused
     bool fuse = true;                               // PVR_FUSE=0 or pvr_encoder_debug_set_fusion(enc, 0) selects sched_plain
     bool low_latency = false;                       // pvr_encoder_set_low_latency: split-K plan for forwards of <= 4 frames
@@ -223,7 +254,6 @@ struct pvr_encoder {
     int stem_c1_blk = 0;                            // form does not apply, the forward launches it in front of the plan; _blk: the tail behind it reads t1 blocked
     u16 *d_stem_c1w = nullptr;                      // its weights as the stem's fragment image (stem_c1_pack)
     std::vector<uint8_t> kinds;                     // LaunchKind of launch i for a forward of nb frames: kinds[(nb - 1) * plan.size() + i] (resolve_kinds)
-    size_t kinds_stride = 0;
     bool last_pooled = false;                       // the last forward wrote the pooled rows from the last convolution: the B_F32 tap does not exist
     bool tail32 = false;                            // round 3: + the last trunk stage entirely in fp32 (conv_f32.hip), fp32 stream one stage earlier
     bool resid32 = false;                           // compressed PVRs, f16: fp32 residual stream from layer3 on + fp32 compression head
@@ -319,7 +349,6 @@ pvr_status launch_cls_head(const float *x, const float *gamma, const float *beta
 // clip_rn50.hip
 pvr_status launch_avgpool2(const void *in, void *out, int n, int h, int w, int c, int dtype, hipStream_t st);
 pvr_status launch_attnpool_tokens(const float *x, const float *pos, void *tokens, int n, int hw, int c, int dtype, hipStream_t st);
-pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
 pvr_status vit_forward(pvr_encoder *e, int lane, const uint8_t *frames, int n, int h, int w, float *out, int64_t out_stride, hipStream_t st);
 void vit_destroy(pvr_encoder *e);
 pvr_status vit_tap(pvr_encoder *e, const char *name, float *out, int64_t cap, int64_t *count, hipStream_t st);

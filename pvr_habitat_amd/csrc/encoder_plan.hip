@@ -10,24 +10,37 @@ const char *launch_kind_name(int k) {
     static const char *nm[] = {"conv", "bneck_frame(front1)", "bneck_frame", "bneck_frame(run)", "(in the run)", "frame_members", "conv_pp256(dual)", "dual_members", "chain", "cast",
                                "conv_f32", "conv_split16", "conv_split16(pair)", "conv_split16(in32)", "splitk(small)", "splitk", "conv_expand(blocked)",
                                "conv_wfrag(pool)", "conv_wfrag", "chain(y_s2)", "conv_expand(y_s2)"};
-    return k >= 0 && k < (int)(sizeof nm / sizeof nm[0]) ? nm[k] : "?";
+    static_assert(sizeof nm / sizeof nm[0] == LK_COUNT, "one name per LaunchKind");
+    return k >= 0 && k < LK_COUNT ? nm[k] : "?";
 }
 
-static void add_conv(pvr_encoder *e, const std::string &conv, const std::string &bn, int in_buf, int out_buf,
-                     int res_buf, int h, int w, int cin, int cin_real, int cout, int cout_real, int k, int stride,
-                     int relu, int out_f32 = 0) {
+// The builders emit ops by role: the role gives the state-dict names behind the block's prefix `p`.  Returns the op's index.
+static int add_conv(pvr_encoder *e, OpRole role, const std::string &p, int in_buf, int out_buf, int res_buf, int hw, int cin, int cin_real, int cout,
+                    int cout_real, int k, int stride, int relu, int out_f32 = 0) {
+    static const char *const name[][2] = {{".conv1", ".bn1"}, {".conv2", ".bn2"}, {".conv3", ".bn3"}, {".downsample.0", ".downsample.1"}, {".conv1", ".bn1"},
+                                          {".downsample.0", ".downsample.1"}, {".conv2", ".bn2"}, {".conv2", ".bn2"}, {".conv3", ".bn3"}};
+    static_assert(sizeof name / sizeof name[0] == R_AVGPOOL2, "one pair of names per convolution role");
     ConvOp op;
-    op.conv = conv; op.bn = bn; op.in_buf = in_buf; op.out_buf = out_buf; op.res_buf = res_buf;
-    op.h = h; op.w = w; op.cin = cin; op.cin_real = cin_real; op.cout = cout; op.cout_real = cout_real;
+    op.role = role; op.conv = p + name[role][0]; op.bn = p + name[role][1]; op.in_buf = in_buf; op.out_buf = out_buf; op.res_buf = res_buf;
+    op.h = hw; op.w = hw; op.cin = cin; op.cin_real = cin_real; op.cout = cout; op.cout_real = cout_real;
     op.k = k; op.stride = stride; op.pad = k / 2; op.relu = relu; op.out_f32 = out_f32;
     e->ops.push_back(op);
+    return (int)e->ops.size() - 1;
 }
 
-static void add_cast(pvr_encoder *e, int in_buf, int out_buf, int hw, int c) {
+static int add_cast(pvr_encoder *e, int in_buf, int out_buf, int hw, int c) {
     ConvOp op;
-    op.kind = 2; op.conv = "cast"; op.in_buf = in_buf; op.out_buf = out_buf; op.res_buf = B_NONE;
+    op.role = R_CAST; op.conv = "cast"; op.in_buf = in_buf; op.out_buf = out_buf; op.res_buf = B_NONE;
     op.h = hw; op.w = hw; op.cin = op.cout = op.cout_real = c; op.cin_real = 0; op.k = 1; op.stride = 1; op.pad = 0; op.relu = 0; op.out_f32 = 0;
     e->ops.push_back(op);
+    return (int)e->ops.size() - 1;
+}
+
+// the last op of a stage's last block is the stage's tap "layer<stage + 1>"
+static void tap_stage(pvr_encoder *e, int stage, int buf, int hw, int c, int f32) {
+    const std::string tn = "layer" + std::to_string(stage + 1);
+    e->ops.back().tap = tn;
+    e->taps[tn] = {buf, {hw, hw, c, f32}};
 }
 
 // torchvision resnet50 v1.5: layers [3,4,6,3], stride on the 3x3 (conv2), downsample on block 0
@@ -71,62 +84,46 @@ static void build_resnet50(pvr_encoder *e) {
             const int stride = (bi == 0 && li > 0) ? 2 : 1;
             const int ohw = hw / stride;
             const int y = x == B_X0 ? B_X1 : B_X0;
-            const bool last = (li == stages - 1 && bi == nblk[li] - 1);
-            char tn[16]; snprintf(tn, sizeof tn, "layer%d", li + 1);
+            const int y32 = x32 == B_Y0 ? B_Y1 : B_Y0;
+            const bool last = (li == stages - 1 && bi == nblk[li] - 1), stage_end = bi == nblk[li] - 1;
+            Block b{BK_BOTTLENECK, li, bi};
             if (f32stage) {
                 // every tensor of the block is fp32 (the 16-bit ping-pong buffers are large enough: the stage's activations are
                 // 1/4 ... 1/16 of layer1's elements); the block reads the fp32 stream directly
-                const size_t first = e->ops.size();
-                const int y32 = x32 == B_Y0 ? B_Y1 : B_Y0;
-                add_conv(e, p + ".conv1", p + ".bn1", x32, B_T1, B_NONE, hw, hw, inpl, inpl, planes, planes, 1, 1, 1);
-                add_conv(e, p + ".conv2", p + ".bn2", B_T1, B_T2, B_NONE, hw, hw, planes, planes, planes, planes, 3, stride, 1);
-                int res32 = x32;
-                if (bi == 0) {
-                    add_conv(e, p + ".downsample.0", p + ".downsample.1", x32, B_DS, B_NONE, hw, hw, inpl, inpl, planes * 4, planes * 4, 1, stride, 0, 1);
-                    res32 = B_DS;
-                }
-                add_conv(e, p + ".conv3", p + ".bn3", B_T2, y32, res32, ohw, ohw, planes, planes, planes * 4, planes * 4, 1, 1, 1, 1 | 2);
-                for (size_t i = first; i < e->ops.size(); ++i) e->ops[i].f32op = true;
-                if (bi == nblk[li] - 1) {
-                    e->ops.back().tap = tn;
-                    e->taps[tn] = {y32, {ohw, ohw, planes * 4, 1}};
-                }
-                x32 = y32; hw = ohw; inpl = planes * 4;
-                continue;
-            }
-            add_conv(e, p + ".conv1", p + ".bn1", x_is_32 ? x32 : x, B_T1, B_NONE, hw, hw, inpl, inpl, planes, planes, 1, 1, 1);
-            e->ops.back().from32 = x_is_32;
-            add_conv(e, p + ".conv2", p + ".bn2", B_T1, B_T2, B_NONE, hw, hw, planes, planes, planes, planes, 3, stride, 1);
-            int res = r32 ? x32 : x;
-            if (bi == 0) {
-                add_conv(e, p + ".downsample.0", p + ".downsample.1", x_is_32 ? x32 : x, B_DS, B_NONE, hw, hw, inpl, inpl, planes * 4,
-                         planes * 4, 1, stride, 0, r32 ? 1 : 0);
+                b.conv1 = add_conv(e, R_CONV1, p, x32, B_T1, B_NONE, hw, inpl, inpl, planes, planes, 1, 1, 1);
+                b.conv2 = add_conv(e, R_CONV2, p, B_T1, B_T2, B_NONE, hw, planes, planes, planes, planes, 3, stride, 1);
+                if (bi == 0) b.ds = add_conv(e, R_DOWNSAMPLE, p, x32, B_DS, B_NONE, hw, inpl, inpl, planes * 4, planes * 4, 1, stride, 0, 1);
+                b.conv3 = add_conv(e, R_CONV3, p, B_T2, y32, bi == 0 ? B_DS : x32, ohw, planes, planes, planes * 4, planes * 4, 1, 1, 1, 1 | 2);
+                for (int i = b.conv1; i <= b.conv3; ++i) e->ops[i].f32op = true;
+                if (stage_end) tap_stage(e, li, y32, ohw, planes * 4, 1);
+                x32 = y32;
+            } else {
+                b.conv1 = add_conv(e, R_CONV1, p, x_is_32 ? x32 : x, B_T1, B_NONE, hw, inpl, inpl, planes, planes, 1, 1, 1);
                 e->ops.back().from32 = x_is_32;
-                res = B_DS;
-            }
-            if (r32) {
-                const int y32 = x32 == B_Y0 ? B_Y1 : B_Y0;
-                add_conv(e, p + ".conv3", p + ".bn3", B_T2, y32, res, ohw, ohw, planes, planes, planes * 4, planes * 4, 1, 1, 1, 1 | 2);
-                // the 16-bit copy feeds the next block's convolutions - unless that block is fp32 (it reads the stream itself), as the head does
-                const bool next_f32 = e->tail32 && li == stages - 2 && bi == nblk[li] - 1;
-                if (!last && !next_f32 && !in32) add_cast(e, y32, y, ohw, planes * 4);
-                if (bi == nblk[li] - 1) {
-                    e->ops.back().tap = tn;
-                    e->taps[tn] = {y32, {ohw, ohw, planes * 4, 1}};
+                b.conv2 = add_conv(e, R_CONV2, p, B_T1, B_T2, B_NONE, hw, planes, planes, planes, planes, 3, stride, 1);
+                if (bi == 0) {
+                    b.ds = add_conv(e, R_DOWNSAMPLE, p, x_is_32 ? x32 : x, B_DS, B_NONE, hw, inpl, inpl, planes * 4, planes * 4, 1, stride, 0, r32 ? 1 : 0);
+                    e->ops.back().from32 = x_is_32;
                 }
-                x32 = y32; x = y; hw = ohw; inpl = planes * 4;
-                x_is_32 = in32;
-                continue;
+                const int res = bi == 0 ? B_DS : r32 ? x32 : x;
+                if (r32) {
+                    b.conv3 = add_conv(e, R_CONV3, p, B_T2, y32, res, ohw, planes, planes, planes * 4, planes * 4, 1, 1, 1, 1 | 2);
+                    // the 16-bit copy feeds the next block's convolutions - unless that block is fp32 (it reads the stream itself), as the head does
+                    const bool next_f32 = e->tail32 && li == stages - 2 && stage_end;
+                    if (!last && !next_f32 && !in32) b.cast = add_cast(e, y32, y, ohw, planes * 4);
+                    if (stage_end) tap_stage(e, li, y32, ohw, planes * 4, 1);
+                    x32 = y32;
+                    x_is_32 = in32;
+                } else {
+                    // the trunk's last block feeds avgpool: keep fp32 (conv5 variant only)
+                    const int f32 = (last && arch == PVR_ARCH_RESNET50) ? 1 : 0;
+                    b.conv3 = add_conv(e, R_CONV3, p, B_T2, f32 ? B_F32 : y, res, ohw, planes, planes, planes * 4, planes * 4, 1, 1, 1, f32);
+                    if (stage_end) tap_stage(e, li, f32 ? B_F32 : y, ohw, planes * 4, f32);
+                }
+                x = y;
             }
-            // the trunk's last block feeds avgpool: keep fp32 (conv5 variant only)
-            const int f32 = (last && arch == PVR_ARCH_RESNET50) ? 1 : 0;
-            add_conv(e, p + ".conv3", p + ".bn3", B_T2, f32 ? B_F32 : y, res, ohw, ohw, planes, planes, planes * 4,
-                     planes * 4, 1, 1, 1, f32);
-            if (bi == nblk[li] - 1) {
-                e->ops.back().tap = tn;
-                e->taps[tn] = {f32 ? B_F32 : y, {ohw, ohw, planes * 4, f32}};
-            }
-            x = y; hw = ohw; inpl = planes * 4;
+            e->blocks.push_back(b);
+            hw = ohw; inpl = planes * 4;
         }
     }
     if (arch == PVR_ARCH_RESNET50) {
@@ -138,10 +135,12 @@ static void build_resnet50(pvr_encoder *e) {
     const int c = arch == PVR_ARCH_RESNET50_L3 ? 11 : 42;
     const std::string p = arch == PVR_ARCH_RESNET50_L3 ? "layer3.1" : "layer4.1";
     const int hx = e->resid32 ? x32 : x;
-    add_conv(e, p + ".conv1", p + ".bn1", hx, B_T1, B_NONE, hw, hw, cin, cin, 64, c, 3, 1, 1);
-    add_conv(e, p + ".downsample.0", p + ".downsample.1", hx, B_DS, B_NONE, hw, hw, cin, cin, 64, c, 3, 1, 0);
-    add_conv(e, p + ".conv2", p + ".bn2", B_T1, B_F32, B_DS, hw, hw, 64, c, 64, c, 3, 1, 1, 1);
-    if (e->resid32) for (size_t i = e->ops.size() - 3; i < e->ops.size(); ++i) e->ops[i].f32op = true;
+    Block b{BK_HEAD, stages - 1, 1};
+    b.conv1 = add_conv(e, R_HEAD_CONV1, p, hx, B_T1, B_NONE, hw, cin, cin, 64, c, 3, 1, 1);
+    b.ds = add_conv(e, R_HEAD_DOWNSAMPLE, p, hx, B_DS, B_NONE, hw, cin, cin, 64, c, 3, 1, 0);
+    b.conv2 = add_conv(e, R_HEAD_CONV2, p, B_T1, B_F32, B_DS, hw, 64, c, 64, c, 3, 1, 1, 1);
+    if (e->resid32) for (int i = b.conv1; i <= b.conv2; ++i) e->ops[i].f32op = true;
+    e->blocks.push_back(b);
     e->out_size = c * hw * hw; e->final_hw = hw * hw; e->final_c = 64; e->final_creal = c;
 }
 
@@ -161,18 +160,12 @@ static void build_basic_resnet(pvr_encoder *e) {
             const int ohw = hw / stride;
             const int y = x == B_X0 ? B_X1 : B_X0;
             const bool last = (li == 3 && bi == nblk[li] - 1);
-            add_conv(e, p + ".conv1", p + ".bn1", x, B_T1, B_NONE, hw, hw, inpl, inpl, planes, planes, 3, stride, 1);
-            int res = x;
-            if (stride > 1 || inpl != planes) {
-                add_conv(e, p + ".downsample.0", p + ".downsample.1", x, B_DS, B_NONE, hw, hw, inpl, inpl, planes, planes, 1, stride, 0);
-                res = B_DS;
-            }
-            add_conv(e, p + ".conv2", p + ".bn2", B_T1, last ? B_F32 : y, res, ohw, ohw, planes, planes, planes, planes, 3, 1, 1, last ? 1 : 0);
-            if (bi == nblk[li] - 1) {
-                char tn[16]; snprintf(tn, sizeof tn, "layer%d", li + 1);
-                e->ops.back().tap = tn;
-                e->taps[tn] = {last ? B_F32 : y, {ohw, ohw, planes, last ? 1 : 0}};
-            }
+            Block b{BK_BASIC, li, bi};
+            b.conv1 = add_conv(e, R_CONV1, p, x, B_T1, B_NONE, hw, inpl, inpl, planes, planes, 3, stride, 1);
+            if (stride > 1 || inpl != planes) b.ds = add_conv(e, R_DOWNSAMPLE, p, x, B_DS, B_NONE, hw, inpl, inpl, planes, planes, 1, stride, 0);
+            b.conv2 = add_conv(e, R_CONV2, p, B_T1, last ? B_F32 : y, b.ds >= 0 ? B_DS : x, ohw, planes, planes, planes, planes, 3, 1, 1, last ? 1 : 0);
+            if (bi == nblk[li] - 1) tap_stage(e, li, last ? B_F32 : y, ohw, planes, last ? 1 : 0);
+            e->blocks.push_back(b);
             x = y; hw = ohw; inpl = planes;
         }
     }
@@ -184,15 +177,14 @@ static void build_basic_resnet(pvr_encoder *e) {
 // stride 1 - the stride is an AvgPool2d after conv2 and in front of the downsample convolution.  Channels 32 are padded to 64.
 static void add_pool(pvr_encoder *e, int in_buf, int out_buf, int h, int c) {
     ConvOp op;
-    op.kind = 1; op.conv = "avgpool2"; op.in_buf = in_buf; op.out_buf = out_buf; op.res_buf = B_NONE;
+    op.role = R_AVGPOOL2; op.conv = "avgpool2"; op.in_buf = in_buf; op.out_buf = out_buf; op.res_buf = B_NONE;
     op.h = h; op.w = h; op.cin = op.cin_real = op.cout = op.cout_real = c; op.k = 2; op.stride = 2; op.pad = 0; op.relu = 0; op.out_f32 = 0;
     e->ops.push_back(op);
 }
 
 static void build_clip_rn50(pvr_encoder *e) {
-    const std::string v = "visual.";
-    add_conv(e, v + "conv2", v + "bn2", B_STEM, B_X0, B_NONE, 112, 112, 64, 32, 64, 32, 3, 1, 1);
-    add_conv(e, v + "conv3", v + "bn3", B_X0, B_X1, B_NONE, 112, 112, 64, 32, 64, 64, 3, 1, 1);
+    add_conv(e, R_STEM_CONV2, "visual", B_STEM, B_X0, B_NONE, 112, 64, 32, 64, 32, 3, 1, 1);
+    add_conv(e, R_STEM_CONV3, "visual", B_X0, B_X1, B_NONE, 112, 64, 32, 64, 64, 3, 1, 1);
     add_pool(e, B_X1, B_X0, 112, 64);
     e->ops.back().tap = "stem3";
     e->taps["stem3"] = {B_X0, {56, 56, 64, 0}};
@@ -208,22 +200,20 @@ static void build_clip_rn50(pvr_encoder *e) {
             const int ohw = hw / stride;
             const int y = x == B_X0 ? B_X1 : B_X0;
             const bool last = (li == 3 && bi == nblk[li] - 1);
-            add_conv(e, p + ".conv1", p + ".bn1", x, B_T1, B_NONE, hw, hw, inpl, inpl, planes, planes, 1, 1, 1);
-            add_conv(e, p + ".conv2", p + ".bn2", B_T1, B_T2, B_NONE, hw, hw, planes, planes, planes, planes, 3, 1, 1);
+            Block b{BK_BOTTLENECK, li, bi};
+            b.conv1 = add_conv(e, R_CONV1, p, x, B_T1, B_NONE, hw, inpl, inpl, planes, planes, 1, 1, 1);
+            b.conv2 = add_conv(e, R_CONV2, p, B_T1, B_T2, B_NONE, hw, planes, planes, planes, planes, 3, 1, 1);
             int c3_in = B_T2, res = x;
             if (stride > 1) { add_pool(e, B_T2, B_T1, hw, planes); c3_in = B_T1; }
             if (stride > 1 || inpl != planes * 4) {
                 int ds_in = x;
                 if (stride > 1) { add_pool(e, x, B_T2, hw, inpl); ds_in = B_T2; }
-                add_conv(e, p + ".downsample.0", p + ".downsample.1", ds_in, B_DS, B_NONE, ohw, ohw, inpl, inpl, planes * 4, planes * 4, 1, 1, 0);
+                b.ds = add_conv(e, R_DOWNSAMPLE, p, ds_in, B_DS, B_NONE, ohw, inpl, inpl, planes * 4, planes * 4, 1, 1, 0);
                 res = B_DS;
             }
-            add_conv(e, p + ".conv3", p + ".bn3", c3_in, last ? B_F32 : y, res, ohw, ohw, planes, planes, planes * 4, planes * 4, 1, 1, 1, last ? 1 : 0);
-            if (bi == nblk[li] - 1) {
-                char tn[16]; snprintf(tn, sizeof tn, "layer%d", li + 1);
-                e->ops.back().tap = tn;
-                e->taps[tn] = {last ? B_F32 : y, {ohw, ohw, planes * 4, last ? 1 : 0}};
-            }
+            b.conv3 = add_conv(e, R_CONV3, p, c3_in, last ? B_F32 : y, res, ohw, planes, planes, planes * 4, planes * 4, 1, 1, 1, last ? 1 : 0);
+            if (bi == nblk[li] - 1) tap_stage(e, li, last ? B_F32 : y, ohw, planes * 4, last ? 1 : 0);
+            e->blocks.push_back(b);
             x = y; hw = ohw; inpl = planes * 4;
         }
     }
@@ -239,9 +229,8 @@ static void plan_splitk(pvr_encoder *e) {
     const int n = (int)e->ops.size();
     for (int i = 0; i < n; ++i) {
         ConvOp &op = e->ops[i];
-        if (op.kind != 0 || op.f32op || op.from32 || op.cout > 64 || op.k * op.k * op.cin < 16384 || (op.out_f32 & 2)) continue;
-        const int ho = (op.h + 2 * op.pad - op.k) / op.stride + 1;
-        const size_t need = (size_t)8 * e->desc.chunk * ho * ho * op.cout * sizeof(float);
+        if (!op.is_conv() || op.f32op || op.from32 || op.cout > 64 || op.k * op.k * op.cin < 16384 || (op.out_f32 & 2)) continue;
+        const size_t need = (size_t)8 * e->desc.chunk * op.ho() * op.ho() * op.cout * sizeof(float);
         if (need > e->buf_elems * 2) continue;
         for (int b = 0; b < B_F32 && op.ks_buf == B_NONE; ++b) {      // (16-bit ping-pong buffers only)
             if (b == op.in_buf || b == op.out_buf || b == op.res_buf) continue;
@@ -256,159 +245,122 @@ static void plan_splitk(pvr_encoder *e) {
     }
 }
 
-static bool ends_with(const std::string &s, const char *suf) {
-    const size_t n = strlen(suf);
-    return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
+// a convolution with 16-bit operands, a 16-bit output and no padded channel: what the fused 16-bit kernels take
+static bool plain16(const ConvOp &o) { return o.is_conv() && !o.f32op && !o.from32 && !o.out_f32 && o.cin_real == o.cin && o.cout_real == o.cout; }
+
+// How a block's tail (conv2 -> conv3 + residual) can run fused: only a bottleneck whose every convolution is plain16 - not the fp32 stage or the fp32
+// residual stream of the parity plan, not the block that writes the trunk's fp32 output, no basic block, not the head.  The kernels' widths are disjoint:
+// per-frame launches take layer3's stride-1 blocks (bneck_frame_supported), chains take widths 64 / 128 (chain_supported).
+static LaunchForm tail_form(const pvr_encoder *e, const Block &b) {
+    if (b.type != BK_BOTTLENECK) return LF_SINGLE;
+    const ConvOp &c2 = e->ops[b.conv2], &c3 = e->ops[b.conv3];
+    if (!plain16(e->ops[b.conv1]) || !plain16(c2) || !plain16(c3) || (b.ds >= 0 && !plain16(e->ops[b.ds]))) return LF_SINGLE;
+    if (b.ds < 0 && bneck_frame_supported(e->sw, e->desc.chunk, c2.h, c2.w, c2.cout, c3.cout, c2.stride)) return LF_FRAME;
+    return chain_supported(c2.cout, 0) ? LF_CHAIN : LF_SINGLE;
 }
 
-static void push_single(pvr_encoder *e, int op) { Launch l; l.conv2 = op; e->sched_fused.push_back(l); }
+// Block `b` feeds the next block's conv1 directly - no cast in between - and that block's tail runs in the same form, so it knows where to find the t1 that
+// a fused launch of `b` leaves for it.  Returns that conv1, or -1.
+static int next_conv1(const pvr_encoder *e, size_t b, LaunchForm form) {
+    if (b + 1 >= e->blocks.size() || e->blocks[b + 1].conv1 != e->blocks[b].conv3 + 1 || tail_form(e, e->blocks[b + 1]) != form) return -1;
+    return e->blocks[b + 1].conv1;
+}
 
-// Pass 1, per block: every bottleneck of width 64 / 128 (layer1, layer2) runs as
+static Launch &push(pvr_encoder *e, LaunchForm form, int op) {
+    Launch l; l.form = form; l.conv2 = op;
+    e->sched_fused.push_back(l);
+    return e->sched_fused.back();
+}
+
+// An op as a launch of its own.  A convolution with few pixels and a deep K (layer3 / layer4's 1 x 1 and 3 x 3 at 14 x 14 and 7 x 7): conv_wfrag.hip may
+// take it at run time (conv_wfrag_preferred: by the batch) - it reads the fragment-blocked copy of the weights
+static void push_single(pvr_encoder *e, int i) {
+    if (i < 0) return;
+    ConvOp &op = e->ops[i];
+    push(e, LF_SINGLE, i);
+    if (op.is_conv() && !op.f32op && !op.from32 && op.h == op.w && op.h <= 14 && op.cout_real == op.cout && (int64_t)op.k * op.k * op.cin >= 512 &&
+        conv_wfrag_supported(1, 1, op.cin, op.cout, op.k, op.k, op.pad, op.relu, op.out_f32))
+        op.wfrag = true;
+}
+
+// Pass 1, per block.  A bottleneck of width 64 / 128 (layer1, layer2) runs as
 // [conv1 unless the previous chain already produced it] [downsample] [chain: conv2 -> conv3 (+res) -> next conv1]; layer3's stride-1 bottlenecks as
 // per-frame launches; layer3.0 / layer4.0's conv3 & downsample as one two-operand launch; the compression head's conv1 & downsample as one
 // conv_split16 pair; everything else as a launch of its own.  ConvOp::wfrag marks the ops whose launches read the fragment-blocked weight image.
 static void plan_blocks(pvr_encoder *e) {
-    const int n = (int)e->ops.size();
-    int cur_t1 = B_T1;
-    bool conv1_done = false;
-    int conv1_frame_out = -1;                                   // t1 buffer the previous per-frame launch wrote the next conv1's output to
-    // index of the conv3 that closes the chain starting at conv2 `j`, or -1 when that bottleneck does not run as a chain
-    auto chain_end = [&](int j) -> int {
-        if (j < 0 || j >= n) return -1;
-        const ConvOp &o2 = e->ops[j];
-        if (!(ends_with(o2.conv, ".conv2") && o2.k == 3 && o2.cin == o2.cout && o2.cin_real == o2.cin && o2.cout_real == o2.cout) || o2.f32op) return -1;
-        int c = j + 1;
-        if (c < n && ends_with(e->ops[c].conv, ".downsample.0")) ++c;
-        if (!(c < n && ends_with(e->ops[c].conv, ".conv3") && e->ops[c].cout == 4 * o2.cout && e->ops[c].relu &&
-              !e->ops[c].out_f32 && e->ops[c].res_buf != B_NONE && chain_supported(o2.cout, 0)))
-            return -1;
-        return c;
-    };
-    for (int i = 0; i < n;) {
-        ConvOp &op = e->ops[i];
-        if (ends_with(op.conv, ".conv1") && conv1_done) { conv1_done = false; ++i; continue; }
-        // layer3's stride-1 bottlenecks as ONE launch per block: conv1 -> conv2 -> conv3 + identity of one 14 x 14 image per workgroup
-        // (bneck_frame.hip with the block's own conv1 in front; PVR_FRAME_FRONT1=0: conv1 keeps its launch)
-        {
-            const bool front_on = e->sw.frame_front1 && !e->sw.frame_next1;
-            if (front_on && ends_with(op.conv, ".conv1") && op.k == 1 && op.stride == 1 && op.relu == 1 && !op.f32op && !op.out_f32 && op.tap.empty() && i + 2 < n &&
-                op.cin_real == op.cin && op.cout_real == op.cout) {
-                const ConvOp &o2 = e->ops[i + 1], &o3 = e->ops[i + 2];
-                if (ends_with(o2.conv, ".conv2") && o2.k == 3 && !o2.f32op && o2.relu == 1 && o2.cin == o2.cout && o2.cin_real == o2.cin && o2.in_buf == op.out_buf &&
-                    ends_with(o3.conv, ".conv3") && !o3.f32op && !o3.out_f32 && o3.relu == 1 && o3.res_buf == op.in_buf && o3.cout == op.cin && o3.cout_real == o3.cout &&
-                    o3.in_buf == o2.out_buf && op.cout == o2.cin && bneck_frame_supported(e->sw, e->desc.chunk, o2.h, o2.w, o2.cout, o3.cout, o2.stride)) {
-                    Launch l;
-                    l.conv1 = i; l.conv2 = i + 1; l.conv3 = i + 2; l.frame = 1; l.t1_in = op.out_buf;
-                    e->sched_fused.push_back(l);
-                    for (int oi : {l.conv1, l.conv2, l.conv3}) e->ops[oi].wfrag = true;
-                    i += 3;
-                    continue;
-                }
-            }
-        }
-        // layer3's stride-1 bottlenecks: conv2 -> conv3 + residual of one 14 x 14 image per workgroup (bneck_frame.hip); with PVR_FRAME_NEXT1=1 the
-        // next block's conv1 rides in the same launch (it then reads / writes the two t1 buffers in turns, as the layer1 / layer2 chains do)
-        if (ends_with(op.conv, ".conv2") && op.k == 3 && !op.f32op && i + 1 < n && ends_with(e->ops[i + 1].conv, ".conv3") && !e->ops[i + 1].f32op &&
-            !e->ops[i + 1].out_f32 && e->ops[i + 1].relu == 1 && e->ops[i + 1].res_buf != B_NONE && op.relu == 1 && op.cin == op.cout && op.cin_real == op.cin &&
-            e->ops[i + 1].cout_real == e->ops[i + 1].cout && bneck_frame_supported(e->sw, e->desc.chunk, op.h, op.w, op.cout, e->ops[i + 1].cout, op.stride)) {
-            Launch l;
-            l.conv2 = i; l.conv3 = i + 1; l.frame = 1; l.t1_in = conv1_frame_out >= 0 ? conv1_frame_out : op.in_buf;
-            conv1_frame_out = -1;
-            const bool next1_on = e->sw.frame_next1 != 0;
-            const int nx = i + 2;
-            if (next1_on && nx + 2 < n && ends_with(e->ops[nx].conv, ".conv1") && e->ops[nx].k == 1 && e->ops[nx].stride == 1 && e->ops[nx].relu == 1 && !e->ops[nx].f32op &&
-                e->ops[nx].cin == e->ops[i + 1].cout && e->ops[nx].cout == op.cout && e->ops[nx].in_buf == e->ops[i + 1].out_buf && e->ops[nx].cout_real == e->ops[nx].cout &&
-                e->ops[i + 1].tap.empty() && ends_with(e->ops[nx + 1].conv, ".conv2") && ends_with(e->ops[nx + 2].conv, ".conv3") &&
-                bneck_frame_supported(e->sw, e->desc.chunk, e->ops[nx + 1].h, e->ops[nx + 1].w, e->ops[nx + 1].cout, e->ops[nx + 2].cout, e->ops[nx + 1].stride)) {
-                l.next1 = nx;
-                l.t1_out = l.t1_in == B_T1 ? B_T2 : B_T1;
-                conv1_frame_out = l.t1_out;
-                conv1_done = true;                              // (the loop skips that conv1: it ran inside this launch)
-            }
-            e->sched_fused.push_back(l);
-            for (int oi : {l.conv2, l.conv3, l.next1}) if (oi >= 0) e->ops[oi].wfrag = true;
-            i += 2;
-            continue;
-        }
-        const int c3 = chain_end(i);
-        if (c3 < 0) {
-            // A stride-2 bottleneck outside the chains (layer3.0, layer4.0): its 1 x 1 downsample and the conv3 that adds it run as ONE two-operand
-            // launch (conv_pp256 DUAL: K = conv3's channels, then the block input's) - the identity branch is accumulated in fp32 and never exists in
-            // HBM (- 2 x 103 MB at layer3.0, - 2 x 51 MB at layer4.0 per 256 frames, one launch less).  PVR_DUAL_DS=0: separate launches.
-            const bool dual_on = e->sw.dual_ds != 0;
-            if (dual_on && ends_with(op.conv, ".downsample.0") && op.kind == 0 && !op.f32op && op.k == 1 && op.pad == 0 && !op.relu && !op.out_f32 &&
-                op.res_buf == B_NONE && op.tap.empty() && op.cin_real == op.cin && op.cout_real == op.cout && op.cin % 64 == 0 && i + 1 < n) {
-                const ConvOp &o3 = e->ops[i + 1];
-                if (ends_with(o3.conv, ".conv3") && o3.kind == 0 && !o3.f32op && o3.k == 1 && o3.stride == 1 && o3.pad == 0 && o3.relu == 1 && !o3.out_f32 &&
-                    o3.res_buf == op.out_buf && o3.cout == op.cout && o3.cout_real == o3.cout && o3.cin_real == o3.cin && o3.cin % 64 == 0 &&
-                    (op.h - 1) / op.stride + 1 == o3.h && (op.w - 1) / op.stride + 1 == o3.w && o3.cout >= 256 && o3.ksplit <= 1 && op.ksplit <= 1) {
-                    Launch l; l.conv2 = i + 1; l.ds = i;
-                    e->sched_fused.push_back(l);
-                    i += 2;
-                    continue;
-                }
-            }
-            // the compression head: conv1 (+ ReLU) and the downsample convolution read the SAME fp32 tensor with the same geometry: one conv_split16 launch over
+    int cur_t1 = B_T1;                                          // where the next chain finds its t1: chains read one t1 buffer while they write the next conv1's to the other
+    bool conv1_done = false;                                    // the previous block's launch ran this block's conv1
+    int conv1_frame_out = -1;                                   // t1 buffer the previous per-frame launch wrote that conv1's output to
+    for (size_t bi = 0; bi < e->blocks.size(); ++bi) {
+        const Block &b = e->blocks[bi];
+        const LaunchForm form = tail_form(e, b);
+        const bool own_conv1 = !conv1_done;
+        conv1_done = false;
+        if (b.type == BK_HEAD) {
+            // conv1 (+ ReLU) and the downsample convolution read the SAME fp32 tensor with the same geometry: one conv_split16 launch over
             // [W1 ; Wd] (128 couts), two outputs - the 205 / 103 MB input is read once
-            if (op.f32op && op.split16 && i + 1 < n) {
-                const ConvOp &od = e->ops[i + 1];
-                if (od.f32op && od.split16 && od.in_buf == op.in_buf && od.k == op.k && od.stride == op.stride && od.pad == op.pad && od.cin == op.cin && od.h == op.h &&
-                    op.cout == 64 && od.cout == 64 && op.relu == 1 && od.relu == 0 && op.res_buf == B_NONE && od.res_buf == B_NONE && op.tap.empty() && od.tap.empty() &&
-                    ends_with(op.conv, ".conv1") && ends_with(od.conv, ".downsample.0")) {
-                    Launch l; l.conv2 = i; l.pair = i + 1;
-                    e->sched_fused.push_back(l);
-                    i += 2;
-                    continue;
+            const ConvOp &c1 = e->ops[b.conv1], &cd = e->ops[b.ds];
+            if (c1.f32op && c1.split16 && cd.f32op && cd.split16) push(e, LF_PAIR, b.conv1).pair = b.ds;
+            else { push_single(e, b.conv1); push_single(e, b.ds); }
+            push_single(e, b.conv2);
+        } else if (b.type == BK_BASIC) {
+            for (int oi : {b.conv1, b.ds, b.conv2}) push_single(e, oi);
+        } else if (form == LF_FRAME && own_conv1 && e->sw.frame_front1 && !e->sw.frame_next1) {
+            // layer3's stride-1 bottlenecks as ONE launch per block: conv1 -> conv2 -> conv3 + identity of one 14 x 14 image per workgroup
+            // (bneck_frame.hip with the block's own conv1 in front; PVR_FRAME_FRONT1=0: conv1 keeps its launch)
+            Launch &l = push(e, LF_FRAME, b.conv2);
+            l.conv1 = b.conv1; l.conv3 = b.conv3; l.t1_in = e->ops[b.conv1].out_buf;
+            for (int oi : {l.conv1, l.conv2, l.conv3}) e->ops[oi].wfrag = true;
+        } else {
+            if (own_conv1) { push_single(e, b.conv1); cur_t1 = B_T1; }
+            if (form == LF_FRAME) {
+                // conv2 -> conv3 + residual of one 14 x 14 image per workgroup (bneck_frame.hip); with PVR_FRAME_NEXT1=1 the next block's conv1 rides in
+                // the same launch (it then reads / writes the two t1 buffers in turns, as the layer1 / layer2 chains do)
+                Launch &l = push(e, LF_FRAME, b.conv2);
+                l.conv3 = b.conv3; l.t1_in = conv1_frame_out >= 0 ? conv1_frame_out : e->ops[b.conv2].in_buf;
+                conv1_frame_out = -1;
+                if (e->sw.frame_next1 && (l.next1 = next_conv1(e, bi, LF_FRAME)) >= 0) {
+                    conv1_frame_out = l.t1_out = l.t1_in == B_T1 ? B_T2 : B_T1;
+                    conv1_done = true;
                 }
+                for (int oi : {l.conv2, l.conv3, l.next1}) if (oi >= 0) e->ops[oi].wfrag = true;
+            } else if (form == LF_CHAIN) {
+                // The next block's conv1 rides in this chain only if that block is a chain itself: the chain leaves t1' in the OTHER of the two
+                // t1 buffers (it reads one while it writes the next), which only a following chain knows to read (l.t1_in); a plain conv2 launch
+                // reads its own in_buf.  (Round 3: with the fp32 residual stream of the compressed PVRs' parity plan starting at layer2, layer1's
+                // last chain is followed by plain launches.)
+                const ConvOp &c2 = e->ops[b.conv2];
+                int next1 = next_conv1(e, bi, LF_CHAIN);
+                if (next1 >= 0 && !chain_supported(c2.cout, e->ops[next1].cout)) next1 = -1;
+                // layer1's block 0: its 64-channel stride-1 downsample is accumulated inside the chain's conv3 (PVR_CHAIN_DS=0: own launch) - in the instance
+                // that carries a next conv1, so only with one; otherwise the downsample launches first
+                const bool ds_inside = b.ds >= 0 && next1 >= 0 && e->sw.chain_ds && c2.stride == 1 &&
+                                       chain_ds_supported(c2.cout, e->ops[next1].cout, e->ops[b.ds].cin, e->ops[b.ds].stride);
+                if (!ds_inside) push_single(e, b.ds);
+                Launch &l = push(e, LF_CHAIN, b.conv2);
+                l.conv3 = b.conv3; l.t1_in = cur_t1; l.next1 = next1;
+                if (ds_inside) l.ds = b.ds;
+                if (next1 >= 0) {
+                    cur_t1 = l.t1_out = cur_t1 == B_T1 ? B_T2 : B_T1;
+                    conv1_done = true;
+                }
+            } else {
+                push_single(e, b.conv2);
+                // A stride-2 bottleneck outside the chains (layer3.0, layer4.0): its 1 x 1 downsample and the conv3 that adds it run as ONE two-operand
+                // launch (conv_pp256 DUAL: K = conv3's channels, then the block input's) - the identity branch is accumulated in fp32 and never exists in
+                // HBM (- 2 x 103 MB at layer3.0, - 2 x 51 MB at layer4.0 per 256 frames, one launch less).  PVR_DUAL_DS=0: separate launches.
+                if (b.ds >= 0 && e->sw.dual_ds && plain16(e->ops[b.ds]) && plain16(e->ops[b.conv3])) push(e, LF_DUAL, b.conv3).ds = b.ds;
+                else { push_single(e, b.ds); push_single(e, b.conv3); }
             }
-            push_single(e, i);
-            // a stand-alone convolution with few pixels and a deep K (layer3 / layer4's 1 x 1 and 3 x 3 at 14 x 14 and 7 x 7): conv_wfrag.hip may take it at
-            // run time (conv_wfrag_preferred: by the batch) - it reads the fragment-blocked copy of the weights
-            if (op.kind == 0 && !op.f32op && !op.from32 && op.h == op.w && op.h <= 14 && op.cout_real == op.cout && (int64_t)op.k * op.k * op.cin >= 512 &&
-                conv_wfrag_supported(1, 1, op.cin, op.cout, op.k, op.k, op.pad, op.relu, op.out_f32))
-                op.wfrag = true;
-            if (ends_with(op.conv, ".conv1")) cur_t1 = B_T1;
-            ++i;
-            continue;
         }
-        Launch l;
-        l.conv2 = i; l.conv3 = c3; l.t1_in = cur_t1;
-        const int nx = c3 + 1;
-        // layer1's block 0: its 64-channel stride-1 downsample is accumulated inside the chain's conv3 (PVR_CHAIN_DS=0: own launch)
-        const bool ds_on = e->sw.chain_ds != 0;
-        if (c3 == i + 2 && ds_on && nx < n) {
-            const ConvOp &d = e->ops[i + 1];
-            if (d.k == 1 && d.pad == 0 && !d.relu && !d.out_f32 && !d.f32op && d.cin_real == d.cin && d.cout == 4 * op.cout &&
-                d.out_buf == e->ops[c3].res_buf && chain_ds_supported(op.cout, e->ops[nx].cout, d.cin, d.stride) && op.stride == 1)
-                l.ds = i + 1;
-        }
-        if (l.ds < 0)
-            for (int d = i + 1; d < c3; ++d) push_single(e, d);   // the downsample runs first
-        // the next block's conv1 rides in this chain only if that block is a chain itself: the chain leaves t1' in the OTHER of the two
-        // t1 buffers (it reads one while it writes the next), which only a following chain knows to read (l.t1_in); a plain conv2 launch
-        // reads its own in_buf.  (Round 3: with the fp32 residual stream of the compressed PVRs' parity plan starting at layer2, layer1's
-        // last chain is followed by plain launches.)
-        if (nx < n && ends_with(e->ops[nx].conv, ".conv1") && e->ops[nx].k == 1 && e->ops[nx].stride == 1 && e->ops[nx].relu &&
-            e->ops[nx].cin == 4 * op.cout && e->ops[nx].in_buf == e->ops[c3].out_buf && e->ops[nx].cout_real == e->ops[nx].cout &&
-            chain_supported(op.cout, e->ops[nx].cout) && chain_end(nx + 1) >= 0) {
-            l.next1 = nx;
-            l.t1_out = cur_t1 == B_T1 ? B_T2 : B_T1;
-            cur_t1 = l.t1_out;
-            conv1_done = true;
-        }
-        if (l.ds >= 0 && l.next1 < 0) {               // (the DS instance carries a next conv1)
-            for (int d = i + 1; d < c3; ++d) push_single(e, d);
-            l.ds = -1;
-        }
-        e->sched_fused.push_back(l);
-        i = c3 + 1;
+        push_single(e, b.cast);
     }
 }
 
 // Pass 2: which tails run on the wave form (chain_wave.hip)
 static void plan_wave_forms(pvr_encoder *e) {
     for (Launch &l : e->sched_fused)
-        if (l.conv3 >= 0 && !l.frame) {
+        if (l.form == LF_CHAIN) {
             const ConvOp &c2 = e->ops[l.conv2];
             l.wave = chain_uses_wave_form(e->sw, c2.cout, l.next1 >= 0 ? e->ops[l.next1].cout : 0, c2.stride, l.ds >= 0);
         }
@@ -419,7 +371,7 @@ static void plan_wave_forms(pvr_encoder *e) {
 static void plan_blocked_handoffs(pvr_encoder *e) {
     for (size_t a = 0; a + 1 < e->sched_fused.size(); ++a) {
         Launch &A = e->sched_fused[a], &B = e->sched_fused[a + 1];
-        if (A.conv3 < 0 || B.conv3 < 0 || A.next1 < 0 || B.ds >= 0 || A.frame || B.frame) continue;
+        if (A.form != LF_CHAIN || B.form != LF_CHAIN || A.next1 < 0 || B.ds >= 0) continue;
         const ConvOp &a2 = e->ops[A.conv2], &a3 = e->ops[A.conv3], &b2 = e->ops[B.conv2], &b3 = e->ops[B.conv3];
         const int a_cmn = e->ops[A.next1].cout;
         if (!e->sw.chain_blocked) continue;
@@ -437,9 +389,9 @@ static void plan_blocked_handoffs(pvr_encoder *e) {
         // which directly precedes it (conv_expand.hip writes either layout; whether THAT kernel runs is known per forward: batch size)
         if (A.ds >= 0 && a > 0 && a2.w == 56 && e->sw.chain_wave_halo) {   // (the downsample tail reads a blocked t1 through the halo form only)
             Launch &C = e->sched_fused[a - 1];
-            if (C.conv3 < 0 && C.conv2 >= 0) {
+            if (C.form == LF_SINGLE) {
                 const ConvOp &c1 = e->ops[C.conv2];
-                if (c1.kind == 0 && !c1.f32op && c1.k == 1 && c1.stride == 1 && c1.out_buf == A.t1_in && c1.tap.empty() && c1.res_buf == B_NONE && !c1.out_f32 &&
+                if (c1.is_conv() && !c1.f32op && c1.k == 1 && c1.stride == 1 && c1.out_buf == A.t1_in && c1.tap.empty() && c1.res_buf == B_NONE && !c1.out_f32 &&
                     c1.ksplit <= 1) { C.out_blk = 1; A.in_blk = 1; }
             }
         }
@@ -451,9 +403,9 @@ static void plan_blocked_handoffs(pvr_encoder *e) {
 static void plan_stem_c1(pvr_encoder *e) {
     if (!e->sw.stem_conv1 || e->sched_fused.empty() || !(e->desc.arch == PVR_ARCH_RESNET50 || e->desc.arch == PVR_ARCH_RESNET50_L3 || e->desc.arch == PVR_ARCH_RESNET50_L4)) return;
     const Launch &L0 = e->sched_fused[0];
-    if (L0.conv3 >= 0 || L0.ds >= 0 || L0.pair >= 0 || L0.frame || L0.conv2 != 0) return;
+    if (L0.form != LF_SINGLE || L0.conv2 != 0) return;
     const ConvOp &c1 = e->ops[0];
-    if (c1.kind == 0 && !c1.f32op && !c1.from32 && c1.k == 1 && c1.stride == 1 && c1.cin == 64 && c1.cout == 64 && c1.cin_real == 64 && c1.cout_real == 64 && c1.relu == 1 &&
+    if (c1.role == R_CONV1 && !c1.f32op && !c1.from32 && c1.k == 1 && c1.stride == 1 && c1.cin == 64 && c1.cout == 64 && c1.cin_real == 64 && c1.cout_real == 64 && c1.relu == 1 &&
         c1.in_buf == B_X0 && c1.out_buf == B_T1 && c1.res_buf == B_NONE && !c1.out_f32 && c1.tap.empty() && c1.ksplit <= 1 && c1.h == 56) {
         e->stem_c1 = 0; e->stem_c1_blk = L0.out_blk;
         e->sched_fused.erase(e->sched_fused.begin());
@@ -469,7 +421,7 @@ static void plan_y_s2(pvr_encoder *e) {
     std::vector<Launch> &sc = e->sched_fused;
     for (size_t a = 0; a < sc.size(); ++a) {
         Launch &A = sc[a];
-        if (A.conv3 < 0 || A.frame || A.wave != 1 || A.next1 < 0 || A.ds >= 0) continue;
+        if (A.form != LF_CHAIN || A.wave != 1 || A.next1 < 0 || A.ds >= 0) continue;
         const ConvOp &a2 = e->ops[A.conv2], &a3 = e->ops[A.conv3];
         if (a2.stride != 1 || !chain_wave_y_s2_ok(a2.cout, e->ops[A.next1].cout, a2.h, a2.w, A.out_blk)) continue;   // (a tap on y: forwards that stop there run LK_CHAIN)
         const int yb = a3.out_buf;
@@ -489,7 +441,7 @@ static void plan_y_s2(pvr_encoder *e) {
         if (readers != 1) continue;
         const Launch &R = sc[reader];
         const ConvOp &r = e->ops[R.conv2];
-        if (R.conv3 >= 0 || R.ds >= 0 || R.pair >= 0 || R.frame || R.out_blk || r.kind != 0 || r.f32op || r.from32 || r.k != 1 || r.stride != 2 || r.pad != 0 ||
+        if (R.form != LF_SINGLE || R.out_blk || !r.is_conv() || r.f32op || r.from32 || r.k != 1 || r.stride != 2 || r.pad != 0 ||
             r.in_buf != yb || r.res_buf != B_NONE || r.out_f32 || r.ksplit > 1 || !r.tap.empty() || r.h != a2.h || r.w != a2.w || r.cin != a3.cout)
             continue;
         A.y_s2 = reader;
@@ -520,11 +472,10 @@ bool pooled_head(const pvr_encoder *enc) {   // global average pool of the fp32 
 // not depend on N within the plan; against the unsplit plan they differ by fp32 regrouping (<= 1 ulp of the storage type), which
 // is why the plan is opt-in and batch-size independence of the default plan stays bit-exact.
 int small_batch_ksplit(const pvr_encoder *enc, const ConvOp &op, int nb) {
-    if (!enc->low_latency || nb > 4 || op.kind != 0 || op.f32op || op.from32 || op.ksplit > 1 || op.relu > 1 || (op.out_f32 & 2)) return 0;
+    if (!enc->low_latency || nb > 4 || !op.is_conv() || op.f32op || op.from32 || op.ksplit > 1 || op.relu > 1 || (op.out_f32 & 2)) return 0;
     const int K = op.k * op.k * op.cin, nk = K / 64;
     if (nk < 8) return 0;                                        // K < 512: nothing to share
-    const int ho = (op.h + 2 * op.pad - op.k) / op.stride + 1;
-    const long long M = (long long)nb * ho * ho, blocks = ((M + 127) / 128) * ((op.cout + 127) / 128);
+    const long long M = (long long)nb * op.ho() * op.ho(), blocks = ((M + 127) / 128) * ((op.cout + 127) / 128);
     if (blocks > 64) return 0;
     const int div = enc->sw.smallk_div;                          // K slices per block (PVR_SMALLK_DIV, read at create)
     int ks = nk / div;
@@ -537,24 +488,26 @@ int small_batch_ksplit(const pvr_encoder *enc, const ConvOp &op, int nb) {
 // pooled epilogue's 16-byte stores).  A pure function of the plan, the switches and nb: tabulated by resolve_kinds, off the hot path.
 uint8_t resolve_kind(const pvr_encoder *enc, const std::vector<Launch> &plan, size_t li, int nb, bool allow_pool) {
     const Launch &l = plan[li];
-    const ConvOp &op = enc->ops[l.conv3 >= 0 ? l.conv3 : l.conv2];
+    const ConvOp &op = enc->ops[l.out_op()];
     if (enc->desc.dtype == PVR_F32S) return LK_SPLIT16;          // one launch per convolution, whatever the batch: no fused plan, no split-K, no frame kernels
     const bool ll = enc->low_latency && nb <= 4;                 // (the low-latency plan covers forwards of <= 4 frames: small_batch_ksplit)
     const bool autoalgo = enc->sw.conv_algo == -1;
-    if (l.frame) {
+    switch (l.form) {
+    case LF_FRAME:
         // small batches (a frame per workgroup leaves most CUs idle): the member convolutions as their own launches - bit-identical
         if (nb >= enc->sw.frame_min_n && !enc->low_latency) return l.conv1 >= 0 ? LK_FRAME_FRONT1 : LK_FRAME;
         return LK_FRAME_MEMBERS;
+    case LF_DUAL: return (!ll && autoalgo) ? LK_DUAL : LK_DUAL_MEMBERS;
+    case LF_CHAIN: return LK_CHAIN;
+    case LF_PAIR: return LK_SPLIT16_PAIR;
+    case LF_SINGLE: break;
     }
-    if (l.conv3 < 0 && l.ds >= 0) return (!ll && autoalgo) ? LK_DUAL : LK_DUAL_MEMBERS;
-    if (l.conv3 >= 0) return LK_CHAIN;
-    if (op.kind == 2) return LK_CAST;
-    if (l.pair >= 0) return LK_SPLIT16_PAIR;
+    if (op.role == R_CAST) return LK_CAST;
     if (op.f32op) return op.split16 ? LK_SPLIT16 : LK_F32;
     if (op.from32) return LK_SPLIT16_IN32;
     if (small_batch_ksplit(enc, op, nb)) return LK_SPLITK_SMALL;
     if (op.ksplit > 1) return LK_SPLITK;
-    const int ho = (op.h + 2 * op.pad - op.k) / op.stride + 1, wo = (op.w + 2 * op.pad - op.k) / op.stride + 1;
+    const int ho = op.ho(), wo = op.wo();
     if (l.out_blk && autoalgo && op.cin == 64 &&                 // (blocked output: the cin = 64 instances of conv_expand only)
         conv_expand_supported(enc->sw, (int64_t)nb * op.h * op.w, op.h, op.w, op.cin, op.cout, 1, 1, 1, 0, op.relu, 0, false))
         return LK_EXPAND_BLOCKED;
@@ -571,11 +524,10 @@ uint8_t resolve_kind(const pvr_encoder *enc, const std::vector<Launch> &plan, si
 const std::vector<Launch> &cur_plan(const pvr_encoder *enc) { return enc->fuse ? enc->sched_fused : enc->sched_plain; }
 
 // kinds[(nb - 1) * launches + i] for nb = 1 .. chunk: rebuilt whenever something it depends on changes (create, set_low_latency,
-// debug_set_fusion, debug_set_switch)
+// debug_set_fusion, debug_set_switch, set_host_backend, check_range around its forward), so the table is always the current plan's
 void resolve_kinds(pvr_encoder *enc) {
     const std::vector<Launch> &plan = cur_plan(enc);
     const int chunk = enc->desc.chunk;
-    enc->kinds_stride = plan.size();
     enc->kinds.assign((size_t)chunk * plan.size(), enc->desc.dtype == PVR_F32S ? LK_SPLIT16 : LK_CONV);
     if (stores_f32(enc->desc.dtype) || enc->desc.arch == PVR_ARCH_CLIP_RN50 || enc->vit || enc->rnd || enc->host) return;
     for (int nb = 1; nb <= chunk; ++nb)
@@ -618,7 +570,7 @@ void plan_encoder(pvr_encoder *e) {
     else build_resnet50(e);
     e->buf_elems = (size_t)e->desc.chunk * 56 * 56 * 256;         // largest activation (layer1 output)
     for (ConvOp &op : e->ops)                                     // the fp32 stage / head of the parity plan and the readers of its fp32 stream, on the 16-bit MFMA
-        op.split16 = e->desc.dtype == PVR_F32S ? op.kind == 0                   // the fp32-parity mode on the 16-bit MFMA: every convolution (pvr_encoder_create refuses a plan with a shape conv_split16 cannot take)
+        op.split16 = e->desc.dtype == PVR_F32S ? op.is_conv()                  // the fp32-parity mode on the 16-bit MFMA: every convolution (pvr_encoder_create refuses a plan with a shape conv_split16 cannot take)
                                                : (op.f32op || op.from32) && e->desc.dtype == PVR_F16 && e->sw.split16 && conv_split16_supported(op.cin, op.cout, op.k);
     plan_splitk(e);
     build_schedules(e);
@@ -638,9 +590,7 @@ int32_t pvr_encoder_launch_kernel(const pvr_encoder *enc, int32_t n, int32_t ind
     const int i = index - 3;
     if (i >= (int)plan.size()) return 0;
     const int nb = n < enc->desc.chunk ? n : enc->desc.chunk;
-    // the forward's own table when it is current (it knows the runs: several plan entries in one launch), else the per-entry rule
-    const bool tab = enc->kinds_stride == plan.size() && enc->kinds.size() == (size_t)enc->desc.chunk * plan.size();
-    const int kind = tab ? enc->kinds[(size_t)(nb - 1) * plan.size() + i] : resolve_kind(enc, plan, (size_t)i, nb);
+    const int kind = enc->kinds[(size_t)(nb - 1) * plan.size() + i];   // the forward's own table: whatever changes the plan or a switch rebuilds it (resolve_kinds)
     const char *nm = enc->desc.dtype == PVR_F32 ? "conv_f32" : launch_kind_name(kind);
     if (enc->desc.dtype != PVR_F32 && (kind == LK_CHAIN || kind == LK_CHAIN_YS2)) nm = plan[i].wave ? "chain_wave" : "bottleneck_chain";
     snprintf(buf, (size_t)cap, "%s", nm);
@@ -654,13 +604,12 @@ int32_t pvr_encoder_launch_name(const pvr_encoder *enc, int32_t index, char *buf
     static const char *head[3] = {"preprocess", "stem", "maxpool"};
     if (index < 3) nm = head[index];
     else {
-        const bool fused = enc->fuse && !stores_f32(enc->desc.dtype);
-        const std::vector<Launch> &sc = fused ? enc->sched_fused : enc->sched_plain;
+        const std::vector<Launch> &sc = cur_plan(enc);
         const int i = index - 3;
         if (i < (int)sc.size()) {
             nm = enc->ops[sc[i].conv1 >= 0 ? sc[i].conv1 : sc[i].conv2].conv;
             if (sc[i].conv1 >= 0) nm += "+conv2";
-            if (sc[i].conv3 >= 0) nm += "+" + enc->ops[sc[i].conv3].conv.substr(enc->ops[sc[i].conv3].conv.rfind('.') + 1);
+            if (sc[i].conv3 >= 0) nm += "+conv3";
             if (sc[i].ds >= 0 || sc[i].pair >= 0) nm += "&downsample";
             if (sc[i].next1 >= 0) nm += "+" + enc->ops[sc[i].next1].conv;
         } else if (i == (int)sc.size() && !enc->vit && !enc->rnd) nm = "pool/flatten";

@@ -224,10 +224,10 @@ pvr_status pvr_trainer_create(const pvr_encoder_desc *desc, pvr_trainer **out) {
         TrainOp o;
         o.conv = op.conv; o.bn = op.bn;
         o.h = op.h; o.w = op.w; o.cin = op.cin; o.cout = op.cout; o.k = op.k; o.stride = op.stride; o.pad = op.pad; o.relu = op.relu;
-        o.ho = (op.h + 2 * op.pad - op.k) / op.stride + 1; o.wo = (op.w + 2 * op.pad - op.k) / op.stride + 1;
+        o.ho = op.ho(); o.wo = op.wo();
         o.in_src = writer[op.in_buf];
         o.res_src = op.res_buf == B_NONE ? -2 : writer[op.res_buf];
-        ok = ok && op.kind == 0 && o.in_src >= -1 && o.res_src >= -2 && op.cin % 32 == 0 && op.cout % 64 == 0 && (op.k == 1 || op.k == 3) &&
+        ok = ok && op.is_conv() && o.in_src >= -1 && o.res_src >= -2 && op.cin % 32 == 0 && op.cout % 64 == 0 && (op.k == 1 || op.k == 3) &&
              (op.stride == 1 || (op.stride == 2 && op.h % 2 == 0 && op.w % 2 == 0)) && op.pad == op.k / 2 && op.cin == op.cin_real && op.cout == op.cout_real;
         writer[op.out_buf] = (int)t->ops.size();
         add_params(t, o);

@@ -23,6 +23,8 @@ void resized_size(int h, int w, int size, int *rh, int *rw);
 struct HostConv {
     std::vector<float> w, b;       // [cout][k][k][cin] with BN's scale folded in; bias = BN shift (+ scale * conv bias)
     int in_buf, out_buf, res_buf, h, w_, cin, cout, k, stride, pad, relu;
+    int ho() const { return conv_out_size(h, k, stride, pad); }
+    int wo() const { return conv_out_size(w_, k, stride, pad); }
 };
 
 struct HostPlan {
@@ -34,7 +36,7 @@ struct HostPlan {
 
 // one convolution over n frames: direct for 1x1 / stride 1 (the input row IS the K vector), im2col rows per pixel tile otherwise
 static void host_conv(const HostConv &c, const float *in, const float *res, float *out, int n, int threads) {
-    const int ho = (c.h + 2 * c.pad - c.k) / c.stride + 1, wo = (c.w_ + 2 * c.pad - c.k) / c.stride + 1;
+    const int ho = c.ho(), wo = c.wo();
     const int K = c.k * c.k * c.cin, TP = 32;
     const long M = (long)n * ho * wo;
     const int tiles = (int)((M + TP - 1) / TP);
@@ -146,7 +148,7 @@ pvr_status host_finalize(pvr_encoder *e) {
         for (int c = 0; c < 3; ++c)
             for (int t = 0; t < 49; ++t) hp->stem_w[((size_t)co * 49 + t) * 3 + c] = w->data[((size_t)co * 3 + c) * 49 + t] * scale[co];
     for (const ConvOp &op : e->ops) {
-        PVR_REQUIRE(op.kind == 0, "host backend: op kind %d has no CPU form", op.kind);
+        PVR_REQUIRE(op.is_conv(), "host backend: %s has no CPU form", op.conv.c_str());
         HostConv c;
         c.in_buf = op.in_buf; c.out_buf = op.out_buf; c.res_buf = op.res_buf; c.h = op.h; c.w_ = op.w; c.cin = op.cin_real; c.cout = op.cout_real;
         c.k = op.k; c.stride = op.stride; c.pad = op.pad; c.relu = op.relu;
@@ -182,8 +184,7 @@ pvr_status host_forward(pvr_encoder *e, const uint8_t *frames, int n, int h, int
     size_t need[B_COUNT] = {0};
     need[B_X0] = (size_t)n * 56 * 56 * 64;
     for (const HostConv &c : hp->ops) {
-        const int ho = (c.h + 2 * c.pad - c.k) / c.stride + 1, wo = (c.w_ + 2 * c.pad - c.k) / c.stride + 1;
-        const size_t o = (size_t)n * ho * wo * c.cout, i = (size_t)n * c.h * c.w_ * c.cin;
+        const size_t o = (size_t)n * c.ho() * c.wo() * c.cout, i = (size_t)n * c.h * c.w_ * c.cin;
         if (o > need[c.out_buf]) need[c.out_buf] = o;
         if (i > need[c.in_buf]) need[c.in_buf] = i;
     }
@@ -223,7 +224,7 @@ pvr_status host_forward(pvr_encoder *e, const uint8_t *frames, int n, int h, int
     PVR_REQUIRE(last, "host backend: empty plan");
     const float *y = hp->buf[last->out_buf].data();
     const int hw = e->final_hw, cr = e->final_creal;
-    const bool pooled = e->desc.arch == PVR_ARCH_RESNET50 || e->desc.arch == PVR_ARCH_RESNET18 || e->desc.arch == PVR_ARCH_RESNET34;
+    const bool pooled = pooled_head(e);
     for (int f = 0; f < n; ++f) {
         float *o = out + (size_t)f * out_stride;
         if (pooled) {
