@@ -6,7 +6,8 @@
  * Scope: the torchvision trunks resnet18 / resnet34 / resnet50 (arch PVR_ARCH_RESNET18 / _RESNET34 / _RESNET50), fp32 storage,
  * every product of a convolution, a data gradient or a weight gradient on the f32-input MFMA (the arithmetic of the PVR_F32
  * plan), one GPU.  BatchNorm runs on the statistics of the WHOLE batch of a forward (they cannot be chunked) or, after
- * pvr_trainer_set_bn_frozen, on its running statistics (frames independent: a step is a sum over passes).
+ * pvr_trainer_set_bn_frozen, on its running statistics (frames independent: a step is a sum over passes).  After
+ * pvr_trainer_set_wgrad_split16 the weight gradients alone run as exact-split products on the f16 matrix pipe.
  *
  * Buffers follow pvr_policy.h's convention: the caller owns ONE flat fp32 device buffer of parameters, every tensor in its
  * state_dict shape (conv weights in torch's (cout, cin, kh, kw) layout - the library repacks them inside the forward), and
@@ -73,6 +74,15 @@ pvr_status pvr_trainer_set_bn_frozen(pvr_trainer *tr, int32_t on);
  * depend on how a caller steps. */
 pvr_status pvr_trainer_backward_acc(pvr_trainer *tr, const float *params_dev, const float *dout_dev, int64_t dout_stride, float *grads_dev,
                                     int32_t accumulate, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+/* Weight-gradient arithmetic of the handle.  on == 0 (the default): every weight gradient on the f32-input MFMA, everything above, bit for bit.
+ * on != 0: every weight gradient, conv1's included, is an exact-split product on the f16 matrix pipe (pvr_op_conv_wgrad_split16 /
+ * pvr_op_stem_wgrad_split16: per-tensor power-of-two scales, a = a_hi + 2^-11 a_lo in f16, three MFMAs per fragment pair, fp32 accumulation, the
+ * same fixed-order double reduction).  The forward, the data gradients and BatchNorm are untouched, so embeddings, running statistics and the
+ * BatchNorm gradients keep their bits; a convolution weight gradient moves by about 2^-22 relative.  Legal in both BatchNorm modes.  The mode
+ * decides the workspace (one scale slot per saved tensor, the split kernels' scratch), so it must be chosen before the first forward makes it:
+ * afterwards the call returns PVR_ERR_STATE with a message.  pvr_trainer_workspace_bytes reports the size of the current mode; off, it is
+ * what it was without the mode, to the byte. */
+pvr_status pvr_trainer_set_wgrad_split16(pvr_trainer *tr, int32_t on);
 
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
@@ -126,6 +136,30 @@ pvr_status pvr_op_conv_dgrad(const float *dz_dev, const float *w_dev, float *dx_
 int64_t pvr_op_stem_wgrad_scratch_floats(int32_t n, int32_t S);
 pvr_status pvr_op_stem_wgrad(const float *img_dev, const float *dz_dev, float *dw_dev, int32_t n, int32_t S, float *scratch_dev, int64_t scratch_floats,
                              void *hip_stream);
+/* s = 2^(14 - floor(log2 max|x|)) over `count` floats, written to the device float scale_dev: the scaled maximum lies in [2^14, 2^15), inside f16's
+ * normal range.  An all-zero (or empty) tensor and a non-finite maximum give 1; the exponent is clamped to [-126, 126] so that s and 1 / s are normal
+ * fp32 numbers.  The maximum is an integer max over the bit patterns of |x| (order-independent, so deterministic); no host synchronisation - the
+ * consumers read the scale from device memory. */
+pvr_status pvr_op_absmax_scale(const float *x_dev, int64_t count, float *scale_dev, void *hip_stream);
+/* the same rule for one or two tensors in ONE launch (the trainer's form: dz and, on its first use in a backward, the saved activation).  x1_dev and
+ * scale1_dev may both be null.  aux_dev: four uint32 of device memory that are zero on entry - the caller zeroes them once - and zero again when the
+ * launch has finished (per tensor a running maximum and a count of finished blocks; the block that finishes last writes the scale). */
+pvr_status pvr_op_absmax_scale_pair(const float *x0_dev, int64_t count0, float *scale0_dev, const float *x1_dev, int64_t count1, float *scale1_dev,
+                                    uint32_t *aux_dev, void *hip_stream);
+/* pvr_op_conv_wgrad (same shapes, layouts and refusals) as an exact-split product on the f16 matrix pipe: x and dz are multiplied by *x_scale_dev and
+ * *dz_scale_dev (powers of two, from pvr_op_absmax_scale), split in registers into hi = f16(a'), lo = f16((a' - hi) * 2048), and every fragment pair
+ * takes three v_mfma_f32_16x16x32_f16 (hi*hi; the two cross terms into a second accumulator scaled by 2^-11 once).  The partials of the pixel ranges
+ * are summed in split order in double; that reduction undoes the two scales (exact) and writes torch's (cout, cin, k, k).  Two runs give the same bits.
+ * |error| <= (L + 20) 2^-24 sum|dz||x| + 2^-27 (max|x| sum|dz| + max|dz| sum|x|) per element, L the pixels of the sum. */
+int64_t pvr_op_conv_wgrad_split16_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad);
+pvr_status pvr_op_conv_wgrad_split16(const float *x_dev, const float *dz_dev, float *dw_dev, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout,
+                                     int32_t k, int32_t stride, int32_t pad, const float *x_scale_dev, const float *dz_scale_dev, float *scratch_dev,
+                                     int64_t scratch_floats, void *hip_stream);
+/* pvr_op_stem_wgrad (conv1, 7x7 / 2, pad 3; img (n,S,S,4), dz (n,S/2,S/2,64), dw (64,3,7,7), S even) as the same split product: 64 couts x 196
+ * (tap, channel) columns, gathered from the unpadded image with border masks, reduced over the n (S/2)^2 output pixels. */
+int64_t pvr_op_stem_wgrad_split16_scratch_floats(int32_t n, int32_t S);
+pvr_status pvr_op_stem_wgrad_split16(const float *img_dev, const float *dz_dev, float *dw_dev, int32_t n, int32_t S, const float *img_scale_dev,
+                                     const float *dz_scale_dev, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
 /* MaxPool2d(3, 2, 1) backward as a gather: x (n,h,w,c) the pool's input, dy (n,ho,wo,c), dx (n,h,w,c) fully written; a tie goes to the first maximum of a
  * window in scan order (torch's rule) */
 pvr_status pvr_op_maxpool_backward(const float *x_dev, const float *dy_dev, float *dx_dev, int32_t n, int32_t h, int32_t w, int32_t c, void *hip_stream);

@@ -111,6 +111,13 @@ _SIGS = {
     'pvr_op_conv_dgrad': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_stem_wgrad_scratch_floats': (C.c_int64, [C.c_int32, C.c_int32]),
     'pvr_op_stem_wgrad': (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_trainer_set_wgrad_split16': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pvr_op_absmax_scale': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'pvr_op_absmax_scale_pair': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pvr_op_conv_wgrad_split16_scratch_floats': (C.c_int64, [C.c_int32] * 8),
+    'pvr_op_conv_wgrad_split16': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_stem_wgrad_split16_scratch_floats': (C.c_int64, [C.c_int32, C.c_int32]),
+    'pvr_op_stem_wgrad_split16': (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_maxpool_backward': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p]),
     'pvr_op_avgpool_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
 }

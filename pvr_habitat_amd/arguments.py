@@ -36,6 +36,10 @@ def make_parser():
                         help='with --freeze_embedding_bn: frames per trainer pass (default: the largest count within the trainer\'s own limit - 668 frames '
                              'for resnet18 / 34, 334 for resnet50 - whose workspace fits the free device memory, never above unroll_length x batch_size x '
                              'frames)')
+    parser.add_argument('--embedding_wgrad_split16', action='store_true',
+                        help='with --train_embedding: every weight gradient of the encoder, conv1\'s included, as an exact-split product on the f16 matrix '
+                             'pipe (per-tensor power-of-two scales, three MFMAs per fragment pair, fp32 accumulation: about 2^-22 relative to the fp32 '
+                             'path); the forward, the data gradients and BatchNorm stay fp32.  Works with and without --freeze_embedding_bn')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

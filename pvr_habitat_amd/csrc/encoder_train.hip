@@ -3,6 +3,7 @@
 // dataflow f32_chunk walks) with ONE saved pre-BN and one post-BN tensor per op instead of the reused workspace buffers, and walks it backwards for the
 // gradients.  The device code of the backward pass is train_kernels.hip; every product of a convolution, data gradient or weight gradient runs on the
 // f32-input MFMA (conv_f32.hip / conv_wgrad_kernel), BatchNorm statistics are two-pass, and every split reduction is summed in a fixed order.
+// pvr_trainer_set_wgrad_split16 moves the weight gradients, and nothing else, to the exact-split f16 products of wgrad_split16.hip.
 #include "encoder_internal.h"
 #include "train_internal.h"
 #include "../../include/pvr_train.h"
@@ -49,6 +50,9 @@ struct pvr_trainer {
     int64_t wg_floats = 0, bn_floats = 0;
     int fwd_n = 0;                               // frames of the forward whose activations are held (0: none - a backward is PVR_ERR_STATE)
     bool bn_frozen = false;                      // BatchNorm normalises with its running statistics (pvr_trainer_set_bn_frozen)
+    bool wgrad_split16 = false;                  // weight gradients as exact-split f16 products (pvr_trainer_set_wgrad_split16); fixed once the arena exists
+    float *scales = nullptr;                     // split mode: one absmax scale per saved tensor (index src + 1), the image (ops + 1), dz (ops + 2),
+                                                 // then pvr_op_absmax_scale_pair's four aux words (zeroed with the workspace)
     bool timing = false;
     std::vector<Timed> times;                    // launch i of a step is bracketed by events[i]
     std::vector<EventPair> events;               // made once each, on demand; destroyed with the trainer (no error path leaves one behind)
@@ -112,6 +116,9 @@ void carve(pvr_trainer *t, Carver &c) {
         w_max = std::max(w_max, (size_t)std::max((op.cout + 63) / 64 * 64 * op.cin, (op.cin + 63) / 64 * 64 * op.cout) * op.k * op.k);
         for (int n = 1; n <= B; ++n)               // (the number of pixel ranges is not monotone in the batch: the range length is rounded to 32)
             wg_max = std::max(wg_max, pvr_op_conv_wgrad_scratch_floats(n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad));
+        if (t->wgrad_split16)
+            for (int n = 1; n <= B; ++n)
+                wg_max = std::max(wg_max, pvr_op_conv_wgrad_split16_scratch_floats(n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad));
         bn_max = std::max(bn_max, pvr_op_bn_scratch_floats((int64_t)B * op.ho * op.wo, op.cout));
         c_max = std::max(c_max, std::max(op.cin, op.cout));
     }
@@ -119,6 +126,10 @@ void carve(pvr_trainer *t, Carver &c) {
     c.take(&t->dil, dil_max);
     c.take(&t->wpack, w_max);
     c.take(&t->stem_wpack, (size_t)64 * 49 * 4);
+    if (t->wgrad_split16) {                       // (off: not a byte of the workspace changes)
+        wg_max = std::max(wg_max, pvr_op_stem_wgrad_split16_scratch_floats(B, S_IMG));
+        c.take(&t->scales, t->ops.size() + 3 + 4);
+    }
     c.take(&t->wg_scratch, (size_t)wg_max);
     c.take(&t->bn_scratch, (size_t)bn_max);
     c.take(&t->zero_bias, (size_t)c_max);
@@ -138,7 +149,8 @@ pvr_status ensure_workspace(pvr_trainer *t) {
     carve(t, c);
     const size_t img_bytes = (size_t)t->desc.max_batch * (S_IMG + 6) * (S_IMG + 8) * 4 * 2;
     const size_t zero_bytes = (size_t)((char *)a + size.used - (char *)t->zero_bias);      // (the arena's last piece)
-    if (hipMemset(t->d_img, 0, img_bytes) != hipSuccess || hipMemset(t->zero_bias, 0, zero_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    if (hipMemset(t->d_img, 0, img_bytes) != hipSuccess || hipMemset(t->zero_bias, 0, zero_bytes) != hipSuccess ||
+        (t->scales && hipMemset(t->scales, 0, (t->ops.size() + 3 + 4) * sizeof(float)) != hipSuccess) || hipDeviceSynchronize() != hipSuccess) {
         (void)hipFree(a);
         set_error("pvr_trainer: workspace initialisation failed");
         return PVR_ERR_HIP;
@@ -374,6 +386,16 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
     const auto bn_bwd = t->bn_frozen ? pvr_op_bn_frozen_backward : pvr_op_bn_train_backward;      // (the same arguments: mean / rstd are the slots the forward wrote)
     std::vector<char> have(t->ops.size() + 1, 0);  // gradient of tensor src (index src + 1) holds a value already: the next contribution accumulates
     const int last = (int)t->ops.size() - 1;
+    // split mode: the scale of a saved activation is computed once per backward, by its first consumer; dz's right after the BatchNorm backward
+    const bool split = t->wgrad_split16;
+    std::vector<char> scaled(t->ops.size() + 1, 0);
+    float *dz_scale = split ? t->scales + t->ops.size() + 2 : nullptr;
+    uint32_t *scale_aux = split ? (uint32_t *)(t->scales + t->ops.size() + 3) : nullptr;
+    // one launch per convolution: dz, and the input tensor when this is its first consumer of the backward (x == nullptr: scaled already)
+    auto scales_of = [&](const std::string &conv, size_t dz_count, const float *x, size_t x_count, float *x_slot) -> pvr_status {
+        TR_RUN(conv + " scale", 0, pvr_op_absmax_scale_pair(t->dz, (int64_t)dz_count, dz_scale, x, (int64_t)x_count, x ? x_slot : nullptr, scale_aux, st));
+        return PVR_OK;
+    };
     TR_RUN("avgpool bwd", 0, pvr_op_avgpool_backward(dout, dout_stride, t->ops[last].dy, n, t->final_hw, t->final_c, st));
     have[last + 1] = 1;
     for (int i = last; i >= 0; --i) {
@@ -386,8 +408,18 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
                       rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st));
         if (dres) have[op.res_src + 1] = 1;
         const double fl = 2.0 * rows * op.cout * op.cin * op.k * op.k;
-        TR_RUN(op.conv + " wgrad", fl,
-               pvr_op_conv_wgrad(tensor_of(t, op.in_src), t->dz, grads + op.w_off, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, t->wg_scratch, t->wg_floats, st));
+        if (split) {
+            float *x_scale = t->scales + op.in_src + 1;
+            if ((s = scales_of(op.conv, out_elems(op, n), scaled[op.in_src + 1] ? nullptr : tensor_of(t, op.in_src), (size_t)n * op.h * op.w * op.cin, x_scale)))
+                return s;
+            scaled[op.in_src + 1] = 1;
+            TR_RUN(op.conv + " wgrad", fl,
+                   pvr_op_conv_wgrad_split16(tensor_of(t, op.in_src), t->dz, grads + op.w_off, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, x_scale,
+                                             dz_scale, t->wg_scratch, t->wg_floats, st));
+        } else
+            TR_RUN(op.conv + " wgrad", fl,
+                   pvr_op_conv_wgrad(tensor_of(t, op.in_src), t->dz, grads + op.w_off, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, t->wg_scratch,
+                                     t->wg_floats, st));
         TR_RUN(op.conv + " dgrad", fl,
                launch_conv_dgrad(t->dz, params + op.w_off, grad_of(t, op.in_src), have[op.in_src + 1], n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad,
                                  t->wpack, t->dil, t->zero_bias, st));
@@ -399,7 +431,13 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
     TR_RUN("bn1 bwd", 0,
            bn_bwd(sm.z, sm.y, sm.dy, params + sm.g_off, sm.mean, sm.rstd, t->dz, nullptr, 0, grads + sm.g_off, grads + sm.b_off, (int64_t)n * 112 * 112, 64, 1,
                   t->bn_scratch, t->bn_floats, st));
-    TR_RUN("conv1 wgrad", 2.0 * n * 112 * 112 * 64 * 147, pvr_op_stem_wgrad(t->d_imgf, t->dz, grads + sm.w_off, n, S_IMG, t->wg_scratch, t->wg_floats, st));
+    if (split) {
+        float *img_scale = t->scales + t->ops.size() + 1;
+        if ((s = scales_of("conv1", (size_t)n * 112 * 112 * 64, t->d_imgf, (size_t)n * S_IMG * S_IMG * 4, img_scale))) return s;
+        TR_RUN("conv1 wgrad", 2.0 * n * 112 * 112 * 64 * 147,
+               pvr_op_stem_wgrad_split16(t->d_imgf, t->dz, grads + sm.w_off, n, S_IMG, img_scale, dz_scale, t->wg_scratch, t->wg_floats, st));
+    } else
+        TR_RUN("conv1 wgrad", 2.0 * n * 112 * 112 * 64 * 147, pvr_op_stem_wgrad(t->d_imgf, t->dz, grads + sm.w_off, n, S_IMG, t->wg_scratch, t->wg_floats, st));
     return collect_times(t, first_time, st);
 }
 
@@ -438,6 +476,17 @@ pvr_status pvr_trainer_set_bn_frozen(pvr_trainer *t, int32_t on) {
     PVR_REQUIRE(t, "pvr_trainer_set_bn_frozen: null trainer");
     t->bn_frozen = on != 0;
     t->fwd_n = 0;                                 // a held forward was made in the other mode: its mean / rstd slots mean something else
+    return PVR_OK;
+}
+
+pvr_status pvr_trainer_set_wgrad_split16(pvr_trainer *t, int32_t on) {
+    PVR_REQUIRE(t, "pvr_trainer_set_wgrad_split16: null trainer");
+    if (t->arena && (on != 0) != t->wgrad_split16) {
+        set_error("pvr_trainer_set_wgrad_split16: the workspace of this handle exists already (the first forward made it for the %s weight gradients): choose "
+                  "the mode before the first forward", t->wgrad_split16 ? "split-f16" : "fp32");
+        return PVR_ERR_STATE;
+    }
+    t->wgrad_split16 = on != 0;
     return PVR_OK;
 }
 

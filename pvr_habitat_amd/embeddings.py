@@ -423,9 +423,13 @@ class HipTrainableResNet(_Node):
     num_batches_tracked untouched (pvr_trainer_set_bn_frozen).  Every frame is then independent of the others and max_batch is the CHUNK: a
     training-mode forward of n > max_batch frames runs as ceil(n / max_batch) passes in frame order, its backward recomputes each pass but the
     last (whose activations are still held) and accumulates the gradients (pvr_trainer_backward_acc: the last pass first, then the others in frame
-    order), so the workspace is sized by the chunk and not by n.  n <= max_batch stays one forward and one backward."""
+    order), so the workspace is sized by the chunk and not by n.  n <= max_batch stays one forward and one backward.
 
-    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False):
+    wgrad_split16: every weight gradient, conv1's included, as an exact-split product on the f16 matrix pipe (pvr_trainer_set_wgrad_split16: per-tensor
+    power-of-two scales, three MFMAs per fragment pair, fp32 accumulation).  The forward, the data gradients and BatchNorm are untouched; a
+    convolution weight gradient moves by about 2^-22 relative.  Chosen at construction (it decides the workspace); legal in both BatchNorm modes."""
+
+    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False):
         super().__init__()
         assert variant in _TRAINABLE, variant
         _lib.require_gpu()
@@ -445,6 +449,9 @@ class HipTrainableResNet(_Node):
         h = C.c_void_p()
         _lib.check(L.pvr_trainer_create(C.byref(desc), C.byref(h)))
         self._handle = h
+        self._wgrad_split16 = False
+        if wgrad_split16:
+            self.set_wgrad_split16(True)
         dev = torch.device('cuda')
         self._flat = torch.zeros(L.pvr_trainer_param_count(h), dtype=torch.float32, device=dev)
         self._bufs = torch.zeros(L.pvr_trainer_buffer_count(h), dtype=torch.float32, device=dev)
@@ -517,6 +524,16 @@ class HipTrainableResNet(_Node):
         _lib.check(_lib.lib().pvr_trainer_set_bn_frozen(self._handle, 1 if on else 0))
         self._freeze_bn = bool(on)
         self._fwd_gen += 1
+
+    @property
+    def wgrad_split16(self):
+        return self._wgrad_split16
+
+    def set_wgrad_split16(self, on=True):
+        """split-f16 weight gradients on / off (see the class docstring); only before the first training forward has made the workspace - afterwards
+        the library refuses with a state error"""
+        _lib.check(_lib.lib().pvr_trainer_set_wgrad_split16(self._handle, 1 if on else 0))
+        self._wgrad_split16 = bool(on)
 
     def _passes(self, n):
         """[(lo, hi)] of the passes of a training forward of n frames, in frame order"""
@@ -600,9 +617,10 @@ def require_trainable(embedding_name):
     return _SINGLE[embedding_name][1]
 
 
-def trainer_workspace_bytes(embedding_name, max_batch):
+def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False):
     """bytes of device memory the training workspace of `embedding_name` takes for max_batch frames (pvr_trainer_workspace_bytes on a handle made
-    for the question: host arithmetic, no GPU needed); None when the trainer refuses that max_batch (a tensor of the workspace would pass 2 GiB)"""
+    for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients; None when the trainer refuses that max_batch (a
+    tensor of the workspace would pass 2 GiB)"""
     variant = require_trainable(embedding_name)
     L = _lib.lib()
     tr = transforms_for('')
@@ -615,12 +633,14 @@ def trainer_workspace_bytes(embedding_name, max_batch):
             return None
         _lib.check(1)
     try:
+        if wgrad_split16:
+            _lib.check(L.pvr_trainer_set_wgrad_split16(h, 1))
         return int(L.pvr_trainer_workspace_bytes(h))
     finally:
         L.pvr_trainer_destroy(h)
 
 
-def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False):
+def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -631,7 +651,7 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
         raise ValueError("train=True computes in fp32 (compute_dtype None or 'f32'), got %r" % (compute_dtype,))
     sd, variant = _load_named_state_dict(embedding_name, pretrained)
-    return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn)
+    return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16)
 
 
 class UberModel(nn.Module):
@@ -826,7 +846,7 @@ class EmbeddingNet(nn.Module):
     """
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
-                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False):
+                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -840,9 +860,13 @@ class EmbeddingNet(nn.Module):
             raise NotImplementedError('train=True with crops=5: the 5-crop extension wraps the frozen encoder only')
         if freeze_bn and not train:
             raise ValueError('freeze_bn is a mode of the trainable encoder (train=True): a frozen encoder already runs on the running statistics')
+        if wgrad_split16 and not train:
+            raise ValueError('wgrad_split16 is a mode of the trainable encoder (train=True): a frozen encoder computes no weight gradient')
         # freeze_bn (train=True only): frozen BatchNorm, max_batch is then the chunk of a training forward (HipTrainableResNet)
+        # wgrad_split16 (train=True only): the weight gradients as exact-split products on the f16 matrix pipe
         self.embedding, self.transforms = _get_embedding(embedding_name, in_channels, pretrained, train, compute_dtype=compute_dtype, max_batch=max_batch,
-                                                         chunk=chunk, host=self._host, **({'freeze_bn': True} if freeze_bn else {}))
+                                                         chunk=chunk, host=self._host, **({'freeze_bn': True} if freeze_bn else {}),
+                                                         **({'wgrad_split16': True} if wgrad_split16 else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

@@ -10,6 +10,9 @@ reference's T = 100 -> profiles/frozen_bn_step_times.txt.  B = 16, two frames pe
      largest shape of the two new kernels - next to their byte floor (tensors streamed x bytes / 6.0 TB/s, the in-order HBM sweep rate).
 
     python scripts/frozen_bn_step_times.py [--steps 5] [--T 100] [--only resnet50] [--out profiles/frozen_bn_step_times.txt]
+
+--wgrad_split16 measures item 1 alone, with the fp32 and with the split-f16 weight gradients (pvr_trainer_set_wgrad_split16) in the same process, and
+APPENDS the lines to --out (default profiles/wgrad_split16_times.txt, next to the per-launch figures of scripts/train_step_times.py --wgrad_split16).
 """
 import argparse
 import ctypes as C
@@ -52,10 +55,10 @@ def spread(ms):
     return '%9.2f ms median (min %.2f, max %.2f, %d steps)' % (statistics.median(ms), min(ms), max(ms), len(ms))
 
 
-def step_times(name, T, chunk, freeze, steps):
+def step_times(name, T, chunk, freeze, steps, split16=False):
     """-> (per-step ms list, workspace bytes, passes, loss, norm) of the fused step"""
     n = T * B * F_
-    net = E.EmbeddingNet(name, pretrained=False, train=True, freeze_bn=freeze, max_batch=chunk)
+    net = E.EmbeddingNet(name, pretrained=False, train=True, freeze_bn=freeze, max_batch=chunk, **({'wgrad_split16': True} if split16 else {}))
     model = M.PolicyNetWithEncoder(net, 3, True, num_frames=F_, max_unroll=T, max_batch=B)
     model.train()
     opt = M.HipJointRMSprop(model, lr=1e-4, max_epochs=1000)
@@ -163,13 +166,40 @@ def one(name, T, chunk, steps, lines):
     lines.append('')
 
 
+def split16_compare(name, T, chunk, steps, lines):
+    n = T * B * F_
+    lines.append('== %s, frozen BatchNorm, fused step, T %d x B %d x %d frames = %d frames per step in passes of %d ==' % (name, T, B, F_, n, chunk))
+    med = {}
+    for split16 in (False, True):
+        ms, ws, passes, loss, norm = step_times(name, T, chunk, True, steps, split16)
+        med[split16] = statistics.median(ms)
+        lines.append('%-24s %s, %7.1f frames/s, workspace %.2f GB, %d passes (loss %.4f, gradient norm %.3f)'
+                     % ('split-f16 weight gradients' if split16 else 'fp32 weight gradients', spread(ms), n / med[split16] * 1e3, ws / 2 ** 30, passes, loss, norm))
+    lines.append('step time fp32 / split-f16: %.2fx' % (med[False] / med[True]))
+    lines.append('')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--T', type=int, default=100)
     ap.add_argument('--only', default=None)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'frozen_bn_step_times.txt'))
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--wgrad_split16', action='store_true', help='the chunked frozen step with fp32 and with split-f16 weight gradients; appends to --out')
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, 'profiles', 'wgrad_split16_times.txt' if a.wgrad_split16 else 'frozen_bn_step_times.txt')
+    if a.wgrad_split16:
+        lines = ['fused end-to-end BC step with frozen BatchNorm (scripts/frozen_bn_step_times.py --wgrad_split16), %s; one process, a warm-up step, then '
+                 '--steps timed steps per mode' % torch.cuda.get_device_name(0), '']
+        for name, chunk in (('resnet50', 320), ('resnet18', 640)):
+            if a.only in (None, name):
+                split16_compare(name, a.T, chunk, a.steps, lines)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write('\n'.join(lines) + '\n')
+        print('\n'.join(lines))
+        return
     lines = ['fused end-to-end BC step with frozen BatchNorm (scripts/frozen_bn_step_times.py), %s; eager launches, BatchNorm1d on, 64x64 frames'
              % torch.cuda.get_device_name(0),
              'one session, one process: both BatchNorm modes of the same build, measured when the frozen mode was added; a warm-up step, then --steps timed steps', '']
