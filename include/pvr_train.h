@@ -7,7 +7,9 @@
  * every product of a convolution, a data gradient or a weight gradient on the f32-input MFMA (the arithmetic of the PVR_F32
  * plan), one GPU.  BatchNorm runs on the statistics of the WHOLE batch of a forward (they cannot be chunked) or, after
  * pvr_trainer_set_bn_frozen, on its running statistics (frames independent: a step is a sum over passes).  After
- * pvr_trainer_set_wgrad_split16 the weight gradients alone run as exact-split products on the f16 matrix pipe.
+ * pvr_trainer_set_wgrad_split16 the weight gradients alone run as exact-split products on the f16 matrix pipe; after
+ * pvr_trainer_set_conv_split16 the forward convolutions and the data gradients of layer1 .. layer4 do (conv1's forward, BatchNorm
+ * and the pools stay in fp32).  Both modes are off by default and independent of each other and of the BatchNorm mode.
  *
  * Buffers follow pvr_policy.h's convention: the caller owns ONE flat fp32 device buffer of parameters, every tensor in its
  * state_dict shape (conv weights in torch's (cout, cin, kh, kw) layout - the library repacks them inside the forward), and
@@ -83,6 +85,20 @@ pvr_status pvr_trainer_backward_acc(pvr_trainer *tr, const float *params_dev, co
  * afterwards the call returns PVR_ERR_STATE with a message.  pvr_trainer_workspace_bytes reports the size of the current mode; off, it is
  * what it was without the mode, to the byte. */
 pvr_status pvr_trainer_set_wgrad_split16(pvr_trainer *tr, int32_t on);
+
+/* Forward and data-gradient arithmetic of the handle.  on == 0 (the default): every convolution and data gradient on the f32-input MFMA, everything
+ * above, bit for bit, and the same workspace to the byte.  on != 0: every convolution of layer1 .. layer4 computes z = conv(x, W), and every data gradient
+ * dx [+]= conv(dz or its zero-filled stride-2 grid, rot180(W) transposed), as an exact-split product on the f16 matrix pipe (pvr_op_conv_fwd_split16 /
+ * pvr_op_conv_dgrad_split16): both operands times a per-tensor power of two (pvr_op_absmax_scale's rule, read on the device), a = a_hi + 2^-11 a_lo in
+ * f16, three MFMAs per fragment pair, fp32 accumulation, the scales undone exactly in the epilogue.  An activation's scale is computed once per forward,
+ * in the launch that also takes its first consumer's weight scale; the backward reuses it (with pvr_trainer_set_wgrad_split16 too: the saved
+ * activations and dz are scaled once for both uses).  conv1's forward, BatchNorm in either mode, the pools and - unless wgrad_split16 is on - the
+ * weight gradients stay in fp32.  Results move by about 2^-22 relative per product; two runs give the same bits.  Legal in both BatchNorm modes, with
+ * or without wgrad_split16.  The mode adds scale slots to the workspace, so it must be chosen before the first forward makes it: afterwards the call
+ * returns PVR_ERR_STATE with a message.  pvr_trainer_workspace_bytes reports the size of the current mode.  pvr_trainer_launch_time names the mode's
+ * launches: in the forward "<conv> scale" (weights [+ input]) and "<conv> split16" (weight pack + convolution), in the backward "<conv> bwd scale"
+ * (dz + weights) and "<conv> dgrad split16" (weight pack [+ grid] + convolution). */
+pvr_status pvr_trainer_set_conv_split16(pvr_trainer *tr, int32_t on);
 
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
@@ -160,6 +176,23 @@ pvr_status pvr_op_conv_wgrad_split16(const float *x_dev, const float *dz_dev, fl
 int64_t pvr_op_stem_wgrad_split16_scratch_floats(int32_t n, int32_t S);
 pvr_status pvr_op_stem_wgrad_split16(const float *img_dev, const float *dz_dev, float *dw_dev, int32_t n, int32_t S, const float *img_scale_dev,
                                      const float *dz_scale_dev, float *scratch_dev, int64_t scratch_floats, void *hip_stream);
+/* z (n,ho,wo,cout) = conv(x (n,h,w,cin), w torch's (cout,cin,k,k)) without bias, as an exact-split product on the f16 matrix pipe: x times *x_scale_dev
+ * and w times *w_scale_dev (powers of two from pvr_op_absmax_scale, read on the device), each scaled value split into hi = f16(a'), lo = f16((a' - hi)
+ * * 2048); a pack launch writes the split weights to the scratch, the convolution takes three v_mfma_f32_16x16x32_f16 per fragment pair (hi*hi; the two
+ * cross terms into a second accumulator scaled by 2^-11 once) and its epilogue multiplies by 1 / s_x and 1 / s_w (exact).  k 1..3, stride 1 or 2,
+ * pad < k, cin % 32 == 0, cout % 4 == 0; every operand below 2 GiB.  Two runs give the same bits.
+ * |error| <= (K + 20) 2^-24 sum|x||w| + 2^-27 (max|x| sum|w| + max|w| sum|x|) per element, K = k*k*cin the products of the sum. */
+int64_t pvr_op_conv_fwd_split16_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad);
+pvr_status pvr_op_conv_fwd_split16(const float *x_dev, const float *w_dev, float *z_dev, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k,
+                                   int32_t stride, int32_t pad, const float *x_scale_dev, const float *w_scale_dev, float *scratch_dev, int64_t scratch_floats,
+                                   void *hip_stream);
+/* pvr_op_conv_dgrad (same shapes, layouts and refusals) as the same split product: the pack launch writes the rotated, transposed split weights, a
+ * stride-2 convolution's dz goes to the even pixels of the zeroed grid (its scale is dz's: zeros do not move a maximum), and the epilogue adds what
+ * dx holds when accumulate != 0 (one fp32 addition; the bound gains 2^-24 (|previous| + |result|)).  K = k*k*cout. */
+int64_t pvr_op_conv_dgrad_split16_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad);
+pvr_status pvr_op_conv_dgrad_split16(const float *dz_dev, const float *w_dev, float *dx_dev, int32_t accumulate, int32_t n, int32_t h, int32_t w, int32_t cin,
+                                     int32_t cout, int32_t k, int32_t stride, int32_t pad, const float *dz_scale_dev, const float *w_scale_dev,
+                                     float *scratch_dev, int64_t scratch_floats, void *hip_stream);
 /* MaxPool2d(3, 2, 1) backward as a gather: x (n,h,w,c) the pool's input, dy (n,ho,wo,c), dx (n,h,w,c) fully written; a tie goes to the first maximum of a
  * window in scan order (torch's rule) */
 pvr_status pvr_op_maxpool_backward(const float *x_dev, const float *dy_dev, float *dx_dev, int32_t n, int32_t h, int32_t w, int32_t c, void *hip_stream);

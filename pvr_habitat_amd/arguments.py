@@ -40,6 +40,11 @@ def make_parser():
                         help='with --train_embedding: every weight gradient of the encoder, conv1\'s included, as an exact-split product on the f16 matrix '
                              'pipe (per-tensor power-of-two scales, three MFMAs per fragment pair, fp32 accumulation: about 2^-22 relative to the fp32 '
                              'path); the forward, the data gradients and BatchNorm stay fp32.  Works with and without --freeze_embedding_bn')
+    parser.add_argument('--embedding_conv_split16', action='store_true',
+                        help='with --train_embedding: every forward convolution and data gradient of the encoder\'s layer1 .. layer4 as an exact-split '
+                             'product on the f16 matrix pipe (both operands scaled per tensor on the device, three MFMAs per fragment pair, fp32 '
+                             'accumulation: about 2^-22 relative per product); conv1, BatchNorm and the pools stay fp32, the weight gradients too unless '
+                             '--embedding_wgrad_split16 is given as well.  Works with and without --freeze_embedding_bn')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

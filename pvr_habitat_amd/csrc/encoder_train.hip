@@ -3,7 +3,8 @@
 // dataflow f32_chunk walks) with ONE saved pre-BN and one post-BN tensor per op instead of the reused workspace buffers, and walks it backwards for the
 // gradients.  The device code of the backward pass is train_kernels.hip; every product of a convolution, data gradient or weight gradient runs on the
 // f32-input MFMA (conv_f32.hip / conv_wgrad_kernel), BatchNorm statistics are two-pass, and every split reduction is summed in a fixed order.
-// pvr_trainer_set_wgrad_split16 moves the weight gradients, and nothing else, to the exact-split f16 products of wgrad_split16.hip.
+// pvr_trainer_set_wgrad_split16 moves the weight gradients, and nothing else, to the exact-split f16 products of wgrad_split16.hip;
+// pvr_trainer_set_conv_split16 moves the forward convolutions and the data gradients of layer1 .. layer4 to those of conv_split16_scaled.hip.
 #include "encoder_internal.h"
 #include "train_internal.h"
 #include "../../include/pvr_train.h"
@@ -51,8 +52,12 @@ struct pvr_trainer {
     int fwd_n = 0;                               // frames of the forward whose activations are held (0: none - a backward is PVR_ERR_STATE)
     bool bn_frozen = false;                      // BatchNorm normalises with its running statistics (pvr_trainer_set_bn_frozen)
     bool wgrad_split16 = false;                  // weight gradients as exact-split f16 products (pvr_trainer_set_wgrad_split16); fixed once the arena exists
-    float *scales = nullptr;                     // split mode: one absmax scale per saved tensor (index src + 1), the image (ops + 1), dz (ops + 2),
-                                                 // then pvr_op_absmax_scale_pair's four aux words (zeroed with the workspace)
+    bool conv_split16 = false;                   // forward convolutions and data gradients of the op list as exact-split f16 products
+                                                 // (pvr_trainer_set_conv_split16); fixed once the arena exists
+    float *scales = nullptr;                     // split modes: one absmax scale per saved tensor (index src + 1), the image (ops + 1), dz (ops + 2),
+                                                 // then pvr_op_absmax_scale_pair's four aux words (zeroed with the workspace); conv_split16: one more
+                                                 // slot behind them, the scale of the weights of the convolution at hand
+    size_t scale_slots() const { return ops.size() + 3 + 4 + (conv_split16 ? 1 : 0); }
     bool timing = false;
     std::vector<Timed> times;                    // launch i of a step is bracketed by events[i]
     std::vector<EventPair> events;               // made once each, on demand; destroyed with the trainer (no error path leaves one behind)
@@ -126,10 +131,9 @@ void carve(pvr_trainer *t, Carver &c) {
     c.take(&t->dil, dil_max);
     c.take(&t->wpack, w_max);
     c.take(&t->stem_wpack, (size_t)64 * 49 * 4);
-    if (t->wgrad_split16) {                       // (off: not a byte of the workspace changes)
-        wg_max = std::max(wg_max, pvr_op_stem_wgrad_split16_scratch_floats(B, S_IMG));
-        c.take(&t->scales, t->ops.size() + 3 + 4);
-    }
+    if (t->wgrad_split16) wg_max = std::max(wg_max, pvr_op_stem_wgrad_split16_scratch_floats(B, S_IMG));
+    // (both modes off: not a byte of the workspace changes.  The split weights of conv_split16 take wpack as they are: two f16 per value)
+    if (t->wgrad_split16 || t->conv_split16) c.take(&t->scales, t->scale_slots());
     c.take(&t->wg_scratch, (size_t)wg_max);
     c.take(&t->bn_scratch, (size_t)bn_max);
     c.take(&t->zero_bias, (size_t)c_max);
@@ -150,7 +154,7 @@ pvr_status ensure_workspace(pvr_trainer *t) {
     const size_t img_bytes = (size_t)t->desc.max_batch * (S_IMG + 6) * (S_IMG + 8) * 4 * 2;
     const size_t zero_bytes = (size_t)((char *)a + size.used - (char *)t->zero_bias);      // (the arena's last piece)
     if (hipMemset(t->d_img, 0, img_bytes) != hipSuccess || hipMemset(t->zero_bias, 0, zero_bytes) != hipSuccess ||
-        (t->scales && hipMemset(t->scales, 0, (t->ops.size() + 3 + 4) * sizeof(float)) != hipSuccess) || hipDeviceSynchronize() != hipSuccess) {
+        (t->scales && hipMemset(t->scales, 0, t->scale_slots() * sizeof(float)) != hipSuccess) || hipDeviceSynchronize() != hipSuccess) {
         (void)hipFree(a);
         set_error("pvr_trainer: workspace initialisation failed");
         return PVR_ERR_HIP;
@@ -360,8 +364,26 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
     TR_RUN("conv1", 2.0 * n * 112 * 112 * 64 * 147, launch_stem_f32(t->d_imgf, t->stem_wpack, nullptr, sm.z, n, S_IMG, st, true));
     TR_RUN("bn1", 0, bn(sm, nullptr, (int64_t)n * 112 * 112));
     TR_RUN("maxpool", 0, launch_maxpool_f32(sm.y, t->pool, n, 112, 112, 64, st));
+    // conv_split16: a tensor's scale is computed once per forward, in the launch of its first consumer, next to that convolution's weight scale; the
+    // slots stay valid for the backward (the saved activations do not change)
+    std::vector<char> scaled(t->ops.size() + 1, 0);
+    float *w_scale = t->conv_split16 ? t->scales + t->ops.size() + 7 : nullptr;
+    uint32_t *scale_aux = t->conv_split16 ? (uint32_t *)(t->scales + t->ops.size() + 3) : nullptr;
     for (TrainOp &op : t->ops) {
         const int64_t rows = (int64_t)n * op.ho * op.wo;
+        if (t->conv_split16) {
+            const float *x = tensor_of(t, op.in_src);
+            float *x_scale = t->scales + op.in_src + 1;
+            const bool first = !scaled[op.in_src + 1];
+            TR_RUN(op.conv + " scale", 0,
+                   pvr_op_absmax_scale_pair(params + op.w_off, (int64_t)op.cout * op.cin * op.k * op.k, w_scale, first ? x : nullptr,
+                                            (int64_t)n * op.h * op.w * op.cin, first ? x_scale : nullptr, scale_aux, st));
+            scaled[op.in_src + 1] = 1;
+            TR_RUN(op.conv + " split16", 2.0 * rows * op.cout * op.cin * op.k * op.k,
+                   launch_conv_fwd_split16(x, params + op.w_off, op.z, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, x_scale, w_scale, t->wpack, st));
+            TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows));
+            continue;
+        }
         TR_RUN(op.conv + " pack", 0, launch_pack_conv_weights(params + op.w_off, t->wpack, op.cout, op.cin, op.k, false, st));
         TR_RUN(op.conv, 2.0 * rows * op.cout * op.cin * op.k * op.k,
                launch_conv_f32(tensor_of(t, op.in_src), t->wpack, t->zero_bias, nullptr, op.z, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, 0, st));
@@ -387,10 +409,12 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
     std::vector<char> have(t->ops.size() + 1, 0);  // gradient of tensor src (index src + 1) holds a value already: the next contribution accumulates
     const int last = (int)t->ops.size() - 1;
     // split mode: the scale of a saved activation is computed once per backward, by its first consumer; dz's right after the BatchNorm backward
-    const bool split = t->wgrad_split16;
-    std::vector<char> scaled(t->ops.size() + 1, 0);
-    float *dz_scale = split ? t->scales + t->ops.size() + 2 : nullptr;
-    uint32_t *scale_aux = split ? (uint32_t *)(t->scales + t->ops.size() + 3) : nullptr;
+    // conv_split16: the forward left every saved activation's scale in its slot, so the launch takes dz and the convolution's weights instead
+    const bool split = t->wgrad_split16, csplit = t->conv_split16;
+    std::vector<char> scaled(t->ops.size() + 1, csplit ? 1 : 0);
+    float *dz_scale = split || csplit ? t->scales + t->ops.size() + 2 : nullptr;
+    uint32_t *scale_aux = split || csplit ? (uint32_t *)(t->scales + t->ops.size() + 3) : nullptr;
+    float *w_scale = csplit ? t->scales + t->ops.size() + 7 : nullptr;
     // one launch per convolution: dz, and the input tensor when this is its first consumer of the backward (x == nullptr: scaled already)
     auto scales_of = [&](const std::string &conv, size_t dz_count, const float *x, size_t x_count, float *x_slot) -> pvr_status {
         TR_RUN(conv + " scale", 0, pvr_op_absmax_scale_pair(t->dz, (int64_t)dz_count, dz_scale, x, (int64_t)x_count, x ? x_slot : nullptr, scale_aux, st));
@@ -408,9 +432,13 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
                       rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st));
         if (dres) have[op.res_src + 1] = 1;
         const double fl = 2.0 * rows * op.cout * op.cin * op.k * op.k;
+        if (csplit)
+            TR_RUN(op.conv + " bwd scale", 0,
+                   pvr_op_absmax_scale_pair(t->dz, (int64_t)out_elems(op, n), dz_scale, params + op.w_off, (int64_t)op.cout * op.cin * op.k * op.k, w_scale,
+                                            scale_aux, st));
         if (split) {
             float *x_scale = t->scales + op.in_src + 1;
-            if ((s = scales_of(op.conv, out_elems(op, n), scaled[op.in_src + 1] ? nullptr : tensor_of(t, op.in_src), (size_t)n * op.h * op.w * op.cin, x_scale)))
+            if (!csplit && (s = scales_of(op.conv, out_elems(op, n), scaled[op.in_src + 1] ? nullptr : tensor_of(t, op.in_src), (size_t)n * op.h * op.w * op.cin, x_scale)))
                 return s;
             scaled[op.in_src + 1] = 1;
             TR_RUN(op.conv + " wgrad", fl,
@@ -420,9 +448,14 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
             TR_RUN(op.conv + " wgrad", fl,
                    pvr_op_conv_wgrad(tensor_of(t, op.in_src), t->dz, grads + op.w_off, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, t->wg_scratch,
                                      t->wg_floats, st));
-        TR_RUN(op.conv + " dgrad", fl,
-               launch_conv_dgrad(t->dz, params + op.w_off, grad_of(t, op.in_src), have[op.in_src + 1], n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad,
-                                 t->wpack, t->dil, t->zero_bias, st));
+        if (csplit)
+            TR_RUN(op.conv + " dgrad split16", fl,
+                   launch_conv_dgrad_split16(t->dz, params + op.w_off, grad_of(t, op.in_src), have[op.in_src + 1], n, op.h, op.w, op.cin, op.cout, op.k, op.stride,
+                                             op.pad, dz_scale, w_scale, t->wpack, t->dil, st));
+        else
+            TR_RUN(op.conv + " dgrad", fl,
+                   launch_conv_dgrad(t->dz, params + op.w_off, grad_of(t, op.in_src), have[op.in_src + 1], n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad,
+                                     t->wpack, t->dil, t->zero_bias, st));
         have[op.in_src + 1] = 1;
     }
     PVR_REQUIRE(have[0], "pvr_trainer_backward: the max pool's output has no consumer");
@@ -487,6 +520,17 @@ pvr_status pvr_trainer_set_wgrad_split16(pvr_trainer *t, int32_t on) {
         return PVR_ERR_STATE;
     }
     t->wgrad_split16 = on != 0;
+    return PVR_OK;
+}
+
+pvr_status pvr_trainer_set_conv_split16(pvr_trainer *t, int32_t on) {
+    PVR_REQUIRE(t, "pvr_trainer_set_conv_split16: null trainer");
+    if (t->arena && (on != 0) != t->conv_split16) {
+        set_error("pvr_trainer_set_conv_split16: the workspace of this handle exists already (the first forward made it for the %s convolutions): choose "
+                  "the mode before the first forward", t->conv_split16 ? "split-f16" : "fp32");
+        return PVR_ERR_STATE;
+    }
+    t->conv_split16 = on != 0;
     return PVR_OK;
 }
 

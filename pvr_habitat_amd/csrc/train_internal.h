@@ -13,4 +13,13 @@ pvr_status launch_conv_dgrad(const float *dz, const float *w, float *dx, int acc
                              float *wflip, float *dil, const float *zero_bias, hipStream_t st);
 // grads[i] += pass[i] over n floats: one fp32 addition per element (gradient accumulation over the passes of a chunked step)
 pvr_status launch_grad_add(float *grads, const float *pass, int64_t n, hipStream_t st);
+// dz (n, h/2, w/2, c) -> the even pixels of a zeroed (n, h, w, c) grid: the stride-2 data gradients' input
+pvr_status launch_dilate2(const float *dz, float *out, int n, int h, int w, int c, hipStream_t st);
+// conv_split16_scaled.hip: the forward and the data gradient of a convolution as exact-split f16 products with per-tensor scales read from the device
+// (sx / sdz / sw: one float each, pvr_op_absmax_scale's rule).  w: torch's (cout, cin, k, k).  wpack / wflip: the split weights, rows_pad * k*k * cols floats
+// as launch_pack_conv_weights; dil: n*h*w*cout floats (stride 2 only).  Refusals as pvr_op_conv_fwd_split16 / pvr_op_conv_dgrad_split16.
+pvr_status launch_conv_fwd_split16(const float *x, const float *w, float *z, int n, int h, int wd, int cin, int cout, int k, int stride, int pad, const float *sx,
+                                   const float *sw, float *wpack, hipStream_t st);
+pvr_status launch_conv_dgrad_split16(const float *dz, const float *w, float *dx, int accumulate, int n, int h, int wd, int cin, int cout, int k, int stride, int pad,
+                                     const float *sdz, const float *sw, float *wflip, float *dil, hipStream_t st);
 }  // namespace pvr

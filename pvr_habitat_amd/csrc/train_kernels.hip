@@ -414,6 +414,13 @@ __global__ __launch_bounds__(256) void dilate2_kernel(const float *__restrict__ 
     }
 }
 
+// (the split-f16 data gradient's use of the same grid: conv_split16_scaled.hip)
+pvr_status launch_dilate2(const float *dz, float *out, int n, int h, int w, int c, hipStream_t st) {
+    hipLaunchKernelGGL(dilate2_kernel, dim3(ew_blocks((size_t)n * h * w * c / 4)), dim3(256), 0, st, dz, out, n, h, w, c);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
 static pvr_status dgrad_check(int n, int h, int w, int cin, int cout, int k, int stride, int pad) {
     PVR_REQUIRE(n > 0 && h > 0 && w > 0, "conv_dgrad: empty input");
     PVR_REQUIRE((k == 3 && pad == 1) || (k == 1 && pad == 0), "conv_dgrad: (k, pad) = (%d, %d); built for (3, 1) and (1, 0)", k, pad);

@@ -427,9 +427,14 @@ class HipTrainableResNet(_Node):
 
     wgrad_split16: every weight gradient, conv1's included, as an exact-split product on the f16 matrix pipe (pvr_trainer_set_wgrad_split16: per-tensor
     power-of-two scales, three MFMAs per fragment pair, fp32 accumulation).  The forward, the data gradients and BatchNorm are untouched; a
-    convolution weight gradient moves by about 2^-22 relative.  Chosen at construction (it decides the workspace); legal in both BatchNorm modes."""
+    convolution weight gradient moves by about 2^-22 relative.  Chosen at construction (it decides the workspace); legal in both BatchNorm modes.
 
-    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False):
+    conv_split16: every forward convolution and data gradient of layer1 .. layer4 as the same kind of product (pvr_trainer_set_conv_split16: both
+    operands scaled per tensor on the device, so gradients of 1e-6 and activations past 65504 keep their precision); conv1's forward, BatchNorm, the
+    pools and - unless wgrad_split16 is on as well - the weight gradients stay fp32.  Embeddings and gradients move by about 2^-22 relative per
+    product.  Chosen at construction; legal in both BatchNorm modes, with or without wgrad_split16.  Eval mode keeps running the frozen 'f32' plan."""
+
+    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False):
         super().__init__()
         assert variant in _TRAINABLE, variant
         _lib.require_gpu()
@@ -452,6 +457,9 @@ class HipTrainableResNet(_Node):
         self._wgrad_split16 = False
         if wgrad_split16:
             self.set_wgrad_split16(True)
+        self._conv_split16 = False
+        if conv_split16:
+            self.set_conv_split16(True)
         dev = torch.device('cuda')
         self._flat = torch.zeros(L.pvr_trainer_param_count(h), dtype=torch.float32, device=dev)
         self._bufs = torch.zeros(L.pvr_trainer_buffer_count(h), dtype=torch.float32, device=dev)
@@ -535,6 +543,16 @@ class HipTrainableResNet(_Node):
         _lib.check(_lib.lib().pvr_trainer_set_wgrad_split16(self._handle, 1 if on else 0))
         self._wgrad_split16 = bool(on)
 
+    @property
+    def conv_split16(self):
+        return self._conv_split16
+
+    def set_conv_split16(self, on=True):
+        """split-f16 forward convolutions and data gradients on / off (see the class docstring); only before the first training forward has made the
+        workspace - afterwards the library refuses with a state error"""
+        _lib.check(_lib.lib().pvr_trainer_set_conv_split16(self._handle, 1 if on else 0))
+        self._conv_split16 = bool(on)
+
     def _passes(self, n):
         """[(lo, hi)] of the passes of a training forward of n frames, in frame order"""
         return [(lo, min(lo + self._max_batch, n)) for lo in range(0, n, self._max_batch)]
@@ -617,9 +635,9 @@ def require_trainable(embedding_name):
     return _SINGLE[embedding_name][1]
 
 
-def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False):
+def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv_split16=False):
     """bytes of device memory the training workspace of `embedding_name` takes for max_batch frames (pvr_trainer_workspace_bytes on a handle made
-    for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients; None when the trainer refuses that max_batch (a
+    for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients and convolutions; None when the trainer refuses that max_batch (a
     tensor of the workspace would pass 2 GiB)"""
     variant = require_trainable(embedding_name)
     L = _lib.lib()
@@ -635,12 +653,15 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False):
     try:
         if wgrad_split16:
             _lib.check(L.pvr_trainer_set_wgrad_split16(h, 1))
+        if conv_split16:
+            _lib.check(L.pvr_trainer_set_conv_split16(h, 1))
         return int(L.pvr_trainer_workspace_bytes(h))
     finally:
         L.pvr_trainer_destroy(h)
 
 
-def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False):
+def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
+                   conv_split16=False):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -651,7 +672,7 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
         raise ValueError("train=True computes in fp32 (compute_dtype None or 'f32'), got %r" % (compute_dtype,))
     sd, variant = _load_named_state_dict(embedding_name, pretrained)
-    return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16)
+    return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16, conv_split16=conv_split16)
 
 
 class UberModel(nn.Module):
@@ -846,7 +867,7 @@ class EmbeddingNet(nn.Module):
     """
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
-                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False):
+                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -862,11 +883,16 @@ class EmbeddingNet(nn.Module):
             raise ValueError('freeze_bn is a mode of the trainable encoder (train=True): a frozen encoder already runs on the running statistics')
         if wgrad_split16 and not train:
             raise ValueError('wgrad_split16 is a mode of the trainable encoder (train=True): a frozen encoder computes no weight gradient')
+        if conv_split16 and not train:
+            raise ValueError('conv_split16 is a mode of the trainable encoder (train=True): a frozen encoder has its own plans (compute_dtype \'f32s\' is '
+                             'the split-f16 one)')
         # freeze_bn (train=True only): frozen BatchNorm, max_batch is then the chunk of a training forward (HipTrainableResNet)
         # wgrad_split16 (train=True only): the weight gradients as exact-split products on the f16 matrix pipe
+        # conv_split16 (train=True only): the forward convolutions and the data gradients of layer1 .. layer4 as such products
         self.embedding, self.transforms = _get_embedding(embedding_name, in_channels, pretrained, train, compute_dtype=compute_dtype, max_batch=max_batch,
                                                          chunk=chunk, host=self._host, **({'freeze_bn': True} if freeze_bn else {}),
-                                                         **({'wgrad_split16': True} if wgrad_split16 else {}))
+                                                         **({'wgrad_split16': True} if wgrad_split16 else {}),
+                                                         **({'conv_split16': True} if conv_split16 else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

@@ -43,14 +43,15 @@ def load_raw(flags, from_env):
     return obs, action, reward, done
 
 
-def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False):
-    """the largest frame count <= frames_wanted whose training workspace (with fp32 or split-f16 weight gradients) fits free_bytes (0: not even one
-    frame)"""
+def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False, conv_split16=False):
+    """the largest frame count <= frames_wanted whose training workspace (with fp32 or split-f16 weight gradients / convolutions) fits free_bytes
+    (0: not even one frame)"""
+    conv16 = {'conv_split16': True} if conv_split16 else {}
     from .embeddings import trainer_workspace_bytes
     lo, hi = 0, int(frames_wanted)                              # invariant: lo fits (or is 0), hi + 1 does not
     while lo < hi:
         mid = (lo + hi + 1) // 2
-        need = trainer_workspace_bytes(embedding_name, mid, wgrad_split16)     # (None: more frames than the trainer's launches can address)
+        need = trainer_workspace_bytes(embedding_name, mid, wgrad_split16, **conv16)     # (None: more frames than the trainer's launches can address)
         if need is not None and need <= free_bytes:
             lo = mid
         else:
@@ -68,10 +69,11 @@ def check_workspace_fits(flags, n_frames_per_obs):
     if getattr(flags, 'freeze_embedding_bn', False):
         return check_chunk_fits(flags, want)
     split16 = bool(getattr(flags, 'embedding_wgrad_split16', False))       # (the mode's scale slots and scratch are part of the workspace)
-    need = trainer_workspace_bytes(flags.embedding_name, want, split16)
+    conv16 = {'conv_split16': True} if getattr(flags, 'embedding_conv_split16', False) else {}
+    need = trainer_workspace_bytes(flags.embedding_name, want, split16, **conv16)
     free = int(torch.cuda.mem_get_info()[0])
     if need is None or need > free:
-        fit = largest_fitting_frames(flags.embedding_name, want, free, split16)
+        fit = largest_fitting_frames(flags.embedding_name, want, free, split16, **conv16)
         why = 'is more than the trainer\'s launches can address (one tensor of its workspace would pass 2 GiB)' if need is None \
             else 'takes %.2f GB, %.2f GB of device memory are free' % (need / 2 ** 30, free / 2 ** 30)
         raise RuntimeError("--train_embedding: the training workspace of '%s' for unroll_length %d x batch_size %d x %d frames = %d frames %s; "
@@ -91,17 +93,18 @@ def check_chunk_fits(flags, want):
     free = int(torch.cuda.mem_get_info()[0])
     chunk = getattr(flags, 'embedding_chunk', None)
     split16 = bool(getattr(flags, 'embedding_wgrad_split16', False))
+    conv16 = {'conv_split16': True} if getattr(flags, 'embedding_conv_split16', False) else {}
     if chunk is None:
-        chunk = largest_fitting_frames(flags.embedding_name, want, free // 10 * 9, split16)
+        chunk = largest_fitting_frames(flags.embedding_name, want, free // 10 * 9, split16, **conv16)
         if chunk < 1:
             raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for a chunk of one frame takes %.2f GB, %.2f GB "
-                               "of device memory are free" % (flags.embedding_name, trainer_workspace_bytes(flags.embedding_name, 1, split16) / 2 ** 30, free / 2 ** 30))
+                               "of device memory are free" % (flags.embedding_name, trainer_workspace_bytes(flags.embedding_name, 1, split16, **conv16) / 2 ** 30, free / 2 ** 30))
     if chunk < 1:
         raise ValueError('--embedding_chunk %d: a pass takes at least one frame' % chunk)
     chunk = min(int(chunk), want)
-    need = trainer_workspace_bytes(flags.embedding_name, chunk, split16)
+    need = trainer_workspace_bytes(flags.embedding_name, chunk, split16, **conv16)
     if need is None or need > free:
-        fit = largest_fitting_frames(flags.embedding_name, chunk, free, split16)
+        fit = largest_fitting_frames(flags.embedding_name, chunk, free, split16, **conv16)
         why = 'is more than the trainer\'s launches can address (one tensor of its workspace would pass 2 GiB)' if need is None \
             else 'takes %.2f GB, %.2f GB of device memory are free' % (need / 2 ** 30, free / 2 ** 30)
         raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for --embedding_chunk %d frames %s; the largest "
@@ -164,6 +167,9 @@ def run_end_to_end(flags, make_env=None):
     split16 = {'wgrad_split16': True} if getattr(flags, 'embedding_wgrad_split16', False) else {}
     if split16:
         print('  ', 'weight gradients: exact-split products on the f16 matrix pipe')
+    if getattr(flags, 'embedding_conv_split16', False):
+        split16 = dict(split16, conv_split16=True)
+        print('  ', 'forward convolutions and data gradients: exact-split products on the f16 matrix pipe')
     if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
         if not flags.pretrained_embedding:
             print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')

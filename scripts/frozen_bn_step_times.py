@@ -13,6 +13,8 @@ reference's T = 100 -> profiles/frozen_bn_step_times.txt.  B = 16, two frames pe
 
 --wgrad_split16 measures item 1 alone, with the fp32 and with the split-f16 weight gradients (pvr_trainer_set_wgrad_split16) in the same process, and
 APPENDS the lines to --out (default profiles/wgrad_split16_times.txt, next to the per-launch figures of scripts/train_step_times.py --wgrad_split16).
+--conv_split16 measures item 1 in four modes - fp32, split-f16 weight gradients, split-f16 convolutions and data gradients
+(pvr_trainer_set_conv_split16), both - and APPENDS to --out (default profiles/conv_split16_times.txt).
 """
 import argparse
 import ctypes as C
@@ -55,10 +57,11 @@ def spread(ms):
     return '%9.2f ms median (min %.2f, max %.2f, %d steps)' % (statistics.median(ms), min(ms), max(ms), len(ms))
 
 
-def step_times(name, T, chunk, freeze, steps, split16=False):
+def step_times(name, T, chunk, freeze, steps, split16=False, conv16=False):
     """-> (per-step ms list, workspace bytes, passes, loss, norm) of the fused step"""
     n = T * B * F_
-    net = E.EmbeddingNet(name, pretrained=False, train=True, freeze_bn=freeze, max_batch=chunk, **({'wgrad_split16': True} if split16 else {}))
+    net = E.EmbeddingNet(name, pretrained=False, train=True, freeze_bn=freeze, max_batch=chunk, **({'wgrad_split16': True} if split16 else {}),
+                         **({'conv_split16': True} if conv16 else {}))
     model = M.PolicyNetWithEncoder(net, 3, True, num_frames=F_, max_unroll=T, max_batch=B)
     model.train()
     opt = M.HipJointRMSprop(model, lr=1e-4, max_epochs=1000)
@@ -179,6 +182,21 @@ def split16_compare(name, T, chunk, steps, lines):
     lines.append('')
 
 
+def conv16_compare(name, T, chunk, steps, lines):
+    n = T * B * F_
+    lines.append('== %s, frozen BatchNorm, fused step, T %d x B %d x %d frames = %d frames per step in passes of %d ==' % (name, T, B, F_, n, chunk))
+    med = {}
+    for conv16, split16 in ((False, False), (False, True), (True, False), (True, True)):
+        ms, ws, passes, loss, norm = step_times(name, T, chunk, True, steps, split16, conv16)
+        med[(conv16, split16)] = statistics.median(ms)
+        what = '%s convolutions and data gradients, %s weight gradients' % ('split-f16' if conv16 else 'fp32', 'split-f16' if split16 else 'fp32')
+        lines.append('%-72s %s, %7.1f frames/s, workspace %.2f GB, %d passes (loss %.4f, gradient norm %.3f)'
+                     % (what, spread(ms), n / med[(conv16, split16)] * 1e3, ws / 2 ** 30, passes, loss, norm))
+    lines.append('step time fp32 / split-f16 convolutions: %.2fx with fp32 weight gradients, %.2fx with split-f16 weight gradients; all fp32 / all split-f16 %.2fx'
+                 % (med[(False, False)] / med[(True, False)], med[(False, True)] / med[(True, True)], med[(False, False)] / med[(True, True)]))
+    lines.append('')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=5)
@@ -186,15 +204,17 @@ def main():
     ap.add_argument('--only', default=None)
     ap.add_argument('--out', default=None)
     ap.add_argument('--wgrad_split16', action='store_true', help='the chunked frozen step with fp32 and with split-f16 weight gradients; appends to --out')
+    ap.add_argument('--conv_split16', action='store_true', help='the chunked frozen step in the four combinations of the two split modes; appends to --out')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'wgrad_split16_times.txt' if a.wgrad_split16 else 'frozen_bn_step_times.txt')
-    if a.wgrad_split16:
-        lines = ['fused end-to-end BC step with frozen BatchNorm (scripts/frozen_bn_step_times.py --wgrad_split16), %s; one process, a warm-up step, then '
-                 '--steps timed steps per mode' % torch.cuda.get_device_name(0), '']
+        a.out = os.path.join(ROOT, 'profiles', 'conv_split16_times.txt' if a.conv_split16 else 'wgrad_split16_times.txt' if a.wgrad_split16
+                             else 'frozen_bn_step_times.txt')
+    if a.wgrad_split16 or a.conv_split16:
+        lines = ['fused end-to-end BC step with frozen BatchNorm (scripts/frozen_bn_step_times.py --%s), %s; one process, a warm-up step, then '
+                 '--steps timed steps per mode' % ('conv_split16' if a.conv_split16 else 'wgrad_split16', torch.cuda.get_device_name(0)), '']
         for name, chunk in (('resnet50', 320), ('resnet18', 640)):
             if a.only in (None, name):
-                split16_compare(name, a.T, chunk, a.steps, lines)
+                (conv16_compare if a.conv_split16 else split16_compare)(name, a.T, chunk, a.steps, lines)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, 'a') as f:
             f.write('\n'.join(lines) + '\n')

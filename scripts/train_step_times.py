@@ -12,9 +12,17 @@ per-launch events of --reps steps each (minimum / median / maximum show the spre
 mode's scale launches counted in, and the step totals -> profiles/wgrad_split16_times.txt.
 
     python scripts/train_step_times.py --wgrad_split16 [--batch 32] [--reps 5] [--out profiles/wgrad_split16_times.txt]
+
+--conv_split16 does the same for the forward convolutions and the data gradients of layer1 .. layer4 (pvr_trainer_set_conv_split16): per convolution
+the fp32 launches (forward: weight pack + convolution; data gradient: its one bracket of pack [+ grid] + convolution) against the split launches with
+the scale launch that serves them (forward: "<conv> scale"; backward: "<conv> bwd scale", counted with the data gradient), their sums and the step
+totals -> profiles/conv_split16_times.txt.  --names picks the trunks, --append adds to the file (batch 32, then the frozen-BatchNorm pass sizes).
+
+    python scripts/train_step_times.py --conv_split16 [--batch 32] [--names resnet18,resnet50] [--reps 5] [--append]
 """
 import argparse
 import ctypes as C
+import gc
 import os
 import sys
 
@@ -82,11 +90,12 @@ def one(name, batch, lines):
     lines.append('')
 
 
-def measure_mode(name, batch, split16, reps):
-    """-> (ms per step without per-launch events, [launch rows of each of `reps` steps]) of one weight-gradient arithmetic"""
-    net = E.EmbeddingNet(name, pretrained=False, train=True, max_batch=batch, **({'wgrad_split16': True} if split16 else {}))
+def measure_mode(name, batch, split16, reps, conv16=False):
+    """-> (ms per step without per-launch events, [launch rows of each of `reps` steps]) of one arithmetic"""
+    net = E.EmbeddingNet(name, pretrained=False, train=True, max_batch=batch, **({'wgrad_split16': True} if split16 else {}),
+                         **({'conv_split16': True} if conv16 else {}))
     m = net.embedding
-    fr = torch.from_numpy(synth.smooth_frames(11, batch, 64, 64)).cuda()
+    fr = torch.from_numpy(synth.smooth_frames(11, 64, 64, 64)).cuda()[torch.arange(batch, device='cuda') % 64].contiguous()
     dout = torch.randn((batch, net.out_size), device='cuda', generator=torch.Generator('cuda').manual_seed(3)) / batch
 
     def step():
@@ -112,6 +121,8 @@ def measure_mode(name, batch, split16, reps):
         runs.append(launches(m._handle))
     _lib.check(_lib.lib().pvr_trainer_debug_set_timing(m._handle, 0))
     net.close()
+    del step, m, net                                  # (the workspace goes with the module: the next mode's fits next to nothing)
+    gc.collect()
     return total, runs
 
 
@@ -159,16 +170,78 @@ def compare(name, batch, reps, lines):
     lines.append('')
 
 
+def compare_conv(name, batch, reps, lines):
+    """forward convolutions and data gradients of layer1 .. layer4 in both modes, the scale and pack launches counted with the launch they serve"""
+    t_off, off = measure_mode(name, batch, False, reps)
+    t_on, on = measure_mode(name, batch, False, reps, conv16=True)
+
+    def per_conv(runs, split):                        # conv -> {'fwd': [ms per rep], 'dgrad': [...], 'scale': [...]} (scale: part of the two sums)
+        out = {}
+        for i, rows in enumerate(runs):
+            for n, ms, fl in rows:
+                w = n.split()
+                if not w[0].startswith('layer') or 'bn' in w[0] or w[0].endswith('downsample.1') or w[-1] in ('wgrad', 'bwd'):
+                    continue
+                tail = ' '.join(w[1:])
+                part = {'': 'fwd', 'pack': 'fwd', 'split16': 'fwd', 'scale': 'fwd', 'dgrad': 'dgrad', 'dgrad split16': 'dgrad', 'bwd scale': 'dgrad'}[tail]
+                e = out.setdefault(w[0], dict(fwd=[0.0] * len(runs), dgrad=[0.0] * len(runs), scale=[0.0] * len(runs), flops=0.0))
+                e[part][i] += ms
+                if tail.endswith('scale'):
+                    e['scale'][i] += ms
+                e['flops'] = max(e['flops'], fl)
+        return out
+    a, b = per_conv(off, False), per_conv(on, True)
+    assert list(a) == list(b) and len(a) > 10
+    lines.append('== %s, batch %d, %d timed steps per mode after a warm-up; ms as minimum / median / maximum ==' % (name, batch, reps))
+    lines.append('forward + backward per step without per-launch events: fp32 %.2f ms, split-f16 convolutions and data gradients %.2f ms (%.2fx)'
+                 % (t_off, t_on, t_off / t_on))
+    sums = {}
+    for part, what in (('fwd', 'forward convolutions'), ('dgrad', 'data gradients')):
+        s_off = _stat([sum(a[k][part][i] for k in a) for i in range(reps)])
+        s_on = _stat([sum(b[k][part][i] for k in b) for i in range(reps)])
+        sums[part] = (s_off, s_on)
+        lines.append('%s, summed (%d convolutions): fp32 %.3f / %.3f / %.3f ms; split-f16 with scale and pack launches %.3f / %.3f / %.3f ms; median ratio %.2fx'
+                     % ((what, len(a)) + s_off + s_on + (s_off[1] / s_on[1],)))
+    both_off = _stat([sum(a[k]['fwd'][i] + a[k]['dgrad'][i] for k in a) for i in range(reps)])
+    both_on = _stat([sum(b[k]['fwd'][i] + b[k]['dgrad'][i] for k in b) for i in range(reps)])
+    s_sc = _stat([sum(b[k]['scale'][i] for k in b) for i in range(reps)])
+    gain, spreads = both_off[1] - both_on[1], (both_off[2] - both_off[0]) + (both_on[2] - both_on[0])
+    lines.append('both, summed: fp32 %.3f / %.3f / %.3f ms; split-f16 %.3f / %.3f / %.3f ms (of which scale launches %.3f); median ratio %.2fx'
+                 % (both_off + both_on + (s_sc[1], both_off[1] / both_on[1])))
+    lines.append('criterion (the split median below the fp32 median by more than the two spreads): fp32 - split %.3f ms, spreads %.3f ms: %s'
+                 % (gain, spreads, 'MET' if gain > spreads else 'NOT MET'))
+    lines.append('%-26s %9s %9s %9s %7s   %9s %9s %9s %7s' % ('convolution (median ms)', 'fwd fp32', 'TFLOP/s', 'fwd split', 'ratio', 'dgr fp32', 'TFLOP/s',
+                                                             'dgr split', 'ratio'))
+    lost = []
+    for k in a:
+        fo, fs, do, ds = (_stat(d[k][p])[1] for d, p in ((a, 'fwd'), (b, 'fwd'), (a, 'dgrad'), (b, 'dgrad')))
+        lines.append('%-26s %9.3f %9.2f %9.3f %6.2fx   %9.3f %9.2f %9.3f %6.2fx' % (k, fo, a[k]['flops'] / fo / 1e9, fs, fo / fs, do, a[k]['flops'] / do / 1e9, ds,
+                                                                                  do / ds))
+        if fs > fo or ds > do:
+            lost.append(k)
+    lines.append('shapes at which a split launch with its scale and pack launches is slower than the fp32 launches: %s' % (', '.join(lost) if lost else 'none'))
+    lines.append('')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=32)
     ap.add_argument('--out', default=None)
     ap.add_argument('--wgrad_split16', action='store_true', help='compare the fp32 and the split-f16 weight gradients (both modes in this process)')
-    ap.add_argument('--reps', type=int, default=5, help='with --wgrad_split16: timed steps per mode')
+    ap.add_argument('--conv_split16', action='store_true', help='compare the fp32 and the split-f16 forward convolutions and data gradients')
+    ap.add_argument('--names', default='resnet18,resnet50', help='with --conv_split16: the trunks to measure')
+    ap.add_argument('--append', action='store_true', help='with --conv_split16: append to --out')
+    ap.add_argument('--reps', type=int, default=5, help='with --wgrad_split16 / --conv_split16: timed steps per mode')
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'wgrad_split16_times.txt' if a.wgrad_split16 else 'train_step_times.txt')
-    if a.wgrad_split16:
+        a.out = os.path.join(ROOT, 'profiles', 'conv_split16_times.txt' if a.conv_split16 else 'wgrad_split16_times.txt' if a.wgrad_split16
+                             else 'train_step_times.txt')
+    if a.conv_split16:
+        lines = ['forward-convolution and data-gradient launches of one training step, fp32 (f32-input MFMA) against split-f16 (pvr_trainer_set_conv_split16), '
+                 'per-launch events (scripts/train_step_times.py --conv_split16), %s' % torch.cuda.get_device_name(0), '']
+        for name in a.names.split(','):
+            compare_conv(name, a.batch, a.reps, lines)
+    elif a.wgrad_split16:
         lines = ['weight-gradient launches of one training step, fp32 (f32-input MFMA) against split-f16 (pvr_trainer_set_wgrad_split16), per-launch events '
                  '(scripts/train_step_times.py --wgrad_split16), %s' % torch.cuda.get_device_name(0), '']
         for name in ('resnet18', 'resnet50'):
@@ -178,7 +251,7 @@ def main():
         for name in ('resnet18', 'resnet50'):
             one(name, a.batch, lines)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
+    with open(a.out, 'a' if a.conv_split16 and a.append else 'w') as f:
         f.write('\n'.join(lines) + '\n')
     print('\n'.join(lines))
 
