@@ -9,7 +9,9 @@
  * pvr_trainer_set_bn_frozen, on its running statistics (frames independent: a step is a sum over passes).  After
  * pvr_trainer_set_wgrad_split16 the weight gradients alone run as exact-split products on the f16 matrix pipe; after
  * pvr_trainer_set_conv_split16 the forward convolutions and the data gradients of layer1 .. layer4 do (conv1's forward, BatchNorm
- * and the pools stay in fp32).  Both modes are off by default and independent of each other and of the BatchNorm mode.
+ * and the pools stay in fp32).  Both modes are off by default and independent of each other and of the BatchNorm mode.  After
+ * pvr_trainer_set_train_from(stage) only layer<stage> .. layer4 train (partial fine-tuning): conv1 / bn1 and the layers below are a
+ * frozen prefix that runs on its running statistics, keeps no activations and has no backward; its gradient span is zero.
  *
  * Buffers follow pvr_policy.h's convention: the caller owns ONE flat fp32 device buffer of parameters, every tensor in its
  * state_dict shape (conv weights in torch's (cout, cin, kh, kw) layout - the library repacks them inside the forward), and
@@ -100,6 +102,30 @@ pvr_status pvr_trainer_set_wgrad_split16(pvr_trainer *tr, int32_t on);
  * (dz + weights) and "<conv> dgrad split16" (weight pack [+ grid] + convolution). */
 pvr_status pvr_trainer_set_conv_split16(pvr_trainer *tr, int32_t on);
 
+/* Partial fine-tuning: the stage the handle trains from.  stage == 0 (the default): everything trains, everything above, bit for bit, and the same
+ * workspace to the byte.  stage 1 .. 4: layer<stage> .. layer4 train; conv1 / bn1 and every layer below layer<stage> are the FROZEN PREFIX (torch:
+ * those modules in .eval() with requires_grad = False).  Any other value is PVR_ERR_INVALID.
+ *   forward: BatchNorm of every prefix op normalises with its running statistics whatever the handle's BatchNorm mode is, and reads its buffers only;
+ *     in batch-statistics mode only the trained stages use and update batch statistics.  No prefix tensor is kept but the one a trained op reads (the
+ *     boundary tensor: the last prefix output - for resnet18 / 34 at stage 1 the max pool's output, which is also layer1.0's residual): the prefix's
+ *     tensors rotate through a small pool of buffers assigned by liveness, and a prefix op has no gradient tensor and no mean / rstd slots.  In the fp32
+ *     arithmetic a prefix op of layer1 .. layer<stage-1> is ONE launch (pvr_op_conv_bn_frozen_forward: no pre-BN tensor exists); with conv_split16 on
+ *     it is the mode's scale + split convolution followed by the frozen BatchNorm launch, because a mode has one arithmetic.  The stem stays conv1,
+ *     bn1 and the max pool.
+ *   backward: walks from the last op down to the first trained op and stops.  The ops that read the boundary tensor (the first block's conv1 and its
+ *     downsample) compute their weight gradient and no data gradient; a residual that comes from the prefix gets no gradient; there is no max-pool
+ *     backward, no bn1 backward and no conv1 weight gradient.  grads_dev stays fully overwritten: the span [0, pvr_trainer_trained_offset) is set to
+ *     zero on the caller's stream (launch "prefix grads zero"); pvr_trainer_backward_acc adds those zeros like everything else.
+ * The trained stages compute what they compute at stage 0: with frozen BatchNorm and conv_split16 (the prefix then runs the same launches as at
+ * stage 0) the embeddings and every trained tensor's gradient keep their bits.  Legal in both BatchNorm modes and with either or both split modes.
+ * The stage decides the workspace, so it must be chosen before the first forward makes it: afterwards a different stage is PVR_ERR_STATE with a
+ * message.  pvr_trainer_workspace_bytes reports the size of the current stage. */
+pvr_status pvr_trainer_set_train_from(pvr_trainer *tr, int32_t stage);
+int32_t pvr_trainer_train_from(const pvr_trainer *tr);
+/* float offset in the flat parameter buffer at which the trained parameters begin (0 at stage 0).  Parameters are laid out in op order, so the frozen
+ * prefix is the one leading span [0, offset) and the offset is that of layer<stage>.0.conv1.weight. */
+int64_t pvr_trainer_trained_offset(const pvr_trainer *tr);
+
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
  * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */
@@ -129,6 +155,16 @@ pvr_status pvr_op_bn_train_backward(const float *z_dev, const float *y_dev, cons
 pvr_status pvr_op_bn_frozen_forward(const float *z_dev, const float *residual_dev, const float *gamma_dev, const float *beta_dev,
                                     const float *running_mean_dev, const float *running_var_dev, float *y_dev, float *mean_out_dev, float *rstd_out_dev,
                                     int64_t rows, int32_t c, int32_t relu, void *hip_stream);
+/* A frozen prefix op (pvr_trainer_set_train_from) as ONE convolution launch behind the weight pack: y (n,ho,wo,cout) = (conv(x (n,h,w,cin), w torch's
+ * (cout,cin,k,k)) - running_mean) * rstd * gamma + beta [+ residual] [ReLU], rstd = 1 / sqrtf(running_var + 1e-5) evaluated per channel in the kernel.
+ * The convolution is pvr_op_conv2d_f32's single fp32 fma chain over K = k*k*cin in the same order, the epilogue pvr_op_bn_frozen_forward's expression
+ * per element; no pre-BN tensor and no mean / rstd are written.  The scratch holds the packed weights.  cin % 32 == 0, cout % 4 == 0, k 1 .. 3,
+ * stride 1 or 2, pad < k, every operand below 2 GiB; anything else is refused by name and launches nothing.  Two runs give the same bits. */
+int64_t pvr_op_conv_bn_frozen_forward_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad);
+pvr_status pvr_op_conv_bn_frozen_forward(const float *x_dev, const float *w_dev, const float *gamma_dev, const float *beta_dev, const float *running_mean_dev,
+                                         const float *running_var_dev, const float *residual_dev, float *y_dev, int32_t n, int32_t h, int32_t w, int32_t cin,
+                                         int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t relu, float *scratch_dev, int64_t scratch_floats,
+                                         void *hip_stream);
 /* its backward (arguments as pvr_op_bn_train_backward, scratch of pvr_op_bn_scratch_floats): g = dy where (relu == 0 or y > 0) else 0;
  * dbeta = sum g; dgamma = sum g * xhat, xhat = (z - mean) * rstd; dz = gamma * rstd * g (the statistics are constants: no mean terms);
  * dres (optional) = g, added to what it holds when dres_accumulate != 0.  One kernel streams z, y, dy -> dz, dres and writes per-block partial

@@ -119,7 +119,12 @@ _SIGS = {
     'pvr_op_stem_wgrad_split16_scratch_floats': (C.c_int64, [C.c_int32, C.c_int32]),
     'pvr_op_stem_wgrad_split16': (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_trainer_set_conv_split16': (C.c_int, [C.c_void_p, C.c_int32]),
-    'pvr_op_conv_fwd_split16_scratch_floats': (C.c_int64, [C.c_int32] * 8),
+    'pvr_trainer_set_train_from': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pvr_trainer_train_from': (C.c_int32, [C.c_void_p]),
+    'pvr_trainer_trained_offset': (C.c_int64, [C.c_void_p]),
+    'pvr_op_conv_bn_frozen_forward_scratch_floats': (C.c_int64, [C.c_int32] * 8),
+    'pvr_op_conv_bn_frozen_forward': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 9 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_conv_fwd_split16_scratch_floats':(C.c_int64, [C.c_int32] * 8),
     'pvr_op_conv_fwd_split16': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 8 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_conv_dgrad_split16_scratch_floats': (C.c_int64, [C.c_int32] * 8),
     'pvr_op_conv_dgrad_split16': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

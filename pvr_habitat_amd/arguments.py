@@ -45,6 +45,11 @@ def make_parser():
                              'product on the f16 matrix pipe (both operands scaled per tensor on the device, three MFMAs per fragment pair, fp32 '
                              'accumulation: about 2^-22 relative per product); conv1, BatchNorm and the pools stay fp32, the weight gradients too unless '
                              '--embedding_wgrad_split16 is given as well.  Works with and without --freeze_embedding_bn')
+    parser.add_argument('--embedding_train_from', type=str, default=None, choices=['layer1', 'layer2', 'layer3', 'layer4'],
+                        help='with --train_embedding: partial fine-tuning - the named stage of the ResNet trunk and the ones above it train; conv1 / bn1 '
+                             'and the stages below are frozen (eval-mode BatchNorm, no gradient), keep no activations and have no backward, so the '
+                             'training workspace and the step shrink with the stage and the default --embedding_chunk grows.  Works with and without '
+                             '--freeze_embedding_bn and the split16 modes; a resumed run must name the same stage')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

@@ -13,6 +13,7 @@ struct ConvF {
     float *out;
     int N, H, W, Cin, Ho, Wo, Cout, CoutPad, KH, KW, stride, pad, M, K, act, n_tiles;     // act: 0 none, 1 relu, 2 QuickGELU x*sigmoid(1.702x), 3 GELU (erf)
     unsigned in_bytes, w_bytes;
+    const float *gamma, *beta, *run_mean, *run_var;      // BNF only: the frozen BatchNorm of the epilogue (bias is not read)
 };
 
 // NHWC implicit GEMM, 64 pixels x 64 couts x 32 k per step, 2x2 waves, 2-stage LDS pipeline.
@@ -20,7 +21,10 @@ struct ConvF {
 // SETS = 1: one fma chain over the whole of K per output (every convolution of the ResNet plans).  SETS = 8, the linear-layer form (the ViT plans' GEMMs,
 // K up to 5120): k-step ks of every slice feeds accumulator set ks, so an output is eight chains of K / 8 products summed pairwise at the end - the
 // rounding error of a chain grows with its length, and one chain of 3072 products measured 5.8x the max-norm error of a blocked fp32 GEMM (with eight: 2x).
-template <int SETS>
+// BNF (SETS = 1, raw packed weights): the frozen prefix op of the trainable encoder as ONE launch - the accumulator holds the pre-BN z (the same K order
+// as the plain instance, so the same bits) and the epilogue is bn_frozen_apply_kernel's expression per element, y = (z - running_mean) * rstd * gamma + beta
+// [+ residual] [ReLU] with rstd = 1 / sqrtf(running_var + 1e-5) evaluated per channel; z is never written.  act: 0 none, 1 ReLU.
+template <int SETS, bool BNF = false>
 __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
     constexpr int BM = 64, BN = 64, BK = 32, LD = 36, TILE = 64 * 36;
     __shared__ __attribute__((aligned(16))) float sm[2][2][TILE];
@@ -119,6 +123,27 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(ConvF p) {
                 acc[i][j] = ((accs[0][i][j] + accs[1][i][j]) + (accs[2][i][j] + accs[3][i][j])) + ((accs[4][i][j] + accs[5][i][j]) + (accs[6][i][j] + accs[7][i][j]));
     }
     // D: row = pixel (4*fq + r), col = cout (fr)
+    if constexpr (BNF) {
+        static_assert(SETS == 1, "the fused frozen BatchNorm follows the single-chain convolution");
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int co = n0 + wn * 32 + j * 16 + fr;
+            if (co >= p.Cout) continue;
+            // a lane's column is one channel: its four per-channel values are loaded once, outside the row loop
+            const float mu = p.run_mean[co], rs = 1.f / sqrtf(p.run_var[co] + 1e-5f), ga = p.gamma[co], be = p.beta[co];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int m = m0 + wm * 32 + i * 16 + fq * 4 + r;
+                    if (m >= p.M) continue;
+                    float t = (acc[i][j][r] - mu) * rs * ga + be;
+                    if (p.res) t += p.res[(size_t)m * p.Cout + co];
+                    p.out[(size_t)m * p.Cout + co] = p.act ? fmaxf(t, 0.f) : t;
+                }
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int co = n0 + wn * 32 + j * 16 + fr;
@@ -212,6 +237,7 @@ pvr_status launch_conv_f32(const float *in, const float *wgt, const float *bias,
     PVR_REQUIRE(cin % 32 == 0 && k <= 3, "conv_f32: cin %d must be a multiple of 32 and k <= 3", cin);
     ConvF p;
     p.in = in; p.wgt = wgt; p.bias = bias; p.res = res; p.out = out;
+    p.gamma = p.beta = p.run_mean = p.run_var = nullptr;
     p.N = n; p.H = h; p.W = w; p.Cin = cin; p.Cout = cout; p.CoutPad = (cout + 63) / 64 * 64; p.KH = k; p.KW = k;
     p.stride = stride; p.pad = pad; p.Ho = (h + 2 * pad - k) / stride + 1; p.Wo = (w + 2 * pad - k) / stride + 1;
     const int64_t M = (int64_t)n * p.Ho * p.Wo, inb = (int64_t)n * h * w * cin * 4, wb = (int64_t)p.CoutPad * k * k * cin * 4;
@@ -223,6 +249,28 @@ pvr_status launch_conv_f32(const float *in, const float *wgt, const float *bias,
     // single chain, bit for bit
     if (h == 1 && w == 1 && k == 1) hipLaunchKernelGGL(conv_f32_kernel<8>, dim3(grid), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(conv_f32_kernel<1>, dim3(grid), dim3(256), 0, stream, p);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// convolution (raw packed weights, launch_pack_conv_weights' (cout_pad, k*k*cin) matrix) + frozen BatchNorm [+ residual] [ReLU] -> y, one launch
+pvr_status launch_conv_bn_frozen_f32(const float *in, const float *wgt, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                     const float *res, float *out, int n, int h, int w, int cin, int cout, int k, int stride, int pad, int relu,
+                                     hipStream_t stream) {
+    PVR_REQUIRE(cin > 0 && cin % 32 == 0 && k >= 1 && k <= 3, "conv_bn_frozen_f32: cin %d must be a multiple of 32 and k %d in 1 .. 3", cin, k);
+    PVR_REQUIRE(n > 0 && h > 0 && w > 0 && cout > 0 && cout % 4 == 0 && (stride == 1 || stride == 2) && pad >= 0 && pad < k && h + 2 * pad >= k && w + 2 * pad >= k,
+                "conv_bn_frozen_f32: n %d, h %d, w %d, cout %d (%% 4 == 0), stride %d (1 or 2), pad %d (< k)", n, h, w, cout, stride, pad);
+    ConvF p;
+    p.in = in; p.wgt = wgt; p.bias = nullptr; p.res = res; p.out = out;
+    p.gamma = gamma; p.beta = beta; p.run_mean = run_mean; p.run_var = run_var;
+    p.N = n; p.H = h; p.W = w; p.Cin = cin; p.Cout = cout; p.CoutPad = (cout + 63) / 64 * 64; p.KH = k; p.KW = k;
+    p.stride = stride; p.pad = pad; p.Ho = (h + 2 * pad - k) / stride + 1; p.Wo = (w + 2 * pad - k) / stride + 1;
+    const int64_t M = (int64_t)n * p.Ho * p.Wo, inb = (int64_t)n * h * w * cin * 4, wb = (int64_t)p.CoutPad * k * k * cin * 4;
+    PVR_REQUIRE(M < (1ll << 31) && inb < 0x7ffffff0ll && wb < 0x7ffffff0ll && M * cout * 4 < 0x7ffffff0ll, "conv_bn_frozen_f32: operand larger than 2 GiB (use a smaller chunk)");
+    p.M = (int)M; p.K = k * k * cin; p.act = relu ? 1 : 0; p.in_bytes = (unsigned)inb; p.w_bytes = (unsigned)wb;
+    p.n_tiles = (cout + 63) / 64;
+    const int grid = ((p.M + 63) / 64) * p.n_tiles;
+    hipLaunchKernelGGL((conv_f32_kernel<1, true>), dim3(grid), dim3(256), 0, stream, p);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }

@@ -5,6 +5,8 @@
 // f32-input MFMA (conv_f32.hip / conv_wgrad_kernel), BatchNorm statistics are two-pass, and every split reduction is summed in a fixed order.
 // pvr_trainer_set_wgrad_split16 moves the weight gradients, and nothing else, to the exact-split f16 products of wgrad_split16.hip;
 // pvr_trainer_set_conv_split16 moves the forward convolutions and the data gradients of layer1 .. layer4 to those of conv_split16_scaled.hip.
+// pvr_trainer_set_train_from makes conv1 / bn1 and the layers below a stage a frozen prefix: eval-mode BatchNorm, tensors from a liveness pool, in fp32
+// one fused launch per op (conv_f32.hip: launch_conv_bn_frozen_f32), and a backward that stops at the first trained op.
 #include "encoder_internal.h"
 #include "train_internal.h"
 #include "../../include/pvr_train.h"
@@ -57,6 +59,10 @@ struct pvr_trainer {
     float *scales = nullptr;                     // split modes: one absmax scale per saved tensor (index src + 1), the image (ops + 1), dz (ops + 2),
                                                  // then pvr_op_absmax_scale_pair's four aux words (zeroed with the workspace); conv_split16: one more
                                                  // slot behind them, the scale of the weights of the convolution at hand
+    int train_from = 0;                          // pvr_trainer_set_train_from: 0 everything trains; s: layer{s} .. layer4 train, conv1 / bn1 and the ops
+    int first_trained = 0;                       // [0, first_trained) are the frozen prefix; fixed once the arena exists
+    int prefix_ops() const { return train_from > 0 ? first_trained : 0; }
+    bool in_prefix(int src) const { return train_from > 0 && src < first_trained; }       // (src: an op index, or -1 the max pool's output)
     size_t scale_slots() const { return ops.size() + 3 + 4 + (conv_split16 ? 1 : 0); }
     bool timing = false;
     std::vector<Timed> times;                    // launch i of a step is bracketed by events[i]
@@ -97,12 +103,64 @@ struct Carver {                                  // sizes, then pointers, of one
     }
 };
 
+// The frozen prefix (train_from > 0) keeps no tensor but what a trained op reads.  Its z / y tensors (and the max pool's output) come from a small pool of
+// buffers assigned by liveness over in_src / res_src: a tensor's buffer is free again after its last consumer has run; a tensor a trained op reads (the
+// boundary tensor) gets a piece of its own.  Prefix ops get no dy and no mean / rstd slots, and no z where the op is one fused launch.
+void carve_prefix(pvr_trainer *t, Carver &c) {
+    const int B = t->desc.max_batch, P = t->first_trained;
+    const bool need_z = t->conv_split16;          // (fp32: a prefix op is ONE launch, convolution + BatchNorm, and has no z)
+    std::vector<int> last(P + 1, -1);             // last consumer (op index) of tensor src (index src + 1)
+    for (int i = 0; i < (int)t->ops.size(); ++i) {
+        const TrainOp &op = t->ops[i];
+        if (op.in_src < P) last[op.in_src + 1] = i;
+        if (op.res_src != -2 && op.res_src < P) last[op.res_src + 1] = i;
+    }
+    struct Buf { size_t cap; bool busy; };
+    std::vector<Buf> bufs;
+    std::vector<std::pair<float **, int>> uses;   // (pointer to set, buffer)
+    auto get = [&](float **p, size_t need) {      // the smallest free buffer that holds `need`, else the largest free one (grown), else a new one
+        int best = -1;
+        for (int b = 0; b < (int)bufs.size(); ++b)
+            if (!bufs[b].busy && bufs[b].cap >= need && (best < 0 || bufs[b].cap < bufs[best].cap)) best = b;
+        if (best < 0)
+            for (int b = 0; b < (int)bufs.size(); ++b)
+                if (!bufs[b].busy && (best < 0 || bufs[b].cap > bufs[best].cap)) best = b;
+        if (best < 0) { bufs.push_back(Buf{need, false}); best = (int)bufs.size() - 1; }
+        bufs[best].cap = std::max(bufs[best].cap, need);
+        bufs[best].busy = true;
+        uses.push_back({p, best});
+        return best;
+    };
+    std::vector<int> held(P + 1, -1);             // buffer of tensor src (index src + 1); -1: a piece of its own
+    TrainOp &sm = t->stem;
+    sm.dy = sm.mean = sm.rstd = nullptr;
+    const int sz = get(&sm.z, out_elems(sm, B)), sy = get(&sm.y, out_elems(sm, B));
+    if (last[0] >= P) c.take(&t->pool, (size_t)B * 56 * 56 * 64);
+    else held[0] = get(&t->pool, (size_t)B * 56 * 56 * 64);
+    bufs[sz].busy = bufs[sy].busy = false;
+    for (int i = 0; i < P; ++i) {
+        TrainOp &op = t->ops[i];
+        op.z = op.dy = op.mean = op.rstd = nullptr;
+        const int zb = need_z ? get(&op.z, out_elems(op, B)) : -1;
+        if (last[i + 1] >= P) c.take(&op.y, out_elems(op, B));
+        else held[i + 1] = get(&op.y, out_elems(op, B));
+        if (zb >= 0) bufs[zb].busy = false;
+        for (int s = 0; s <= i + 1; ++s)           // (a tensor nobody reads - there is none - is free at once)
+            if (held[s] >= 0 && last[s] <= i) { bufs[held[s]].busy = false; held[s] = -1; }
+    }
+    std::vector<float *> ptr(bufs.size(), nullptr);
+    for (size_t b = 0; b < bufs.size(); ++b) c.take(&ptr[b], bufs[b].cap);
+    if (c.base)
+        for (auto &u : uses) *u.first = ptr[u.second];
+}
+
 void carve(pvr_trainer *t, Carver &c) {
-    const int B = t->desc.max_batch;
+    const int B = t->desc.max_batch, P = t->prefix_ops();
+    const bool part = t->train_from > 0;          // (off: not a byte of the workspace changes)
     c.take(&t->d_img, (size_t)B * (S_IMG + 6) * (S_IMG + 8) * 4);
     c.take(&t->d_imgf, (size_t)B * S_IMG * S_IMG * 4);
-    size_t dz_max = out_elems(t->stem, B), dil_max = 1, w_max = 1;
-    int64_t wg_max = pvr_op_stem_wgrad_scratch_floats(B, S_IMG), bn_max = pvr_op_bn_scratch_floats((int64_t)B * t->stem.ho * t->stem.wo, 64);
+    size_t dz_max = part ? 1 : out_elems(t->stem, B), dil_max = 1, w_max = 1;
+    int64_t wg_max = part ? 1 : pvr_op_stem_wgrad_scratch_floats(B, S_IMG), bn_max = part ? 1 : pvr_op_bn_scratch_floats((int64_t)B * t->stem.ho * t->stem.wo, 64);
     int c_max = 64;
     auto take_op = [&](TrainOp &op) {
         c.take(&op.z, out_elems(op, B));
@@ -111,13 +169,22 @@ void carve(pvr_trainer *t, Carver &c) {
         c.take(&op.mean, op.cout);
         c.take(&op.rstd, op.cout);
     };
-    take_op(t->stem);
-    c.take(&t->pool, (size_t)B * 56 * 56 * 64);
-    c.take(&t->dpool, (size_t)B * 56 * 56 * 64);
-    for (TrainOp &op : t->ops) {
+    if (part) carve_prefix(t, c);
+    else {
+        take_op(t->stem);
+        c.take(&t->pool, (size_t)B * 56 * 56 * 64);
+        c.take(&t->dpool, (size_t)B * 56 * 56 * 64);
+    }
+    for (int i = 0; i < (int)t->ops.size(); ++i) {
+        TrainOp &op = t->ops[i];
+        if (i < P) {                              // a prefix op: its weights are packed and its channels take the zero bias; nothing of a backward
+            w_max = std::max(w_max, (size_t)std::max((op.cout + 63) / 64 * 64 * op.cin, (op.cin + 63) / 64 * 64 * op.cout) * op.k * op.k);
+            c_max = std::max(c_max, std::max(op.cin, op.cout));
+            continue;
+        }
         take_op(op);
         dz_max = std::max(dz_max, out_elems(op, B));
-        if (op.stride == 2) dil_max = std::max(dil_max, (size_t)B * op.h * op.w * op.cout);
+        if (op.stride == 2 && !t->in_prefix(op.in_src)) dil_max = std::max(dil_max, (size_t)B * op.h * op.w * op.cout);
         w_max = std::max(w_max, (size_t)std::max((op.cout + 63) / 64 * 64 * op.cin, (op.cin + 63) / 64 * 64 * op.cout) * op.k * op.k);
         for (int n = 1; n <= B; ++n)               // (the number of pixel ranges is not monotone in the batch: the range length is rounded to 32)
             wg_max = std::max(wg_max, pvr_op_conv_wgrad_scratch_floats(n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad));
@@ -131,7 +198,7 @@ void carve(pvr_trainer *t, Carver &c) {
     c.take(&t->dil, dil_max);
     c.take(&t->wpack, w_max);
     c.take(&t->stem_wpack, (size_t)64 * 49 * 4);
-    if (t->wgrad_split16) wg_max = std::max(wg_max, pvr_op_stem_wgrad_split16_scratch_floats(B, S_IMG));
+    if (t->wgrad_split16 && !part) wg_max = std::max(wg_max, pvr_op_stem_wgrad_split16_scratch_floats(B, S_IMG));
     // (both modes off: not a byte of the workspace changes.  The split weights of conv_split16 take wpack as they are: two f16 per value)
     if (t->wgrad_split16 || t->conv_split16) c.take(&t->scales, t->scale_slots());
     c.take(&t->wg_scratch, (size_t)wg_max);
@@ -203,6 +270,11 @@ pvr_status collect_times(pvr_trainer *t, size_t from, hipStream_t st) {
         if ((s = (call_))) return s;                \
         if ((s = tick.end())) return s;             \
     } while (0)
+
+pvr_status memset_floats(float *p, int64_t count, hipStream_t st) {
+    PVR_HIP_TRY(hipMemsetAsync(p, 0, (size_t)count * sizeof(float), st));
+    return PVR_OK;
+}
 
 const float *tensor_of(const pvr_trainer *t, int src) { return src == -1 ? t->pool : t->ops[src].y; }
 float *grad_of(pvr_trainer *t, int src) { return src == -1 ? t->dpool : t->ops[src].dy; }
@@ -350,7 +422,12 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
     if (t->timing) t->times.clear();
     Tick tick{t, st};
     float *bufs = (float *)bn_buffers;
-    auto bn = [&](TrainOp &op, const float *res, int64_t rows) {
+    const int P = t->prefix_ops();
+    const bool part = t->train_from > 0;
+    auto bn = [&](TrainOp &op, const float *res, int64_t rows, bool prefix) {
+        if (prefix)                               // a frozen module in eval: running statistics whatever the handle's BatchNorm mode; nothing kept for a backward
+            return launch_bn_frozen_apply(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, op.y, nullptr, nullptr, rows,
+                                          op.cout, op.relu, st);
         if (t->bn_frozen)                         // running statistics, read only: neither they nor num_batches_tracked are touched
             return pvr_op_bn_frozen_forward(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, op.y, op.mean, op.rstd, rows,
                                             op.cout, op.relu, st);
@@ -362,14 +439,15 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
     TrainOp &sm = t->stem;
     TR_RUN("conv1 pack", 0, launch_pack_stem_weights(params + sm.w_off, t->stem_wpack, st));
     TR_RUN("conv1", 2.0 * n * 112 * 112 * 64 * 147, launch_stem_f32(t->d_imgf, t->stem_wpack, nullptr, sm.z, n, S_IMG, st, true));
-    TR_RUN("bn1", 0, bn(sm, nullptr, (int64_t)n * 112 * 112));
+    TR_RUN("bn1", 0, bn(sm, nullptr, (int64_t)n * 112 * 112, part));
     TR_RUN("maxpool", 0, launch_maxpool_f32(sm.y, t->pool, n, 112, 112, 64, st));
     // conv_split16: a tensor's scale is computed once per forward, in the launch of its first consumer, next to that convolution's weight scale; the
     // slots stay valid for the backward (the saved activations do not change)
     std::vector<char> scaled(t->ops.size() + 1, 0);
     float *w_scale = t->conv_split16 ? t->scales + t->ops.size() + 7 : nullptr;
     uint32_t *scale_aux = t->conv_split16 ? (uint32_t *)(t->scales + t->ops.size() + 3) : nullptr;
-    for (TrainOp &op : t->ops) {
+    for (int i = 0; i < (int)t->ops.size(); ++i) {
+        TrainOp &op = t->ops[i];
         const int64_t rows = (int64_t)n * op.ho * op.wo;
         if (t->conv_split16) {
             const float *x = tensor_of(t, op.in_src);
@@ -381,13 +459,20 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
             scaled[op.in_src + 1] = 1;
             TR_RUN(op.conv + " split16", 2.0 * rows * op.cout * op.cin * op.k * op.k,
                    launch_conv_fwd_split16(x, params + op.w_off, op.z, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, x_scale, w_scale, t->wpack, st));
-            TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows));
+            TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows, i < P));
             continue;
         }
         TR_RUN(op.conv + " pack", 0, launch_pack_conv_weights(params + op.w_off, t->wpack, op.cout, op.cin, op.k, false, st));
+        if (i < P) {                              // a frozen prefix op: convolution and BatchNorm on the running statistics as one launch, no z
+            TR_RUN(op.conv + " bn frozen", 2.0 * rows * op.cout * op.cin * op.k * op.k,
+                   launch_conv_bn_frozen_f32(tensor_of(t, op.in_src), t->wpack, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off,
+                                             op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), op.y, n, op.h, op.w, op.cin, op.cout, op.k, op.stride,
+                                             op.pad, op.relu, st));
+            continue;
+        }
         TR_RUN(op.conv, 2.0 * rows * op.cout * op.cin * op.k * op.k,
                launch_conv_f32(tensor_of(t, op.in_src), t->wpack, t->zero_bias, nullptr, op.z, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, 0, st));
-        TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows));
+        TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows, i < P));
     }
     TR_RUN("avgpool", 0, launch_avgpool(t->ops.back().y, out, out_stride, n, t->final_hw, t->final_c, 1, PVR_F32, st));
     t->fwd_n = n;
@@ -422,17 +507,19 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
     };
     TR_RUN("avgpool bwd", 0, pvr_op_avgpool_backward(dout, dout_stride, t->ops[last].dy, n, t->final_hw, t->final_c, st));
     have[last + 1] = 1;
-    for (int i = last; i >= 0; --i) {
+    const int P = t->prefix_ops();                // the walk stops at the first trained op: the frozen prefix has no backward
+    for (int i = last; i >= P; --i) {
         TrainOp &op = t->ops[i];
+        const bool x_frozen = t->in_prefix(op.in_src);      // reads the boundary tensor: a weight gradient and no data gradient
         PVR_REQUIRE(have[i + 1], "pvr_trainer_backward: %s has no consumer", op.conv.c_str());
         const int64_t rows = (int64_t)n * op.ho * op.wo;
-        float *dres = op.res_src == -2 ? nullptr : grad_of(t, op.res_src);
+        float *dres = op.res_src == -2 || t->in_prefix(op.res_src) ? nullptr : grad_of(t, op.res_src);
         TR_RUN(op.bn + " bwd", 0,
                bn_bwd(op.z, op.y, op.dy, params + op.g_off, op.mean, op.rstd, t->dz, dres, dres ? have[op.res_src + 1] : 0, grads + op.g_off, grads + op.b_off,
                       rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st));
         if (dres) have[op.res_src + 1] = 1;
         const double fl = 2.0 * rows * op.cout * op.cin * op.k * op.k;
-        if (csplit)
+        if (csplit && (split || !x_frozen))
             TR_RUN(op.conv + " bwd scale", 0,
                    pvr_op_absmax_scale_pair(t->dz, (int64_t)out_elems(op, n), dz_scale, params + op.w_off, (int64_t)op.cout * op.cin * op.k * op.k, w_scale,
                                             scale_aux, st));
@@ -448,6 +535,7 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
             TR_RUN(op.conv + " wgrad", fl,
                    pvr_op_conv_wgrad(tensor_of(t, op.in_src), t->dz, grads + op.w_off, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, t->wg_scratch,
                                      t->wg_floats, st));
+        if (x_frozen) continue;
         if (csplit)
             TR_RUN(op.conv + " dgrad split16", fl,
                    launch_conv_dgrad_split16(t->dz, params + op.w_off, grad_of(t, op.in_src), have[op.in_src + 1], n, op.h, op.w, op.cin, op.cout, op.k, op.stride,
@@ -457,6 +545,10 @@ pvr_status backward_into(pvr_trainer *t, const float *params, const float *dout,
                    launch_conv_dgrad(t->dz, params + op.w_off, grad_of(t, op.in_src), have[op.in_src + 1], n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad,
                                      t->wpack, t->dil, t->zero_bias, st));
         have[op.in_src + 1] = 1;
+    }
+    if (t->train_from > 0) {                      // grads stays fully overwritten: the prefix's span is one leading run of zeros
+        TR_RUN("prefix grads zero", 0, memset_floats(grads, t->ops[P].w_off, st));
+        return collect_times(t, first_time, st);
     }
     PVR_REQUIRE(have[0], "pvr_trainer_backward: the max pool's output has no consumer");
     TrainOp &sm = t->stem;
@@ -533,5 +625,32 @@ pvr_status pvr_trainer_set_conv_split16(pvr_trainer *t, int32_t on) {
     t->conv_split16 = on != 0;
     return PVR_OK;
 }
+
+pvr_status pvr_trainer_set_train_from(pvr_trainer *t, int32_t stage) {
+    PVR_REQUIRE(t, "pvr_trainer_set_train_from: null trainer");
+    PVR_REQUIRE(stage >= 0 && stage <= 4, "pvr_trainer_set_train_from: stage %d (0: everything trains; 1 .. 4: layer<stage> .. layer4 train, conv1 / bn1 and "
+                "the layers below are frozen)", stage);
+    if (t->arena && stage != t->train_from) {
+        set_error("pvr_trainer_set_train_from: the workspace of this handle exists already (the first forward made it for train_from stage %d): choose "
+                  "the stage before the first forward", t->train_from);
+        return PVR_ERR_STATE;
+    }
+    int first = 0;
+    if (stage > 0) {
+        const std::string pre = "layer" + std::to_string(stage) + ".";
+        first = -1;
+        for (int i = 0; i < (int)t->ops.size() && first < 0; ++i)
+            if (t->ops[i].conv.compare(0, pre.size(), pre) == 0) first = i;
+        PVR_REQUIRE(first >= 0, "pvr_trainer_set_train_from: this trunk has no %s", pre.c_str());
+        for (int i = first; i < (int)t->ops.size(); ++i)       // (op order is layer order: the prefix is one leading span of the parameters)
+            PVR_REQUIRE(t->ops[i].in_src >= -1 && t->ops[i].w_off >= t->ops[first].w_off, "pvr_trainer_set_train_from: the ops of %s do not end the plan", pre.c_str());
+    }
+    if (stage != t->train_from) t->fwd_n = 0;     // (only before the arena exists: no forward is held)
+    t->train_from = stage;
+    t->first_trained = first;
+    return PVR_OK;
+}
+int32_t pvr_trainer_train_from(const pvr_trainer *t) { return t ? t->train_from : 0; }
+int64_t pvr_trainer_trained_offset(const pvr_trainer *t) { return t && t->train_from > 0 ? t->ops[t->first_trained].w_off : 0; }
 
 }  // extern "C"

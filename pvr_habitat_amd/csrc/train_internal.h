@@ -13,6 +13,12 @@ pvr_status launch_conv_dgrad(const float *dz, const float *w, float *dx, int acc
                              float *wflip, float *dil, const float *zero_bias, hipStream_t st);
 // grads[i] += pass[i] over n floats: one fp32 addition per element (gradient accumulation over the passes of a chunked step)
 pvr_status launch_grad_add(float *grads, const float *pass, int64_t n, hipStream_t st);
+// pvr_op_bn_frozen_forward's launch (same refusals); mean_out / rstd_out may both be null: nothing is kept for a backward
+pvr_status launch_bn_frozen_apply(const float *z, const float *res, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                  float *y, float *mean_out, float *rstd_out, int64_t rows, int c, int relu, hipStream_t st);
+// conv_f32.hip: convolution (wpack: launch_pack_conv_weights' plain matrix) + frozen BatchNorm [+ residual] [ReLU] -> y in one launch; no z is written
+pvr_status launch_conv_bn_frozen_f32(const float *in, const float *wpack, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                     const float *res, float *out, int n, int h, int w, int cin, int cout, int k, int stride, int pad, int relu, hipStream_t st);
 // dz (n, h/2, w/2, c) -> the even pixels of a zeroed (n, h, w, c) grid: the stride-2 data gradients' input
 pvr_status launch_dilate2(const float *dz, float *out, int n, int h, int w, int c, hipStream_t st);
 // conv_split16_scaled.hip: the forward and the data gradient of a convolution as exact-split f16 products with per-tensor scales read from the device

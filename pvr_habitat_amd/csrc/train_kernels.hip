@@ -238,6 +238,34 @@ __global__ __launch_bounds__(256) void grad_add_kernel(float *__restrict__ g, co
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) g[n4 * 4 + threadIdx.x] += s[n4 * 4 + threadIdx.x];
 }
 
+static pvr_status bn_frozen_check(const char *what, int64_t rows, int c) {
+    PVR_REQUIRE(rows >= 1 && c > 0 && c % 4 == 0, "%s: %lld rows of %d channels (rows >= 1 and c %% 4 == 0)", what, (long long)rows, c);
+    PVR_REQUIRE(rows * c < (1ll << 40) && rows / BN_CHUNK < 65535, "%s: %lld rows are more than one launch takes", what, (long long)rows);
+    return PVR_OK;
+}
+// pvr_op_bn_frozen_forward's launch; mean_out / rstd_out may both be null (the frozen prefix of pvr_trainer_set_train_from keeps nothing for a backward)
+pvr_status launch_bn_frozen_apply(const float *z, const float *res, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                  float *y, float *mean_out, float *rstd_out, int64_t rows, int c, int relu, hipStream_t stream) {
+    pvr_status s;
+    if ((s = bn_frozen_check("pvr_op_bn_frozen_forward", rows, c))) return s;
+    const size_t total4 = (size_t)rows * c / 4;
+    // a grid whose stride (blocks * 256 float4s) is a multiple of the c / 4 channel groups of a row keeps a thread on the same four channels
+    int blocks = ew_blocks(total4);
+    int per = c / 4, a = per, b = 256;
+    while (b) { const int t = a % b; a = b; b = t; }
+    per /= a;                                     // blocks must be a multiple of (c / 4) / gcd(c / 4, 256)
+    const bool fixed = blocks >= per;
+    if (fixed) blocks -= blocks % per;
+    if (fixed)
+        hipLaunchKernelGGL(bn_frozen_apply_kernel<true>, dim3(blocks), dim3(256), 0, stream, z, res, gamma, beta, run_mean, run_var, y, mean_out,
+                           rstd_out, total4, c, relu);
+    else
+        hipLaunchKernelGGL(bn_frozen_apply_kernel<false>, dim3(blocks), dim3(256), 0, stream, z, res, gamma, beta, run_mean, run_var, y, mean_out,
+                           rstd_out, total4, c, relu);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
 pvr_status launch_grad_add(float *grads, const float *pass, int64_t n, hipStream_t st) {
     hipLaunchKernelGGL(grad_add_kernel, dim3(ew_blocks((size_t)(n + 3) / 4)), dim3(256), 0, st, grads, pass, (size_t)n);
     PVR_LAUNCH_CHECK();
@@ -579,33 +607,10 @@ pvr_status pvr_op_bn_train_backward(const float *z, const float *y, const float 
     return PVR_OK;
 }
 
-static pvr_status bn_frozen_check(const char *what, int64_t rows, int c) {
-    PVR_REQUIRE(rows >= 1 && c > 0 && c % 4 == 0, "%s: %lld rows of %d channels (rows >= 1 and c %% 4 == 0)", what, (long long)rows, c);
-    PVR_REQUIRE(rows * c < (1ll << 40) && rows / BN_CHUNK < 65535, "%s: %lld rows are more than one launch takes", what, (long long)rows);
-    return PVR_OK;
-}
-
 pvr_status pvr_op_bn_frozen_forward(const float *z, const float *res, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
                                     float *y, float *mean_out, float *rstd_out, int64_t rows, int32_t c, int32_t relu, void *stream) {
     PVR_REQUIRE(z && gamma && beta && run_mean && run_var && y && mean_out && rstd_out, "pvr_op_bn_frozen_forward: null argument");
-    pvr_status s;
-    if ((s = bn_frozen_check("pvr_op_bn_frozen_forward", rows, c))) return s;
-    const size_t total4 = (size_t)rows * c / 4;
-    // a grid whose stride (blocks * 256 float4s) is a multiple of the c / 4 channel groups of a row keeps a thread on the same four channels
-    int blocks = ew_blocks(total4);
-    int per = c / 4, a = per, b = 256;
-    while (b) { const int t = a % b; a = b; b = t; }
-    per /= a;                                     // blocks must be a multiple of (c / 4) / gcd(c / 4, 256)
-    const bool fixed = blocks >= per;
-    if (fixed) blocks -= blocks % per;
-    if (fixed)
-        hipLaunchKernelGGL(bn_frozen_apply_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, res, gamma, beta, run_mean, run_var, y, mean_out,
-                           rstd_out, total4, c, relu);
-    else
-        hipLaunchKernelGGL(bn_frozen_apply_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, res, gamma, beta, run_mean, run_var, y, mean_out,
-                           rstd_out, total4, c, relu);
-    PVR_LAUNCH_CHECK();
-    return PVR_OK;
+    return pvr::launch_bn_frozen_apply(z, res, gamma, beta, run_mean, run_var, y, mean_out, rstd_out, rows, c, relu, (hipStream_t)stream);
 }
 
 pvr_status pvr_op_bn_frozen_backward(const float *z, const float *y, const float *dy, const float *gamma, const float *mean, const float *rstd, float *dz,
@@ -625,6 +630,30 @@ pvr_status pvr_op_bn_frozen_backward(const float *z, const float *y, const float
     hipLaunchKernelGGL(bn_finalize_kernel<2>, dim3((c + 255) / 256), dim3(256), 0, st, f);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
+}
+
+// scratch: the packed weights, launch_pack_conv_weights' (cout_pad, k*k*cin) matrix
+int64_t pvr_op_conv_bn_frozen_forward_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad) {
+    if (n <= 0 || h <= 0 || w <= 0 || cin <= 0 || cin % 32 || cout <= 0 || cout % 4 || k < 1 || k > 3 || (stride != 1 && stride != 2) || pad < 0 || pad >= k) return 0;
+    return (int64_t)((cout + 63) / 64 * 64) * k * k * cin;
+}
+
+pvr_status pvr_op_conv_bn_frozen_forward(const float *x, const float *wt, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                         const float *res, float *y, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride,
+                                         int32_t pad, int32_t relu, float *scratch, int64_t scratch_floats, void *stream) {
+    PVR_REQUIRE(x && wt && gamma && beta && run_mean && run_var && y && scratch, "pvr_op_conv_bn_frozen_forward: null argument");
+    const int64_t need = pvr_op_conv_bn_frozen_forward_scratch_floats(n, h, w, cin, cout, k, stride, pad);
+    PVR_REQUIRE(need > 0, "pvr_op_conv_bn_frozen_forward: n %d, h %d, w %d, cin %d (%% 32 == 0), cout %d (%% 4 == 0), k %d (1 .. 3), stride %d (1 or 2), pad %d (< k)",
+                n, h, w, cin, cout, k, stride, pad);
+    PVR_REQUIRE(h + 2 * pad >= k && w + 2 * pad >= k, "pvr_op_conv_bn_frozen_forward: a %d x %d image is smaller than the %d x %d filter", h, w, k, k);
+    PVR_REQUIRE(scratch_floats >= need, "pvr_op_conv_bn_frozen_forward: scratch of %lld floats, pvr_op_conv_bn_frozen_forward_scratch_floats asks for %lld",
+                (long long)scratch_floats, (long long)need);
+    const int64_t ho = (h + 2 * pad - k) / stride + 1, wo = (w + 2 * pad - k) / stride + 1;
+    PVR_REQUIRE((int64_t)n * h * w * cin * 4 < 0x7ffffff0ll && need * 4 < 0x7ffffff0ll && (int64_t)n * ho * wo * cout * 4 < 0x7ffffff0ll,
+                "pvr_op_conv_bn_frozen_forward: operand larger than 2 GiB (use fewer frames)");
+    pvr_status s;
+    if ((s = launch_pack_conv_weights(wt, scratch, cout, cin, k, false, (hipStream_t)stream))) return s;
+    return launch_conv_bn_frozen_f32(x, scratch, gamma, beta, run_mean, run_var, res, y, n, h, w, cin, cout, k, stride, pad, relu, (hipStream_t)stream);
 }
 
 int64_t pvr_op_conv_wgrad_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad) {

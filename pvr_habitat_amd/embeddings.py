@@ -383,7 +383,7 @@ _TRAINABLE_MSG = ("trainable (train=True) are the torchvision ResNet trunks: 're
 
 class _EncoderFunction(torch.autograd.Function):
     """Training-mode forward of the whole encoder as one autograd node (the pattern of models._PolicyFunction).  Inputs: the module, the uint8
-    frames, then every parameter, so autograd routes a gradient to each of them.  The library keeps the activations of ONE forward: a backward
+    frames, then every trained parameter (all, or those from train_from's stage up), so autograd routes a gradient to each of them.  The library keeps the activations of ONE forward: a backward
     after a later training forward of the same module raises.  The node keeps the uint8 frames (tiny next to an activation): with frozen BatchNorm
     a forward of more than max_batch frames ran as several passes, and the backward recomputes every pass but the last."""
 
@@ -404,7 +404,7 @@ class _EncoderFunction(torch.autograd.Function):
         g = torch.empty_like(m._flat)
         m._backward_raw(ctx.frames, dout, g)
         ctx.frames = None
-        return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._slots)
+        return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._trained_slots)
 
 
 class HipTrainableResNet(_Node):
@@ -432,9 +432,16 @@ class HipTrainableResNet(_Node):
     conv_split16: every forward convolution and data gradient of layer1 .. layer4 as the same kind of product (pvr_trainer_set_conv_split16: both
     operands scaled per tensor on the device, so gradients of 1e-6 and activations past 65504 keep their precision); conv1's forward, BatchNorm, the
     pools and - unless wgrad_split16 is on as well - the weight gradients stay fp32.  Embeddings and gradients move by about 2^-22 relative per
-    product.  Chosen at construction; legal in both BatchNorm modes, with or without wgrad_split16.  Eval mode keeps running the frozen 'f32' plan."""
+    product.  Chosen at construction; legal in both BatchNorm modes, with or without wgrad_split16.  Eval mode keeps running the frozen 'f32' plan.
 
-    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False):
+    train_from: None (everything trains) or 'layer1' .. 'layer4' - partial fine-tuning (pvr_trainer_set_train_from): that stage and the ones above it
+    train; conv1 / bn1 and the stages below are the frozen prefix (torch: those modules in .eval() with requires_grad = False).  The prefix runs on its
+    running statistics in either BatchNorm mode, keeps no activation but the one the first trained block reads, and has no backward: the workspace
+    (workspace_bytes) and the step shrink with the stage.  Prefix parameters stay nn.Parameters with requires_grad = False and stay in state_dict();
+    the autograd node takes only the trained parameters, so a prefix parameter's .grad stays None.  Chosen at construction (it decides the
+    workspace); legal in both BatchNorm modes and with either or both split modes."""
+
+    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None):
         super().__init__()
         assert variant in _TRAINABLE, variant
         _lib.require_gpu()
@@ -460,6 +467,11 @@ class HipTrainableResNet(_Node):
         self._conv_split16 = False
         if conv_split16:
             self.set_conv_split16(True)
+        self._train_from = None
+        if train_stage(train_from):
+            _lib.check(L.pvr_trainer_set_train_from(h, train_stage(train_from)))
+            self._train_from = train_from
+        self._trained_offset = int(L.pvr_trainer_trained_offset(h))     # floats of the flat buffer below it are the frozen prefix (one leading span)
         dev = torch.device('cuda')
         self._flat = torch.zeros(L.pvr_trainer_param_count(h), dtype=torch.float32, device=dev)
         self._bufs = torch.zeros(L.pvr_trainer_buffer_count(h), dtype=torch.float32, device=dev)
@@ -492,6 +504,9 @@ class HipTrainableResNet(_Node):
         missing = sum(n for _, n, _ in self._slots) != self._flat.numel()
         if missing:                               # (the reference asserts missing_keys == [], moco.py:24)
             raise KeyError("trainable '%s' encoder: the state_dict does not hold every parameter" % variant)
+        trained = [i for i, (o, _, _) in enumerate(self._slots) if o >= self._trained_offset]
+        self._trained_slots = [self._slots[i] for i in trained]
+        self._trained_plist = [self._plist[i] for i in trained]
         if freeze_bn:
             self.set_bn_frozen(True)
 
@@ -532,6 +547,25 @@ class HipTrainableResNet(_Node):
         _lib.check(_lib.lib().pvr_trainer_set_bn_frozen(self._handle, 1 if on else 0))
         self._freeze_bn = bool(on)
         self._fwd_gen += 1
+
+    @property
+    def train_from(self):
+        """None or 'layer1' .. 'layer4' (see the class docstring)"""
+        return self._train_from
+
+    @property
+    def trained_offset(self):
+        """float offset in the flat parameter buffer at which the trained parameters begin (pvr_trainer_trained_offset; 0 when everything trains)"""
+        return self._trained_offset
+
+    def trained_parameters(self):
+        """the parameters a training step moves: all of them, or those of train_from's stage and above"""
+        return list(self._trained_plist)
+
+    def prefix_parameters(self):
+        """the parameters of the frozen prefix (empty unless train_from is set)"""
+        t = set(id(p) for p in self._trained_plist)
+        return [p for p in self._plist if id(p) not in t]
 
     @property
     def wgrad_split16(self):
@@ -622,9 +656,22 @@ class HipTrainableResNet(_Node):
     def forward(self, frames_u8):
         if self.training:
             self.close()
-            return _EncoderFunction.apply(self, frames_u8.contiguous(), *self._plist)
+            return _EncoderFunction.apply(self, frames_u8.contiguous(), *self._trained_plist)
         with torch.no_grad():
             return self._eval_model()(frames_u8)
+
+
+TRAIN_FROM = ('layer1', 'layer2', 'layer3', 'layer4')
+
+
+def train_stage(train_from):
+    """pvr_trainer_set_train_from's stage of a train_from value: 0 for None, 1 .. 4 for 'layer1' .. 'layer4'; anything else is a ValueError"""
+    if train_from is None:
+        return 0
+    if train_from not in TRAIN_FROM:
+        raise ValueError("train_from %r: the choices are None (everything trains) or one of %s (that stage and the ones above it train)"
+                         % (train_from, ', '.join(repr(x) for x in TRAIN_FROM)))
+    return TRAIN_FROM.index(train_from) + 1
 
 
 def require_trainable(embedding_name):
@@ -635,11 +682,12 @@ def require_trainable(embedding_name):
     return _SINGLE[embedding_name][1]
 
 
-def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv_split16=False):
+def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv_split16=False, train_from=None):
     """bytes of device memory the training workspace of `embedding_name` takes for max_batch frames (pvr_trainer_workspace_bytes on a handle made
-    for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients and convolutions; None when the trainer refuses that max_batch (a
+    for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients and convolutions, training everything or from train_from's stage up; None when the trainer refuses that max_batch (a
     tensor of the workspace would pass 2 GiB)"""
     variant = require_trainable(embedding_name)
+    stage = train_stage(train_from)
     L = _lib.lib()
     tr = transforms_for('')
     desc = _lib.EncoderDesc(arch=_ARCH[variant], dtype=_lib.PVR_F32, max_batch=int(max_batch), chunk=0, resize=tr.resize, crop=tr.crop)
@@ -655,24 +703,28 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
             _lib.check(L.pvr_trainer_set_wgrad_split16(h, 1))
         if conv_split16:
             _lib.check(L.pvr_trainer_set_conv_split16(h, 1))
+        if stage:
+            _lib.check(L.pvr_trainer_set_train_from(h, stage))
         return int(L.pvr_trainer_workspace_bytes(h))
     finally:
         L.pvr_trainer_destroy(h)
 
 
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
-                   conv_split16=False):
+                   conv_split16=False, train_from=None):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
         raise NotImplementedError("Requested model not available.")                 # embeddings.py:321
     require_trainable(embedding_name)
+    train_stage(train_from)                       # (ValueError names the choices)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
         raise ValueError("train=True computes in fp32 (compute_dtype None or 'f32'), got %r" % (compute_dtype,))
     sd, variant = _load_named_state_dict(embedding_name, pretrained)
-    return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16, conv_split16=conv_split16)
+    return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16, conv_split16=conv_split16,
+                              **({'train_from': train_from} if train_from is not None else {}))
 
 
 class UberModel(nn.Module):
@@ -806,7 +858,7 @@ def _get_embedding(embedding_name='random', in_channels=3, pretrained=True, trai
     if train:                                                                        # embeddings.py:323-326
         model = _get_trainable(embedding_name, pretrained, **hip_kw)
         model.train()
-        for p in model.parameters():
+        for p in model.trained_parameters():      # (train_from: the frozen prefix keeps requires_grad = False)
             p.requires_grad = True
         return model, transforms_for(embedding_name)
     if embedding_name in _SINGLE:
@@ -867,7 +919,7 @@ class EmbeddingNet(nn.Module):
     """
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
-                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False):
+                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -886,13 +938,18 @@ class EmbeddingNet(nn.Module):
         if conv_split16 and not train:
             raise ValueError('conv_split16 is a mode of the trainable encoder (train=True): a frozen encoder has its own plans (compute_dtype \'f32s\' is '
                              'the split-f16 one)')
+        if train_from is not None and not train:
+            raise ValueError('train_from is a mode of the trainable encoder (train=True): a frozen encoder trains nothing')
+        train_stage(train_from)                   # (ValueError names the choices)
+        # train_from (train=True only): partial fine-tuning - that stage and the ones above train, everything below is the frozen prefix
         # freeze_bn (train=True only): frozen BatchNorm, max_batch is then the chunk of a training forward (HipTrainableResNet)
         # wgrad_split16 (train=True only): the weight gradients as exact-split products on the f16 matrix pipe
         # conv_split16 (train=True only): the forward convolutions and the data gradients of layer1 .. layer4 as such products
         self.embedding, self.transforms = _get_embedding(embedding_name, in_channels, pretrained, train, compute_dtype=compute_dtype, max_batch=max_batch,
                                                          chunk=chunk, host=self._host, **({'freeze_bn': True} if freeze_bn else {}),
                                                          **({'wgrad_split16': True} if wgrad_split16 else {}),
-                                                         **({'conv_split16': True} if conv_split16 else {}))
+                                                         **({'conv_split16': True} if conv_split16 else {}),
+                                                         **({'train_from': train_from} if train_from is not None else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

@@ -43,10 +43,12 @@ def load_raw(flags, from_env):
     return obs, action, reward, done
 
 
-def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False, conv_split16=False):
-    """the largest frame count <= frames_wanted whose training workspace (with fp32 or split-f16 weight gradients / convolutions) fits free_bytes
-    (0: not even one frame)"""
+def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False, conv_split16=False, train_from=None):
+    """the largest frame count <= frames_wanted whose training workspace (with fp32 or split-f16 weight gradients / convolutions, training everything
+    or from train_from's stage up) fits free_bytes (0: not even one frame)"""
     conv16 = {'conv_split16': True} if conv_split16 else {}
+    if train_from is not None:
+        conv16['train_from'] = train_from
     from .embeddings import trainer_workspace_bytes
     lo, hi = 0, int(frames_wanted)                              # invariant: lo fits (or is 0), hi + 1 does not
     while lo < hi:
@@ -59,6 +61,23 @@ def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_spli
     return lo
 
 
+def check_train_from_flag(flags):
+    """--embedding_train_from is a mode of --train_embedding: a ValueError without it (argparse has checked the choices)"""
+    stage = getattr(flags, 'embedding_train_from', None)
+    if stage is not None and not getattr(flags, 'train_embedding', False):
+        raise ValueError('--embedding_train_from %s needs --train_embedding: it chooses the stage a trainable encoder trains from (a frozen encoder '
+                         'trains nothing)' % stage)
+    return stage
+
+
+def workspace_modes(flags):
+    """the keywords of trainer_workspace_bytes / largest_fitting_frames behind the weight-gradient mode, from the flags (only what is on)"""
+    kw = {'conv_split16': True} if getattr(flags, 'embedding_conv_split16', False) else {}
+    if getattr(flags, 'embedding_train_from', None) is not None:  # (a frozen prefix keeps no activations: the workspace shrinks with the stage)
+        kw['train_from'] = flags.embedding_train_from
+    return kw
+
+
 def check_workspace_fits(flags, n_frames_per_obs):
     """The trainer keeps every activation of a step: its workspace grows with unroll_length x batch_size x frames (about 0.03 GB per frame for
     resnet18, 0.14 GB for resnet50: the reference's default T=100, B=32 does not fit an MI355X), and the trainer refuses a frame count at which one of
@@ -69,7 +88,7 @@ def check_workspace_fits(flags, n_frames_per_obs):
     if getattr(flags, 'freeze_embedding_bn', False):
         return check_chunk_fits(flags, want)
     split16 = bool(getattr(flags, 'embedding_wgrad_split16', False))       # (the mode's scale slots and scratch are part of the workspace)
-    conv16 = {'conv_split16': True} if getattr(flags, 'embedding_conv_split16', False) else {}
+    conv16 = workspace_modes(flags)
     need = trainer_workspace_bytes(flags.embedding_name, want, split16, **conv16)
     free = int(torch.cuda.mem_get_info()[0])
     if need is None or need > free:
@@ -93,7 +112,7 @@ def check_chunk_fits(flags, want):
     free = int(torch.cuda.mem_get_info()[0])
     chunk = getattr(flags, 'embedding_chunk', None)
     split16 = bool(getattr(flags, 'embedding_wgrad_split16', False))
-    conv16 = {'conv_split16': True} if getattr(flags, 'embedding_conv_split16', False) else {}
+    conv16 = workspace_modes(flags)
     if chunk is None:
         chunk = largest_fitting_frames(flags.embedding_name, want, free // 10 * 9, split16, **conv16)
         if chunk < 1:
@@ -122,6 +141,9 @@ def run_end_to_end(flags, make_env=None):
     from . import embeddings as E
     from .models import PolicyNetWithEncoder, HipJointRMSprop
     E.require_trainable(flags.embedding_name)                   # NotImplementedError names what is trainable
+    train_from = check_train_from_flag(flags)
+    if train_from is not None:                                  # the run's first line names the stage
+        print('=== Training the embedding from %s up: conv1 / bn1 and the stages below are frozen ===' % train_from)
     world = max(rank_world()[1], int(os.environ.get('WORLD_SIZE', '1')))
     if world > 1:
         raise NotImplementedError('--train_embedding with a world size of %d: data-parallel encoder training is not built (the trainable encoder and its '
@@ -170,6 +192,8 @@ def run_end_to_end(flags, make_env=None):
     if getattr(flags, 'embedding_conv_split16', False):
         split16 = dict(split16, conv_split16=True)
         print('  ', 'forward convolutions and data gradients: exact-split products on the f16 matrix pipe')
+    if train_from is not None:
+        split16 = dict(split16, train_from=train_from)
     if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
         if not flags.pretrained_embedding:
             print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')
@@ -190,6 +214,10 @@ def run_end_to_end(flags, make_env=None):
     if resume:
         print('=== Resuming previous run ===')
         checkpoint = torch.load(save_path + '.tar', weights_only=False, map_location='cpu')
+        saved_from = checkpoint.get('flags', {}).get('embedding_train_from', None)
+        if saved_from != train_from:              # (the optimizer state and the schedule belong to the parameters that run trained)
+            raise ValueError('--embedding_train_from %s: the checkpoint %s was trained with --embedding_train_from %s; resume with the same stage'
+                             % (train_from, save_path + '.tar', saved_from))
         model.load_state_dict(checkpoint['actor_model_state_dict'])
         optimizer.load_state_dict(checkpoint['actor_model_optimizer_state_dict'])
         if fused:
@@ -254,6 +282,7 @@ def run_end_to_end(flags, make_env=None):
 
 
 def run(flags, make_env=None):
+    check_train_from_flag(flags)
     if getattr(flags, 'train_embedding', False):
         return run_end_to_end(flags, make_env)
     rank, world = rank_world()
