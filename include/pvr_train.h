@@ -110,7 +110,8 @@ pvr_status pvr_trainer_set_conv_split16(pvr_trainer *tr, int32_t on);
  *     boundary tensor: the last prefix output - for resnet18 / 34 at stage 1 the max pool's output, which is also layer1.0's residual): the prefix's
  *     tensors rotate through a small pool of buffers assigned by liveness, and a prefix op has no gradient tensor and no mean / rstd slots.  In the fp32
  *     arithmetic a prefix op of layer1 .. layer<stage-1> is ONE launch (pvr_op_conv_bn_frozen_forward: no pre-BN tensor exists); with conv_split16 on
- *     it is the mode's scale + split convolution followed by the frozen BatchNorm launch, because a mode has one arithmetic.  The stem stays conv1,
+ *     it is the mode's scale + split convolution followed by the frozen BatchNorm launch, because a mode has one arithmetic (one launch with the
+ *     same bits after pvr_trainer_set_prefix_fused).  The stem stays conv1,
  *     bn1 and the max pool.
  *   backward: walks from the last op down to the first trained op and stops.  The ops that read the boundary tensor (the first block's conv1 and its
  *     downsample) compute their weight gradient and no data gradient; a residual that comes from the prefix gets no gradient; there is no max-pool
@@ -125,6 +126,33 @@ int32_t pvr_trainer_train_from(const pvr_trainer *tr);
 /* float offset in the flat parameter buffer at which the trained parameters begin (0 at stage 0).  Parameters are laid out in op order, so the frozen
  * prefix is the one leading span [0, offset) and the offset is that of layer<stage>.0.conv1.weight. */
 int64_t pvr_trainer_trained_offset(const pvr_trainer *tr);
+
+/* The frozen prefix once per frame and step (the Python mode prefix_once).  With frozen BatchNorm a step runs as passes of <= max_batch frames and the
+ * backward recomputes every pass but the last; the prefix (preprocess, normalize, conv1, bn1, max pool, every prefix op) is frozen, has no backward and
+ * produces ONE tensor a trained op reads - the boundary tensor (the max pool's output, or the last prefix op's y).  A caller that keeps that tensor
+ * across the passes of a step lets a recompute pass start at the first trained op.  The cache is the caller's, as pvr_trainer_backward_acc's scratch is:
+ * pvr_trainer_workspace_bytes does not depend on how a caller steps, and the handle keeps no state about what the cache holds.
+ * pvr_trainer_boundary_floats: floats per frame of the boundary tensor (host arithmetic; 0 at stage 0).  Per frame 56*56*64, 56*56*256, 28*28*512,
+ *   14*14*1024 floats for resnet50 at stages 1 .. 4 and 56*56*64, 56*56*64, 28*28*128, 14*14*256 for resnet18 / 34.
+ * pvr_trainer_forward_boundary, reuse == 0: pvr_trainer_forward, except that the launch that produces the boundary tensor of this pass writes it straight
+ *   to boundary_dev (n x boundary_floats floats; nothing is copied) and the trained ops read it there.  reuse != 0: boundary_dev holds what an earlier
+ *   reuse == 0 call wrote for these n frames; no preprocess, normalize, stem, pool or prefix launch runs, frames_dev may be null and the pass starts at the
+ *   first trained op (pvr_trainer_launch_time lists nothing before it) - the same bits, because the trained ops read the same tensor.
+ *   Either way the held forward remembers the pointer: its backward reads the boundary tensor there (the first block's weight gradients, the residual of
+ *   resnet18's layer1.0, the split modes' scale of it), so the caller leaves that memory unchanged until the backward has run.  The whole cache of a step
+ *   may pass 2 GiB: only the n frames of one call are an operand.  pvr_trainer_forward itself keeps using the workspace's own boundary piece.
+ *   Refused by name, launching nothing: stage 0 (PVR_ERR_STATE: there is no prefix), a null or not 16-byte aligned boundary_dev, n outside
+ *   1 .. max_batch, reuse == 0 with null frames. */
+int64_t pvr_trainer_boundary_floats(const pvr_trainer *tr);
+pvr_status pvr_trainer_forward_boundary(pvr_trainer *tr, const float *params_dev, void *bn_buffers_dev, const uint8_t *frames_dev, int32_t n, int32_t h,
+                                        int32_t w, float *boundary_dev, int32_t reuse, float *out_dev, int64_t out_stride, void *hip_stream);
+/* The split prefix op as one launch.  on == 0 (the default): everything above, bit for bit, and the same workspace to the byte.  on != 0, with
+ * conv_split16 and a stage above 0: a prefix op is "<conv> scale" and "<conv> split16 bn frozen" (pvr_op_conv_bn_frozen_forward_split16: weight pack + the
+ * split convolution with the frozen BatchNorm in its epilogue) instead of scale, split convolution and a BatchNorm launch; no pre-BN tensor of the prefix
+ * exists, so the workspace shrinks.  The output keeps its bits.  Without conv_split16, or at stage 0, the mode changes nothing.  It decides the workspace,
+ * so it must be chosen before the first forward makes it: afterwards the call returns PVR_ERR_STATE with a message.  pvr_trainer_workspace_bytes reports the
+ * size of the current mode. */
+pvr_status pvr_trainer_set_prefix_fused(pvr_trainer *tr, int32_t on);
 
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
@@ -222,6 +250,17 @@ int64_t pvr_op_conv_fwd_split16_scratch_floats(int32_t n, int32_t h, int32_t w, 
 pvr_status pvr_op_conv_fwd_split16(const float *x_dev, const float *w_dev, float *z_dev, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k,
                                    int32_t stride, int32_t pad, const float *x_scale_dev, const float *w_scale_dev, float *scratch_dev, int64_t scratch_floats,
                                    void *hip_stream);
+/* pvr_op_conv_bn_frozen_forward on the split product: the arguments of that entry point plus the two scales, the shapes and refusals of
+ * pvr_op_conv_fwd_split16.  The pack launch of pvr_op_conv_fwd_split16 followed by ONE launch whose K loop and scale undoing are that convolution's and
+ * whose epilogue is pvr_op_bn_frozen_forward's expression in the same order of roundings: y has the bits of pvr_op_conv_fwd_split16 followed by
+ * pvr_op_bn_frozen_forward on the same inputs and scales.  No pre-BN tensor, mean or rstd is written; the running statistics are read only. */
+int64_t pvr_op_conv_bn_frozen_forward_split16_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride,
+                                                             int32_t pad);
+pvr_status pvr_op_conv_bn_frozen_forward_split16(const float *x_dev, const float *w_dev, const float *gamma_dev, const float *beta_dev,
+                                                 const float *running_mean_dev, const float *running_var_dev, const float *residual_dev, float *y_dev, int32_t n,
+                                                 int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t relu,
+                                                 const float *x_scale_dev, const float *w_scale_dev, float *scratch_dev, int64_t scratch_floats,
+                                                 void *hip_stream);
 /* pvr_op_conv_dgrad (same shapes, layouts and refusals) as the same split product: the pack launch writes the rotated, transposed split weights, a
  * stride-2 convolution's dz goes to the even pixels of the zeroed grid (its scale is dz's: zeros do not move a maximum), and the epilogue adds what
  * dx holds when accumulate != 0 (one fp32 addition; the bound gains 2^-24 (|previous| + |result|)).  K = k*k*cout. */

@@ -50,6 +50,11 @@ def make_parser():
                              'and the stages below are frozen (eval-mode BatchNorm, no gradient), keep no activations and have no backward, so the '
                              'training workspace and the step shrink with the stage and the default --embedding_chunk grows.  Works with and without '
                              '--freeze_embedding_bn and the split16 modes; a resumed run must name the same stage')
+    parser.add_argument('--embedding_prefix_once', action='store_true',
+                        help='with --embedding_train_from: the frozen prefix runs once per frame and step - its one output, the boundary tensor, is kept '
+                             'for the unroll_length x batch_size x frames frames of a step (0.2 .. 3.2 MB per frame, counted next to the workspace) and '
+                             'the recompute passes of a --freeze_embedding_bn step start at the first trained stage; with --embedding_conv_split16 a '
+                             'prefix convolution and its BatchNorm are one launch.  The bits do not change: a run may be resumed with or without it')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

@@ -7,7 +7,10 @@
 // are O(1).  A trainer's operands are not: dz has magnitudes near 1e-6 (its f16 high parts would be subnormal), weights may be 1e-5, an activation
 // behind a large BatchNorm gamma may pass 65504.  The scales are read from device memory (no host synchronisation); the epilogue multiplies by 1 / s_x
 // and 1 / s_w (powers of two: exact) and adds the optional fp32 operand - the data gradient's accumulate form - with one fp32 addition.  No bias, no
-// activation, no 16-bit output.
+// activation, no 16-bit output.  The BNF instance is the frozen prefix op of the trainer as ONE launch behind the pack (pvr_trainer_set_prefix_fused): the same
+// K loop and scale undoing give the pre-BN z in registers, and the epilogue is bn_frozen_apply_kernel's expression per element,
+// y = (z - running_mean) * rstd * gamma + beta [+ residual] [ReLU] with rstd = 1 / sqrtf(running_var + 1e-5f), in that kernel's order of roundings
+// (subtract, multiply, one fma, add, max): the bits of pvr_op_conv_fwd_split16 followed by pvr_op_bn_frozen_forward; no z, mean or rstd is written.
 //
 // Kernel: the implicit GEMM of conv_split16_kernel<BM, BN, 3>: BM pixels x BN couts per 512-thread workgroup, K steps of 32 channels of one tap;
 //   * weights: split16_scaled_pack_kernel reads torch's (cout, cin, k, k), multiplies by *s_w, splits, and writes MFMA A fragments
@@ -30,9 +33,11 @@ struct ConvSS {
     float *out;
     int N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, M, n_ctiles, nsteps;
     unsigned in_bytes, w_bytes;
+    const float *gamma, *beta, *run_mean, *run_var;      // BNF only: the frozen BatchNorm of the epilogue
+    int relu;
 };
 
-template <int BM, int BN>
+template <int BM, int BN, bool BNF = false>
 __global__ __launch_bounds__(512) void conv_split16_scaled_kernel(ConvSS p) {
     constexpr int NWC = BN / 16, NWP = 8 / NWC, WP = BM / NWP, JT = WP / 16, RPT = BM / 64;
     static_assert(NWC * NWP == 8 && WP % 16 == 0 && RPT >= 1, "tile shape");
@@ -130,6 +135,31 @@ __global__ __launch_bounds__(512) void conv_split16_scaled_kernel(ConvSS p) {
     const int co = n0 + wc * 16 + fq * 4;
     if (co >= p.Cout) return;
     const float ix = 1.f / sx, iw = 1.f / *p.sw;                                  // powers of two, exponents in [-126, 126]: exact and normal
+    if constexpr (BNF) {
+        // a lane's four channels are the same for every pixel tile: their constants are loaded once, outside the pixel loop
+        float mu[4], rs[4], ga[4], be[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            mu[r] = p.run_mean[co + r]; rs[r] = 1.f / sqrtf(p.run_var[co + r] + 1e-5f);
+            ga[r] = p.gamma[co + r]; be[r] = p.beta[co + r];
+        }
+#pragma unroll
+        for (int j = 0; j < JT; ++j) {
+            const int m = m0 + wp * WP + j * 16 + fr;
+            if (m >= p.M) continue;
+            f32x4 rv = f32x4{0.f, 0.f, 0.f, 0.f}, o;
+            if (p.res) rv = *reinterpret_cast<const f32x4 *>(p.res + (size_t)m * p.Cout + co);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float z = ((acc0[j][r] + acc1[j][r] * (1.f / 2048.f)) * ix) * iw;
+                float t = __fmaf_rn(__fmul_rn(__fsub_rn(z, mu[r]), rs[r]), ga[r], be[r]);
+                if (p.res) t = __fadd_rn(t, rv[r]);
+                o[r] = p.relu ? fmaxf(t, 0.f) : t;
+            }
+            *reinterpret_cast<f32x4 *>(p.out + (size_t)m * p.Cout + co) = o;
+        }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < JT; ++j) {
         const int m = m0 + wp * WP + j * 16 + fr;
@@ -178,11 +208,35 @@ __global__ __launch_bounds__(256) void split16_scaled_pack_kernel(const float *_
 
 namespace {
 
-// x (n, h, w, cin) * packed rows (cout) -> out (n, ho, wo, cout) [+ res]; the shapes have passed the callers' checks
+struct FrozenBn {                                // the BNF instance's epilogue operands
+    const float *gamma, *beta, *run_mean, *run_var;
+    int relu;
+};
+
+// conv_split16's tiles: 128 couts where the padded rows allow it, 128 pixels where that still fills the chip
+template <bool BNF>
+void launch_tiles(ConvSS &p, int cout_pad, int64_t M, int cus, hipStream_t stream) {
+    if (cout_pad % 128 == 0) {
+        p.n_ctiles = cout_pad / 128;
+        const int64_t t128 = ((M + 127) / 128) * p.n_ctiles;
+        if (t128 >= cus) hipLaunchKernelGGL((conv_split16_scaled_kernel<128, 128, BNF>), dim3((unsigned)t128), dim3(512), 0, stream, p);
+        else hipLaunchKernelGGL((conv_split16_scaled_kernel<64, 128, BNF>), dim3((unsigned)(((M + 63) / 64) * p.n_ctiles)), dim3(512), 0, stream, p);
+    } else {
+        p.n_ctiles = cout_pad / 64;
+        const int64_t t128 = ((M + 127) / 128) * p.n_ctiles;
+        if (t128 >= cus) hipLaunchKernelGGL((conv_split16_scaled_kernel<128, 64, BNF>), dim3((unsigned)t128), dim3(512), 0, stream, p);
+        else hipLaunchKernelGGL((conv_split16_scaled_kernel<64, 64, BNF>), dim3((unsigned)(((M + 63) / 64) * p.n_ctiles)), dim3(512), 0, stream, p);
+    }
+}
+
+// x (n, h, w, cin) * packed rows (cout) -> out (n, ho, wo, cout) [+ res]; the shapes have passed the callers' checks.  bn: the frozen BatchNorm of the
+// BNF instance (res is then the residual behind it), null for the plain convolution
 pvr_status launch_kernel(const float *in, const void *wsp, const float *res, float *out, int n, int h, int w, int cin, int cout, int k, int stride, int pad,
-                         const float *sx, const float *sw, hipStream_t stream) {
+                         const float *sx, const float *sw, hipStream_t stream, const FrozenBn *bn = nullptr) {
     ConvSS p;
     p.in = in; p.res = res; p.sx = sx; p.sw = sw; p.w = (const u16 *)wsp; p.out = out;
+    p.gamma = p.beta = p.run_mean = p.run_var = nullptr; p.relu = 0;
+    if (bn) { p.gamma = bn->gamma; p.beta = bn->beta; p.run_mean = bn->run_mean; p.run_var = bn->run_var; p.relu = bn->relu; }
     p.N = n; p.H = h; p.W = w; p.Cin = cin; p.Cout = cout; p.KH = k; p.KW = k; p.stride = stride; p.pad = pad;
     p.Ho = (h + 2 * pad - k) / stride + 1; p.Wo = (w + 2 * pad - k) / stride + 1;
     const int cout_pad = (cout + 63) / 64 * 64;
@@ -190,18 +244,8 @@ pvr_status launch_kernel(const float *in, const void *wsp, const float *res, flo
     PVR_REQUIRE(M < (1ll << 31) && inb < 0x7ffffff0ll && wb < 0x7ffffff0ll, "conv_split16_scaled: operand larger than 2 GiB (use a smaller batch)");
     p.M = (int)M; p.in_bytes = (unsigned)inb; p.w_bytes = (unsigned)wb; p.nsteps = k * k * cin / 32;
     static const int cus = [] { int v = 0, dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev); return v > 0 ? v : 256; }();
-    // conv_split16's tiles: 128 couts where the padded rows allow it, 128 pixels where that still fills the chip
-    if (cout_pad % 128 == 0) {
-        p.n_ctiles = cout_pad / 128;
-        const int64_t t128 = ((M + 127) / 128) * p.n_ctiles;
-        if (t128 >= cus) hipLaunchKernelGGL((conv_split16_scaled_kernel<128, 128>), dim3((unsigned)t128), dim3(512), 0, stream, p);
-        else hipLaunchKernelGGL((conv_split16_scaled_kernel<64, 128>), dim3((unsigned)(((M + 63) / 64) * p.n_ctiles)), dim3(512), 0, stream, p);
-    } else {
-        p.n_ctiles = cout_pad / 64;
-        const int64_t t128 = ((M + 127) / 128) * p.n_ctiles;
-        if (t128 >= cus) hipLaunchKernelGGL((conv_split16_scaled_kernel<128, 64>), dim3((unsigned)t128), dim3(512), 0, stream, p);
-        else hipLaunchKernelGGL((conv_split16_scaled_kernel<64, 64>), dim3((unsigned)(((M + 63) / 64) * p.n_ctiles)), dim3(512), 0, stream, p);
-    }
+    if (bn) launch_tiles<true>(p, cout_pad, M, cus, stream);
+    else launch_tiles<false>(p, cout_pad, M, cus, stream);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }
@@ -251,6 +295,16 @@ pvr_status launch_conv_fwd_split16(const float *x, const float *w, float *z, int
     return launch_kernel(x, wpack, nullptr, z, n, h, wd, cin, cout, k, stride, pad, sx, sw, st);
 }
 
+pvr_status launch_conv_bn_frozen_split16(const float *x, const float *w, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                         const float *res, float *y, int n, int h, int wd, int cin, int cout, int k, int stride, int pad, int relu, const float *sx,
+                                         const float *sw, float *wpack, hipStream_t st) {
+    pvr_status s;
+    if ((s = fwd_check(n, h, wd, cin, cout, k, stride, pad))) return s;
+    if ((s = launch_split16_scaled_pack(w, wpack, cout, cin, k, false, sw, st))) return s;
+    const FrozenBn bn{gamma, beta, run_mean, run_var, relu ? 1 : 0};
+    return launch_kernel(x, wpack, res, y, n, h, wd, cin, cout, k, stride, pad, sx, sw, st, &bn);
+}
+
 pvr_status launch_conv_dgrad_split16(const float *dz, const float *w, float *dx, int accumulate, int n, int h, int wd, int cin, int cout, int k, int stride, int pad,
                                      const float *sdz, const float *sw, float *wflip, float *dil, hipStream_t st) {
     pvr_status s;
@@ -286,6 +340,25 @@ pvr_status pvr_op_conv_fwd_split16(const float *x, const float *wt, float *z, in
     PVR_REQUIRE(scratch_floats >= need, "pvr_op_conv_fwd_split16: scratch of %lld floats, pvr_op_conv_fwd_split16_scratch_floats asks for %lld",
                 (long long)scratch_floats, (long long)need);
     return launch_conv_fwd_split16(x, wt, z, n, h, w, cin, cout, k, stride, pad, x_scale, w_scale, scratch, (hipStream_t)stream);
+}
+
+int64_t pvr_op_conv_bn_frozen_forward_split16_scratch_floats(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad) {
+    return pvr_op_conv_fwd_split16_scratch_floats(n, h, w, cin, cout, k, stride, pad);
+}
+
+pvr_status pvr_op_conv_bn_frozen_forward_split16(const float *x, const float *wt, const float *gamma, const float *beta, const float *run_mean,
+                                                 const float *run_var, const float *res, float *y, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout,
+                                                 int32_t k, int32_t stride, int32_t pad, int32_t relu, const float *x_scale, const float *w_scale, float *scratch,
+                                                 int64_t scratch_floats, void *stream) {
+    PVR_REQUIRE(x && wt && gamma && beta && run_mean && run_var && y && scratch, "pvr_op_conv_bn_frozen_forward_split16: null argument");
+    PVR_REQUIRE(x_scale && w_scale, "pvr_op_conv_bn_frozen_forward_split16: null scale (pvr_op_absmax_scale writes one per operand)");
+    pvr_status s;
+    if ((s = fwd_check(n, h, w, cin, cout, k, stride, pad))) return s;
+    const int64_t need = pvr_op_conv_fwd_split16_scratch_floats(n, h, w, cin, cout, k, stride, pad);
+    PVR_REQUIRE(scratch_floats >= need, "pvr_op_conv_bn_frozen_forward_split16: scratch of %lld floats, pvr_op_conv_bn_frozen_forward_split16_scratch_floats asks "
+                "for %lld", (long long)scratch_floats, (long long)need);
+    return launch_conv_bn_frozen_split16(x, wt, gamma, beta, run_mean, run_var, res, y, n, h, w, cin, cout, k, stride, pad, relu, x_scale, w_scale, scratch,
+                                         (hipStream_t)stream);
 }
 
 // scratch: [rotated split weights (cin_pad, k*k*cout)] [dz on the zero-filled grid (stride 2)]

@@ -64,6 +64,10 @@ struct pvr_trainer {
     int prefix_ops() const { return train_from > 0 ? first_trained : 0; }
     bool in_prefix(int src) const { return train_from > 0 && src < first_trained; }       // (src: an op index, or -1 the max pool's output)
     size_t scale_slots() const { return ops.size() + 3 + 4 + (conv_split16 ? 1 : 0); }
+    int boundary_src = -2;                       // train_from > 0: the ONE prefix tensor a trained op reads (an op index, or -1 the max pool's output)
+    float *ext_boundary = nullptr;               // pvr_trainer_forward_boundary: the caller's memory the held forward's boundary tensor lives in (else the arena's)
+    bool prefix_fused = false;                   // pvr_trainer_set_prefix_fused: with conv_split16 a prefix op is scale + ONE launch, no z; fixed once the arena exists
+    bool fused_prefix() const { return prefix_fused && conv_split16 && train_from > 0; }
     bool timing = false;
     std::vector<Timed> times;                    // launch i of a step is bracketed by events[i]
     std::vector<EventPair> events;               // made once each, on demand; destroyed with the trainer (no error path leaves one behind)
@@ -108,7 +112,7 @@ struct Carver {                                  // sizes, then pointers, of one
 // boundary tensor) gets a piece of its own.  Prefix ops get no dy and no mean / rstd slots, and no z where the op is one fused launch.
 void carve_prefix(pvr_trainer *t, Carver &c) {
     const int B = t->desc.max_batch, P = t->first_trained;
-    const bool need_z = t->conv_split16;          // (fp32: a prefix op is ONE launch, convolution + BatchNorm, and has no z)
+    const bool need_z = t->conv_split16 && !t->prefix_fused;      // (fp32, or prefix_fused: a prefix op is ONE launch, convolution + BatchNorm, and has no z)
     std::vector<int> last(P + 1, -1);             // last consumer (op index) of tensor src (index src + 1)
     for (int i = 0; i < (int)t->ops.size(); ++i) {
         const TrainOp &op = t->ops[i];
@@ -276,7 +280,11 @@ pvr_status memset_floats(float *p, int64_t count, hipStream_t st) {
     return PVR_OK;
 }
 
-const float *tensor_of(const pvr_trainer *t, int src) { return src == -1 ? t->pool : t->ops[src].y; }
+// tensor `src` of the forward at hand: the caller's memory for the boundary tensor of a pvr_trainer_forward_boundary pass, else the arena's piece
+float *tensor_of(const pvr_trainer *t, int src) {
+    if (t->ext_boundary && src == t->boundary_src) return t->ext_boundary;
+    return src == -1 ? t->pool : t->ops[src].y;
+}
 float *grad_of(pvr_trainer *t, int src) { return src == -1 ? t->dpool : t->ops[src].dy; }
 
 }  // namespace
@@ -406,49 +414,54 @@ int32_t pvr_trainer_launch_time(const pvr_trainer *t, int32_t index, char *name,
     return (int32_t)x.name.size();
 }
 
-pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *out,
-                               int64_t out_stride, void *stream) {
-    PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward: null argument");
-    if (t->bn_frozen)
-        PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward: %d frames, the workspace holds max_batch = %d (with frozen BatchNorm the frames are "
-                    "independent: run them as passes of at most max_batch and accumulate with pvr_trainer_backward_acc)", n, t->desc.max_batch);
-    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward: %d frames, the workspace holds max_batch = %d (BatchNorm takes the whole batch of a forward "
-                "together: it is not chunked)", n, t->desc.max_batch);
-    TraceScope ts("pvr_trainer_forward");
+}  // extern "C"
+
+namespace {
+
+// pvr_trainer_forward (boundary == nullptr) and pvr_trainer_forward_boundary: the arguments have passed the callers' checks.  boundary: where this pass's
+// boundary tensor lives instead of the arena's piece - the producing launch writes it there and every reader goes through tensor_of.  reuse: it holds the
+// tensor already, and the pass starts at the first trained op.
+pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *boundary, bool reuse,
+                        float *out, int64_t out_stride, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     pvr_status s;
     if ((s = ensure_workspace(t))) return s;
     t->fwd_n = 0;                                 // the held activations are being overwritten
+    t->ext_boundary = boundary;
     if (t->timing) t->times.clear();
     Tick tick{t, st};
     float *bufs = (float *)bn_buffers;
     const int P = t->prefix_ops();
     const bool part = t->train_from > 0;
-    auto bn = [&](TrainOp &op, const float *res, int64_t rows, bool prefix) {
+    auto bn = [&](TrainOp &op, const float *res, int64_t rows, bool prefix, float *y_prefix = nullptr) {
         if (prefix)                               // a frozen module in eval: running statistics whatever the handle's BatchNorm mode; nothing kept for a backward
-            return launch_bn_frozen_apply(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, op.y, nullptr, nullptr, rows,
-                                          op.cout, op.relu, st);
+            return launch_bn_frozen_apply(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, y_prefix ? y_prefix : op.y, nullptr,
+                                          nullptr, rows, op.cout, op.relu, st);
         if (t->bn_frozen)                         // running statistics, read only: neither they nor num_batches_tracked are touched
             return pvr_op_bn_frozen_forward(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, op.y, op.mean, op.rstd, rows,
                                             op.cout, op.relu, st);
         return pvr_op_bn_train_forward(op.z, res, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off, (int64_t *)(bufs + op.nbt_off), op.y,
                                        op.mean, op.rstd, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st);
     };
-    TR_RUN("preprocess", 0, launch_preprocess(frames, n, h, w, t->desc.resize, t->desc.crop, t->d_img, PVR_BF16, st, 0));
-    TR_RUN("normalize", 0, launch_normalize_nhwc4(t->d_img, t->d_imgf, n, t->desc.crop, t->desc.mean, t->desc.std_, PVR_BF16, st, false));
-    TrainOp &sm = t->stem;
-    TR_RUN("conv1 pack", 0, launch_pack_stem_weights(params + sm.w_off, t->stem_wpack, st));
-    TR_RUN("conv1", 2.0 * n * 112 * 112 * 64 * 147, launch_stem_f32(t->d_imgf, t->stem_wpack, nullptr, sm.z, n, S_IMG, st, true));
-    TR_RUN("bn1", 0, bn(sm, nullptr, (int64_t)n * 112 * 112, part));
-    TR_RUN("maxpool", 0, launch_maxpool_f32(sm.y, t->pool, n, 112, 112, 64, st));
+    if (!reuse) {
+        TR_RUN("preprocess", 0, launch_preprocess(frames, n, h, w, t->desc.resize, t->desc.crop, t->d_img, PVR_BF16, st, 0));
+        TR_RUN("normalize", 0, launch_normalize_nhwc4(t->d_img, t->d_imgf, n, t->desc.crop, t->desc.mean, t->desc.std_, PVR_BF16, st, false));
+        TrainOp &sm = t->stem;
+        TR_RUN("conv1 pack", 0, launch_pack_stem_weights(params + sm.w_off, t->stem_wpack, st));
+        TR_RUN("conv1", 2.0 * n * 112 * 112 * 64 * 147, launch_stem_f32(t->d_imgf, t->stem_wpack, nullptr, sm.z, n, S_IMG, st, true));
+        TR_RUN("bn1", 0, bn(sm, nullptr, (int64_t)n * 112 * 112, part));
+        TR_RUN("maxpool", 0, launch_maxpool_f32(sm.y, tensor_of(t, -1), n, 112, 112, 64, st));
+    }
     // conv_split16: a tensor's scale is computed once per forward, in the launch of its first consumer, next to that convolution's weight scale; the
     // slots stay valid for the backward (the saved activations do not change)
     std::vector<char> scaled(t->ops.size() + 1, 0);
     float *w_scale = t->conv_split16 ? t->scales + t->ops.size() + 7 : nullptr;
     uint32_t *scale_aux = t->conv_split16 ? (uint32_t *)(t->scales + t->ops.size() + 3) : nullptr;
-    for (int i = 0; i < (int)t->ops.size(); ++i) {
+    const bool fused = t->fused_prefix();
+    for (int i = reuse ? P : 0; i < (int)t->ops.size(); ++i) {
         TrainOp &op = t->ops[i];
         const int64_t rows = (int64_t)n * op.ho * op.wo;
+        float *y = tensor_of(t, i);               // (op.y, or the caller's memory when this op writes the boundary tensor)
         if (t->conv_split16) {
             const float *x = tensor_of(t, op.in_src);
             float *x_scale = t->scales + op.in_src + 1;
@@ -457,16 +470,23 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
                    pvr_op_absmax_scale_pair(params + op.w_off, (int64_t)op.cout * op.cin * op.k * op.k, w_scale, first ? x : nullptr,
                                             (int64_t)n * op.h * op.w * op.cin, first ? x_scale : nullptr, scale_aux, st));
             scaled[op.in_src + 1] = 1;
+            if (fused && i < P) {                 // a frozen prefix op: the split convolution with the frozen BatchNorm in its epilogue, no z
+                TR_RUN(op.conv + " split16 bn frozen", 2.0 * rows * op.cout * op.cin * op.k * op.k,
+                       launch_conv_bn_frozen_split16(x, params + op.w_off, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off,
+                                                     op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), y, n, op.h, op.w, op.cin, op.cout, op.k, op.stride,
+                                                     op.pad, op.relu, x_scale, w_scale, t->wpack, st));
+                continue;
+            }
             TR_RUN(op.conv + " split16", 2.0 * rows * op.cout * op.cin * op.k * op.k,
                    launch_conv_fwd_split16(x, params + op.w_off, op.z, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, x_scale, w_scale, t->wpack, st));
-            TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows, i < P));
+            TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows, i < P, y));
             continue;
         }
         TR_RUN(op.conv + " pack", 0, launch_pack_conv_weights(params + op.w_off, t->wpack, op.cout, op.cin, op.k, false, st));
         if (i < P) {                              // a frozen prefix op: convolution and BatchNorm on the running statistics as one launch, no z
             TR_RUN(op.conv + " bn frozen", 2.0 * rows * op.cout * op.cin * op.k * op.k,
                    launch_conv_bn_frozen_f32(tensor_of(t, op.in_src), t->wpack, params + op.g_off, params + op.b_off, bufs + op.rm_off, bufs + op.rv_off,
-                                             op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), op.y, n, op.h, op.w, op.cin, op.cout, op.k, op.stride,
+                                             op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), y, n, op.h, op.w, op.cin, op.cout, op.k, op.stride,
                                              op.pad, op.relu, st));
             continue;
         }
@@ -477,6 +497,49 @@ pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buf
     TR_RUN("avgpool", 0, launch_avgpool(t->ops.back().y, out, out_stride, n, t->final_hw, t->final_c, 1, PVR_F32, st));
     t->fwd_n = n;
     return collect_times(t, 0, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+pvr_status pvr_trainer_forward(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *out,
+                               int64_t out_stride, void *stream) {
+    PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward: null argument");
+    if (t->bn_frozen)
+        PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward: %d frames, the workspace holds max_batch = %d (with frozen BatchNorm the frames are "
+                    "independent: run them as passes of at most max_batch and accumulate with pvr_trainer_backward_acc)", n, t->desc.max_batch);
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward: %d frames, the workspace holds max_batch = %d (BatchNorm takes the whole batch of a forward "
+                "together: it is not chunked)", n, t->desc.max_batch);
+    TraceScope ts("pvr_trainer_forward");
+    return forward_pass(t, params, bn_buffers, frames, n, h, w, nullptr, false, out, out_stride, stream);
+}
+
+int64_t pvr_trainer_boundary_floats(const pvr_trainer *t) {
+    if (!t || t->train_from <= 0) return 0;
+    if (t->boundary_src == -1) return (int64_t)56 * 56 * 64;
+    const TrainOp &op = t->ops[t->boundary_src];
+    return (int64_t)op.ho * op.wo * op.cout;
+}
+
+pvr_status pvr_trainer_forward_boundary(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,
+                                        float *boundary, int32_t reuse, float *out, int64_t out_stride, void *stream) {
+    PVR_REQUIRE(t && params && bn_buffers && out, "pvr_trainer_forward_boundary: null argument");
+    if (t->train_from <= 0) {
+        set_error("pvr_trainer_forward_boundary: everything trains (pvr_trainer_set_train_from stage 0): there is no frozen prefix and no boundary tensor to "
+                  "keep; use pvr_trainer_forward");
+        return PVR_ERR_STATE;
+    }
+    PVR_REQUIRE(boundary, "pvr_trainer_forward_boundary: null boundary_dev (n x pvr_trainer_boundary_floats = %lld floats of device memory)",
+                (long long)pvr_trainer_boundary_floats(t));
+    PVR_REQUIRE(((uintptr_t)boundary & 15) == 0, "pvr_trainer_forward_boundary: boundary_dev %p is not 16-byte aligned (the launches move it as float4s)",
+                (void *)boundary);
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward_boundary: %d frames, the workspace holds max_batch = %d (run the frames as passes of at most "
+                "max_batch, each on its own rows of the boundary cache)", n, t->desc.max_batch);
+    PVR_REQUIRE(reuse || frames, "pvr_trainer_forward_boundary: null frames_dev with reuse == 0 (only a reuse pass, which starts at the first trained op, reads no "
+                "frames)");
+    TraceScope ts("pvr_trainer_forward_boundary");
+    return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, reuse != 0, out, out_stride, stream);
 }
 
 }  // extern "C"
@@ -645,9 +708,31 @@ pvr_status pvr_trainer_set_train_from(pvr_trainer *t, int32_t stage) {
         for (int i = first; i < (int)t->ops.size(); ++i)       // (op order is layer order: the prefix is one leading span of the parameters)
             PVR_REQUIRE(t->ops[i].in_src >= -1 && t->ops[i].w_off >= t->ops[first].w_off, "pvr_trainer_set_train_from: the ops of %s do not end the plan", pre.c_str());
     }
+    // the boundary: for these trunks the trained ops read exactly ONE tensor of the prefix (carve_prefix's "piece of its own")
+    int bsrc = -2;
+    if (stage > 0)
+        for (int i = first; i < (int)t->ops.size(); ++i)
+            for (int src : {t->ops[i].in_src, t->ops[i].res_src}) {
+                if (src == -2 || src >= first) continue;
+                PVR_REQUIRE(bsrc == -2 || bsrc == src, "pvr_trainer_set_train_from: the trained ops of stage %d read more than one tensor of the prefix", stage);
+                bsrc = src;
+            }
+    PVR_REQUIRE(stage == 0 || bsrc != -2, "pvr_trainer_set_train_from: no trained op of stage %d reads the prefix", stage);
     if (stage != t->train_from) t->fwd_n = 0;     // (only before the arena exists: no forward is held)
     t->train_from = stage;
     t->first_trained = first;
+    t->boundary_src = bsrc;
+    return PVR_OK;
+}
+
+pvr_status pvr_trainer_set_prefix_fused(pvr_trainer *t, int32_t on) {
+    PVR_REQUIRE(t, "pvr_trainer_set_prefix_fused: null trainer");
+    if (t->arena && (on != 0) != t->prefix_fused) {
+        set_error("pvr_trainer_set_prefix_fused: the workspace of this handle exists already (the first forward made it for the %s prefix ops): choose "
+                  "the mode before the first forward", t->prefix_fused ? "fused" : "unfused");
+        return PVR_ERR_STATE;
+    }
+    t->prefix_fused = on != 0;
     return PVR_OK;
 }
 int32_t pvr_trainer_train_from(const pvr_trainer *t) { return t ? t->train_from : 0; }

@@ -26,6 +26,11 @@ pvr_status launch_dilate2(const float *dz, float *out, int n, int h, int w, int 
 // as launch_pack_conv_weights; dil: n*h*w*cout floats (stride 2 only).  Refusals as pvr_op_conv_fwd_split16 / pvr_op_conv_dgrad_split16.
 pvr_status launch_conv_fwd_split16(const float *x, const float *w, float *z, int n, int h, int wd, int cin, int cout, int k, int stride, int pad, const float *sx,
                                    const float *sw, float *wpack, hipStream_t st);
+// launch_conv_fwd_split16 with the frozen BatchNorm [+ residual] [ReLU] in the convolution's epilogue (the BNF instance): pack + ONE launch -> y, the bits of
+// launch_conv_fwd_split16 followed by launch_bn_frozen_apply; no z is written
+pvr_status launch_conv_bn_frozen_split16(const float *x, const float *w, const float *gamma, const float *beta, const float *run_mean, const float *run_var,
+                                         const float *res, float *y, int n, int h, int wd, int cin, int cout, int k, int stride, int pad, int relu, const float *sx,
+                                         const float *sw, float *wpack, hipStream_t st);
 pvr_status launch_conv_dgrad_split16(const float *dz, const float *w, float *dx, int accumulate, int n, int h, int wd, int cin, int cout, int k, int stride, int pad,
                                      const float *sdz, const float *sw, float *wflip, float *dil, hipStream_t st);
 }  // namespace pvr

@@ -392,6 +392,7 @@ class _EncoderFunction(torch.autograd.Function):
         out = model._forward_raw(frames_u8)
         model._fwd_gen += 1
         ctx.model, ctx.gen, ctx.frames = model, model._fwd_gen, frames_u8
+        ctx.boundary, model._boundary = model._boundary, None       # (prefix_once: the cache lives on the node, exactly as long as the frames do)
         return out
 
     @staticmethod
@@ -402,8 +403,8 @@ class _EncoderFunction(torch.autograd.Function):
                                'encoder overwrote them (one backward per forward, right after it)')
         dout = dout.contiguous().float()
         g = torch.empty_like(m._flat)
-        m._backward_raw(ctx.frames, dout, g)
-        ctx.frames = None
+        m._backward_raw(ctx.frames, dout, g, ctx.boundary)
+        ctx.frames = ctx.boundary = None
         return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._trained_slots)
 
 
@@ -439,9 +440,17 @@ class HipTrainableResNet(_Node):
     running statistics in either BatchNorm mode, keeps no activation but the one the first trained block reads, and has no backward: the workspace
     (workspace_bytes) and the step shrink with the stage.  Prefix parameters stay nn.Parameters with requires_grad = False and stay in state_dict();
     the autograd node takes only the trained parameters, so a prefix parameter's .grad stays None.  Chosen at construction (it decides the
-    workspace); legal in both BatchNorm modes and with either or both split modes."""
+    workspace); legal in both BatchNorm modes and with either or both split modes.
 
-    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None):
+    prefix_once (needs train_from): the frozen prefix runs once per frame and step.  A training forward allocates one (n, boundary_floats) fp32 tensor -
+    the one prefix tensor a trained op reads, trainer_boundary_bytes per frame - every pass writes its rows (pvr_trainer_forward_boundary), and the
+    recompute passes of a chunked backward start at the first trained op on theirs instead of running preprocess, the stem and the prefix again.  The
+    tensor lives as long as the kept uint8 frames do and is released after the backward.  With conv_split16 a prefix op is also one launch instead of
+    three (pvr_trainer_set_prefix_fused), and the workspace holds no pre-BN tensor of the prefix.  Embeddings and gradients keep their bits.  Chosen at
+    construction; legal in both BatchNorm modes (with batch statistics a step is one pass and only the fused launches matter) and with either split mode."""
+
+    def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
+                 prefix_once=False):
         super().__init__()
         assert variant in _TRAINABLE, variant
         _lib.require_gpu()
@@ -471,6 +480,12 @@ class HipTrainableResNet(_Node):
         if train_stage(train_from):
             _lib.check(L.pvr_trainer_set_train_from(h, train_stage(train_from)))
             self._train_from = train_from
+        check_prefix_once(prefix_once, train_from)
+        self._prefix_once = bool(prefix_once)
+        self._boundary = None                    # prefix_once: the boundary cache between _forward_raw and its consumer (the autograd node or the joint step)
+        self._boundary_floats = int(L.pvr_trainer_boundary_floats(h))
+        if self._prefix_once:
+            _lib.check(L.pvr_trainer_set_prefix_fused(h, 1))
         self._trained_offset = int(L.pvr_trainer_trained_offset(h))     # floats of the flat buffer below it are the frozen prefix (one leading span)
         dev = torch.device('cuda')
         self._flat = torch.zeros(L.pvr_trainer_param_count(h), dtype=torch.float32, device=dev)
@@ -554,6 +569,15 @@ class HipTrainableResNet(_Node):
         return self._train_from
 
     @property
+    def prefix_once(self):
+        """the frozen prefix runs once per frame and step (see the class docstring)"""
+        return self._prefix_once
+
+    def boundary_bytes(self):
+        """bytes per frame of the boundary tensor prefix_once keeps (0 when everything trains)"""
+        return 4 * self._boundary_floats
+
+    @property
     def trained_offset(self):
         """float offset in the flat parameter buffer at which the trained parameters begin (pvr_trainer_trained_offset; 0 when everything trains)"""
         return self._trained_offset
@@ -623,23 +647,35 @@ class HipTrainableResNet(_Node):
             raise ValueError('training forward of %d frames: the workspace was made for max_batch = %d (BatchNorm takes the whole batch together, '
                              'it cannot be chunked)' % (n, self._max_batch))
         out = torch.empty((n, self.out_size), dtype=torch.float32, device=frames_u8.device)
+        # prefix_once: the boundary tensor of every frame of the step; its consumer (the autograd node, or the joint step under the generation
+        # counter) takes it from here and hands it to _backward_raw
+        self._boundary = torch.empty((n, self._boundary_floats), dtype=torch.float32, device=frames_u8.device) if self._prefix_once else None
         for lo, hi in self._passes(n):            # (one pass unless BatchNorm is frozen; the last pass's activations stay held)
-            self._forward_pass(frames_u8, lo, hi, out[lo:hi])
+            self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary)
         return out
 
-    def _forward_pass(self, frames_u8, lo, hi, out):
+    def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False):
+        """one pass over frames [lo, hi).  boundary: the step's (n, boundary_floats) cache - this pass writes its rows (reuse False) or starts at the first
+        trained op on what they hold (reuse True)"""
         vp = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(_lib.lib().pvr_trainer_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8[lo:hi]), hi - lo, frames_u8.shape[1],
-                                                  frames_u8.shape[2], vp(out), out.stride(0), _lib.stream_ptr()))
+        if boundary is None:
+            _lib.check(_lib.lib().pvr_trainer_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8[lo:hi]), hi - lo, frames_u8.shape[1],
+                                                      frames_u8.shape[2], vp(out), out.stride(0), _lib.stream_ptr()))
+            return
+        _lib.check(_lib.lib().pvr_trainer_forward_boundary(self._handle, vp(self._flat), vp(self._bufs), None if reuse else vp(frames_u8[lo:hi]), hi - lo,
+                                                           frames_u8.shape[1], frames_u8.shape[2], vp(boundary[lo:hi]), 1 if reuse else 0, vp(out),
+                                                           out.stride(0), _lib.stream_ptr()))
 
-    def _backward_raw(self, frames_u8, dout, grads):
+    def _backward_raw(self, frames_u8, dout, grads, boundary=None):
         """d(loss)/d(embeddings) of the training forward that just ran on frames_u8 -> the flat gradient `grads` (fully written).  One pass: one
         pvr_trainer_backward.  Several (frozen BatchNorm): the last pass first - its activations are still held - then every other pass in frame
-        order, each recomputed and added by pvr_trainer_backward_acc."""
+        order, each recomputed and added by pvr_trainer_backward_acc.  boundary (prefix_once): the cache that forward filled; a recomputed pass
+        starts at the first trained op on its rows."""
         L = _lib.lib()
         vp = lambda t: C.c_void_p(t.data_ptr())
         passes = self._passes(frames_u8.shape[0])
         assert dout.shape[0] == frames_u8.shape[0] and dout.stride(1) == 1
+        assert (boundary is not None) == self._prefix_once, 'prefix_once: the backward takes the boundary cache of its forward'
         if len(passes) == 1:
             _lib.check(L.pvr_trainer_backward(self._handle, vp(self._flat), vp(dout), dout.stride(0), vp(grads), _lib.stream_ptr()))
             return
@@ -649,7 +685,7 @@ class HipTrainableResNet(_Node):
         again = torch.empty((self._max_batch, self.out_size), dtype=torch.float32, device=dout.device)       # the recomputed embeddings are not used
         for i, (lo, hi) in enumerate(passes[-1:] + passes[:-1]):
             if i:
-                self._forward_pass(frames_u8, lo, hi, again[:hi - lo])
+                self._forward_pass(frames_u8, lo, hi, again[:hi - lo], boundary, reuse=True)
             _lib.check(L.pvr_trainer_backward_acc(self._handle, vp(self._flat), vp(dout[lo:hi]), dout.stride(0), vp(grads), 1 if i else 0, vp(sc), sc.numel(),
                                                   _lib.stream_ptr()))
 
@@ -662,6 +698,13 @@ class HipTrainableResNet(_Node):
 
 
 TRAIN_FROM = ('layer1', 'layer2', 'layer3', 'layer4')
+
+
+def check_prefix_once(prefix_once, train_from):
+    """prefix_once keeps the frozen prefix's boundary tensor across the passes of a step: a ValueError where nothing is frozen"""
+    if prefix_once and train_from is None:
+        raise ValueError('prefix_once needs train_from: with everything training there is no frozen prefix to keep (its one output is what the mode '
+                         'caches across the passes of a step)')
 
 
 def train_stage(train_from):
@@ -682,12 +725,9 @@ def require_trainable(embedding_name):
     return _SINGLE[embedding_name][1]
 
 
-def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv_split16=False, train_from=None):
-    """bytes of device memory the training workspace of `embedding_name` takes for max_batch frames (pvr_trainer_workspace_bytes on a handle made
-    for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients and convolutions, training everything or from train_from's stage up; None when the trainer refuses that max_batch (a
-    tensor of the workspace would pass 2 GiB)"""
+def _sizing_handle(embedding_name, max_batch):
+    """a trainer handle made for a question of sizes (host arithmetic, no GPU needed); None when the trainer refuses that max_batch"""
     variant = require_trainable(embedding_name)
-    stage = train_stage(train_from)
     L = _lib.lib()
     tr = transforms_for('')
     desc = _lib.EncoderDesc(arch=_ARCH[variant], dtype=_lib.PVR_F32, max_batch=int(max_batch), chunk=0, resize=tr.resize, crop=tr.crop)
@@ -698,7 +738,37 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
         if 'largest max_batch' in _lib.last_error():
             return None
         _lib.check(1)
+    return h
+
+
+def trainer_boundary_bytes(embedding_name, train_from):
+    """bytes per frame of the boundary tensor prefix_once keeps for a step's frames (pvr_trainer_boundary_floats on a handle made for the question:
+    host arithmetic, no GPU needed); 0 when everything trains"""
+    stage = train_stage(train_from)
+    h = _sizing_handle(embedding_name, 1)
+    L = _lib.lib()
     try:
+        if stage:
+            _lib.check(L.pvr_trainer_set_train_from(h, stage))
+        return 4 * int(L.pvr_trainer_boundary_floats(h))
+    finally:
+        L.pvr_trainer_destroy(h)
+
+
+def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv_split16=False, train_from=None, prefix_once=False):
+    """bytes of device memory the training workspace of `embedding_name` takes for max_batch frames (pvr_trainer_workspace_bytes on a handle made
+    for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients and convolutions, training everything or from train_from's stage up; None when the trainer refuses that max_batch (a
+    tensor of the workspace would pass 2 GiB).  prefix_once: the workspace of that mode (with conv_split16 it holds no pre-BN tensor of the prefix); the
+    boundary cache is the caller's and is counted by trainer_boundary_bytes"""
+    stage = train_stage(train_from)
+    check_prefix_once(prefix_once, train_from)
+    L = _lib.lib()
+    h = _sizing_handle(embedding_name, max_batch)
+    if h is None:
+        return None
+    try:
+        if prefix_once:
+            _lib.check(L.pvr_trainer_set_prefix_fused(h, 1))
         if wgrad_split16:
             _lib.check(L.pvr_trainer_set_wgrad_split16(h, 1))
         if conv_split16:
@@ -711,20 +781,21 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
 
 
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
-                   conv_split16=False, train_from=None):
+                   conv_split16=False, train_from=None, prefix_once=False):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
         raise NotImplementedError("Requested model not available.")                 # embeddings.py:321
     require_trainable(embedding_name)
     train_stage(train_from)                       # (ValueError names the choices)
+    check_prefix_once(prefix_once, train_from)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
         raise ValueError("train=True computes in fp32 (compute_dtype None or 'f32'), got %r" % (compute_dtype,))
     sd, variant = _load_named_state_dict(embedding_name, pretrained)
     return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16, conv_split16=conv_split16,
-                              **({'train_from': train_from} if train_from is not None else {}))
+                              **({'train_from': train_from} if train_from is not None else {}), **({'prefix_once': True} if prefix_once else {}))
 
 
 class UberModel(nn.Module):
@@ -919,7 +990,8 @@ class EmbeddingNet(nn.Module):
     """
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
-                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None):
+                 compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
+                 prefix_once=False):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -941,6 +1013,11 @@ class EmbeddingNet(nn.Module):
         if train_from is not None and not train:
             raise ValueError('train_from is a mode of the trainable encoder (train=True): a frozen encoder trains nothing')
         train_stage(train_from)                   # (ValueError names the choices)
+        if prefix_once and not train:
+            raise ValueError('prefix_once is a mode of the trainable encoder (train=True, with train_from): a frozen encoder has no training step and '
+                             'no frozen prefix to keep across its passes')
+        check_prefix_once(prefix_once, train_from)
+        # prefix_once (train=True with train_from only): the frozen prefix runs once per frame and step; its boundary tensor is kept across the passes
         # train_from (train=True only): partial fine-tuning - that stage and the ones above train, everything below is the frozen prefix
         # freeze_bn (train=True only): frozen BatchNorm, max_batch is then the chunk of a training forward (HipTrainableResNet)
         # wgrad_split16 (train=True only): the weight gradients as exact-split products on the f16 matrix pipe
@@ -949,7 +1026,8 @@ class EmbeddingNet(nn.Module):
                                                          chunk=chunk, host=self._host, **({'freeze_bn': True} if freeze_bn else {}),
                                                          **({'wgrad_split16': True} if wgrad_split16 else {}),
                                                          **({'conv_split16': True} if conv_split16 else {}),
-                                                         **({'train_from': train_from} if train_from is not None else {}))
+                                                         **({'train_from': train_from} if train_from is not None else {}),
+                                                         **({'prefix_once': True} if prefix_once else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

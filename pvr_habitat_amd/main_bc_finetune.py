@@ -43,12 +43,14 @@ def load_raw(flags, from_env):
     return obs, action, reward, done
 
 
-def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False, conv_split16=False, train_from=None):
+def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False, conv_split16=False, train_from=None, prefix_once=False):
     """the largest frame count <= frames_wanted whose training workspace (with fp32 or split-f16 weight gradients / convolutions, training everything
-    or from train_from's stage up) fits free_bytes (0: not even one frame)"""
+    or from train_from's stage up, in the prefix_once mode or not) fits free_bytes (0: not even one frame)"""
     conv16 = {'conv_split16': True} if conv_split16 else {}
     if train_from is not None:
         conv16['train_from'] = train_from
+    if prefix_once:
+        conv16['prefix_once'] = True
     from .embeddings import trainer_workspace_bytes
     lo, hi = 0, int(frames_wanted)                              # invariant: lo fits (or is 0), hi + 1 does not
     while lo < hi:
@@ -70,11 +72,30 @@ def check_train_from_flag(flags):
     return stage
 
 
+def check_prefix_once_flag(flags):
+    """--embedding_prefix_once keeps the frozen prefix's output across the passes of a step: a ValueError without --embedding_train_from"""
+    on = bool(getattr(flags, 'embedding_prefix_once', False))
+    if on and getattr(flags, 'embedding_train_from', None) is None:
+        raise ValueError('--embedding_prefix_once needs --embedding_train_from: with everything training there is no frozen prefix whose output could be '
+                         'kept across the passes of a step')
+    return on
+
+
+def boundary_cache_bytes(flags, n_frames):
+    """--embedding_prefix_once: bytes of the boundary tensors of a step's n_frames frames, which live next to the workspace (0 without the flag)"""
+    if not getattr(flags, 'embedding_prefix_once', False):
+        return 0
+    from .embeddings import trainer_boundary_bytes
+    return int(n_frames) * trainer_boundary_bytes(flags.embedding_name, flags.embedding_train_from)
+
+
 def workspace_modes(flags):
     """the keywords of trainer_workspace_bytes / largest_fitting_frames behind the weight-gradient mode, from the flags (only what is on)"""
     kw = {'conv_split16': True} if getattr(flags, 'embedding_conv_split16', False) else {}
     if getattr(flags, 'embedding_train_from', None) is not None:  # (a frozen prefix keeps no activations: the workspace shrinks with the stage)
         kw['train_from'] = flags.embedding_train_from
+    if check_prefix_once_flag(flags):             # (with conv_split16 the prefix keeps no pre-BN tensor; the step's boundary cache is counted by the callers)
+        kw['prefix_once'] = True
     return kw
 
 
@@ -91,10 +112,14 @@ def check_workspace_fits(flags, n_frames_per_obs):
     conv16 = workspace_modes(flags)
     need = trainer_workspace_bytes(flags.embedding_name, want, split16, **conv16)
     free = int(torch.cuda.mem_get_info()[0])
+    cache = boundary_cache_bytes(flags, want)     # (--embedding_prefix_once: the step's boundary tensors live next to the workspace)
+    if need is not None:
+        need += cache
     if need is None or need > free:
-        fit = largest_fitting_frames(flags.embedding_name, want, free, split16, **conv16)
+        fit = largest_fitting_frames(flags.embedding_name, want, max(free - cache, 0), split16, **conv16)
         why = 'is more than the trainer\'s launches can address (one tensor of its workspace would pass 2 GiB)' if need is None \
-            else 'takes %.2f GB, %.2f GB of device memory are free' % (need / 2 ** 30, free / 2 ** 30)
+            else 'takes %.2f GB%s, %.2f GB of device memory are free' % (need / 2 ** 30, ' (%.2f GB of them the boundary cache of '
+                                                                        '--embedding_prefix_once)' % (cache / 2 ** 30) if cache else '', free / 2 ** 30)
         raise RuntimeError("--train_embedding: the training workspace of '%s' for unroll_length %d x batch_size %d x %d frames = %d frames %s; "
                            "the largest unroll_length x batch_size x frames that fits is %d (unroll_length <= %d at this batch_size)"
                            % (flags.embedding_name, flags.unroll_length, flags.batch_size, n_frames_per_obs, want, why, fit,
@@ -107,25 +132,32 @@ def check_chunk_fits(flags, want):
     workspace that has to fit.  Without --embedding_chunk the chunk is the largest frame count <= want that the trainer admits and whose workspace
     fits nine tenths of the free device memory (the policy's workspace, the batch, the embeddings and one pass's gradient live next to it).  A given
     chunk is compared with the free memory and the trainer's limit as it is, and the error names the largest chunk that fits.  The resolved chunk
-    is written back to flags.embedding_chunk (a checkpoint's flags carry it); returns the chunk's workspace bytes."""
+    is written back to flags.embedding_chunk (a checkpoint's flags carry it); returns the chunk's workspace bytes.  --embedding_prefix_once: the
+    boundary tensors of ALL `want` frames of a step live next to the chunk's workspace; the default chunk is the largest one that fits the nine tenths
+    together with that cache, `need` includes it and the messages name both sizes."""
     from .embeddings import trainer_workspace_bytes
     free = int(torch.cuda.mem_get_info()[0])
     chunk = getattr(flags, 'embedding_chunk', None)
     split16 = bool(getattr(flags, 'embedding_wgrad_split16', False))
     conv16 = workspace_modes(flags)
+    cache = boundary_cache_bytes(flags, want)
+    with_cache = ' next to the %.2f GB boundary cache of --embedding_prefix_once for %d frames' % (cache / 2 ** 30, want) if cache else ''
     if chunk is None:
-        chunk = largest_fitting_frames(flags.embedding_name, want, free // 10 * 9, split16, **conv16)
+        chunk = largest_fitting_frames(flags.embedding_name, want, max(free // 10 * 9 - cache, 0), split16, **conv16)
         if chunk < 1:
-            raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for a chunk of one frame takes %.2f GB, %.2f GB "
-                               "of device memory are free" % (flags.embedding_name, trainer_workspace_bytes(flags.embedding_name, 1, split16, **conv16) / 2 ** 30, free / 2 ** 30))
+            raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for a chunk of one frame takes %.2f GB%s, %.2f GB "
+                               "of device memory are free" % (flags.embedding_name, trainer_workspace_bytes(flags.embedding_name, 1, split16, **conv16) / 2 ** 30,
+                                                              with_cache, free / 2 ** 30))
     if chunk < 1:
         raise ValueError('--embedding_chunk %d: a pass takes at least one frame' % chunk)
     chunk = min(int(chunk), want)
     need = trainer_workspace_bytes(flags.embedding_name, chunk, split16, **conv16)
+    if need is not None:
+        need += cache
     if need is None or need > free:
-        fit = largest_fitting_frames(flags.embedding_name, chunk, free, split16, **conv16)
+        fit = largest_fitting_frames(flags.embedding_name, chunk, max(free - cache, 0), split16, **conv16)
         why = 'is more than the trainer\'s launches can address (one tensor of its workspace would pass 2 GiB)' if need is None \
-            else 'takes %.2f GB, %.2f GB of device memory are free' % (need / 2 ** 30, free / 2 ** 30)
+            else 'takes %.2f GB%s, %.2f GB of device memory are free' % ((need - cache) / 2 ** 30, with_cache, free / 2 ** 30)
         raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for --embedding_chunk %d frames %s; the largest "
                            "--embedding_chunk that fits is %d" % (flags.embedding_name, chunk, why, fit))
     flags.embedding_chunk = chunk
@@ -144,6 +176,9 @@ def run_end_to_end(flags, make_env=None):
     train_from = check_train_from_flag(flags)
     if train_from is not None:                                  # the run's first line names the stage
         print('=== Training the embedding from %s up: conv1 / bn1 and the stages below are frozen ===' % train_from)
+    prefix_once = check_prefix_once_flag(flags)
+    if prefix_once:
+        print('  ', 'prefix once: the frozen prefix runs once per frame and step (--embedding_prefix_once)')
     world = max(rank_world()[1], int(os.environ.get('WORLD_SIZE', '1')))
     if world > 1:
         raise NotImplementedError('--train_embedding with a world size of %d: data-parallel encoder training is not built (the trainable encoder and its '
@@ -194,6 +229,8 @@ def run_end_to_end(flags, make_env=None):
         print('  ', 'forward convolutions and data gradients: exact-split products on the f16 matrix pipe')
     if train_from is not None:
         split16 = dict(split16, train_from=train_from)
+    if prefix_once:                                             # (the bits are the same with and without it: a resume may change the flag)
+        split16 = dict(split16, prefix_once=True)
     if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
         if not flags.pretrained_embedding:
             print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')
@@ -283,6 +320,7 @@ def run_end_to_end(flags, make_env=None):
 
 def run(flags, make_env=None):
     check_train_from_flag(flags)
+    check_prefix_once_flag(flags)
     if getattr(flags, 'train_embedding', False):
         return run_end_to_end(flags, make_env)
     rank, world = rank_world()

@@ -809,7 +809,10 @@ class HipJointRMSprop(object):
             g = self._grads
             pol._checked(L.pvr_policy_backward_dobs(pol._handle, vp(pol._flat), C.byref(bn) if bn else None, vp(emb), vp(d), vp(a), T, B,
                                                     vp(g['policy']), vp(stats), None, vp(dobs), _lib.stream_ptr()))
-            enc._backward_raw(frames, dobs, g['embedding'])                   # one pvr_trainer_backward, or the chunk walk of a frozen-BatchNorm encoder
+            boundary, enc._boundary = getattr(enc, '_boundary', None), None  # (prefix_once: the step's boundary cache, released when the step is done)
+            # one pvr_trainer_backward, or the chunk walk of a frozen-BatchNorm encoder (prefix_once: its recompute passes start at the first trained op)
+            enc._backward_raw(frames, dobs, g['embedding'], *(() if boundary is None else (boundary,)))
+            del boundary
             arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
             counts = (C.c_int64 * 2)(pol._n_train, enc._flat.numel())
             _lib.check(L.pvr_joint_apply_rmsprop(2, arr((pol._flat, enc._flat)), arr((self.square_avg['policy'], self.square_avg['embedding'])),
