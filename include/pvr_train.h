@@ -154,6 +154,32 @@ pvr_status pvr_trainer_forward_boundary(pvr_trainer *tr, const float *params_dev
  * size of the current mode. */
 pvr_status pvr_trainer_set_prefix_fused(pvr_trainer *tr, int32_t on);
 
+/* The frozen prefix once per DATASET frame (the Python mode prefix_cache).  The prefix is frozen, runs on running statistics in either BatchNorm mode
+ * and reads a frame behind a deterministic resize and centre crop: the boundary tensor of a frame is the same bits in every step.  A caller that holds
+ * the dataset on the device computes every frame's boundary tensor once, before training (pvr_trainer_prefix_forward in blocks of <= max_batch frames
+ * into one (N, boundary_floats) tensor of its own), and a training pass is then pvr_op_gather_rows of the pass's rows into a staging buffer followed by
+ * pvr_trainer_forward_boundary(reuse != 0) on it.  The cache is the caller's and so is the rule of its validity: it holds what the prefix's
+ * parameters and BatchNorm buffers gave when it was filled; the handle keeps no state about it.
+ * pvr_trainer_prefix_forward: preprocess, normalize, conv1, bn1, the max pool and the prefix ops of n frames and nothing else - the launches
+ *   pvr_trainer_forward_boundary(reuse == 0) runs before its first trained op (after pvr_trainer_set_prefix_fused the fused split launches), so the
+ *   same bits; the launch that produces the boundary tensor writes it straight to boundary_dev (n x pvr_trainer_boundary_floats floats).  No trained op
+ *   runs and no forward is held: a held forward is dropped (the call overwrites the stem's workspace) and a following pvr_trainer_backward is
+ *   PVR_ERR_STATE.  pvr_trainer_launch_time lists exactly these launches.  Legal in both BatchNorm modes and with either split mode; the running
+ *   statistics are read and never written.  Refused by name, launching nothing: stage 0 (PVR_ERR_STATE: there is no prefix), a null argument, a
+ *   boundary_dev that is not 16-byte aligned, n outside 1 .. max_batch. */
+pvr_status pvr_trainer_prefix_forward(pvr_trainer *tr, const float *params_dev, const void *bn_buffers_dev, const uint8_t *frames_dev, int32_t n, int32_t h,
+                                      int32_t w, float *boundary_dev, void *hip_stream);
+/* dst[i, :] = src[rows[i], :] for i < n: src (n_src_rows, row_floats) and dst (n, row_floats) fp32, rows n int64 indices on the device; all three in
+ * device memory.  The gather of a cached pass, and the one new launch on its hot path: 16-byte lanes (row_floats % 4 == 0, both pointers 16-byte
+ * aligned), a long row split over several workgroups (pieces of at most 16 KiB walked by a bounded grid, so that 2 rows of 3.2 MB and 334 rows of
+ * 0.2 MB both fill the device).  Source offsets are 64-bit throughout: the source may pass 2 GiB, 4 GiB and 2^31 floats.  An index outside
+ * [0, n_src_rows) is never dereferenced: its destination row is filled with quiet NaNs (0x7fc00000), so that a wrong index shows in the loss and cannot
+ * fault.  Repeated indices are legal.  Plain vector loads and stores, no atomics: two runs give the same bits.  Refused by name, launching nothing: a
+ * null argument, n < 1, n_src_rows < 1, row_floats < 4 or not a multiple of 4, a src_dev or dst_dev that is not 16-byte aligned or a rows_dev that is
+ * not 8-byte aligned. */
+pvr_status pvr_op_gather_rows(const float *src_dev, int64_t n_src_rows, int64_t row_floats, const int64_t *rows_dev, int64_t n, float *dst_dev,
+                              void *hip_stream);
+
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
  * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */

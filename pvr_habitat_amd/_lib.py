@@ -128,6 +128,8 @@ _SIGS = {
     'pvr_trainer_forward_boundary': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                                C.c_int64, C.c_void_p]),
     'pvr_trainer_set_prefix_fused': (C.c_int, [C.c_void_p, C.c_int32]),
+    'pvr_trainer_prefix_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'pvr_op_gather_rows': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     'pvr_op_conv_bn_frozen_forward_split16_scratch_floats': (C.c_int64, [C.c_int32] * 8),
     'pvr_op_conv_bn_frozen_forward_split16': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_conv_fwd_split16_scratch_floats':(C.c_int64, [C.c_int32] * 8),

@@ -55,6 +55,12 @@ def make_parser():
                              'for the unroll_length x batch_size x frames frames of a step (0.2 .. 3.2 MB per frame, counted next to the workspace) and '
                              'the recompute passes of a --freeze_embedding_bn step start at the first trained stage; with --embedding_conv_split16 a '
                              'prefix convolution and its BatchNorm are one launch.  The bits do not change: a run may be resumed with or without it')
+    parser.add_argument('--embedding_prefix_cache', action='store_true',
+                        help='with --embedding_train_from: the frozen prefix runs once per DATASET frame - before training the boundary tensor of every '
+                             'frame of the scene is computed into one device tensor (samples x frames x 0.2 .. 3.2 MB, counted with a pass\'s staging '
+                             'tensor next to the workspace; a cache that does not fit is refused with both sizes), and every pass of a step gathers '
+                             'its frames\' rows and starts at the first trained stage.  Replaces the step-sized cache of --embedding_prefix_once.  The '
+                             'bits do not change: a run may be resumed with or without it (the cache is rebuilt)')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

@@ -39,6 +39,19 @@ class DeviceDataset(object):
         self.row_bytes = int(self.obs[0].numel() * self.obs.element_size())
         assert self.row_bytes % 16 == 0, 'observation rows must be a multiple of 16 bytes (got %d)' % self.row_bytes
 
+    def rows(self, starting_i, unroll_length):
+        """(T, B) int64 sample indices on the dataset's device: row (t, b) = (starting_i[b] + t) mod n - the index arithmetic of gather without the
+        rows themselves (a prefix-cached step reads its frames' boundary tensors by index).  The start indices are validated on the host."""
+        T = int(unroll_length)
+        starts = [int(i) for i in starting_i]
+        if T < 1 or not starts:
+            raise ValueError('DeviceDataset.rows: unroll_length %d and %d start indices (at least one of each)' % (T, len(starts)))
+        for i in starts:
+            if not 0 <= i < self.n:
+                raise IndexError('DeviceDataset.rows: start index %d outside the dataset\'s [0, %d)' % (i, self.n))
+        idx = (torch.tensor(starts, dtype=torch.int64)[None, :] + torch.arange(T, dtype=torch.int64)[:, None]) % self.n
+        return idx.to(self.obs.device)
+
     def gather(self, starting_i, unroll_length):
         """(T, B, ...) observations, (T, B) int64 actions, (T, B) bool dones for the start indices of
         sample_with_minimum_distance: row (t, b) = dataset row (starting_i[b] + t) mod n  (main_bc_2.py:194-201)."""

@@ -420,9 +420,10 @@ namespace {
 
 // pvr_trainer_forward (boundary == nullptr) and pvr_trainer_forward_boundary: the arguments have passed the callers' checks.  boundary: where this pass's
 // boundary tensor lives instead of the arena's piece - the producing launch writes it there and every reader goes through tensor_of.  reuse: it holds the
-// tensor already, and the pass starts at the first trained op.
+// tensor already, and the pass starts at the first trained op.  prefix_only (pvr_trainer_prefix_forward): the pass ends behind the last prefix op - the
+// same launches up to there, nothing written but the boundary tensor and the prefix's own buffers, and no forward is held.
 pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *boundary, bool reuse,
-                        float *out, int64_t out_stride, void *stream) {
+                        float *out, int64_t out_stride, void *stream, bool prefix_only = false) {
     hipStream_t st = (hipStream_t)stream;
     pvr_status s;
     if ((s = ensure_workspace(t))) return s;
@@ -458,7 +459,8 @@ pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, c
     float *w_scale = t->conv_split16 ? t->scales + t->ops.size() + 7 : nullptr;
     uint32_t *scale_aux = t->conv_split16 ? (uint32_t *)(t->scales + t->ops.size() + 3) : nullptr;
     const bool fused = t->fused_prefix();
-    for (int i = reuse ? P : 0; i < (int)t->ops.size(); ++i) {
+    const int end = prefix_only ? P : (int)t->ops.size();
+    for (int i = reuse ? P : 0; i < end; ++i) {
         TrainOp &op = t->ops[i];
         const int64_t rows = (int64_t)n * op.ho * op.wo;
         float *y = tensor_of(t, i);               // (op.y, or the caller's memory when this op writes the boundary tensor)
@@ -493,6 +495,10 @@ pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, c
         TR_RUN(op.conv, 2.0 * rows * op.cout * op.cin * op.k * op.k,
                launch_conv_f32(tensor_of(t, op.in_src), t->wpack, t->zero_bias, nullptr, op.z, n, op.h, op.w, op.cin, op.cout, op.k, op.stride, op.pad, 0, st));
         TR_RUN(op.bn, 0, bn(op, op.res_src == -2 ? nullptr : tensor_of(t, op.res_src), rows, i < P));
+    }
+    if (prefix_only) {                            // nothing of a forward is held: the caller's memory is not remembered either
+        t->ext_boundary = nullptr;
+        return collect_times(t, 0, st);
     }
     TR_RUN("avgpool", 0, launch_avgpool(t->ops.back().y, out, out_stride, n, t->final_hw, t->final_c, 1, PVR_F32, st));
     t->fwd_n = n;
@@ -540,6 +546,24 @@ pvr_status pvr_trainer_forward_boundary(pvr_trainer *t, const float *params, voi
                 "frames)");
     TraceScope ts("pvr_trainer_forward_boundary");
     return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, reuse != 0, out, out_stride, stream);
+}
+
+pvr_status pvr_trainer_prefix_forward(pvr_trainer *t, const float *params, const void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,
+                                      float *boundary, void *stream) {
+    PVR_REQUIRE(t && params && bn_buffers && frames && boundary, "pvr_trainer_prefix_forward: null argument (boundary_dev takes n x "
+                "pvr_trainer_boundary_floats floats of device memory)");
+    if (t->train_from <= 0) {
+        set_error("pvr_trainer_prefix_forward: everything trains (pvr_trainer_set_train_from stage 0): there is no frozen prefix and no boundary tensor to "
+                  "compute ahead of a step");
+        return PVR_ERR_STATE;
+    }
+    PVR_REQUIRE(((uintptr_t)boundary & 15) == 0, "pvr_trainer_prefix_forward: boundary_dev %p is not 16-byte aligned (the launches move it as float4s)",
+                (void *)boundary);
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_prefix_forward: %d frames, the workspace holds max_batch = %d (fill a cache in blocks of at most "
+                "max_batch frames, each into its own rows)", n, t->desc.max_batch);
+    TraceScope ts("pvr_trainer_prefix_forward");
+    // (the prefix reads the BatchNorm buffers only: every BatchNorm of a prefix pass is the frozen-apply launch, whatever the handle's mode)
+    return forward_pass(t, params, const_cast<void *>(bn_buffers), frames, n, h, w, boundary, false, nullptr, 0, stream, true);
 }
 
 }  // extern "C"

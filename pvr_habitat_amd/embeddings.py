@@ -14,6 +14,8 @@ box without a GPU raises instead of silently computing something else.
 """
 import ctypes as C
 import os
+import time
+import weakref
 import zlib
 
 import numpy as np
@@ -408,6 +410,56 @@ class _EncoderFunction(torch.autograd.Function):
         return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._trained_slots)
 
 
+class _CachedEncoderFunction(torch.autograd.Function):
+    """_EncoderFunction on rows of a PrefixCache instead of uint8 frames (HipTrainableResNet.forward_cached): the node keeps the cache and the int64
+    rows (tiny), the backward gathers every recomputed pass's rows again.  Inputs: the module, the cache, the rows, then the trained parameters only."""
+
+    @staticmethod
+    def forward(ctx, model, cache, rows, *params):
+        out = model._forward_raw_cached(cache, rows)
+        model._fwd_gen += 1
+        ctx.model, ctx.gen, ctx.cache, ctx.rows = model, model._fwd_gen, cache, rows
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        m = ctx.model
+        if ctx.gen != m._fwd_gen:
+            raise RuntimeError('trainable encoder backward: the activations of this forward are gone - a later training-mode forward of the same '
+                               'encoder overwrote them (one backward per forward, right after it)')
+        dout = dout.contiguous().float()
+        g = torch.empty_like(m._flat)
+        m._backward_raw_cached(ctx.cache, ctx.rows, dout, g)
+        ctx.cache = ctx.rows = None
+        return (None, None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._trained_slots)
+
+
+class PrefixCache(object):
+    """The boundary tensor of every frame of a dataset (HipTrainableResNet.build_prefix_cache): `data` is ONE (n_frames, boundary_floats) fp32 device
+    tensor, row i what the frozen prefix gives for frame i.  It belongs to the encoder that built it, at that encoder's train_from stage, and is valid as
+    long as that encoder's prefix has not been written: it records the encoder's prefix generation at build time (load_state_dict and
+    invalidate_prefix_cache bump it) and a stale cache is refused, never used.  The trained parameters moving invalidates nothing."""
+
+    def __init__(self, data, encoder, fill_seconds=0.0):
+        self.data = data
+        self.train_from = encoder.train_from
+        self.generation = encoder._prefix_gen
+        self.fill_seconds = float(fill_seconds)
+        self._encoder = weakref.ref(encoder)
+
+    @property
+    def encoder(self):
+        return self._encoder()
+
+    @property
+    def n_frames(self):
+        return int(self.data.shape[0])
+
+    @property
+    def nbytes(self):
+        return int(self.data.numel()) * 4
+
+
 class HipTrainableResNet(_Node):
     """One trainable encoder (reference src/embeddings.py:323-326, :396-398): resnet18 / resnet34 / resnet50 in fp32 on the library's pvr_trainer
     (include/pvr_train.h).  Parameters are nn.Parameter CUDA views of ONE flat fp32 buffer the library reads on every forward, so any torch
@@ -447,10 +499,18 @@ class HipTrainableResNet(_Node):
     recompute passes of a chunked backward start at the first trained op on theirs instead of running preprocess, the stem and the prefix again.  The
     tensor lives as long as the kept uint8 frames do and is released after the backward.  With conv_split16 a prefix op is also one launch instead of
     three (pvr_trainer_set_prefix_fused), and the workspace holds no pre-BN tensor of the prefix.  Embeddings and gradients keep their bits.  Chosen at
-    construction; legal in both BatchNorm modes (with batch statistics a step is one pass and only the fused launches matter) and with either split mode."""
+    construction; legal in both BatchNorm modes (with batch statistics a step is one pass and only the fused launches matter) and with either split mode.
+
+    prefix_cache (needs train_from): the frozen prefix runs once per DATASET frame.  build_prefix_cache(frames) computes the boundary tensor of every
+    frame once, before training, into a PrefixCache (pvr_trainer_prefix_forward in blocks of max_batch); forward_cached(cache, rows) is then the
+    training forward of the frames behind those cache rows: every pass gathers its rows into ONE staging tensor of max_batch x boundary_floats
+    (pvr_op_gather_rows) and starts at the first trained op (pvr_trainer_forward_boundary with reuse), in the forward and in the recompute passes of
+    the backward.  No uint8 frame is touched.  The keyword only selects the workspace mode (the fused prefix launches of prefix_once, so that the
+    cache's bits are that mode's); together with prefix_once it means prefix_cache and no step-sized boundary tensor is allocated.  Embeddings and
+    gradients keep the bits of a step on the frames themselves, with prefix_once and with neither mode."""
 
     def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False):
+                 prefix_once=False, prefix_cache=False):
         super().__init__()
         assert variant in _TRAINABLE, variant
         _lib.require_gpu()
@@ -481,10 +541,14 @@ class HipTrainableResNet(_Node):
             _lib.check(L.pvr_trainer_set_train_from(h, train_stage(train_from)))
             self._train_from = train_from
         check_prefix_once(prefix_once, train_from)
-        self._prefix_once = bool(prefix_once)
+        check_prefix_cache(prefix_cache, train_from)
+        self._prefix_cache = bool(prefix_cache)
+        self._prefix_gen = 0                     # bumped by every write path to the frozen prefix: a PrefixCache of an older generation is refused
+        self._staging = None                     # prefix_cache: the (max_batch, boundary_floats) tensor a cached pass gathers its rows into, made once
+        self._prefix_once = bool(prefix_once) and not self._prefix_cache      # (both: prefix_cache - no step-sized boundary tensor)
         self._boundary = None                    # prefix_once: the boundary cache between _forward_raw and its consumer (the autograd node or the joint step)
         self._boundary_floats = int(L.pvr_trainer_boundary_floats(h))
-        if self._prefix_once:
+        if self._prefix_once or self._prefix_cache:
             _lib.check(L.pvr_trainer_set_prefix_fused(h, 1))
         self._trained_offset = int(L.pvr_trainer_trained_offset(h))     # floats of the flat buffer below it are the frozen prefix (one leading span)
         dev = torch.device('cuda')
@@ -547,7 +611,17 @@ class HipTrainableResNet(_Node):
 
     def load_state_dict(self, *a, **k):
         self.close()
+        self.invalidate_prefix_cache()
         return super().load_state_dict(*a, **k)
+
+    def _load_from_state_dict(self, *a, **k):
+        self.invalidate_prefix_cache()            # (a parent module's load_state_dict comes through here, not through load_state_dict above)
+        return super()._load_from_state_dict(*a, **k)
+
+    def invalidate_prefix_cache(self):
+        """a parameter or buffer of the frozen prefix may have moved: every PrefixCache built before this call is refused from now on.  load_state_dict
+        calls it; so must whoever writes a prefix tensor in place"""
+        self._prefix_gen += 1
 
     @property
     def max_batch(self):
@@ -576,6 +650,75 @@ class HipTrainableResNet(_Node):
     def boundary_bytes(self):
         """bytes per frame of the boundary tensor prefix_once keeps (0 when everything trains)"""
         return 4 * self._boundary_floats
+
+    @property
+    def prefix_cache(self):
+        """the workspace was made for cached steps (see the class docstring)"""
+        return self._prefix_cache
+
+    def build_prefix_cache(self, frames_u8):
+        """(N, H, W, 3) uint8 device frames -> a PrefixCache of their N boundary tensors, filled in blocks of max_batch by pvr_trainer_prefix_forward.
+        Always switches the fused prefix launches on (prefix_once's workspace mode): call it before the first training forward, or on an encoder
+        constructed with prefix_cache=True or prefix_once=True - once the workspace exists without that mode the library refuses with a state error.
+        A training forward still waiting for its backward loses its activations."""
+        if self._train_from is None:
+            raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
+        return self._build_prefix_cache(int(frames_u8.shape[0]), [(0, frames_u8)])
+
+    def _build_prefix_cache(self, n_frames, blocks):
+        """build_prefix_cache from an iterable of (first cache row, (k, H, W, 3) uint8 device frames) blocks that cover [0, n_frames): a caller whose
+        frames are not laid out as one (N, H, W, 3) tensor (PolicyNetWithEncoder: F frames side by side per sample) splits block by block"""
+        if self._train_from is None:
+            raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
+        L = _lib.lib()
+        _lib.check(L.pvr_trainer_set_prefix_fused(self._handle, 1))
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        data = torch.empty((n_frames, self._boundary_floats), dtype=torch.float32, device=self._flat.device)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        self._fwd_gen += 1                        # (the stem's workspace is overwritten: a held forward is gone)
+        filled = 0
+        for row0, frames_u8 in blocks:
+            n, h, w, c = frames_u8.shape
+            assert c == 3 and frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and frames_u8.is_contiguous() and row0 == filled and row0 + n <= n_frames
+            for lo in range(0, n, self._max_batch):
+                hi = min(lo + self._max_batch, n)
+                _lib.check(L.pvr_trainer_prefix_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8[lo:hi]), hi - lo, h, w,
+                                                        vp(data[row0 + lo:row0 + hi]), _lib.stream_ptr()))
+            filled += n
+        assert filled == n_frames, (filled, n_frames)
+        torch.cuda.synchronize()
+        return PrefixCache(data, self, time.perf_counter() - t0)
+
+    def check_prefix_cache(self, cache):
+        """raise unless `cache` is a PrefixCache this encoder may use now: of this stage, of this encoder, of the current prefix generation"""
+        if not isinstance(cache, PrefixCache):
+            raise TypeError('forward_cached takes a PrefixCache (build_prefix_cache), got %s' % type(cache).__name__)
+        if cache.train_from != self._train_from:
+            raise RuntimeError('prefix cache of another stage: it holds the boundary tensors of train_from %r, this encoder trains from %r'
+                               % (cache.train_from, self._train_from))
+        if cache.encoder is not self or cache.data.shape[1] != self._boundary_floats:
+            raise RuntimeError('prefix cache of another encoder: a cache holds what the frozen prefix of the encoder that built it computes; build one '
+                               'with this encoder\'s build_prefix_cache')
+        if cache.generation != self._prefix_gen:
+            raise RuntimeError('stale prefix cache: the encoder\'s frozen prefix may have been written since the cache was built (load_state_dict or '
+                               'invalidate_prefix_cache; generation %d, the cache has %d): rebuild it with build_prefix_cache'
+                               % (self._prefix_gen, cache.generation))
+
+    def forward_cached(self, cache, rows):
+        """training-mode forward of the frames behind `rows` (int64 device tensor, one row of `cache` per frame): embeddings with a graph that hands
+        only the trained parameters to autograd.  The bits of forward(frames[rows])."""
+        self.check_prefix_cache(cache)
+        if not self.training:
+            raise RuntimeError('forward_cached is a training-mode forward (the cache holds the input of the trained stages): in eval mode embed the '
+                               'frames themselves')
+        self.close()
+        return _CachedEncoderFunction.apply(self, cache, self._cache_rows(cache, rows), *self._trained_plist)
+
+    def _cache_rows(self, cache, rows):
+        if not (isinstance(rows, torch.Tensor) and rows.dtype == torch.int64 and rows.device == cache.data.device):
+            raise TypeError('forward_cached: rows is an int64 tensor on the cache\'s device, one cache row per frame')
+        return rows.reshape(-1).contiguous()
 
     @property
     def trained_offset(self):
@@ -662,8 +805,9 @@ class HipTrainableResNet(_Node):
             _lib.check(_lib.lib().pvr_trainer_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8[lo:hi]), hi - lo, frames_u8.shape[1],
                                                       frames_u8.shape[2], vp(out), out.stride(0), _lib.stream_ptr()))
             return
+        h, w = (0, 0) if frames_u8 is None else frames_u8.shape[1:3]     # (a reuse pass reads no frames: forward_cached has none)
         _lib.check(_lib.lib().pvr_trainer_forward_boundary(self._handle, vp(self._flat), vp(self._bufs), None if reuse else vp(frames_u8[lo:hi]), hi - lo,
-                                                           frames_u8.shape[1], frames_u8.shape[2], vp(boundary[lo:hi]), 1 if reuse else 0, vp(out),
+                                                           h, w, vp(boundary[lo:hi]), 1 if reuse else 0, vp(out),
                                                            out.stride(0), _lib.stream_ptr()))
 
     def _backward_raw(self, frames_u8, dout, grads, boundary=None):
@@ -689,6 +833,49 @@ class HipTrainableResNet(_Node):
             _lib.check(L.pvr_trainer_backward_acc(self._handle, vp(self._flat), vp(dout[lo:hi]), dout.stride(0), vp(grads), 1 if i else 0, vp(sc), sc.numel(),
                                                   _lib.stream_ptr()))
 
+    def _gather_pass(self, cache, rows, lo, hi):
+        """rows[lo:hi] of the cache -> the first hi - lo rows of the staging tensor (made once: max_batch x boundary_floats)"""
+        if self._staging is None:
+            self._staging = torch.empty((self._max_batch, self._boundary_floats), dtype=torch.float32, device=cache.data.device)
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        _lib.check(_lib.lib().pvr_op_gather_rows(vp(cache.data), cache.data.shape[0], self._boundary_floats, vp(rows[lo:hi]), hi - lo, vp(self._staging),
+                                                 _lib.stream_ptr()))
+        return self._staging
+
+    def _forward_raw_cached(self, cache, rows):
+        """_forward_raw on cache rows: per pass one gather into the staging tensor, then the pass from the first trained op on"""
+        self.check_prefix_cache(cache)
+        n = int(rows.numel())
+        assert n >= 1 and rows.dim() == 1 and rows.dtype == torch.int64 and rows.is_contiguous()
+        if n > self._max_batch and not self._freeze_bn:
+            raise ValueError('training forward of %d frames: the workspace was made for max_batch = %d (BatchNorm takes the whole batch together, '
+                             'it cannot be chunked)' % (n, self._max_batch))
+        out = torch.empty((n, self.out_size), dtype=torch.float32, device=rows.device)
+        for lo, hi in self._passes(n):            # (the staging tensor keeps the last pass's rows: its activations stay held for the backward)
+            self._forward_pass(None, 0, hi - lo, out[lo:hi], self._gather_pass(cache, rows, lo, hi), reuse=True)
+        return out
+
+    def _backward_raw_cached(self, cache, rows, dout, grads):
+        """_backward_raw on cache rows: the last pass first - the staging tensor still holds its rows - then every other pass in frame order, each
+        gathered again, recomputed from the first trained op and added by pvr_trainer_backward_acc"""
+        self.check_prefix_cache(cache)
+        L = _lib.lib()
+        vp = lambda t: C.c_void_p(t.data_ptr())
+        passes = self._passes(int(rows.numel()))
+        assert dout.shape[0] == rows.numel() and dout.stride(1) == 1
+        if len(passes) == 1:
+            _lib.check(L.pvr_trainer_backward(self._handle, vp(self._flat), vp(dout), dout.stride(0), vp(grads), _lib.stream_ptr()))
+            return
+        if self._acc_scratch is None:
+            self._acc_scratch = torch.empty_like(self._flat)
+        sc = self._acc_scratch
+        again = torch.empty((self._max_batch, self.out_size), dtype=torch.float32, device=dout.device)       # the recomputed embeddings are not used
+        for i, (lo, hi) in enumerate(passes[-1:] + passes[:-1]):
+            if i:
+                self._forward_pass(None, 0, hi - lo, again[:hi - lo], self._gather_pass(cache, rows, lo, hi), reuse=True)
+            _lib.check(L.pvr_trainer_backward_acc(self._handle, vp(self._flat), vp(dout[lo:hi]), dout.stride(0), vp(grads), 1 if i else 0, vp(sc), sc.numel(),
+                                                  _lib.stream_ptr()))
+
     def forward(self, frames_u8):
         if self.training:
             self.close()
@@ -705,6 +892,13 @@ def check_prefix_once(prefix_once, train_from):
     if prefix_once and train_from is None:
         raise ValueError('prefix_once needs train_from: with everything training there is no frozen prefix to keep (its one output is what the mode '
                          'caches across the passes of a step)')
+
+
+def check_prefix_cache(prefix_cache, train_from):
+    """prefix_cache computes the frozen prefix's boundary tensor once per dataset frame: a ValueError where nothing is frozen"""
+    if prefix_cache and train_from is None:
+        raise ValueError('prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached for the '
+                         'dataset\'s frames')
 
 
 def train_stage(train_from):
@@ -755,6 +949,13 @@ def trainer_boundary_bytes(embedding_name, train_from):
         L.pvr_trainer_destroy(h)
 
 
+def trainer_prefix_cache_bytes(embedding_name, train_from, n_frames):
+    """bytes of the PrefixCache of n_frames dataset frames: n_frames x trainer_boundary_bytes (host arithmetic, no GPU needed).  The staging tensor of a
+    cached pass (max_batch x trainer_boundary_bytes) lives next to it"""
+    check_prefix_cache(True, train_from)
+    return int(n_frames) * trainer_boundary_bytes(embedding_name, train_from)
+
+
 def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv_split16=False, train_from=None, prefix_once=False):
     """bytes of device memory the training workspace of `embedding_name` takes for max_batch frames (pvr_trainer_workspace_bytes on a handle made
     for the question: host arithmetic, no GPU needed), with fp32 or split-f16 weight gradients and convolutions, training everything or from train_from's stage up; None when the trainer refuses that max_batch (a
@@ -781,7 +982,7 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
 
 
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
-                   conv_split16=False, train_from=None, prefix_once=False):
+                   conv_split16=False, train_from=None, prefix_once=False, prefix_cache=False):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -789,13 +990,15 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     require_trainable(embedding_name)
     train_stage(train_from)                       # (ValueError names the choices)
     check_prefix_once(prefix_once, train_from)
+    check_prefix_cache(prefix_cache, train_from)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
         raise ValueError("train=True computes in fp32 (compute_dtype None or 'f32'), got %r" % (compute_dtype,))
     sd, variant = _load_named_state_dict(embedding_name, pretrained)
     return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16, conv_split16=conv_split16,
-                              **({'train_from': train_from} if train_from is not None else {}), **({'prefix_once': True} if prefix_once else {}))
+                              **({'train_from': train_from} if train_from is not None else {}), **({'prefix_once': True} if prefix_once else {}),
+                              **({'prefix_cache': True} if prefix_cache else {}))
 
 
 class UberModel(nn.Module):
@@ -991,7 +1194,7 @@ class EmbeddingNet(nn.Module):
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
                  compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False):
+                 prefix_once=False, prefix_cache=False):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -1017,6 +1220,11 @@ class EmbeddingNet(nn.Module):
             raise ValueError('prefix_once is a mode of the trainable encoder (train=True, with train_from): a frozen encoder has no training step and '
                              'no frozen prefix to keep across its passes')
         check_prefix_once(prefix_once, train_from)
+        if prefix_cache and not train:
+            raise ValueError('prefix_cache is a mode of the trainable encoder (train=True, with train_from): a frozen encoder has no training step and '
+                             'no frozen prefix whose output could be cached')
+        check_prefix_cache(prefix_cache, train_from)
+        # prefix_cache (train=True with train_from only): the workspace mode of cached steps (build_prefix_cache / forward_cached of the encoder)
         # prefix_once (train=True with train_from only): the frozen prefix runs once per frame and step; its boundary tensor is kept across the passes
         # train_from (train=True only): partial fine-tuning - that stage and the ones above train, everything below is the frozen prefix
         # freeze_bn (train=True only): frozen BatchNorm, max_batch is then the chunk of a training forward (HipTrainableResNet)
@@ -1027,7 +1235,8 @@ class EmbeddingNet(nn.Module):
                                                          **({'wgrad_split16': True} if wgrad_split16 else {}),
                                                          **({'conv_split16': True} if conv_split16 else {}),
                                                          **({'train_from': train_from} if train_from is not None else {}),
-                                                         **({'prefix_once': True} if prefix_once else {}))
+                                                         **({'prefix_once': True} if prefix_once else {}),
+                                                         **({'prefix_cache': True} if prefix_cache else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

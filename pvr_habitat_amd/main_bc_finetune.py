@@ -43,9 +43,11 @@ def load_raw(flags, from_env):
     return obs, action, reward, done
 
 
-def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False, conv_split16=False, train_from=None, prefix_once=False):
+def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_split16=False, conv_split16=False, train_from=None, prefix_once=False,
+                           extra_per_frame=0):
     """the largest frame count <= frames_wanted whose training workspace (with fp32 or split-f16 weight gradients / convolutions, training everything
-    or from train_from's stage up, in the prefix_once mode or not) fits free_bytes (0: not even one frame)"""
+    or from train_from's stage up, in the prefix_once mode or not) fits free_bytes (0: not even one frame).  extra_per_frame: bytes per frame that live
+    next to the workspace and grow with it (--embedding_prefix_cache: the staging tensor of a pass)"""
     conv16 = {'conv_split16': True} if conv_split16 else {}
     if train_from is not None:
         conv16['train_from'] = train_from
@@ -56,7 +58,7 @@ def largest_fitting_frames(embedding_name, frames_wanted, free_bytes, wgrad_spli
     while lo < hi:
         mid = (lo + hi + 1) // 2
         need = trainer_workspace_bytes(embedding_name, mid, wgrad_split16, **conv16)     # (None: more frames than the trainer's launches can address)
-        if need is not None and need <= free_bytes:
+        if need is not None and need + mid * extra_per_frame <= free_bytes:
             lo = mid
         else:
             hi = mid - 1
@@ -81,9 +83,38 @@ def check_prefix_once_flag(flags):
     return on
 
 
+def check_prefix_cache_flag(flags):
+    """--embedding_prefix_cache computes the frozen prefix's output once per dataset frame: a ValueError without --embedding_train_from"""
+    on = bool(getattr(flags, 'embedding_prefix_cache', False))
+    if on and getattr(flags, 'embedding_train_from', None) is None:
+        raise ValueError('--embedding_prefix_cache needs --embedding_train_from: with everything training there is no frozen prefix whose output could be '
+                         'computed once per dataset frame')
+    return on
+
+
+def prefix_cache_bytes(flags, n_dataset_frames):
+    """--embedding_prefix_cache: (bytes of the boundary tensors of all n_dataset_frames = samples x frames dataset frames, bytes per frame of a pass's
+    staging tensor), both next to the workspace; (0, 0) without the flag"""
+    if not getattr(flags, 'embedding_prefix_cache', False):
+        return 0, 0
+    from .embeddings import trainer_prefix_cache_bytes, trainer_boundary_bytes
+    return (trainer_prefix_cache_bytes(flags.embedding_name, flags.embedding_train_from, n_dataset_frames),
+            trainer_boundary_bytes(flags.embedding_name, flags.embedding_train_from))
+
+
+def prefix_cache_does_not_fit(flags, n_dataset_frames, cache, staging, workspace, free):
+    """the RuntimeError of a prefix cache that does not fit next to the workspace: both sizes, the free memory and the alternatives"""
+    return RuntimeError("--embedding_prefix_cache: the prefix cache of '%s' from %s for %d dataset frames takes %.2f GB, next to it live a pass's "
+                        "staging tensor of %.2f GB and the training workspace of %.2f GB; %.2f GB of device memory are free.  Train from a higher "
+                        "stage (its boundary tensor is smaller), or use --embedding_prefix_once, which keeps the boundary tensors of one step only"
+                        % (flags.embedding_name, flags.embedding_train_from, n_dataset_frames, cache / 2 ** 30, staging / 2 ** 30,
+                           workspace / 2 ** 30, free / 2 ** 30))
+
+
 def boundary_cache_bytes(flags, n_frames):
-    """--embedding_prefix_once: bytes of the boundary tensors of a step's n_frames frames, which live next to the workspace (0 without the flag)"""
-    if not getattr(flags, 'embedding_prefix_once', False):
+    """--embedding_prefix_once: bytes of the boundary tensors of a step's n_frames frames, which live next to the workspace (0 without the flag, and
+    with --embedding_prefix_cache, which replaces the step-sized cache)"""
+    if not getattr(flags, 'embedding_prefix_once', False) or getattr(flags, 'embedding_prefix_cache', False):
         return 0
     from .embeddings import trainer_boundary_bytes
     return int(n_frames) * trainer_boundary_bytes(flags.embedding_name, flags.embedding_train_from)
@@ -94,25 +125,30 @@ def workspace_modes(flags):
     kw = {'conv_split16': True} if getattr(flags, 'embedding_conv_split16', False) else {}
     if getattr(flags, 'embedding_train_from', None) is not None:  # (a frozen prefix keeps no activations: the workspace shrinks with the stage)
         kw['train_from'] = flags.embedding_train_from
-    if check_prefix_once_flag(flags):             # (with conv_split16 the prefix keeps no pre-BN tensor; the step's boundary cache is counted by the callers)
+    if check_prefix_once_flag(flags) or check_prefix_cache_flag(flags):             # (with conv_split16 the prefix keeps no pre-BN tensor; the step's boundary cache is counted by the callers)
         kw['prefix_once'] = True
     return kw
 
 
-def check_workspace_fits(flags, n_frames_per_obs):
+def check_workspace_fits(flags, n_frames_per_obs, n_samples=0):
     """The trainer keeps every activation of a step: its workspace grows with unroll_length x batch_size x frames (about 0.03 GB per frame for
     resnet18, 0.14 GB for resnet50: the reference's default T=100, B=32 does not fit an MI355X), and the trainer refuses a frame count at which one of
     its tensors would pass 2 GiB (668 frames for resnet18, 334 for resnet50).  Compared with that limit and the free device memory BEFORE anything
-    is allocated, so that the error names a size that fits instead of an allocation failing inside the first step."""
+    is allocated, so that the error names a size that fits instead of an allocation failing inside the first step.  --embedding_prefix_cache: the
+    boundary tensors of all n_samples x frames dataset frames and the staging tensor of a pass are counted next to the workspace."""
     from .embeddings import trainer_workspace_bytes
     want = flags.unroll_length * flags.batch_size * n_frames_per_obs
     if getattr(flags, 'freeze_embedding_bn', False):
-        return check_chunk_fits(flags, want)
+        return check_chunk_fits(flags, want, int(n_samples) * n_frames_per_obs)
     split16 = bool(getattr(flags, 'embedding_wgrad_split16', False))       # (the mode's scale slots and scratch are part of the workspace)
     conv16 = workspace_modes(flags)
     need = trainer_workspace_bytes(flags.embedding_name, want, split16, **conv16)
     free = int(torch.cuda.mem_get_info()[0])
     cache = boundary_cache_bytes(flags, want)     # (--embedding_prefix_once: the step's boundary tensors live next to the workspace)
+    pc_cache, pc_frame = prefix_cache_bytes(flags, int(n_samples) * n_frames_per_obs)
+    if pc_cache and need is not None and need + pc_cache + want * pc_frame > free:
+        raise prefix_cache_does_not_fit(flags, int(n_samples) * n_frames_per_obs, pc_cache, want * pc_frame, need, free)
+    cache += pc_cache + want * pc_frame           # (one pass: the staging tensor holds the step's frames)
     if need is not None:
         need += cache
     if need is None or need > free:
@@ -127,14 +163,16 @@ def check_workspace_fits(flags, n_frames_per_obs):
     return need
 
 
-def check_chunk_fits(flags, want):
+def check_chunk_fits(flags, want, n_dataset_frames=0):
     """--freeze_embedding_bn: frames are independent and a step of `want` frames runs as passes of --embedding_chunk frames, so it is the CHUNK's
     workspace that has to fit.  Without --embedding_chunk the chunk is the largest frame count <= want that the trainer admits and whose workspace
     fits nine tenths of the free device memory (the policy's workspace, the batch, the embeddings and one pass's gradient live next to it).  A given
     chunk is compared with the free memory and the trainer's limit as it is, and the error names the largest chunk that fits.  The resolved chunk
     is written back to flags.embedding_chunk (a checkpoint's flags carry it); returns the chunk's workspace bytes.  --embedding_prefix_once: the
     boundary tensors of ALL `want` frames of a step live next to the chunk's workspace; the default chunk is the largest one that fits the nine tenths
-    together with that cache, `need` includes it and the messages name both sizes."""
+    together with that cache, `need` includes it and the messages name both sizes.  --embedding_prefix_cache: in its place the boundary tensors of all
+    n_dataset_frames dataset frames and the staging tensor of one pass (chunk frames) live next to the chunk's workspace; a cache that does not fit is
+    a RuntimeError that names the sizes and the alternatives."""
     from .embeddings import trainer_workspace_bytes
     free = int(torch.cuda.mem_get_info()[0])
     chunk = getattr(flags, 'embedding_chunk', None)
@@ -142,8 +180,17 @@ def check_chunk_fits(flags, want):
     conv16 = workspace_modes(flags)
     cache = boundary_cache_bytes(flags, want)
     with_cache = ' next to the %.2f GB boundary cache of --embedding_prefix_once for %d frames' % (cache / 2 ** 30, want) if cache else ''
+    pc_cache, pc_frame = prefix_cache_bytes(flags, n_dataset_frames)
+    if pc_cache:
+        one = trainer_workspace_bytes(flags.embedding_name, 1 if chunk is None else max(min(int(chunk), want), 1), split16, **conv16)
+        frames_of_one = 1 if chunk is None else max(min(int(chunk), want), 1)
+        if one is not None and pc_cache + frames_of_one * pc_frame + one > (free // 10 * 9 if chunk is None else free):
+            raise prefix_cache_does_not_fit(flags, n_dataset_frames, pc_cache, frames_of_one * pc_frame, one, free)
+        cache = pc_cache
+        with_cache = ' next to the %.2f GB prefix cache of --embedding_prefix_cache for %d dataset frames' % (cache / 2 ** 30, n_dataset_frames)
+    fit_kw = dict(conv16, extra_per_frame=pc_frame) if pc_cache else conv16       # (the staging tensor grows with the chunk)
     if chunk is None:
-        chunk = largest_fitting_frames(flags.embedding_name, want, max(free // 10 * 9 - cache, 0), split16, **conv16)
+        chunk = largest_fitting_frames(flags.embedding_name, want, max(free // 10 * 9 - cache, 0), split16, **fit_kw)
         if chunk < 1:
             raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for a chunk of one frame takes %.2f GB%s, %.2f GB "
                                "of device memory are free" % (flags.embedding_name, trainer_workspace_bytes(flags.embedding_name, 1, split16, **conv16) / 2 ** 30,
@@ -153,9 +200,9 @@ def check_chunk_fits(flags, want):
     chunk = min(int(chunk), want)
     need = trainer_workspace_bytes(flags.embedding_name, chunk, split16, **conv16)
     if need is not None:
-        need += cache
+        need += cache + chunk * pc_frame
     if need is None or need > free:
-        fit = largest_fitting_frames(flags.embedding_name, chunk, max(free - cache, 0), split16, **conv16)
+        fit = largest_fitting_frames(flags.embedding_name, chunk, max(free - cache, 0), split16, **fit_kw)
         why = 'is more than the trainer\'s launches can address (one tensor of its workspace would pass 2 GiB)' if need is None \
             else 'takes %.2f GB%s, %.2f GB of device memory are free' % ((need - cache) / 2 ** 30, with_cache, free / 2 ** 30)
         raise RuntimeError("--train_embedding --freeze_embedding_bn: the training workspace of '%s' for --embedding_chunk %d frames %s; the largest "
@@ -179,6 +226,9 @@ def run_end_to_end(flags, make_env=None):
     prefix_once = check_prefix_once_flag(flags)
     if prefix_once:
         print('  ', 'prefix once: the frozen prefix runs once per frame and step (--embedding_prefix_once)')
+    prefix_cache = check_prefix_cache_flag(flags)
+    if prefix_cache:
+        print('  ', 'prefix cache: the frozen prefix runs once per dataset frame, before training (--embedding_prefix_cache)')
     world = max(rank_world()[1], int(os.environ.get('WORLD_SIZE', '1')))
     if world > 1:
         raise NotImplementedError('--train_embedding with a world size of %d: data-parallel encoder training is not built (the trainable encoder and its '
@@ -220,7 +270,7 @@ def run_end_to_end(flags, make_env=None):
     assert int(np.min(action)) >= 0 and int(np.max(action)) < n_actions, \
         'actions in the data (%d..%d) do not fit num_actions=%d' % (int(np.min(action)), int(np.max(action)), n_actions)
     T, B = flags.unroll_length, flags.batch_size
-    check_workspace_fits(flags, n_f)
+    check_workspace_fits(flags, n_f, n_samples)
     split16 = {'wgrad_split16': True} if getattr(flags, 'embedding_wgrad_split16', False) else {}
     if split16:
         print('  ', 'weight gradients: exact-split products on the f16 matrix pipe')
@@ -231,6 +281,8 @@ def run_end_to_end(flags, make_env=None):
         split16 = dict(split16, train_from=train_from)
     if prefix_once:                                             # (the bits are the same with and without it: a resume may change the flag)
         split16 = dict(split16, prefix_once=True)
+    if prefix_cache:                                            # (the workspace mode; the bits are the same: a resume may change this flag too)
+        split16 = dict(split16, prefix_cache=True)
     if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
         if not flags.pretrained_embedding:
             print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')
@@ -268,15 +320,23 @@ def run_end_to_end(flags, make_env=None):
     model.train()
     from .bc_data import DeviceDataset
     dataset = DeviceDataset(obs, action, done, flags.device)
+    if prefix_cache:                                            # after a resume's load_state_dict: the cache holds what the loaded prefix computes
+        pc = model.build_prefix_cache(dataset.obs)
+        print('  ', 'prefix cache: %d frames, %.2f GB, filled in %.2f s (%.0f frames/s)'
+              % (pc.n_frames, pc.nbytes / 2 ** 30, pc.fill_seconds, pc.n_frames / max(pc.fill_seconds, 1e-9)))
     for frames in range(init_frames, flags.max_frames, B * T):
         epoch = frames // (B * T)
         starting_i = sample_with_minimum_distance(n=n_samples, k=B, d=T)
-        o, a, d = dataset.gather(starting_i, T)                 # (T, B, H, W, 3F) uint8
+        if prefix_cache:                                        # (T, B) sample indices: a step reads its frames' boundary tensors, no uint8 frame
+            o = dataset.rows(starting_i, T)
+            a, d = dataset.action[o], dataset.done[o].bool()
+        else:
+            o, a, d = dataset.gather(starting_i, T)             # (T, B, H, W, 3F) uint8
         if fused:
             optimizer.scheduler_step()
-            loss, gradient_norm = optimizer.step(o, d, a)
+            loss, gradient_norm = optimizer.step_cached(o, d, a) if prefix_cache else optimizer.step(o, d, a)
         else:                                                   # main_bc_2.py:206-227, as written there
-            output, _ = model(dict(obs=o, done=d), model.initial_state(batch_size=B))
+            output, _ = model(dict(obs_rows=o, done=d) if prefix_cache else dict(obs=o, done=d), model.initial_state(batch_size=B))
             loss = F.nll_loss(F.log_softmax(torch.flatten(output['policy_logits'], 0, 1), dim=-1), target=torch.flatten(a, 0, 1).long())
             scheduler.step()
             optimizer.zero_grad()
@@ -321,6 +381,7 @@ def run_end_to_end(flags, make_env=None):
 def run(flags, make_env=None):
     check_train_from_flag(flags)
     check_prefix_once_flag(flags)
+    check_prefix_cache_flag(flags)
     if getattr(flags, 'train_embedding', False):
         return run_end_to_end(flags, make_env)
     rank, world = rank_world()

@@ -703,7 +703,11 @@ class PolicyNetWithEncoder(nn.Module):
     (T*B, F*D) observation matrix: the layout of the reference's np.split / np.concatenate(..., -1) (save_embedded_obs.py:153-155).  BatchNorm2d
     batch statistics do not depend on the order of the frames.  state_dict() has `embedding.*` and `policy.*` keys; eval() runs the frozen 'f32'
     plan of the current encoder parameters and the eval policy.  Train it with the reference's own lines (loss.backward() reaches every encoder
-    parameter through PolicyNet's d(loss)/d(obs)) or with HipJointRMSprop."""
+    parameter through PolicyNet's d(loss)/d(obs)) or with HipJointRMSprop.
+
+    With a train_from encoder, build_prefix_cache(dataset observations) computes the frozen prefix's output of every dataset frame once and attaches
+    it; forward then takes inputs['obs_rows'] ((T, B) sample indices, DeviceDataset.rows) in place of inputs['obs'], and
+    HipJointRMSprop.step_cached does the same for the fused step - the same bits, and no uint8 frame is touched."""
 
     def __init__(self, embedding_net, num_actions, batch_norm=False, num_frames=2, max_unroll=100, max_batch=32):
         super().__init__()
@@ -737,7 +741,32 @@ class PolicyNetWithEncoder(nn.Module):
         x = obs_u8.to(device=self.device).reshape(T * B, H, W, self.num_frames, 3).permute(0, 3, 1, 2, 4)
         return x.contiguous().view(T * B * self.num_frames, H, W, 3)
 
+    def build_prefix_cache(self, obs, block=256):
+        """obs: the dataset's (n, H, W, 3F) uint8 observations (device memory, e.g. DeviceDataset.obs) -> the encoder's PrefixCache of all n * F frames,
+        attached to the model (self.prefix_cache).  Blocks of `block` samples are split with split_frames' (observation, frame) order: frame f of
+        sample s is cache row s * F + f.  forward and HipJointRMSprop.step_cached then take (T, B) sample indices in place of observations."""
+        obs = obs if isinstance(obs, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(obs))
+        n, F = int(obs.shape[0]), self.num_frames
+        assert obs.dtype == torch.uint8 and obs.dim() == 4 and obs.shape[3] == 3 * F, tuple(obs.shape)
+        blocks = ((lo * F, self.split_frames(obs[lo:lo + block].unsqueeze(0))) for lo in range(0, n, int(block)))
+        self.prefix_cache = self.embedding._build_prefix_cache(n * F, blocks)
+        return self.prefix_cache
+
+    def cache_rows(self, obs_rows):
+        """(T, B) int64 sample indices -> the (T*B*F,) cache rows of their frames in split_frames' (observation, frame) order: s * F + f"""
+        F = self.num_frames
+        r = obs_rows.to(device=self.device, dtype=torch.int64).reshape(-1, 1)
+        return (r * F + torch.arange(F, dtype=torch.int64, device=r.device)).reshape(-1)
+
     def forward(self, inputs, core_state=()):
+        if 'obs_rows' in inputs:                                              # (T, B) sample indices of the attached prefix cache: no uint8 frame is touched
+            if getattr(self, 'prefix_cache', None) is None:
+                raise RuntimeError("inputs['obs_rows'] needs a prefix cache: call build_prefix_cache(dataset observations) first")
+            rows = inputs['obs_rows']
+            T, B = rows.shape[0], rows.shape[1]
+            emb = self.embedding.forward_cached(self.prefix_cache, self.cache_rows(rows))
+            x = emb.reshape(T, B, self.num_frames * int(self.embedding.out_size))
+            return self.policy(dict(obs=x, done=inputs['done']), core_state)
         obs = inputs['obs']
         T, B = obs.shape[0], obs.shape[1]
         emb = self.embedding(self.split_frames(obs))                          # (T*B*F, D); with its graph in training mode
@@ -783,24 +812,39 @@ class HipJointRMSprop(object):
 
     def step(self, obs_u8, done, actions):
         """obs (T,B,H,W,3F) uint8, done (T,B) bool, actions (T,B) int -> (loss, grad_norm) device scalars (norm over both parameter sets, pre-clip)"""
+        return self._step(obs_u8, None, done, actions)
+
+    def step_cached(self, rows, done, actions):
+        """step on (T, B) sample indices of the model's prefix cache (PolicyNetWithEncoder.build_prefix_cache) in place of observations: every encoder
+        pass gathers its frames' boundary tensors and starts at the first trained op.  The bits of step on the observations behind the indices."""
+        m = self.model
+        if getattr(m, 'prefix_cache', None) is None:
+            raise RuntimeError('HipJointRMSprop.step_cached needs a prefix cache: call model.build_prefix_cache(dataset observations) first')
+        assert rows.dim() == 2, tuple(rows.shape)
+        m.embedding.check_prefix_cache(m.prefix_cache)
+        return self._step(None, rows, done, actions)
+
+    def _step(self, obs_u8, rows, done, actions):
         m = self.model
         pol, enc = m.policy, m.embedding
         if not (m.training and enc.training and pol.training):
             raise RuntimeError('HipJointRMSprop.step: the model is in eval mode; call model.train() first')
-        T, B = obs_u8.shape[0], obs_u8.shape[1]
+        T, B = (obs_u8 if rows is None else rows).shape[:2]
         dev = pol.device
         pol._ensure(T, B)
         if self._grads is None or self._grads['policy'].device != dev:
             self._grads = {'policy': torch.zeros(pol._n_train, dtype=torch.float32, device=dev), 'embedding': torch.zeros_like(enc._flat)}
             self.square_avg = {k: v.to(dev) for k, v in self.square_avg.items()}
-        frames = m.split_frames(obs_u8)
+        frames = m.split_frames(obs_u8) if rows is None else None
+        cache, crows = (None, None) if rows is None else (m.prefix_cache, m.cache_rows(rows))
         d = done.to(device=dev).to(torch.uint8).contiguous()
         a = actions.to(device=dev).long().contiguous()
         L = _plib()
         vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         with torch.no_grad():
             enc.close()                                                       # (a frozen eval plan folds parameters that are about to move)
-            emb = enc._forward_raw(frames)                                    # (T*B*F, D) contiguous = the (T*B, F*D) observation matrix
+            # (T*B*F, D) contiguous = the (T*B, F*D) observation matrix
+            emb = enc._forward_raw(frames) if rows is None else enc._forward_raw_cached(cache, crows)
             enc._fwd_gen += 1                                                 # an autograd forward still waiting for its backward has lost its activations
             pol._fwd_gen = getattr(pol, '_fwd_gen', 0) + 1
             dobs = torch.empty_like(emb)
@@ -811,7 +855,10 @@ class HipJointRMSprop(object):
                                                     vp(g['policy']), vp(stats), None, vp(dobs), _lib.stream_ptr()))
             boundary, enc._boundary = getattr(enc, '_boundary', None), None  # (prefix_once: the step's boundary cache, released when the step is done)
             # one pvr_trainer_backward, or the chunk walk of a frozen-BatchNorm encoder (prefix_once: its recompute passes start at the first trained op)
-            enc._backward_raw(frames, dobs, g['embedding'], *(() if boundary is None else (boundary,)))
+            if rows is None:
+                enc._backward_raw(frames, dobs, g['embedding'], *(() if boundary is None else (boundary,)))
+            else:                                                             # (each recompute pass gathers its rows of the prefix cache again)
+                enc._backward_raw_cached(cache, crows, dobs, g['embedding'])
             del boundary
             arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
             counts = (C.c_int64 * 2)(pol._n_train, enc._flat.numel())
