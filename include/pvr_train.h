@@ -180,6 +180,42 @@ pvr_status pvr_trainer_prefix_forward(pvr_trainer *tr, const float *params_dev, 
 pvr_status pvr_op_gather_rows(const float *src_dev, int64_t n_src_rows, int64_t row_floats, const int64_t *rows_dev, int64_t n, float *dst_dev,
                               void *hip_stream);
 
+/* A random crop window per frame and step (the Python mode random_crop): the augmentation of fine-tuning on a few thousand small frames.  The centre crop
+ * of every forward above becomes a window per frame, (top, left) in the RESIZED frame, chosen by the caller.
+ * pvr_op_crop_windows / pvr_host_crop_windows: n windows, windows[2 i] = top in [0, max_top] and windows[2 i + 1] = left in [0, max_left] of frame
+ *   first_frame + i, into device / host memory.  Frame f draws from Philox-4x32-10 with counter (f, call) and key seed (csrc/sample_rng.h):
+ *   top = (bits0 * (max_top + 1)) >> 32 and left likewise from bits1 - uniform up to a relative bias below 2^-26 for ranges of at most 64 values.  Both
+ *   functions share one inline and agree bit for bit.  The result depends on (seed, call, frame) alone - not on the grid and not on how a step is cut
+ *   into passes: rows lo .. hi of one draw equal a draw with first_frame = lo.  torch's own generator stream is not reproduced; the contract is the
+ *   distribution plus determinism.  The trainer's ranges are resized size - crop (32 x 32 for square frames).  pvr_op_crop_windows refuses by name,
+ *   launching nothing: a null or not 4-byte aligned windows_dev, n < 1, a negative first_frame, max_top or max_left; the host function treats a negative
+ *   maximum as 0 and writes nothing through a null pointer.
+ * pvr_trainer_forward_windows, windows_dev == NULL: exactly pvr_trainer_forward (boundary_dev == NULL) or pvr_trainer_forward_boundary (given) - the
+ *   same launches, names, bits and refusals.  windows_dev != NULL (n x (top, left) int32 on the device): the launches "preprocess" and "normalize" are
+ *   replaced by ONE launch "preprocess windows" (pvr_op_preprocess_windows) that writes the fp32 image of each frame's window; everything after it is
+ *   unchanged, and the held forward's image is the windowed one, so conv1's weight gradient sees it.  A window is clamped in the kernel to
+ *   [0, resized height - crop] x [0, resized width - crop]: no value can make it read outside its frame.  Where the resize is exact arithmetic - no
+ *   resize, and the power-of-two scales of 64 x 64 and 128 x 128 frames - the image has the bits the two launches give at that window; at other scales the
+ *   new launch sums the taps in the rounding order of ATen's host kernel, so a .5 tie of the bilinear sum lands where torchvision's Resize puts it, which
+ *   preprocess_kernel may miss by one uint8 step.  reuse != 0 (with boundary_dev): the pass starts at the first trained op, windows are not read and may be null.  The handle keeps
+ *   nothing about windows: a recompute pass that runs the stem again is handed the same rows again.  pvr_trainer_prefix_forward keeps the centre crop - a
+ *   cache of boundary tensors is only valid for a deterministic crop.  Refused by name, launching nothing: what pvr_trainer_forward_boundary refuses (a
+ *   boundary_dev at stage 0, its alignment, n outside 1 .. max_batch, null frames without reuse), a windows_dev that is not 4-byte aligned, a frame whose
+ *   resized size is below the crop. */
+pvr_status pvr_op_crop_windows(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t max_top, int32_t max_left, int32_t *windows_dev,
+                               void *hip_stream);
+void pvr_host_crop_windows(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t max_top, int32_t max_left, int32_t *windows_host);
+pvr_status pvr_trainer_forward_windows(pvr_trainer *tr, const float *params_dev, void *bn_buffers_dev, const uint8_t *frames_dev, int32_t n, int32_t h,
+                                       int32_t w, const int32_t *windows_dev, float *boundary_dev, int32_t reuse, float *out_dev, int64_t out_stride,
+                                       void *hip_stream);
+/* The kernel of that launch alone: uint8 NHWC frames (n, h, w, 3) -> Resize(resize, bilinear, rounded to uint8 as torchvision does) -> the crop x crop
+ * window at the clamped windows_dev[2 i], windows_dev[2 i + 1] of the resized frame -> (v / 255 - mean) / std per channel, channel 3 = 0 -> out_dev, the
+ * dense fp32 NHWC4 image (n, crop, crop, 4), 16-byte aligned.  One 16-byte store per pixel, plain loads and stores, no atomics: two runs give the same
+ * bits.  Refused by name, launching nothing: a null argument, a non-positive size, a resized frame smaller than the crop, a windows_dev that is not
+ * 4-byte or an out_dev that is not 16-byte aligned, more than 65535 frames. */
+pvr_status pvr_op_preprocess_windows(const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, int32_t resize, int32_t crop, const float *mean,
+                                     const float *std_, const int32_t *windows_dev, float *out_dev, void *hip_stream);
+
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
  * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */

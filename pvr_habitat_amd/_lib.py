@@ -130,6 +130,11 @@ _SIGS = {
     'pvr_trainer_set_prefix_fused': (C.c_int, [C.c_void_p, C.c_int32]),
     'pvr_trainer_prefix_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     'pvr_op_gather_rows': (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    'pvr_op_crop_windows': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'pvr_host_crop_windows': (None, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    'pvr_trainer_forward_windows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_preprocess_windows': (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
     'pvr_op_conv_bn_frozen_forward_split16_scratch_floats': (C.c_int64, [C.c_int32] * 8),
     'pvr_op_conv_bn_frozen_forward_split16': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_conv_fwd_split16_scratch_floats':(C.c_int64, [C.c_int32] * 8),

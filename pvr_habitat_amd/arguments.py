@@ -61,6 +61,12 @@ def make_parser():
                              'tensor next to the workspace; a cache that does not fit is refused with both sizes), and every pass of a step gathers '
                              'its frames\' rows and starts at the first trained stage.  Replaces the step-sized cache of --embedding_prefix_once.  The '
                              'bits do not change: a run may be resumed with or without it (the cache is rebuilt)')
+    parser.add_argument('--embedding_random_crop', action='store_true',
+                        help='with --train_embedding: every frame of a training step goes through Resize(256) and then its own random 224 x 224 window '
+                             'of the resized frame instead of the centre one (one launch writes the windowed image; evaluation keeps the centre crop).  '
+                             'The windows are a function of --run_id, the iteration and the frame, so a resumed run draws what an uninterrupted one '
+                             'would, and a run may be resumed with or without the flag.  Not with --embedding_prefix_cache, whose cache holds the '
+                             'frozen prefix\'s output for ONE window per frame; --embedding_prefix_once is the compatible mode')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

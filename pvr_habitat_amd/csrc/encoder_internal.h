@@ -57,6 +57,10 @@ void read_switches(PlanSwitches &sw);
 PlanSwitches &op_switches();   // the pvr_op_* entry points' instance: read_switches on first use; pvr_debug_set_conv_algo changes it
 
 pvr_status launch_preprocess(const uint8_t *, int, int, int, int, int, void *, int, hipStream_t, int crop_pos = 0);
+void resized_size(int h, int w, int size, int *rh, int *rw);     // torchvision resize(int size): smaller edge -> size
+// frames -> Resize -> a window per frame (windows: n x (top, left) int32 on the device, clamped in the kernel) -> the dense fp32 NHWC4 image, one launch
+pvr_status launch_preprocess_windows(const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
+                                     const int32_t *windows, float *out, hipStream_t stream);
 pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
 pvr_status launch_maxpool(const void *, void *, int, int, int, int, int, hipStream_t);
 // (c1_*: layer1.0.conv1 inside the stem - stem.hip, StemC1; only when stem_conv1_capable(sw))

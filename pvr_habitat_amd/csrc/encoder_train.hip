@@ -421,9 +421,10 @@ namespace {
 // pvr_trainer_forward (boundary == nullptr) and pvr_trainer_forward_boundary: the arguments have passed the callers' checks.  boundary: where this pass's
 // boundary tensor lives instead of the arena's piece - the producing launch writes it there and every reader goes through tensor_of.  reuse: it holds the
 // tensor already, and the pass starts at the first trained op.  prefix_only (pvr_trainer_prefix_forward): the pass ends behind the last prefix op - the
-// same launches up to there, nothing written but the boundary tensor and the prefix's own buffers, and no forward is held.
+// same launches up to there, nothing written but the boundary tensor and the prefix's own buffers, and no forward is held.  windows
+// (pvr_trainer_forward_windows): n x (top, left) on the device - the image is each frame's window instead of the centre crop, made by one launch.
 pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *boundary, bool reuse,
-                        float *out, int64_t out_stride, void *stream, bool prefix_only = false) {
+                        float *out, int64_t out_stride, void *stream, bool prefix_only = false, const int32_t *windows = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     pvr_status s;
     if ((s = ensure_workspace(t))) return s;
@@ -445,8 +446,13 @@ pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, c
                                        op.mean, op.rstd, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st);
     };
     if (!reuse) {
-        TR_RUN("preprocess", 0, launch_preprocess(frames, n, h, w, t->desc.resize, t->desc.crop, t->d_img, PVR_BF16, st, 0));
-        TR_RUN("normalize", 0, launch_normalize_nhwc4(t->d_img, t->d_imgf, n, t->desc.crop, t->desc.mean, t->desc.std_, PVR_BF16, st, false));
+        if (windows) {                            // a window per frame: the same d_imgf bits as the two launches below at that window
+            TR_RUN("preprocess windows", 0,
+                   launch_preprocess_windows(frames, n, h, w, t->desc.resize, t->desc.crop, t->desc.mean, t->desc.std_, windows, t->d_imgf, st));
+        } else {
+            TR_RUN("preprocess", 0, launch_preprocess(frames, n, h, w, t->desc.resize, t->desc.crop, t->d_img, PVR_BF16, st, 0));
+            TR_RUN("normalize", 0, launch_normalize_nhwc4(t->d_img, t->d_imgf, n, t->desc.crop, t->desc.mean, t->desc.std_, PVR_BF16, st, false));
+        }
         TrainOp &sm = t->stem;
         TR_RUN("conv1 pack", 0, launch_pack_stem_weights(params + sm.w_off, t->stem_wpack, st));
         TR_RUN("conv1", 2.0 * n * 112 * 112 * 64 * 147, launch_stem_f32(t->d_imgf, t->stem_wpack, nullptr, sm.z, n, S_IMG, st, true));
@@ -546,6 +552,33 @@ pvr_status pvr_trainer_forward_boundary(pvr_trainer *t, const float *params, voi
                 "frames)");
     TraceScope ts("pvr_trainer_forward_boundary");
     return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, reuse != 0, out, out_stride, stream);
+}
+
+pvr_status pvr_trainer_forward_windows(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,
+                                       const int32_t *windows, float *boundary, int32_t reuse, float *out, int64_t out_stride, void *stream) {
+    if (!windows || (boundary && reuse))          // no window is read: the centre-crop entry points, with their own refusals
+        return boundary ? pvr_trainer_forward_boundary(t, params, bn_buffers, frames, n, h, w, boundary, reuse, out, out_stride, stream)
+                        : pvr_trainer_forward(t, params, bn_buffers, frames, n, h, w, out, out_stride, stream);
+    PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward_windows: null argument (only a reuse pass, which starts at the first trained "
+                "op, reads no frames)");
+    PVR_REQUIRE(((uintptr_t)windows & 3) == 0, "pvr_trainer_forward_windows: windows_dev %p is not 4-byte aligned (n x (top, left) int32)", (const void *)windows);
+    if (boundary && t->train_from <= 0) {
+        set_error("pvr_trainer_forward_windows: everything trains (pvr_trainer_set_train_from stage 0): there is no frozen prefix and no boundary tensor to "
+                  "keep; pass a null boundary_dev");
+        return PVR_ERR_STATE;
+    }
+    PVR_REQUIRE(((uintptr_t)boundary & 15) == 0, "pvr_trainer_forward_windows: boundary_dev %p is not 16-byte aligned (the launches move it as float4s)",
+                (void *)boundary);
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward_windows: %d frames, the workspace holds max_batch = %d (with frozen BatchNorm run the "
+                "frames as passes of at most max_batch, each with its own rows of the windows; batch statistics take the whole batch together)", n,
+                t->desc.max_batch);
+    PVR_REQUIRE(h > 0 && w > 0, "pvr_trainer_forward_windows: bad frame size h=%d w=%d", h, w);
+    int rh, rw;
+    resized_size(h, w, t->desc.resize, &rh, &rw);
+    PVR_REQUIRE(rh >= t->desc.crop && rw >= t->desc.crop, "pvr_trainer_forward_windows: resized frame %dx%d (of %dx%d) smaller than crop %d", rh, rw, h, w,
+                t->desc.crop);
+    TraceScope ts("pvr_trainer_forward_windows");
+    return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, false, out, out_stride, stream, false, windows);
 }
 
 pvr_status pvr_trainer_prefix_forward(pvr_trainer *t, const float *params, const void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,

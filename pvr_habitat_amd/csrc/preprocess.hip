@@ -12,6 +12,8 @@
 // Output layout: (n, crop+6, crop+8, 4) 16-bit, pixel (y,x) at [y+3][x+3], channels
 // (R-128,G-128,B-128,valid=1); the 3-pixel zero border (valid=0) is the conv1 padding and is never written.
 #include "common.h"
+#include "sample_rng.h"
+#include "../../include/pvr_train.h"
 
 namespace pvr {
 
@@ -114,4 +116,130 @@ pvr_status launch_preprocess(const uint8_t *frames, int n, int h, int w, int res
     return PVR_OK;
 }
 
+// The trainer's random-crop input (pvr_trainer_forward_windows): uint8 NHWC frames -> Resize -> a crop x crop window PER FRAME -> /255 -> Normalize, as
+// the dense fp32 NHWC4 image (n, crop, crop, 4) conv1 and its weight gradient read, in ONE launch (preprocess_kernel + normalize_nhwc4_kernel take two
+// and a 16-bit image in between), followed per pixel by normalize_nhwc4_kernel's expression.  HBM-bound: 3 B (12 B for the four taps) read + 16 B
+// written per pixel.
+// The bilinear sum is preprocess_kernel's geometry in the ROUNDING ORDER of ATen's host kernel, which is what oracle/encoder_oracle.py:resize_u8 runs:
+// the source index is one fma, fma(scale, dst + 0.5, -0.5), and each two-tap sum is w0 * a + w1 * b as fma(w0, a, round(w1 * b)), along x and then
+// along y.  preprocess_kernel rounds every product and sum by itself; the two orders agree wherever the arithmetic is exact - no resize, and the
+// power-of-two scales of 64 x 64 and 128 x 128 frames, where this launch has the bits of preprocess + normalize at the same window - and at other
+// scales they part at .5 ties of the sum, where preprocess_kernel can be one uint8 step away from the reference (tests/test_gpu_encoder.py allows it
+// that) and this kernel is not: tests/test_random_crop_cpu.py restates the order in numpy and finds no differing value on whole resized frames.
+struct WinP {
+    const uint8_t *src;
+    float *dst;
+    const int32_t *windows;   // n x (top, left) in the resized frame; clamped here
+    int n, h, w;              // source frame size
+    int rh, rw;               // size after Resize
+    int crop;
+    int resize_needed;
+    float scale_h, scale_w;
+    float m0, m1, m2, s0, s1, s2;
+};
+
+__global__ __launch_bounds__(256) void preprocess_windows_f32_kernel(WinP p) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int n = blockIdx.z;
+    if (x >= p.crop || y >= p.crop) return;
+    // the frame's window, clamped to [0, rh - crop] x [0, rw - crop] (rh, rw >= crop: the launcher refuses smaller frames): whatever the array holds,
+    // 0 <= Y < rh and 0 <= X < rw below, and every tap stays inside the frame
+    int top = p.windows[2 * n], left = p.windows[2 * n + 1];
+    top = top < 0 ? 0 : (top > p.rh - p.crop ? p.rh - p.crop : top);
+    left = left < 0 ? 0 : (left > p.rw - p.crop ? p.rw - p.crop : left);
+    const int Y = y + top, X = x + left;
+    const uint8_t *img = p.src + (size_t)n * p.h * p.w * 3;
+    float v[3];
+    if (!p.resize_needed) {
+        const uint8_t *s = img + ((size_t)Y * p.w + X) * 3;
+        v[0] = (float)s[0]; v[1] = (float)s[1]; v[2] = (float)s[2];
+    } else {
+#pragma clang fp contract(off)
+        // ATen upsample_bilinear2d, align_corners=False: src = scale*(dst+0.5)-0.5 as one fma, clamped at 0 (only the fmas written out are fused)
+        float sy = __builtin_fmaf(p.scale_h, (float)Y + 0.5f, -0.5f);
+        float sx = __builtin_fmaf(p.scale_w, (float)X + 0.5f, -0.5f);
+        sy = sy < 0.f ? 0.f : sy;
+        sx = sx < 0.f ? 0.f : sx;
+        int y0 = (int)sy, x0 = (int)sx;
+        y0 = y0 > p.h - 1 ? p.h - 1 : y0;          // (never taken for Y < rh, X < rw: the taps stay inside the frame whatever the rounding does)
+        x0 = x0 > p.w - 1 ? p.w - 1 : x0;
+        const int y1 = y0 + (y0 < p.h - 1 ? 1 : 0), x1 = x0 + (x0 < p.w - 1 ? 1 : 0);
+        const float ly = sy - (float)y0, lx = sx - (float)x0;
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        const uint8_t *r0 = img + (size_t)y0 * p.w * 3, *r1 = img + (size_t)y1 * p.w * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float p00 = (float)r0[x0 * 3 + c], p01 = (float)r0[x1 * 3 + c];
+            const float p10 = (float)r1[x0 * 3 + c], p11 = (float)r1[x1 * 3 + c];
+            const float a = __builtin_fmaf(hx, p00, lx * p01), b = __builtin_fmaf(hx, p10, lx * p11);
+            const float val = __builtin_fmaf(hy, a, ly * b);
+            v[c] = rintf(val);     // torch.round (half to even) then .to(uint8)
+        }
+    }
+    f32x4 o;
+    o[0] = (v[0] / 255.0f - p.m0) / p.s0; o[1] = (v[1] / 255.0f - p.m1) / p.s1; o[2] = (v[2] / 255.0f - p.m2) / p.s2; o[3] = 0.f;
+    reinterpret_cast<f32x4 *>(p.dst)[((size_t)n * p.crop + y) * p.crop + x] = o;     // one 16-byte store per pixel, a wave's 64 along x
+}
+
+// the arguments have passed the callers' null checks
+pvr_status launch_preprocess_windows(const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
+                                     const int32_t *windows, float *out, hipStream_t stream) {
+    PVR_REQUIRE(n > 0 && h > 0 && w > 0 && crop > 0, "preprocess windows: bad shape n=%d h=%d w=%d crop=%d", n, h, w, crop);
+    PVR_REQUIRE(n <= 65535, "preprocess windows: %d frames in one launch (at most 65535: one grid plane per frame)", n);
+    WinP p;
+    p.src = frames; p.dst = out; p.windows = windows; p.n = n; p.h = h; p.w = w; p.crop = crop;
+    resized_size(h, w, resize, &p.rh, &p.rw);
+    PVR_REQUIRE(p.rh >= crop && p.rw >= crop, "preprocess windows: resized frame %dx%d smaller than crop %d", p.rh, p.rw, crop);
+    PVR_REQUIRE(((uintptr_t)windows & 3) == 0, "preprocess windows: windows_dev %p is not 4-byte aligned (n x (top, left) int32)", (const void *)windows);
+    PVR_REQUIRE(((uintptr_t)out & 15) == 0, "preprocess windows: out_dev %p is not 16-byte aligned (a pixel is one float4 store)", (void *)out);
+    p.resize_needed = (p.rh != h || p.rw != w);
+    p.scale_h = (float)h / (float)p.rh;
+    p.scale_w = (float)w / (float)p.rw;
+    p.m0 = mean[0]; p.m1 = mean[1]; p.m2 = mean[2]; p.s0 = std_[0]; p.s1 = std_[1]; p.s2 = std_[2];
+    dim3 grid((crop + 63) / 64, (crop + 3) / 4, n);
+    hipLaunchKernelGGL(preprocess_windows_f32_kernel, grid, dim3(256), 0, stream, p);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+__global__ __launch_bounds__(256) void crop_windows_kernel(unsigned long long seed, unsigned long long call, long long first_frame, long long n, int max_top,
+                                                           int max_left, int32_t *__restrict__ windows) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int32_t top, left;
+    crop_window(seed, call, (uint64_t)(first_frame + i), max_top, max_left, &top, &left);
+    windows[2 * i] = top;
+    windows[2 * i + 1] = left;
+}
+
 }  // namespace pvr
+
+extern "C" {
+
+pvr_status pvr_op_preprocess_windows(const uint8_t *frames, int32_t n, int32_t h, int32_t w, int32_t resize, int32_t crop, const float *mean,
+                                     const float *std_, const int32_t *windows, float *out, void *stream) {
+    PVR_REQUIRE(frames && mean && std_ && windows && out, "pvr_op_preprocess_windows: null argument");
+    return pvr::launch_preprocess_windows(frames, n, h, w, resize, crop, mean, std_, windows, out, (hipStream_t)stream);
+}
+
+void pvr_host_crop_windows(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t max_top, int32_t max_left, int32_t *windows) {
+    for (int64_t i = 0; windows && i < n; ++i)
+        pvr::crop_window(seed, call, (uint64_t)(first_frame + i), max_top, max_left, &windows[2 * i], &windows[2 * i + 1]);
+}
+
+pvr_status pvr_op_crop_windows(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t max_top, int32_t max_left, int32_t *windows,
+                               void *stream) {
+    PVR_REQUIRE(windows, "pvr_op_crop_windows: null windows_dev (n x (top, left) int32 of device memory)");
+    PVR_REQUIRE(((uintptr_t)windows & 3) == 0, "pvr_op_crop_windows: windows_dev %p is not 4-byte aligned (int32 pairs)", (void *)windows);
+    PVR_REQUIRE(n >= 1 && n <= (1ll << 31), "pvr_op_crop_windows: n = %lld frames (1 .. 2^31)", (long long)n);
+    PVR_REQUIRE(first_frame >= 0, "pvr_op_crop_windows: first_frame = %lld (a frame index of the step, 0 or above)", (long long)first_frame);
+    PVR_REQUIRE(max_top >= 0 && max_left >= 0, "pvr_op_crop_windows: max_top = %d, max_left = %d (the largest legal offsets, resized size - crop: 0 or above)",
+                max_top, max_left);
+    hipLaunchKernelGGL(pvr::crop_windows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long)seed,
+                       (unsigned long long)call, (long long)first_frame, (long long)n, (int)max_top, (int)max_left, windows);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+}  // extern "C"

@@ -39,4 +39,15 @@ __host__ __device__ inline int sample_softmax_row(const float *l, int A, uint64_
     return best;
 }
 
+// The random crop window of one frame (pvr_op_crop_windows / pvr_host_crop_windows, include/pvr_train.h): counter (frame, call), key seed; top from the
+// first word and left from the second by multiply-shift, (bits * (max + 1)) >> 32, which lies in [0, max].  A value's probability differs from
+// 1 / (max + 1) by less than 2^-32: relative to it, a bias below (max + 1) 2^-32 <= 2^-26 for ranges of at most 64 values.  The window depends on
+// (seed, call, frame) alone - not on the grid, and not on how a step's frames are cut into passes.  A negative max counts as 0.
+__host__ __device__ inline void crop_window(uint64_t seed, uint64_t call, uint64_t frame, int32_t max_top, int32_t max_left, int32_t *top, int32_t *left) {
+    uint32_t c[4] = {(uint32_t)frame, (uint32_t)(frame >> 32), (uint32_t)call, (uint32_t)(call >> 32)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    *top = (int32_t)(((uint64_t)c[0] * (uint64_t)((max_top < 0 ? 0 : max_top) + 1)) >> 32);
+    *left = (int32_t)(((uint64_t)c[1] * (uint64_t)((max_left < 0 ? 0 : max_left) + 1)) >> 32);
+}
+
 }  // namespace pvr

@@ -395,6 +395,7 @@ class _EncoderFunction(torch.autograd.Function):
         model._fwd_gen += 1
         ctx.model, ctx.gen, ctx.frames = model, model._fwd_gen, frames_u8
         ctx.boundary, model._boundary = model._boundary, None       # (prefix_once: the cache lives on the node, exactly as long as the frames do)
+        ctx.windows, model._windows = model._windows, None          # (random_crop: the step's windows, for the recompute passes that run the stem again)
         return out
 
     @staticmethod
@@ -405,8 +406,8 @@ class _EncoderFunction(torch.autograd.Function):
                                'encoder overwrote them (one backward per forward, right after it)')
         dout = dout.contiguous().float()
         g = torch.empty_like(m._flat)
-        m._backward_raw(ctx.frames, dout, g, ctx.boundary)
-        ctx.frames = ctx.boundary = None
+        m._backward_raw(ctx.frames, dout, g, ctx.boundary, ctx.windows)
+        ctx.frames = ctx.boundary = ctx.windows = None
         return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._trained_slots)
 
 
@@ -507,12 +508,23 @@ class HipTrainableResNet(_Node):
     (pvr_op_gather_rows) and starts at the first trained op (pvr_trainer_forward_boundary with reuse), in the forward and in the recompute passes of
     the backward.  No uint8 frame is touched.  The keyword only selects the workspace mode (the fused prefix launches of prefix_once, so that the
     cache's bits are that mode's); together with prefix_once it means prefix_cache and no step-sized boundary tensor is allocated.  Embeddings and
-    gradients keep the bits of a step on the frames themselves, with prefix_once and with neither mode."""
+    gradients keep the bits of a step on the frames themselves, with prefix_once and with neither mode.
+
+    random_crop: a random crop window per frame and step, the augmentation of fine-tuning on few small frames.  In training mode every frame of a forward
+    goes through Resize(256) and then its OWN 224 x 224 window of the resized frame instead of the centre one: the step's (n, 2) int32 windows (top, left)
+    are drawn once on the device (pvr_op_crop_windows with seed = crop_seed, call = crop_call, first_frame = 0: frame i of the forward is frame i of the
+    draw, so the two frames of an observation get independent windows), every pass is handed its rows (pvr_trainer_forward_windows: one launch writes the
+    windowed fp32 image) and so is every recompute pass of a chunked backward that runs the stem again, so it sees the same image; with prefix_once the
+    recompute passes start at the boundary tensor as without the mode.  crop_call, a plain int attribute, then goes up by one: a caller that sets it
+    (the driver: the iteration's number) makes a resumed run draw what an uninterrupted one would, and crop_windows(crop_seed, call, n, max_top,
+    max_left) predicts a step's windows on the host.  Off by default; with it off nothing moves.  Eval mode keeps the centre crop on the frozen 'f32'
+    plan.  Not with prefix_cache, build_prefix_cache or forward_cached: a cache holds the prefix's output for ONE window per frame."""
 
     def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False, prefix_cache=False):
+                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0):
         super().__init__()
         assert variant in _TRAINABLE, variant
+        check_random_crop(random_crop, prefix_cache)
         _lib.require_gpu()
         self.variant = variant
         self.out_size = OUT_SIZE[variant]
@@ -548,6 +560,11 @@ class HipTrainableResNet(_Node):
         self._prefix_once = bool(prefix_once) and not self._prefix_cache      # (both: prefix_cache - no step-sized boundary tensor)
         self._boundary = None                    # prefix_once: the boundary cache between _forward_raw and its consumer (the autograd node or the joint step)
         self._boundary_floats = int(L.pvr_trainer_boundary_floats(h))
+        self._random_crop = bool(random_crop)
+        self.crop_seed = int(crop_seed)          # random_crop: Philox key of the windows
+        self.crop_call = 0                       # random_crop: the next training forward's draw; it goes up by one per forward and a caller may set it
+        self._windows = None                     # random_crop: the step's windows between _forward_raw and its consumer (parked as _boundary is)
+        self._resize, self._crop = int(tr.resize), int(tr.crop)
         if self._prefix_once or self._prefix_cache:
             _lib.check(L.pvr_trainer_set_prefix_fused(h, 1))
         self._trained_offset = int(L.pvr_trainer_trained_offset(h))     # floats of the flat buffer below it are the frozen prefix (one leading span)
@@ -652,6 +669,18 @@ class HipTrainableResNet(_Node):
         return 4 * self._boundary_floats
 
     @property
+    def random_crop(self):
+        """a training forward crops a random window per frame (see the class docstring)"""
+        return self._random_crop
+
+    def crop_range(self, h, w):
+        """(max_top, max_left) of an (h, w) frame's window: its size after Resize minus the crop (32, 32 for square frames)"""
+        rh, rw = resized_size(h, w, self._resize)
+        if rh < self._crop or rw < self._crop:
+            raise ValueError('random_crop: a %dx%d frame is %dx%d after Resize(%d), smaller than the %d crop' % (h, w, rh, rw, self._resize, self._crop))
+        return rh - self._crop, rw - self._crop
+
+    @property
     def prefix_cache(self):
         """the workspace was made for cached steps (see the class docstring)"""
         return self._prefix_cache
@@ -663,6 +692,7 @@ class HipTrainableResNet(_Node):
         A training forward still waiting for its backward loses its activations."""
         if self._train_from is None:
             raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
+        check_random_crop(self._random_crop, True, 'build_prefix_cache')
         return self._build_prefix_cache(int(frames_u8.shape[0]), [(0, frames_u8)])
 
     def _build_prefix_cache(self, n_frames, blocks):
@@ -670,6 +700,7 @@ class HipTrainableResNet(_Node):
         frames are not laid out as one (N, H, W, 3) tensor (PolicyNetWithEncoder: F frames side by side per sample) splits block by block"""
         if self._train_from is None:
             raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
+        check_random_crop(self._random_crop, True, 'build_prefix_cache')
         L = _lib.lib()
         _lib.check(L.pvr_trainer_set_prefix_fused(self._handle, 1))
         vp = lambda t: C.c_void_p(t.data_ptr())
@@ -708,6 +739,7 @@ class HipTrainableResNet(_Node):
     def forward_cached(self, cache, rows):
         """training-mode forward of the frames behind `rows` (int64 device tensor, one row of `cache` per frame): embeddings with a graph that hands
         only the trained parameters to autograd.  The bits of forward(frames[rows])."""
+        check_random_crop(self._random_crop, True, 'forward_cached')
         self.check_prefix_cache(cache)
         if not self.training:
             raise RuntimeError('forward_cached is a training-mode forward (the cache holds the input of the trained stages): in eval mode embed the '
@@ -793,14 +825,29 @@ class HipTrainableResNet(_Node):
         # prefix_once: the boundary tensor of every frame of the step; its consumer (the autograd node, or the joint step under the generation
         # counter) takes it from here and hands it to _backward_raw
         self._boundary = torch.empty((n, self._boundary_floats), dtype=torch.float32, device=frames_u8.device) if self._prefix_once else None
+        # random_crop: the step's windows, drawn once; every pass takes its rows, and the consumer hands the tensor to _backward_raw like the boundary cache
+        self._windows = None
+        if self._random_crop:
+            max_top, max_left = self.crop_range(h, w)
+            self._windows = torch.empty((n, 2), dtype=torch.int32, device=frames_u8.device)
+            _lib.check(_lib.lib().pvr_op_crop_windows(self.crop_seed, self.crop_call, 0, n, max_top, max_left, C.c_void_p(self._windows.data_ptr()),
+                                                      _lib.stream_ptr()))
+            self.crop_call += 1
         for lo, hi in self._passes(n):            # (one pass unless BatchNorm is frozen; the last pass's activations stay held)
-            self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary)
+            self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary, windows=self._windows)
         return out
 
-    def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False):
+    def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False, windows=None):
         """one pass over frames [lo, hi).  boundary: the step's (n, boundary_floats) cache - this pass writes its rows (reuse False) or starts at the first
-        trained op on what they hold (reuse True)"""
+        trained op on what they hold (reuse True).  windows (random_crop): the step's (n, 2) int32 windows - this pass crops at its rows"""
         vp = lambda t: C.c_void_p(t.data_ptr())
+        if windows is not None:
+            reuse = reuse and boundary is not None                            # (without a boundary cache a recompute pass runs the stem again, at the same windows)
+            _lib.check(_lib.lib().pvr_trainer_forward_windows(self._handle, vp(self._flat), vp(self._bufs), None if reuse else vp(frames_u8[lo:hi]), hi - lo,
+                                                              frames_u8.shape[1], frames_u8.shape[2], vp(windows[lo:hi]),
+                                                              None if boundary is None else vp(boundary[lo:hi]), 1 if reuse else 0, vp(out),
+                                                              out.stride(0), _lib.stream_ptr()))
+            return
         if boundary is None:
             _lib.check(_lib.lib().pvr_trainer_forward(self._handle, vp(self._flat), vp(self._bufs), vp(frames_u8[lo:hi]), hi - lo, frames_u8.shape[1],
                                                       frames_u8.shape[2], vp(out), out.stride(0), _lib.stream_ptr()))
@@ -810,16 +857,18 @@ class HipTrainableResNet(_Node):
                                                            h, w, vp(boundary[lo:hi]), 1 if reuse else 0, vp(out),
                                                            out.stride(0), _lib.stream_ptr()))
 
-    def _backward_raw(self, frames_u8, dout, grads, boundary=None):
+    def _backward_raw(self, frames_u8, dout, grads, boundary=None, windows=None):
         """d(loss)/d(embeddings) of the training forward that just ran on frames_u8 -> the flat gradient `grads` (fully written).  One pass: one
         pvr_trainer_backward.  Several (frozen BatchNorm): the last pass first - its activations are still held - then every other pass in frame
         order, each recomputed and added by pvr_trainer_backward_acc.  boundary (prefix_once): the cache that forward filled; a recomputed pass
-        starts at the first trained op on its rows."""
+        starts at the first trained op on its rows.  windows (random_crop): the windows that forward drew; a recomputed pass that runs the stem crops
+        at its rows again."""
         L = _lib.lib()
         vp = lambda t: C.c_void_p(t.data_ptr())
         passes = self._passes(frames_u8.shape[0])
         assert dout.shape[0] == frames_u8.shape[0] and dout.stride(1) == 1
         assert (boundary is not None) == self._prefix_once, 'prefix_once: the backward takes the boundary cache of its forward'
+        assert (windows is not None) == self._random_crop, 'random_crop: the backward takes the windows of its forward'
         if len(passes) == 1:
             _lib.check(L.pvr_trainer_backward(self._handle, vp(self._flat), vp(dout), dout.stride(0), vp(grads), _lib.stream_ptr()))
             return
@@ -829,7 +878,7 @@ class HipTrainableResNet(_Node):
         again = torch.empty((self._max_batch, self.out_size), dtype=torch.float32, device=dout.device)       # the recomputed embeddings are not used
         for i, (lo, hi) in enumerate(passes[-1:] + passes[:-1]):
             if i:
-                self._forward_pass(frames_u8, lo, hi, again[:hi - lo], boundary, reuse=True)
+                self._forward_pass(frames_u8, lo, hi, again[:hi - lo], boundary, reuse=True, windows=windows)
             _lib.check(L.pvr_trainer_backward_acc(self._handle, vp(self._flat), vp(dout[lo:hi]), dout.stride(0), vp(grads), 1 if i else 0, vp(sc), sc.numel(),
                                                   _lib.stream_ptr()))
 
@@ -885,6 +934,32 @@ class HipTrainableResNet(_Node):
 
 
 TRAIN_FROM = ('layer1', 'layer2', 'layer3', 'layer4')
+
+
+def resized_size(h, w, size):
+    """(height, width) of an (h, w) frame after torchvision's resize(int size): the smaller edge becomes size, the other int(size * long / short)"""
+    short, long_ = (w, h) if w <= h else (h, w)
+    if short == size:
+        return h, w
+    new_long = int(size * long_ / short)
+    return (new_long, size) if w <= h else (size, new_long)
+
+
+def crop_windows(seed, call, n, max_top, max_left, first_frame=0):
+    """the (n, 2) int32 windows (top, left) random_crop draws for frames first_frame .. first_frame + n of training forward number `call` under crop_seed
+    `seed` (pvr_host_crop_windows: host arithmetic, no GPU needed; bit for bit what the device draws).  max_top, max_left: HipTrainableResNet.crop_range"""
+    out = np.zeros((int(n), 2), np.int32)
+    if n > 0:
+        _lib.lib().pvr_host_crop_windows(int(seed), int(call), int(first_frame), int(n), int(max_top), int(max_left), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def check_random_crop(random_crop, prefix_cache=False, what='prefix_cache'):
+    """random_crop moves a frame's window from step to step: a ValueError together with the prefix cache (`what` names the keyword or the method)"""
+    if random_crop and prefix_cache:
+        raise ValueError('random_crop with %s: the cache holds the frozen prefix\'s output for ONE window per frame (the deterministic centre crop), and a '
+                         'random crop moves the window in every step; prefix_once, which keeps the prefix\'s output for the frames and windows of one '
+                         'step, is the compatible mode' % what)
 
 
 def check_prefix_once(prefix_once, train_from):
@@ -982,7 +1057,7 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
 
 
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
-                   conv_split16=False, train_from=None, prefix_once=False, prefix_cache=False):
+                   conv_split16=False, train_from=None, prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -991,6 +1066,7 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     train_stage(train_from)                       # (ValueError names the choices)
     check_prefix_once(prefix_once, train_from)
     check_prefix_cache(prefix_cache, train_from)
+    check_random_crop(random_crop, prefix_cache)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
@@ -998,7 +1074,8 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     sd, variant = _load_named_state_dict(embedding_name, pretrained)
     return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16, conv_split16=conv_split16,
                               **({'train_from': train_from} if train_from is not None else {}), **({'prefix_once': True} if prefix_once else {}),
-                              **({'prefix_cache': True} if prefix_cache else {}))
+                              **({'prefix_cache': True} if prefix_cache else {}),
+                              **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}))
 
 
 class UberModel(nn.Module):
@@ -1194,7 +1271,7 @@ class EmbeddingNet(nn.Module):
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
                  compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False, prefix_cache=False):
+                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -1224,6 +1301,11 @@ class EmbeddingNet(nn.Module):
             raise ValueError('prefix_cache is a mode of the trainable encoder (train=True, with train_from): a frozen encoder has no training step and '
                              'no frozen prefix whose output could be cached')
         check_prefix_cache(prefix_cache, train_from)
+        if random_crop and not train:
+            raise ValueError('random_crop is a mode of the trainable encoder (train=True): a frozen encoder embeds the centre crop of every frame (crops=5 '
+                             'adds the four corner windows)')
+        check_random_crop(random_crop, prefix_cache)
+        # random_crop (train=True only): a training forward crops a random window per frame; crop_seed keys the draw (HipTrainableResNet.crop_call counts it)
         # prefix_cache (train=True with train_from only): the workspace mode of cached steps (build_prefix_cache / forward_cached of the encoder)
         # prefix_once (train=True with train_from only): the frozen prefix runs once per frame and step; its boundary tensor is kept across the passes
         # train_from (train=True only): partial fine-tuning - that stage and the ones above train, everything below is the frozen prefix
@@ -1236,7 +1318,8 @@ class EmbeddingNet(nn.Module):
                                                          **({'conv_split16': True} if conv_split16 else {}),
                                                          **({'train_from': train_from} if train_from is not None else {}),
                                                          **({'prefix_once': True} if prefix_once else {}),
-                                                         **({'prefix_cache': True} if prefix_cache else {}))
+                                                         **({'prefix_cache': True} if prefix_cache else {}),
+                                                         **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

@@ -782,7 +782,10 @@ class HipJointRMSprop(object):
 
     With a frozen-BatchNorm encoder (EmbeddingNet(..., train=True, freeze_bn=True, max_batch=chunk)) of fewer than T*B*F frames per pass the same
     flow is chunked: the trainer's forward in passes to the (T*B*F, D) matrix, one pvr_policy_backward_dobs, the recompute + pvr_trainer_backward_acc
-    of every pass into the encoder's gradient (HipTrainableResNet._backward_raw), one pvr_joint_apply_rmsprop."""
+    of every pass into the encoder's gradient (HipTrainableResNet._backward_raw), one pvr_joint_apply_rmsprop.
+
+    With a random_crop encoder the step takes the windows the trainer's forward drew (there is no autograd node to carry them) and hands them to
+    _backward_raw next to the boundary cache, so the recompute passes crop where the forward did; step_cached is unreachable with that mode."""
 
     def __init__(self, model, lr=1e-4, alpha=0.99, eps=1e-5, momentum=0, max_grad_norm=40.0, max_epochs=None):
         if float(momentum) != 0:
@@ -855,11 +858,13 @@ class HipJointRMSprop(object):
                                                     vp(g['policy']), vp(stats), None, vp(dobs), _lib.stream_ptr()))
             boundary, enc._boundary = getattr(enc, '_boundary', None), None  # (prefix_once: the step's boundary cache, released when the step is done)
             # one pvr_trainer_backward, or the chunk walk of a frozen-BatchNorm encoder (prefix_once: its recompute passes start at the first trained op)
+            windows, enc._windows = getattr(enc, '_windows', None), None     # (random_crop: the step's windows, for the recompute passes that run the stem)
             if rows is None:
-                enc._backward_raw(frames, dobs, g['embedding'], *(() if boundary is None else (boundary,)))
+                enc._backward_raw(frames, dobs, g['embedding'], *(() if boundary is None else (boundary,)),
+                                  **({} if windows is None else {'windows': windows}))
             else:                                                             # (each recompute pass gathers its rows of the prefix cache again)
                 enc._backward_raw_cached(cache, crows, dobs, g['embedding'])
-            del boundary
+            del boundary, windows
             arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
             counts = (C.c_int64 * 2)(pol._n_train, enc._flat.numel())
             _lib.check(L.pvr_joint_apply_rmsprop(2, arr((pol._flat, enc._flat)), arr((self.square_avg['policy'], self.square_avg['embedding'])),
