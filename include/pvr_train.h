@@ -216,6 +216,48 @@ pvr_status pvr_trainer_forward_windows(pvr_trainer *tr, const float *params_dev,
 pvr_status pvr_op_preprocess_windows(const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, int32_t resize, int32_t crop, const float *mean,
                                      const float *std_, const int32_t *windows_dev, float *out_dev, void *hip_stream);
 
+/* Colour jitter per frame and step (the Python mode color_jitter): brightness, contrast and saturation as torchvision's ColorJitter applies them to a
+ * uint8 tensor, without hue, on the uint8 values of each frame's crop x crop window - after Resize and the window, before / 255 and Normalize.
+ * Arithmetic, every product and sum one fp32 rounding (no contraction):
+ *   gray(r, g, b) = trunc(((0.2989f r) + (0.587f g)) + (0.114f b));   blend(a, b, f) = trunc(clamp((f a) + ((1.0f - f) b), 0, 255)) per channel;
+ *   brightness f: blend(v, 0, f);   saturation f: blend(v, gray(v), f);   contrast f: blend(v, m, f) with m = (float)S / (float)(crop crop), S the INTEGER
+ *   sum of gray over the frame's window of the image as it stands when contrast is applied.  S <= 255 * 256^2 < 2^24: (float)S is exact, m does not
+ *   depend on the order of the sum, and the parallel reduction has the bits of torch.mean.  Factors (1, 1, 1) in any order reproduce the input bits.
+ * A frame's parameters are four 32-bit words: float b, float c, float s, int32 order; order 0 .. 5 indexes the permutations of (brightness, contrast,
+ *   saturation) in lexicographic order (0 = b c s, 1 = b s c, 2 = c b s, 3 = c s b, 4 = s b c, 5 = s c b).  Hardened in the kernels: a NaN factor counts
+ *   as 1, a factor is clamped to [0, 4], an order outside 0 .. 5 counts as 0; no value can produce a NaN image.
+ * pvr_op_color_params / pvr_host_color_params: the parameters of frames first_frame .. first_frame + n into device / host memory.  Frame f draws from
+ *   Philox-4x32-10 with counter (f, call), as the crop windows do, and key (seed_lo, seed_hi ^ 0x434F4C52): a stream of its own, so the windows of the
+ *   same (seed, call) keep their bits.  Words 0 .. 2: factor = fma(hi - lo, u, lo), u uniform in (0, 1), lo = max(0, 1 - strength), hi = 1 + strength
+ *   (torchvision's range; strength 0 gives exactly 1); word 3: order = (bits * 6) >> 32.  Both functions share one inline (csrc/sample_rng.h) and agree
+ *   bit for bit; the result depends on (seed, call, frame) alone: rows lo .. hi of one draw equal a draw with first_frame = lo.  pvr_op_color_params
+ *   refuses by name, launching nothing: a null or not 4-byte aligned color_dev, n < 1, a negative first_frame, a negative or non-finite strength; the
+ *   host function treats such a strength as 0 and writes nothing through a null pointer.
+ * pvr_op_preprocess_color: pvr_op_preprocess_windows with the jitter between the window and / 255, as two launches: "colour stats" adds every frame's
+ *   gray values before contrast into gray_sums_dev[i] (a wave reduction, then one integer atomicAdd per workgroup: no float atomics, two runs give the
+ *   same bits), "preprocess colour" writes the image, one 16-byte store per pixel.  Both recompute the resized, windowed pixel with the expressions of
+ *   pvr_op_preprocess_windows.  gray_sums_dev: n uint32 of the CALLER's scratch (pvr_trainer_workspace_bytes does not depend on how a caller steps); the
+ *   entry point zeroes it on the stream before the stats launch (hipMemsetAsync), so it carries no state between calls.  The stats launch always runs:
+ *   whether contrast is the identity is a fact of device data.  Refused by name, launching nothing: what pvr_op_preprocess_windows refuses, a null or not
+ *   4-byte aligned color_dev or gray_sums_dev, a crop above 256.
+ * pvr_trainer_forward_augmented, color_dev == NULL: exactly pvr_trainer_forward_windows - the same launches, names, bits and refusals.  color_dev != NULL
+ *   needs windows_dev (without a random crop the caller passes the centre window, nearbyint((resized size - crop) / 2), for every frame): the two
+ *   launches above replace "preprocess windows", everything after them is unchanged, and the held forward's image is the jittered one, so conv1's
+ *   weight gradient sees it.  reuse != 0 (with boundary_dev): nothing before the first trained op runs and neither array is read.  The handle keeps
+ *   nothing about the parameters: a recompute pass that runs the stem again is handed the same rows again.  pvr_trainer_prefix_forward keeps the plain
+ *   centre crop.  Refused by name, launching nothing: what pvr_trainer_forward_windows refuses, a color_dev without windows_dev, a color_dev that is not
+ *   4-byte aligned, a null or not 4-byte aligned gray_sums_dev. */
+pvr_status pvr_op_color_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float strength_b, float strength_c, float strength_s,
+                               void *color_dev, void *hip_stream);
+void pvr_host_color_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float strength_b, float strength_c, float strength_s,
+                           void *color_host);
+pvr_status pvr_op_preprocess_color(const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, int32_t resize, int32_t crop, const float *mean,
+                                   const float *std_, const int32_t *windows_dev, const void *color_dev, uint32_t *gray_sums_dev, float *out_dev,
+                                   void *hip_stream);
+pvr_status pvr_trainer_forward_augmented(pvr_trainer *tr, const float *params_dev, void *bn_buffers_dev, const uint8_t *frames_dev, int32_t n, int32_t h,
+                                         int32_t w, const int32_t *windows_dev, const void *color_dev, uint32_t *gray_sums_dev, float *boundary_dev,
+                                         int32_t reuse, float *out_dev, int64_t out_stride, void *hip_stream);
+
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
  * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */

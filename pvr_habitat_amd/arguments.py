@@ -67,6 +67,14 @@ def make_parser():
                              'The windows are a function of --run_id, the iteration and the frame, so a resumed run draws what an uninterrupted one '
                              'would, and a run may be resumed with or without the flag.  Not with --embedding_prefix_cache, whose cache holds the '
                              'frozen prefix\'s output for ONE window per frame; --embedding_prefix_once is the compatible mode')
+    parser.add_argument('--embedding_color_jitter', type=float, nargs=3, default=None, metavar=('B', 'C', 'S'),
+                        help='with --train_embedding: every frame of a training step gets its own brightness, contrast and saturation factor, each '
+                             'uniform in [max(0, 1 - strength), 1 + strength] for the strengths B, C and S, applied in a random order per frame to the '
+                             'uint8 values of its 224 x 224 window, as torchvision\'s ColorJitter does (hue is not offered; evaluation keeps the un-jittered '
+                             'centre crop).  Default off; 0 0 0 is off too.  The factors are a function of --run_id, the iteration and the frame, so a '
+                             'resumed run draws what an uninterrupted one would, and a run may be resumed with or without the flag.  Not with '
+                             '--embedding_prefix_cache, whose cache holds the frozen prefix\'s output for ONE image per frame; --embedding_prefix_once is '
+                             'the compatible mode')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

@@ -61,6 +61,10 @@ void resized_size(int h, int w, int size, int *rh, int *rw);     // torchvision 
 // frames -> Resize -> a window per frame (windows: n x (top, left) int32 on the device, clamped in the kernel) -> the dense fp32 NHWC4 image, one launch
 pvr_status launch_preprocess_windows(const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
                                      const int32_t *windows, float *out, hipStream_t stream);
+// the same with colour jitter per frame (color: n x (float b, c, s, int32 order); gray_sums: n uint32 of scratch), as two launches: stage 0 zeroes the
+// sums and adds every frame's gray values before contrast, stage 1 writes the image; each checks every argument before it launches
+pvr_status launch_color_stage(int stage, const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
+                              const int32_t *windows, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream);
 pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
 pvr_status launch_maxpool(const void *, void *, int, int, int, int, int, hipStream_t);
 // (c1_*: layer1.0.conv1 inside the stem - stem.hip, StemC1; only when stem_conv1_capable(sw))

@@ -423,8 +423,11 @@ namespace {
 // tensor already, and the pass starts at the first trained op.  prefix_only (pvr_trainer_prefix_forward): the pass ends behind the last prefix op - the
 // same launches up to there, nothing written but the boundary tensor and the prefix's own buffers, and no forward is held.  windows
 // (pvr_trainer_forward_windows): n x (top, left) on the device - the image is each frame's window instead of the centre crop, made by one launch.
+// color, gray_sums (pvr_trainer_forward_augmented, with windows): n x (float b, c, s, int32 order) and n uint32 of the caller's scratch - the window's
+// uint8 values are colour-jittered before /255 and Normalize, by two launches in place of that one.
 pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *boundary, bool reuse,
-                        float *out, int64_t out_stride, void *stream, bool prefix_only = false, const int32_t *windows = nullptr) {
+                        float *out, int64_t out_stride, void *stream, bool prefix_only = false, const int32_t *windows = nullptr, const void *color = nullptr,
+                        uint32_t *gray_sums = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     pvr_status s;
     if ((s = ensure_workspace(t))) return s;
@@ -446,7 +449,12 @@ pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, c
                                        op.mean, op.rstd, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st);
     };
     if (!reuse) {
-        if (windows) {                            // a window per frame: the same d_imgf bits as the two launches below at that window
+        if (windows && color) {                   // a window and a colour jitter per frame: the gray sums contrast needs, then the image
+            TR_RUN("colour stats", 0, launch_color_stage(0, frames, n, h, w, t->desc.resize, t->desc.crop, t->desc.mean, t->desc.std_, windows, color, gray_sums,
+                                                         t->d_imgf, st));
+            TR_RUN("preprocess colour", 0, launch_color_stage(1, frames, n, h, w, t->desc.resize, t->desc.crop, t->desc.mean, t->desc.std_, windows, color,
+                                                              gray_sums, t->d_imgf, st));
+        } else if (windows) {                     // a window per frame: the same d_imgf bits as the two launches below at that window
             TR_RUN("preprocess windows", 0,
                    launch_preprocess_windows(frames, n, h, w, t->desc.resize, t->desc.crop, t->desc.mean, t->desc.std_, windows, t->d_imgf, st));
         } else {
@@ -579,6 +587,41 @@ pvr_status pvr_trainer_forward_windows(pvr_trainer *t, const float *params, void
                 t->desc.crop);
     TraceScope ts("pvr_trainer_forward_windows");
     return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, false, out, out_stride, stream, false, windows);
+}
+
+pvr_status pvr_trainer_forward_augmented(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,
+                                         const int32_t *windows, const void *color, uint32_t *gray_sums, float *boundary, int32_t reuse, float *out,
+                                         int64_t out_stride, void *stream) {
+    if (!color || (boundary && reuse))            // no colour parameter is read: the windows entry point, with its own refusals
+        return pvr_trainer_forward_windows(t, params, bn_buffers, frames, n, h, w, windows, boundary, reuse, out, out_stride, stream);
+    PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward_augmented: null argument (only a reuse pass, which starts at the first "
+                "trained op, reads no frames)");
+    PVR_REQUIRE(windows, "pvr_trainer_forward_augmented: color_dev without windows_dev (the jitter acts on a frame's window: pass the centre window, "
+                "nearbyint((resized size - crop) / 2), for every frame where no random crop is wanted)");
+    PVR_REQUIRE(((uintptr_t)windows & 3) == 0, "pvr_trainer_forward_augmented: windows_dev %p is not 4-byte aligned (n x (top, left) int32)",
+                (const void *)windows);
+    PVR_REQUIRE(((uintptr_t)color & 3) == 0, "pvr_trainer_forward_augmented: color_dev %p is not 4-byte aligned (n x (float b, float c, float s, int32 "
+                "order))", color);
+    PVR_REQUIRE(gray_sums && ((uintptr_t)gray_sums & 3) == 0, "pvr_trainer_forward_augmented: gray_sums_dev %p is null or not 4-byte aligned (n uint32 of "
+                "device scratch, the caller's)", (void *)gray_sums);
+    if (boundary && t->train_from <= 0) {
+        set_error("pvr_trainer_forward_augmented: everything trains (pvr_trainer_set_train_from stage 0): there is no frozen prefix and no boundary tensor to "
+                  "keep; pass a null boundary_dev");
+        return PVR_ERR_STATE;
+    }
+    PVR_REQUIRE(((uintptr_t)boundary & 15) == 0, "pvr_trainer_forward_augmented: boundary_dev %p is not 16-byte aligned (the launches move it as float4s)",
+                (void *)boundary);
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward_augmented: %d frames, the workspace holds max_batch = %d (with frozen BatchNorm run the "
+                "frames as passes of at most max_batch, each with its own rows of the windows and colour parameters; batch statistics take the whole batch "
+                "together)", n, t->desc.max_batch);
+    PVR_REQUIRE(h > 0 && w > 0, "pvr_trainer_forward_augmented: bad frame size h=%d w=%d", h, w);
+    int rh, rw;
+    resized_size(h, w, t->desc.resize, &rh, &rw);
+    PVR_REQUIRE(rh >= t->desc.crop && rw >= t->desc.crop, "pvr_trainer_forward_augmented: resized frame %dx%d (of %dx%d) smaller than crop %d", rh, rw, h, w,
+                t->desc.crop);
+    PVR_REQUIRE(t->desc.crop <= 256, "pvr_trainer_forward_augmented: crop %d (at most 256: the gray mean is exact while 255 crop^2 < 2^24)", t->desc.crop);
+    TraceScope ts("pvr_trainer_forward_augmented");
+    return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, false, out, out_stride, stream, false, windows, color, gray_sums);
 }
 
 pvr_status pvr_trainer_prefix_forward(pvr_trainer *t, const float *params, const void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,

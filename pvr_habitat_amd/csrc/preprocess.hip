@@ -138,11 +138,9 @@ struct WinP {
     float m0, m1, m2, s0, s1, s2;
 };
 
-__global__ __launch_bounds__(256) void preprocess_windows_f32_kernel(WinP p) {
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    const int n = blockIdx.z;
-    if (x >= p.crop || y >= p.crop) return;
+// the resized frame's pixel (x, y) of frame n's window, x and y below crop, as three uint8 values held in floats: shared by the windows kernel and the two
+// colour-jitter kernels below, which therefore see the same bits
+__device__ __forceinline__ void window_pixel(const WinP &p, int n, int y, int x, float (&v)[3]) {
     // the frame's window, clamped to [0, rh - crop] x [0, rw - crop] (rh, rw >= crop: the launcher refuses smaller frames): whatever the array holds,
     // 0 <= Y < rh and 0 <= X < rw below, and every tap stays inside the frame
     int top = p.windows[2 * n], left = p.windows[2 * n + 1];
@@ -150,7 +148,6 @@ __global__ __launch_bounds__(256) void preprocess_windows_f32_kernel(WinP p) {
     left = left < 0 ? 0 : (left > p.rw - p.crop ? p.rw - p.crop : left);
     const int Y = y + top, X = x + left;
     const uint8_t *img = p.src + (size_t)n * p.h * p.w * 3;
-    float v[3];
     if (!p.resize_needed) {
         const uint8_t *s = img + ((size_t)Y * p.w + X) * 3;
         v[0] = (float)s[0]; v[1] = (float)s[1]; v[2] = (float)s[2];
@@ -177,30 +174,183 @@ __global__ __launch_bounds__(256) void preprocess_windows_f32_kernel(WinP p) {
             v[c] = rintf(val);     // torch.round (half to even) then .to(uint8)
         }
     }
+}
+
+// /255 and Normalize of three uint8 values, channel 3 = 0: one 16-byte store per pixel, a wave's 64 along x
+__device__ __forceinline__ void store_normalized(const WinP &p, int n, int y, int x, const float (&v)[3]) {
     f32x4 o;
     o[0] = (v[0] / 255.0f - p.m0) / p.s0; o[1] = (v[1] / 255.0f - p.m1) / p.s1; o[2] = (v[2] / 255.0f - p.m2) / p.s2; o[3] = 0.f;
-    reinterpret_cast<f32x4 *>(p.dst)[((size_t)n * p.crop + y) * p.crop + x] = o;     // one 16-byte store per pixel, a wave's 64 along x
+    reinterpret_cast<f32x4 *>(p.dst)[((size_t)n * p.crop + y) * p.crop + x] = o;
+}
+
+__global__ __launch_bounds__(256) void preprocess_windows_f32_kernel(WinP p) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int n = blockIdx.z;
+    if (x >= p.crop || y >= p.crop) return;
+    float v[3];
+    window_pixel(p, n, y, x, v);
+    store_normalized(p, n, y, x, v);
+}
+
+// Colour jitter (pvr_op_preprocess_color, the trainer's "colour stats" and "preprocess colour" launches): torchvision's ColorJitter without hue on the
+// uint8 values of the window, between window_pixel and store_normalized - where T.ColorJitter would sit between CenterCrop and ConvertImageDtype.
+// Every product and sum is one fp32 rounding (contraction off), the blend's result is clamped to [0, 255] and truncated as .to(uint8) does:
+//   gray(r, g, b) = trunc(((0.2989 r) + (0.587 g)) + (0.114 b));   blend(a, b, f) = trunc(clamp((f a) + ((1 - f) b), 0, 255))
+//   brightness f: blend(v, 0, f);   saturation f: blend(v, gray(v), f);   contrast f: blend(v, m, f), m = (float)S / (float)(crop crop),
+// S = the INTEGER sum of gray over the frame's window of the image as it stands when contrast is applied.  S <= 255 * 256^2 < 2^24 (the launcher refuses a larger crop), so (float)S is exact
+// and m does not depend on the order of the sum: a parallel integer reduction gives the bits of torch.mean.  Per frame four words (float b, c, s and the
+// int32 order code 0 .. 5 of the permutation of (brightness, contrast, saturation) in lexicographic order), hardened here: a NaN factor counts as 1, a
+// factor is clamped to [0, 4] (4 * 255 and the blend stay finite: no NaN image), an order outside 0 .. 5 counts as 0.
+struct ColP {
+    WinP win;
+    const uint32_t *color;    // n x (float b, float c, float s, int32 order)
+    uint32_t *gray_sums;      // n integer sums, zeroed by the launcher before the stats kernel
+    float pixels;             // (float)(crop * crop)
+};
+
+struct FrameColor {
+    float f[3];               // brightness, contrast, saturation factors, hardened
+    uint32_t ops;             // the frame's three ops, two bits each, first op lowest: 0 brightness, 1 contrast, 2 saturation
+};
+
+__device__ __forceinline__ FrameColor frame_color(const uint32_t *color, int n) {
+    FrameColor fc;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float f = __uint_as_float(color[4 * n + j]);
+        fc.f[j] = (f != f) ? 1.0f : (f < 0.f ? 0.f : (f > 4.0f ? 4.0f : f));
+    }
+    const uint32_t order = color[4 * n + 3];
+    // the six permutations in lexicographic order: bcs, bsc, cbs, csb, sbc, scb
+    const uint64_t table = 0x24ull | (0x18ull << 8) | (0x21ull << 16) | (0x09ull << 24) | (0x12ull << 32) | (0x06ull << 40);
+    fc.ops = (uint32_t)(table >> (8 * (order < 6u ? order : 0u))) & 0x3fu;
+    return fc;
+}
+
+__device__ __forceinline__ float gray_u8(const float (&v)[3]) {
+#pragma clang fp contract(off)
+    return truncf(((0.2989f * v[0]) + (0.587f * v[1])) + (0.114f * v[2]));
+}
+
+__device__ __forceinline__ float blend_u8(float a, float b, float f) {
+#pragma clang fp contract(off)
+    const float r = (f * a) + ((1.0f - f) * b);
+    return truncf(r < 0.f ? 0.f : (r > 255.0f ? 255.0f : r));
+}
+
+// one op on the pixel; m: the frame's gray mean, read by contrast alone
+__device__ __forceinline__ void color_op(float (&v)[3], uint32_t op, const FrameColor &fc, float m) {
+    const float f = op == 0 ? fc.f[0] : (op == 1 ? fc.f[1] : fc.f[2]);
+    const float g = gray_u8(v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = blend_u8(v[c], op == 0 ? 0.f : (op == 1 ? m : g), f);
+}
+
+// "colour stats": gray_sums[n] += the gray values of frame n's window after the ops that precede contrast in the frame's order.  A workgroup walks
+// STATS_ROWS rows of a 64-pixel column band, four rows at a time (a wave's 64 lanes along x, as the image kernels read); then a wave reduction, the
+// block's four waves through LDS, and one integer atomicAdd per workgroup - 16 per 224 x 224 frame: with one per four rows (224 per frame) the launch
+// was bound by the atomics on n neighbouring words, about twice the time of the image launch.  Integer addition commutes, so two runs give the same bits.
+// No lane leaves before the shuffles; a lane outside the window adds 0 and reads nothing.
+constexpr int STATS_ROWS = 56;
+
+__global__ __launch_bounds__(256) void color_stats_kernel(ColP p) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int n = blockIdx.z;
+    unsigned g = 0;
+    if (x < p.win.crop) {
+        const FrameColor fc = frame_color(p.color, n);
+        for (int r = 0; r < STATS_ROWS; r += 4) {
+            const int y = blockIdx.y * STATS_ROWS + r + (threadIdx.x >> 6);
+            if (y >= p.win.crop) break;
+            float v[3];
+            window_pixel(p.win, n, y, x, v);
+            uint32_t ops = fc.ops;
+            for (int k = 0; k < 3 && (ops & 3u) != 1u; ++k, ops >>= 2) color_op(v, ops & 3u, fc, 0.f);
+            g += (unsigned)gray_u8(v);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) g += __shfl_down(g, off, 64);
+    __shared__ unsigned part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = g;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(&p.gray_sums[n], part[0] + part[1] + part[2] + part[3]);
+}
+
+// "preprocess colour": the image - window_pixel, the frame's three ops in its order (contrast reads the finished sum), /255 and Normalize
+__global__ __launch_bounds__(256) void preprocess_color_f32_kernel(ColP p) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int n = blockIdx.z;
+    if (x >= p.win.crop || y >= p.win.crop) return;
+    const FrameColor fc = frame_color(p.color, n);
+    const float m = (float)p.gray_sums[n] / p.pixels;
+    float v[3];
+    window_pixel(p.win, n, y, x, v);
+    uint32_t ops = fc.ops;
+#pragma unroll
+    for (int k = 0; k < 3; ++k, ops >>= 2) color_op(v, ops & 3u, fc, m);
+    store_normalized(p.win, n, y, x, v);
+}
+
+// the checks and parameters the windows launch and the colour launches share; what: the launch's name in the refusals
+static pvr_status window_params(const char *what, const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
+                                const int32_t *windows, float *out, WinP &p) {
+    PVR_REQUIRE(n > 0 && h > 0 && w > 0 && crop > 0, "%s: bad shape n=%d h=%d w=%d crop=%d", what, n, h, w, crop);
+    PVR_REQUIRE(n <= 65535, "%s: %d frames in one launch (at most 65535: one grid plane per frame)", what, n);
+    p.src = frames; p.dst = out; p.windows = windows; p.n = n; p.h = h; p.w = w; p.crop = crop;
+    resized_size(h, w, resize, &p.rh, &p.rw);
+    PVR_REQUIRE(p.rh >= crop && p.rw >= crop, "%s: resized frame %dx%d smaller than crop %d", what, p.rh, p.rw, crop);
+    PVR_REQUIRE(((uintptr_t)windows & 3) == 0, "%s: windows_dev %p is not 4-byte aligned (n x (top, left) int32)", what, (const void *)windows);
+    PVR_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out_dev %p is not 16-byte aligned (a pixel is one float4 store)", what, (void *)out);
+    p.resize_needed = (p.rh != h || p.rw != w);
+    p.scale_h = (float)h / (float)p.rh;
+    p.scale_w = (float)w / (float)p.rw;
+    p.m0 = mean[0]; p.m1 = mean[1]; p.m2 = mean[2]; p.s0 = std_[0]; p.s1 = std_[1]; p.s2 = std_[2];
+    return PVR_OK;
 }
 
 // the arguments have passed the callers' null checks
 pvr_status launch_preprocess_windows(const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
                                      const int32_t *windows, float *out, hipStream_t stream) {
-    PVR_REQUIRE(n > 0 && h > 0 && w > 0 && crop > 0, "preprocess windows: bad shape n=%d h=%d w=%d crop=%d", n, h, w, crop);
-    PVR_REQUIRE(n <= 65535, "preprocess windows: %d frames in one launch (at most 65535: one grid plane per frame)", n);
     WinP p;
-    p.src = frames; p.dst = out; p.windows = windows; p.n = n; p.h = h; p.w = w; p.crop = crop;
-    resized_size(h, w, resize, &p.rh, &p.rw);
-    PVR_REQUIRE(p.rh >= crop && p.rw >= crop, "preprocess windows: resized frame %dx%d smaller than crop %d", p.rh, p.rw, crop);
-    PVR_REQUIRE(((uintptr_t)windows & 3) == 0, "preprocess windows: windows_dev %p is not 4-byte aligned (n x (top, left) int32)", (const void *)windows);
-    PVR_REQUIRE(((uintptr_t)out & 15) == 0, "preprocess windows: out_dev %p is not 16-byte aligned (a pixel is one float4 store)", (void *)out);
-    p.resize_needed = (p.rh != h || p.rw != w);
-    p.scale_h = (float)h / (float)p.rh;
-    p.scale_w = (float)w / (float)p.rw;
-    p.m0 = mean[0]; p.m1 = mean[1]; p.m2 = mean[2]; p.s0 = std_[0]; p.s1 = std_[1]; p.s2 = std_[2];
+    if (pvr_status s = window_params("preprocess windows", frames, n, h, w, resize, crop, mean, std_, windows, out, p)) return s;
     dim3 grid((crop + 63) / 64, (crop + 3) / 4, n);
     hipLaunchKernelGGL(preprocess_windows_f32_kernel, grid, dim3(256), 0, stream, p);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
+}
+
+// the two launches of pvr_op_preprocess_color, one at a time so that the trainer can name and time each; both check everything before they launch.  The
+// stats launch zeroes the n sums first (hipMemsetAsync on the same stream), so the scratch needs no state between calls.
+pvr_status launch_color_stage(int stage, const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
+                              const int32_t *windows, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream) {
+    ColP p;
+    if (pvr_status s = window_params("preprocess colour", frames, n, h, w, resize, crop, mean, std_, windows, out, p.win)) return s;
+    PVR_REQUIRE(((uintptr_t)color & 3) == 0, "preprocess colour: color_dev %p is not 4-byte aligned (n x (float b, float c, float s, int32 order))", color);
+    PVR_REQUIRE(((uintptr_t)gray_sums & 3) == 0, "preprocess colour: gray_sums_dev %p is not 4-byte aligned (n uint32 of scratch)", (void *)gray_sums);
+    PVR_REQUIRE((int64_t)crop * crop <= (1 << 16), "preprocess colour: crop %d (at most 256: 255 crop^2 must stay below 2^24 for the gray mean to be exact)",
+                crop);
+    p.color = (const uint32_t *)color; p.gray_sums = gray_sums; p.pixels = (float)(crop * crop);
+    dim3 grid((crop + 63) / 64, (crop + 3) / 4, n);
+    if (stage == 0) {
+        PVR_HIP_TRY(hipMemsetAsync(gray_sums, 0, (size_t)n * sizeof(uint32_t), stream));
+        hipLaunchKernelGGL(color_stats_kernel, dim3(grid.x, (crop + STATS_ROWS - 1) / STATS_ROWS, n), dim3(256), 0, stream, p);
+    } else {
+        hipLaunchKernelGGL(preprocess_color_f32_kernel, grid, dim3(256), 0, stream, p);
+    }
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+__global__ __launch_bounds__(256) void color_params_kernel(unsigned long long seed, unsigned long long call, long long first_frame, long long n, float sb,
+                                                           float sc, float ss, uint32_t *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t w[4];
+    color_params(seed, call, (uint64_t)(first_frame + i), sb, sc, ss, w);
+    out[4 * i] = w[0]; out[4 * i + 1] = w[1]; out[4 * i + 2] = w[2]; out[4 * i + 3] = w[3];
 }
 
 __global__ __launch_bounds__(256) void crop_windows_kernel(unsigned long long seed, unsigned long long call, long long first_frame, long long n, int max_top,
@@ -238,6 +388,38 @@ pvr_status pvr_op_crop_windows(uint64_t seed, uint64_t call, int64_t first_frame
                 max_top, max_left);
     hipLaunchKernelGGL(pvr::crop_windows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long)seed,
                        (unsigned long long)call, (long long)first_frame, (long long)n, (int)max_top, (int)max_left, windows);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+pvr_status pvr_op_preprocess_color(const uint8_t *frames, int32_t n, int32_t h, int32_t w, int32_t resize, int32_t crop, const float *mean,
+                                   const float *std_, const int32_t *windows, const void *color, uint32_t *gray_sums, float *out, void *stream) {
+    PVR_REQUIRE(frames && mean && std_ && windows && out, "pvr_op_preprocess_color: null argument");
+    PVR_REQUIRE(color, "pvr_op_preprocess_color: null color_dev (n x (float b, float c, float s, int32 order) of device memory)");
+    PVR_REQUIRE(gray_sums, "pvr_op_preprocess_color: null gray_sums_dev (n uint32 of device scratch, the caller's)");
+    for (int stage = 0; stage < 2; ++stage)
+        if (pvr_status s = pvr::launch_color_stage(stage, frames, n, h, w, resize, crop, mean, std_, windows, color, gray_sums, out, (hipStream_t)stream))
+            return s;
+    return PVR_OK;
+}
+
+void pvr_host_color_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float strength_b, float strength_c, float strength_s,
+                           void *params) {
+    for (int64_t i = 0; params && i < n; ++i)
+        pvr::color_params(seed, call, (uint64_t)(first_frame + i), strength_b, strength_c, strength_s, (uint32_t *)params + 4 * i);
+}
+
+pvr_status pvr_op_color_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float strength_b, float strength_c, float strength_s,
+                               void *params, void *stream) {
+    PVR_REQUIRE(params, "pvr_op_color_params: null color_dev (n x (float b, float c, float s, int32 order) of device memory)");
+    PVR_REQUIRE(((uintptr_t)params & 3) == 0, "pvr_op_color_params: color_dev %p is not 4-byte aligned (four 32-bit words per frame)", params);
+    PVR_REQUIRE(n >= 1 && n <= (1ll << 31), "pvr_op_color_params: n = %lld frames (1 .. 2^31)", (long long)n);
+    PVR_REQUIRE(first_frame >= 0, "pvr_op_color_params: first_frame = %lld (a frame index of the step, 0 or above)", (long long)first_frame);
+    PVR_REQUIRE(strength_b >= 0.f && strength_c >= 0.f && strength_s >= 0.f && strength_b <= 3.4e38f && strength_c <= 3.4e38f && strength_s <= 3.4e38f,
+                "pvr_op_color_params: strengths %g, %g, %g (brightness, contrast, saturation: finite, 0 or above; 0 leaves that factor at 1)",
+                (double)strength_b, (double)strength_c, (double)strength_s);
+    hipLaunchKernelGGL(pvr::color_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long)seed,
+                       (unsigned long long)call, (long long)first_frame, (long long)n, strength_b, strength_c, strength_s, (uint32_t *)params);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
 }

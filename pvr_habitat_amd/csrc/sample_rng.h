@@ -50,4 +50,24 @@ __host__ __device__ inline void crop_window(uint64_t seed, uint64_t call, uint64
     *left = (int32_t)(((uint64_t)c[1] * (uint64_t)((max_left < 0 ? 0 : max_left) + 1)) >> 32);
 }
 
+// The colour-jitter parameters of one frame (pvr_op_color_params / pvr_host_color_params, include/pvr_train.h): counter (frame, call) as crop_window's,
+// key (seed_lo, seed_hi ^ 'COLR'), so the stream is independent of the windows' and leaves them untouched.  Words 0 .. 2 give the brightness, contrast
+// and saturation factors, torchvision's ranges: factor = fma(hi - lo, u, lo) with u = uniform_open01(bits), lo = max(0, 1 - strength), hi = 1 + strength
+// (strength 0: fma(0, u, 1) = 1 exactly); word 3 gives the order code (bits * 6) >> 32 in 0 .. 5, the index of the frame's permutation of (brightness,
+// contrast, saturation) in lexicographic order.  out: four 32-bit words, float b, float c, float s, int32 order.  The only multiply-add is the fma
+// written out, so host and device agree bit for bit.  A negative or NaN strength counts as 0 (the callers refuse it before).
+__host__ __device__ inline void color_params(uint64_t seed, uint64_t call, uint64_t frame, float strength_b, float strength_c, float strength_s,
+                                             uint32_t *out) {
+    uint32_t c[4] = {(uint32_t)frame, (uint32_t)(frame >> 32), (uint32_t)call, (uint32_t)(call >> 32)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32) ^ 0x434F4C52u);
+    const float strength[3] = {strength_b, strength_c, strength_s};
+    for (int j = 0; j < 3; ++j) {
+        const float s = strength[j] > 0.f ? strength[j] : 0.f;
+        const float lo = fmaxf(0.f, 1.0f - s), hi = 1.0f + s;
+        const float f = fmaf(hi - lo, uniform_open01(c[j]), lo);
+        __builtin_memcpy(&out[j], &f, 4);
+    }
+    out[3] = (uint32_t)(((uint64_t)c[3] * 6u) >> 32);
+}
+
 }  // namespace pvr

@@ -396,6 +396,7 @@ class _EncoderFunction(torch.autograd.Function):
         ctx.model, ctx.gen, ctx.frames = model, model._fwd_gen, frames_u8
         ctx.boundary, model._boundary = model._boundary, None       # (prefix_once: the cache lives on the node, exactly as long as the frames do)
         ctx.windows, model._windows = model._windows, None          # (random_crop: the step's windows, for the recompute passes that run the stem again)
+        ctx.color, model._color = model._color, None                # (color_jitter: the step's parameters, parked and handed on exactly as the windows are)
         return out
 
     @staticmethod
@@ -406,8 +407,8 @@ class _EncoderFunction(torch.autograd.Function):
                                'encoder overwrote them (one backward per forward, right after it)')
         dout = dout.contiguous().float()
         g = torch.empty_like(m._flat)
-        m._backward_raw(ctx.frames, dout, g, ctx.boundary, ctx.windows)
-        ctx.frames = ctx.boundary = ctx.windows = None
+        m._backward_raw(ctx.frames, dout, g, ctx.boundary, ctx.windows, ctx.color)
+        ctx.frames = ctx.boundary = ctx.windows = ctx.color = None
         return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._trained_slots)
 
 
@@ -518,13 +519,27 @@ class HipTrainableResNet(_Node):
     recompute passes start at the boundary tensor as without the mode.  crop_call, a plain int attribute, then goes up by one: a caller that sets it
     (the driver: the iteration's number) makes a resumed run draw what an uninterrupted one would, and crop_windows(crop_seed, call, n, max_top,
     max_left) predicts a step's windows on the host.  Off by default; with it off nothing moves.  Eval mode keeps the centre crop on the frozen 'f32'
-    plan.  Not with prefix_cache, build_prefix_cache or forward_cached: a cache holds the prefix's output for ONE window per frame."""
+    plan.  Not with prefix_cache, build_prefix_cache or forward_cached: a cache holds the prefix's output for ONE window per frame.
+
+    color_jitter: brightness, contrast and saturation per frame and step - torchvision's ColorJitter on the uint8 values of the frame's 224 x 224 window,
+    after Resize and the window and before / 255 and Normalize, where T.ColorJitter would sit in the reference's transforms.  (b, c, s) are the three
+    strengths, a scalar means all three, None or zeros mean off: a factor is uniform in [max(0, 1 - strength), 1 + strength], and every frame gets its own
+    random order of the three ops.  Hue is not offered.  In training mode the step's (n, 4) parameters (float b, c, s and the int32 order code,
+    include/pvr_train.h) are drawn once on the device (pvr_op_color_params with seed = color_seed and call = crop_call, the SAME per-forward counter
+    random_crop uses, which goes up by one per training forward whenever either mode is on); every pass is handed its rows
+    (pvr_trainer_forward_augmented: the launches "colour stats" and "preprocess colour" write the jittered fp32 image), and so is every recompute pass
+    that runs the stem again.  Without random_crop every frame's window is the centre one.  color_params(color_seed, call, n, strengths) predicts a
+    step's parameters on the host.  Off by default; with it off nothing moves, and random_crop's windows keep their bits with it on.  Eval mode keeps
+    the un-jittered centre crop.  Not with prefix_cache, build_prefix_cache or forward_cached: a cache holds the prefix's output for ONE image per frame;
+    prefix_once is the compatible mode."""
 
     def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0):
+                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0):
         super().__init__()
         assert variant in _TRAINABLE, variant
         check_random_crop(random_crop, prefix_cache)
+        strengths = color_strengths(color_jitter)
+        check_color_jitter(strengths, prefix_cache)
         _lib.require_gpu()
         self.variant = variant
         self.out_size = OUT_SIZE[variant]
@@ -564,6 +579,10 @@ class HipTrainableResNet(_Node):
         self.crop_seed = int(crop_seed)          # random_crop: Philox key of the windows
         self.crop_call = 0                       # random_crop: the next training forward's draw; it goes up by one per forward and a caller may set it
         self._windows = None                     # random_crop: the step's windows between _forward_raw and its consumer (parked as _boundary is)
+        self._color_jitter = strengths           # color_jitter: the three strengths, None when off
+        self.color_seed = int(color_seed)        # color_jitter: Philox key of the parameters (the call number is crop_call)
+        self._color = None                       # color_jitter: the step's parameters between _forward_raw and its consumer (parked as _windows is)
+        self._gray_sums = None                   # color_jitter: max_batch uint32 of scratch for a pass's gray sums (the trainer's workspace holds none)
         self._resize, self._crop = int(tr.resize), int(tr.crop)
         if self._prefix_once or self._prefix_cache:
             _lib.check(L.pvr_trainer_set_prefix_fused(h, 1))
@@ -673,6 +692,11 @@ class HipTrainableResNet(_Node):
         """a training forward crops a random window per frame (see the class docstring)"""
         return self._random_crop
 
+    @property
+    def color_jitter(self):
+        """the (brightness, contrast, saturation) strengths of a training forward's colour jitter, None when off (see the class docstring)"""
+        return self._color_jitter
+
     def crop_range(self, h, w):
         """(max_top, max_left) of an (h, w) frame's window: its size after Resize minus the crop (32, 32 for square frames)"""
         rh, rw = resized_size(h, w, self._resize)
@@ -693,6 +717,7 @@ class HipTrainableResNet(_Node):
         if self._train_from is None:
             raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
         check_random_crop(self._random_crop, True, 'build_prefix_cache')
+        check_color_jitter(self._color_jitter, True, 'build_prefix_cache')
         return self._build_prefix_cache(int(frames_u8.shape[0]), [(0, frames_u8)])
 
     def _build_prefix_cache(self, n_frames, blocks):
@@ -701,6 +726,7 @@ class HipTrainableResNet(_Node):
         if self._train_from is None:
             raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
         check_random_crop(self._random_crop, True, 'build_prefix_cache')
+        check_color_jitter(self._color_jitter, True, 'build_prefix_cache')
         L = _lib.lib()
         _lib.check(L.pvr_trainer_set_prefix_fused(self._handle, 1))
         vp = lambda t: C.c_void_p(t.data_ptr())
@@ -740,6 +766,7 @@ class HipTrainableResNet(_Node):
         """training-mode forward of the frames behind `rows` (int64 device tensor, one row of `cache` per frame): embeddings with a graph that hands
         only the trained parameters to autograd.  The bits of forward(frames[rows])."""
         check_random_crop(self._random_crop, True, 'forward_cached')
+        check_color_jitter(self._color_jitter, True, 'forward_cached')
         self.check_prefix_cache(cache)
         if not self.training:
             raise RuntimeError('forward_cached is a training-mode forward (the cache holds the input of the trained stages): in eval mode embed the '
@@ -832,15 +859,37 @@ class HipTrainableResNet(_Node):
             self._windows = torch.empty((n, 2), dtype=torch.int32, device=frames_u8.device)
             _lib.check(_lib.lib().pvr_op_crop_windows(self.crop_seed, self.crop_call, 0, n, max_top, max_left, C.c_void_p(self._windows.data_ptr()),
                                                       _lib.stream_ptr()))
+        # color_jitter: the step's parameters, drawn once under the same call number and parked the same way; without random_crop every frame's window
+        # is the centre one
+        self._color = None
+        if self._color_jitter is not None:
+            max_top, max_left = self.crop_range(h, w)
+            if self._windows is None:
+                self._windows = torch.tensor([int(round(max_top / 2.0)), int(round(max_left / 2.0))], dtype=torch.int32,
+                                             device=frames_u8.device).repeat(n, 1)
+            self._color = torch.empty((n, 4), dtype=torch.int32, device=frames_u8.device)
+            _lib.check(_lib.lib().pvr_op_color_params(self.color_seed, self.crop_call, 0, n, *self._color_jitter, C.c_void_p(self._color.data_ptr()),
+                                                      _lib.stream_ptr()))
+        if self._random_crop or self._color_jitter is not None:
             self.crop_call += 1
         for lo, hi in self._passes(n):            # (one pass unless BatchNorm is frozen; the last pass's activations stay held)
-            self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary, windows=self._windows)
+            self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary, windows=self._windows, color=self._color)
         return out
 
-    def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False, windows=None):
+    def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False, windows=None, color=None):
         """one pass over frames [lo, hi).  boundary: the step's (n, boundary_floats) cache - this pass writes its rows (reuse False) or starts at the first
-        trained op on what they hold (reuse True).  windows (random_crop): the step's (n, 2) int32 windows - this pass crops at its rows"""
+        trained op on what they hold (reuse True).  windows (random_crop): the step's (n, 2) int32 windows - this pass crops at its rows.  color
+        (color_jitter, with windows): the step's (n, 4) parameters - this pass jitters its rows"""
         vp = lambda t: C.c_void_p(t.data_ptr())
+        if color is not None:
+            reuse = reuse and boundary is not None                            # (as below: without a boundary cache a recompute pass makes the same image again)
+            if self._gray_sums is None:
+                self._gray_sums = torch.empty((self._max_batch,), dtype=torch.int32, device=color.device)
+            _lib.check(_lib.lib().pvr_trainer_forward_augmented(self._handle, vp(self._flat), vp(self._bufs), None if reuse else vp(frames_u8[lo:hi]), hi - lo,
+                                                                frames_u8.shape[1], frames_u8.shape[2], vp(windows[lo:hi]), vp(color[lo:hi]),
+                                                                vp(self._gray_sums), None if boundary is None else vp(boundary[lo:hi]),
+                                                                1 if reuse else 0, vp(out), out.stride(0), _lib.stream_ptr()))
+            return
         if windows is not None:
             reuse = reuse and boundary is not None                            # (without a boundary cache a recompute pass runs the stem again, at the same windows)
             _lib.check(_lib.lib().pvr_trainer_forward_windows(self._handle, vp(self._flat), vp(self._bufs), None if reuse else vp(frames_u8[lo:hi]), hi - lo,
@@ -857,18 +906,20 @@ class HipTrainableResNet(_Node):
                                                            h, w, vp(boundary[lo:hi]), 1 if reuse else 0, vp(out),
                                                            out.stride(0), _lib.stream_ptr()))
 
-    def _backward_raw(self, frames_u8, dout, grads, boundary=None, windows=None):
+    def _backward_raw(self, frames_u8, dout, grads, boundary=None, windows=None, color=None):
         """d(loss)/d(embeddings) of the training forward that just ran on frames_u8 -> the flat gradient `grads` (fully written).  One pass: one
         pvr_trainer_backward.  Several (frozen BatchNorm): the last pass first - its activations are still held - then every other pass in frame
         order, each recomputed and added by pvr_trainer_backward_acc.  boundary (prefix_once): the cache that forward filled; a recomputed pass
         starts at the first trained op on its rows.  windows (random_crop): the windows that forward drew; a recomputed pass that runs the stem crops
-        at its rows again."""
+        at its rows again.  color (color_jitter): the parameters that forward drew, for the same passes."""
         L = _lib.lib()
         vp = lambda t: C.c_void_p(t.data_ptr())
         passes = self._passes(frames_u8.shape[0])
         assert dout.shape[0] == frames_u8.shape[0] and dout.stride(1) == 1
         assert (boundary is not None) == self._prefix_once, 'prefix_once: the backward takes the boundary cache of its forward'
-        assert (windows is not None) == self._random_crop, 'random_crop: the backward takes the windows of its forward'
+        assert (windows is not None) == (self._random_crop or self._color_jitter is not None), \
+            'random_crop / color_jitter: the backward takes the windows of its forward'
+        assert (color is not None) == (self._color_jitter is not None), 'color_jitter: the backward takes the colour parameters of its forward'
         if len(passes) == 1:
             _lib.check(L.pvr_trainer_backward(self._handle, vp(self._flat), vp(dout), dout.stride(0), vp(grads), _lib.stream_ptr()))
             return
@@ -878,7 +929,7 @@ class HipTrainableResNet(_Node):
         again = torch.empty((self._max_batch, self.out_size), dtype=torch.float32, device=dout.device)       # the recomputed embeddings are not used
         for i, (lo, hi) in enumerate(passes[-1:] + passes[:-1]):
             if i:
-                self._forward_pass(frames_u8, lo, hi, again[:hi - lo], boundary, reuse=True, windows=windows)
+                self._forward_pass(frames_u8, lo, hi, again[:hi - lo], boundary, reuse=True, windows=windows, color=color)
             _lib.check(L.pvr_trainer_backward_acc(self._handle, vp(self._flat), vp(dout[lo:hi]), dout.stride(0), vp(grads), 1 if i else 0, vp(sc), sc.numel(),
                                                   _lib.stream_ptr()))
 
@@ -960,6 +1011,49 @@ def check_random_crop(random_crop, prefix_cache=False, what='prefix_cache'):
         raise ValueError('random_crop with %s: the cache holds the frozen prefix\'s output for ONE window per frame (the deterministic centre crop), and a '
                          'random crop moves the window in every step; prefix_once, which keeps the prefix\'s output for the frames and windows of one '
                          'step, is the compatible mode' % what)
+
+
+def color_strengths(color_jitter):
+    """the color_jitter keyword -> the (brightness, contrast, saturation) strengths as fp32 values, or None when the mode is off (None, 0 or all zeros); a
+    scalar means all three.  A ValueError names a negative or non-finite strength, and a value that is neither a number nor three of them"""
+    if color_jitter is None or color_jitter is False:
+        return None
+    try:
+        v = tuple(float(x) for x in color_jitter) if hasattr(color_jitter, '__len__') else (float(color_jitter),) * 3
+    except (TypeError, ValueError):
+        v = ()
+    if len(v) != 3:
+        raise ValueError('color_jitter=%r: one strength for all of brightness, contrast and saturation, or the three of them (hue is not offered)'
+                         % (color_jitter,))
+    if not all(np.isfinite(x) and 0 <= x <= 3e38 for x in v):
+        raise ValueError('color_jitter=%r: a strength is a finite number, 0 or above (a factor is drawn from [max(0, 1 - strength), 1 + strength]; 0 '
+                         'leaves that factor at 1, and all zeros switch the mode off)' % (color_jitter,))
+    v = tuple(float(np.float32(x)) for x in v)
+    return v if any(v) else None
+
+
+def color_params(seed, call, n, strengths, first_frame=0):
+    """the n parameter rows color_jitter draws for frames first_frame .. first_frame + n of training forward number `call` under color_seed `seed`: a
+    structured array with the fields b, c, s (float32 factors) and order (int32, 0 .. 5: the permutation of (brightness, contrast, saturation) in
+    lexicographic order), 16 bytes per row as the device holds them.  pvr_host_color_params: host arithmetic, no GPU needed; bit for bit what the device
+    draws.  strengths: a scalar or (b, c, s)"""
+    v = color_strengths(strengths) or (0.0, 0.0, 0.0)
+    out = np.zeros(int(n), COLOR_DTYPE)
+    if n > 0:
+        _lib.lib().pvr_host_color_params(int(seed), int(call), int(first_frame), int(n), v[0], v[1], v[2], out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+COLOR_DTYPE = np.dtype([('b', np.float32), ('c', np.float32), ('s', np.float32), ('order', np.int32)])
+
+
+def check_color_jitter(strengths, prefix_cache=False, what='prefix_cache'):
+    """color_jitter changes a frame's image from step to step: a ValueError together with the prefix cache (`what` names the keyword or the method).
+    strengths: what color_strengths returned"""
+    if strengths is not None and prefix_cache:
+        raise ValueError('color_jitter with %s: the cache holds the frozen prefix\'s output for ONE image per frame (the un-jittered centre crop), and the '
+                         'jitter changes the image in every step; prefix_once, which keeps the prefix\'s output for the frames and images of one step, '
+                         'is the compatible mode' % what)
 
 
 def check_prefix_once(prefix_once, train_from):
@@ -1057,7 +1151,8 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
 
 
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
-                   conv_split16=False, train_from=None, prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0):
+                   conv_split16=False, train_from=None, prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None,
+                   color_seed=0):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -1067,6 +1162,8 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     check_prefix_once(prefix_once, train_from)
     check_prefix_cache(prefix_cache, train_from)
     check_random_crop(random_crop, prefix_cache)
+    strengths = color_strengths(color_jitter)
+    check_color_jitter(strengths, prefix_cache)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
@@ -1075,7 +1172,8 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     return HipTrainableResNet(sd, variant, max_batch=max_batch, freeze_bn=freeze_bn, wgrad_split16=wgrad_split16, conv_split16=conv_split16,
                               **({'train_from': train_from} if train_from is not None else {}), **({'prefix_once': True} if prefix_once else {}),
                               **({'prefix_cache': True} if prefix_cache else {}),
-                              **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}))
+                              **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}),
+                              **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}))
 
 
 class UberModel(nn.Module):
@@ -1271,7 +1369,7 @@ class EmbeddingNet(nn.Module):
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
                  compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0):
+                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -1305,6 +1403,12 @@ class EmbeddingNet(nn.Module):
             raise ValueError('random_crop is a mode of the trainable encoder (train=True): a frozen encoder embeds the centre crop of every frame (crops=5 '
                              'adds the four corner windows)')
         check_random_crop(random_crop, prefix_cache)
+        strengths = color_strengths(color_jitter)                # (a ValueError names a negative or non-finite strength)
+        if strengths is not None and not train:
+            raise ValueError('color_jitter is a mode of the trainable encoder (train=True): a frozen encoder embeds the un-jittered centre crop of every '
+                             'frame')
+        check_color_jitter(strengths, prefix_cache)
+        # color_jitter (train=True only): a training forward jitters brightness, contrast and saturation per frame; color_seed keys the draw
         # random_crop (train=True only): a training forward crops a random window per frame; crop_seed keys the draw (HipTrainableResNet.crop_call counts it)
         # prefix_cache (train=True with train_from only): the workspace mode of cached steps (build_prefix_cache / forward_cached of the encoder)
         # prefix_once (train=True with train_from only): the frozen prefix runs once per frame and step; its boundary tensor is kept across the passes
@@ -1319,7 +1423,8 @@ class EmbeddingNet(nn.Module):
                                                          **({'train_from': train_from} if train_from is not None else {}),
                                                          **({'prefix_once': True} if prefix_once else {}),
                                                          **({'prefix_cache': True} if prefix_cache else {}),
-                                                         **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}))
+                                                         **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}),
+                                                         **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

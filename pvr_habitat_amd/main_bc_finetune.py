@@ -105,6 +105,27 @@ def check_random_crop_flag(flags):
     return on
 
 
+def check_color_jitter_flag(flags):
+    """--embedding_color_jitter B C S is a mode of --train_embedding, and not of --embedding_prefix_cache: a ValueError otherwise, and for a negative or
+    non-finite strength.  -> the three strengths, or None when the mode is off (no flag, or 0 0 0)"""
+    given = getattr(flags, 'embedding_color_jitter', None)
+    if given is None:
+        return None
+    from .embeddings import color_strengths
+    try:
+        strengths = color_strengths(tuple(given))
+    except ValueError as e:
+        raise ValueError('--embedding_color_jitter: %s' % e)
+    if strengths is not None and not getattr(flags, 'train_embedding', False):
+        raise ValueError('--embedding_color_jitter needs --train_embedding: it jitters brightness, contrast and saturation per frame in the training '
+                         'steps of a trainable encoder (a frozen encoder embeds the un-jittered centre crop)')
+    if strengths is not None and getattr(flags, 'embedding_prefix_cache', False):
+        raise ValueError('--embedding_color_jitter with --embedding_prefix_cache: the cache holds the frozen prefix\'s output for ONE image per frame (the '
+                         'un-jittered centre crop), and the jitter changes the image in every step; --embedding_prefix_once, which keeps the prefix\'s '
+                         'output for the frames and images of one step, is the compatible mode')
+    return strengths
+
+
 def prefix_cache_bytes(flags, n_dataset_frames):
     """--embedding_prefix_cache: (bytes of the boundary tensors of all n_dataset_frames = samples x frames dataset frames, bytes per frame of a pass's
     staging tensor), both next to the workspace; (0, 0) without the flag"""
@@ -245,6 +266,10 @@ def run_end_to_end(flags, make_env=None):
     random_crop = check_random_crop_flag(flags)
     if random_crop:
         print('  ', 'random crop: every frame of a step is cropped at its own random window, seed %d (--embedding_random_crop)' % flags.run_id)
+    color_jitter = check_color_jitter_flag(flags)
+    if color_jitter is not None:
+        print('  ', 'colour jitter: every frame of a step gets its own brightness, contrast and saturation factor, strengths %g %g %g, in a random '
+              'order, seed %d (--embedding_color_jitter)' % (color_jitter + (flags.run_id,)))
     world = max(rank_world()[1], int(os.environ.get('WORLD_SIZE', '1')))
     if world > 1:
         raise NotImplementedError('--train_embedding with a world size of %d: data-parallel encoder training is not built (the trainable encoder and its '
@@ -301,6 +326,8 @@ def run_end_to_end(flags, make_env=None):
         split16 = dict(split16, prefix_cache=True)
     if random_crop:                                             # (the parameters do not depend on the mode: a resume may switch it on or off)
         split16 = dict(split16, random_crop=True, crop_seed=flags.run_id)
+    if color_jitter is not None:                                # (likewise)
+        split16 = dict(split16, color_jitter=color_jitter, color_seed=flags.run_id)
     if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
         if not flags.pretrained_embedding:
             print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')
@@ -344,7 +371,7 @@ def run_end_to_end(flags, make_env=None):
               % (pc.n_frames, pc.nbytes / 2 ** 30, pc.fill_seconds, pc.n_frames / max(pc.fill_seconds, 1e-9)))
     for frames in range(init_frames, flags.max_frames, B * T):
         epoch = frames // (B * T)
-        model.embedding.crop_call = epoch                       # (--embedding_random_crop: the iteration names the draw, so a resumed run draws what an uninterrupted one would)
+        model.embedding.crop_call = epoch                       # (--embedding_random_crop, --embedding_color_jitter: the iteration names the draw, so a resumed run draws what an uninterrupted one would)
         starting_i = sample_with_minimum_distance(n=n_samples, k=B, d=T)
         if prefix_cache:                                        # (T, B) sample indices: a step reads its frames' boundary tensors, no uint8 frame
             o = dataset.rows(starting_i, T)
@@ -402,6 +429,7 @@ def run(flags, make_env=None):
     check_prefix_once_flag(flags)
     check_prefix_cache_flag(flags)
     check_random_crop_flag(flags)
+    check_color_jitter_flag(flags)
     if getattr(flags, 'train_embedding', False):
         return run_end_to_end(flags, make_env)
     rank, world = rank_world()
