@@ -258,6 +258,50 @@ pvr_status pvr_trainer_forward_augmented(pvr_trainer *tr, const float *params_de
                                          int32_t w, const int32_t *windows_dev, const void *color_dev, uint32_t *gray_sums_dev, float *boundary_dev,
                                          int32_t reuse, float *out_dev, int64_t out_stride, void *hip_stream);
 
+/* Random resized crop per frame and step (the Python mode random_resized_crop): torchvision's RandomResizedCrop(crop, scale = (lo, hi), ratio = (3/4, 4/3))
+ * of the ORIGINAL uint8 frame - a rectangle of random area and aspect ratio, resized to crop x crop - in the place of Resize plus the window, before the
+ * colour jitter, / 255 and Normalize.  A frame's rectangle is four int32: top, left, height, width, in the h x w frame.
+ * pvr_op_crop_rects / pvr_host_crop_rects: the rectangles of frames first_frame .. first_frame + n into device / host memory (n x 4 int32), by
+ *   get_params' rule.  Up to 10 tries; try t of frame f draws four words from Philox-4x32-10 with counter (f, call), as the windows do, and key (seed_lo,
+ *   (seed_hi ^ 0x52454354) + t * 0x9E3779B9): a stream of its own, so pvr_op_crop_windows and pvr_op_color_params keep their bits at the same (seed, call).
+ *   area = (h w) * fma(hi - lo, u, lo), u uniform in (0, 1); r one of 256 constants, the midpoints exp(log(3/4) + (k + 0.5) / 256 * log(16/9)) of the
+ *   log-uniform range, k the word's top 8 bits; width = rint(sqrt(area r)), height = rint(sqrt(area / r)); accepted if 0 < width <= w and 0 < height <= h,
+ *   with top = (bits * (h - height + 1)) >> 32 and left likewise.  After 10 refused tries torchvision's fallback: the whole frame if 3/4 <= w / h <= 4/3,
+ *   else the centred rectangle of the nearest ratio bound.  torchvision draws log r from a continuous uniform; the 256 midpoints keep its mean and lower its
+ *   variance by 1.5e-5 of itself, far below what the rounding to whole pixels does; no exp or log runs at draw time, and every float operation is one
+ *   correctly rounded +, -, *, /, sqrt, fma or rint, so both functions (one inline, csrc/sample_rng.h) agree bit for bit.  torch's generator is not
+ *   reproduced: the contract is the distribution plus determinism.  The result depends on (seed, call, frame, h, w, lo, hi) alone: rows lo .. hi of one
+ *   draw equal a draw with first_frame = lo.  pvr_op_crop_rects refuses by name, launching nothing: a null or not 4-byte aligned rects_dev, n < 1, a
+ *   negative first_frame, h or w below 1, a scale that is not finite or not 0 < lo <= hi <= 1; the host function treats such a scale as (1, 1) and writes
+ *   nothing through a null pointer.
+ * pvr_op_preprocess_rects: frames -> each frame's rectangle resized to crop x crop -> / 255 -> Normalize, the dense fp32 NHWC4 image.  The resize is
+ *   F.interpolate(bilinear, align_corners=False) of the cropped array and round-half-even, in the rounding order of pvr_op_preprocess_windows: per frame and
+ *   axis scale = (float)size / (float)crop, source index fma(scale, dst + 0.5, -0.5) clamped at 0, taps clamped to the rectangle's last row and column
+ *   (not the frame's), each two-tap sum fma(w0, a, round(w1 b)) along x and then y; a crop x crop rectangle is a plain copy.  Hardened in the kernel:
+ *   height is clamped to [1, h], width to [1, w], top to [0, h - height], left to [0, w - width]: no value of the array can make a lane read outside its
+ *   frame or write a NaN.  color_dev == NULL: one launch, "preprocess rects", one 16-byte store per pixel.  color_dev != NULL needs gray_sums_dev and runs
+ *   the launches "colour stats" and "preprocess colour" of pvr_op_preprocess_color with the rectangle as their pixel source (the same kernels,
+ *   instantiated for it), with that op's checks and scratch rules; no atomics beyond its integer gray sums, two runs give the same bits.  Refused by
+ *   name, launching nothing: a null frames, mean, std_, rects_dev or out_dev, a non-positive n, h, w or crop, rects_dev not 4-byte or out_dev not 16-byte
+ *   aligned, more than 65535 frames, and with colour a null or misaligned gray_sums_dev, a misaligned color_dev, a crop above 256.  No Resize comes before
+ *   the rectangle, so a frame smaller than the crop is legal.
+ * pvr_trainer_forward_rects, rects_dev == NULL: exactly pvr_trainer_forward_augmented with null windows - the same launches, names, bits and refusals.
+ *   rects_dev != NULL: "preprocess rects", or with color_dev the colour pair, stands where "preprocess" + "normalize", "preprocess windows" or the colour
+ *   pair stood; everything after is unchanged, and the held forward's image is the cropped one, so conv1's weight gradient sees it.  reuse != 0 (with
+ *   boundary_dev): nothing before the first trained op runs and neither array is read.  The handle keeps nothing about rectangles: a recompute pass that
+ *   runs the stem again is handed the same rows again.  The descriptor's resize is not used by this path.  pvr_trainer_prefix_forward keeps the plain
+ *   centre crop.  Refused by name, launching nothing: what pvr_trainer_forward_augmented refuses for boundary_dev, n, the frames and the colour
+ *   arguments, and a rects_dev that is not 4-byte aligned. */
+pvr_status pvr_op_crop_rects(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t h, int32_t w, float scale_lo, float scale_hi,
+                             int32_t *rects_dev, void *hip_stream);
+void pvr_host_crop_rects(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t h, int32_t w, float scale_lo, float scale_hi,
+                         int32_t *rects_host);
+pvr_status pvr_op_preprocess_rects(const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, int32_t crop, const float *mean, const float *std_,
+                                   const int32_t *rects_dev, const void *color_dev, uint32_t *gray_sums_dev, float *out_dev, void *hip_stream);
+pvr_status pvr_trainer_forward_rects(pvr_trainer *tr, const float *params_dev, void *bn_buffers_dev, const uint8_t *frames_dev, int32_t n, int32_t h,
+                                     int32_t w, const int32_t *rects_dev, const void *color_dev, uint32_t *gray_sums_dev, float *boundary_dev,
+                                     int32_t reuse, float *out_dev, int64_t out_stride, void *hip_stream);
+
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
  * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */

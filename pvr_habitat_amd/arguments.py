@@ -75,6 +75,15 @@ def make_parser():
                              'resumed run draws what an uninterrupted one would, and a run may be resumed with or without the flag.  Not with '
                              '--embedding_prefix_cache, whose cache holds the frozen prefix\'s output for ONE image per frame; --embedding_prefix_once is '
                              'the compatible mode')
+    parser.add_argument('--embedding_random_resized_crop', type=float, nargs=2, default=None, metavar=('LO', 'HI'),
+                        help='with --train_embedding: every frame of a training step is replaced by torchvision\'s RandomResizedCrop(224, scale=(LO, HI), '
+                             'ratio=(3/4, 4/3)) of the original frame - a rectangle whose area is uniform in [LO, HI] of the frame\'s and whose aspect ratio '
+                             'is log-uniform in [3/4, 4/3], resized to 224 x 224 - instead of Resize(256) and the centre crop (MoCo\'s crop is 0.2 1; '
+                             'evaluation keeps Resize(256) and the centre crop).  Default off.  The rectangles are a function of --run_id, the iteration and '
+                             'the frame, so a resumed run draws what an uninterrupted one would, and a run may be resumed with or without the flag.  Composes '
+                             'with --embedding_color_jitter.  Not with --embedding_random_crop (both choose the window), and not with '
+                             '--embedding_prefix_cache, whose cache holds the frozen prefix\'s output for ONE window per frame; --embedding_prefix_once is '
+                             'the compatible mode')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

@@ -65,6 +65,12 @@ pvr_status launch_preprocess_windows(const uint8_t *frames, int n, int h, int w,
 // sums and adds every frame's gray values before contrast, stage 1 writes the image; each checks every argument before it launches
 pvr_status launch_color_stage(int stage, const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
                               const int32_t *windows, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream);
+// frames -> each frame's own rectangle (rects: n x (top, left, height, width) int32 on the device, in the h x w frame, clamped in the kernel) resized to
+// crop x crop -> the dense fp32 NHWC4 image, one launch; and the same with colour jitter, as launch_color_stage's two launches
+pvr_status launch_preprocess_rects(const uint8_t *frames, int n, int h, int w, int crop, const float *mean, const float *std_, const int32_t *rects,
+                                   float *out, hipStream_t stream);
+pvr_status launch_color_stage_rects(int stage, const uint8_t *frames, int n, int h, int w, int crop, const float *mean, const float *std_,
+                                    const int32_t *rects, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream);
 pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
 pvr_status launch_maxpool(const void *, void *, int, int, int, int, int, hipStream_t);
 // (c1_*: layer1.0.conv1 inside the stem - stem.hip, StemC1; only when stem_conv1_capable(sw))

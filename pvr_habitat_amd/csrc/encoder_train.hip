@@ -424,10 +424,12 @@ namespace {
 // same launches up to there, nothing written but the boundary tensor and the prefix's own buffers, and no forward is held.  windows
 // (pvr_trainer_forward_windows): n x (top, left) on the device - the image is each frame's window instead of the centre crop, made by one launch.
 // color, gray_sums (pvr_trainer_forward_augmented, with windows): n x (float b, c, s, int32 order) and n uint32 of the caller's scratch - the window's
-// uint8 values are colour-jittered before /255 and Normalize, by two launches in place of that one.
+// uint8 values are colour-jittered before /255 and Normalize, by two launches in place of that one.  rects (pvr_trainer_forward_rects, without windows):
+// n x (top, left, height, width) on the device - the image is each frame's own rectangle resized to crop x crop (no Resize before it), by one launch, or
+// with color by the two colour launches reading that source.
 pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *boundary, bool reuse,
                         float *out, int64_t out_stride, void *stream, bool prefix_only = false, const int32_t *windows = nullptr, const void *color = nullptr,
-                        uint32_t *gray_sums = nullptr) {
+                        uint32_t *gray_sums = nullptr, const int32_t *rects = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     pvr_status s;
     if ((s = ensure_workspace(t))) return s;
@@ -449,7 +451,13 @@ pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, c
                                        op.mean, op.rstd, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st);
     };
     if (!reuse) {
-        if (windows && color) {                   // a window and a colour jitter per frame: the gray sums contrast needs, then the image
+        if (rects && color) {                     // a random resized crop and a colour jitter per frame: the colour pair on the rectangle's pixels
+            TR_RUN("colour stats", 0, launch_color_stage_rects(0, frames, n, h, w, t->desc.crop, t->desc.mean, t->desc.std_, rects, color, gray_sums, t->d_imgf, st));
+            TR_RUN("preprocess colour", 0,
+                   launch_color_stage_rects(1, frames, n, h, w, t->desc.crop, t->desc.mean, t->desc.std_, rects, color, gray_sums, t->d_imgf, st));
+        } else if (rects) {                       // a random resized crop per frame: the frame's rectangle resized to the crop, /255 and Normalize
+            TR_RUN("preprocess rects", 0, launch_preprocess_rects(frames, n, h, w, t->desc.crop, t->desc.mean, t->desc.std_, rects, t->d_imgf, st));
+        } else if (windows && color) {                   // a window and a colour jitter per frame: the gray sums contrast needs, then the image
             TR_RUN("colour stats", 0, launch_color_stage(0, frames, n, h, w, t->desc.resize, t->desc.crop, t->desc.mean, t->desc.std_, windows, color, gray_sums,
                                                          t->d_imgf, st));
             TR_RUN("preprocess colour", 0, launch_color_stage(1, frames, n, h, w, t->desc.resize, t->desc.crop, t->desc.mean, t->desc.std_, windows, color,
@@ -622,6 +630,37 @@ pvr_status pvr_trainer_forward_augmented(pvr_trainer *t, const float *params, vo
     PVR_REQUIRE(t->desc.crop <= 256, "pvr_trainer_forward_augmented: crop %d (at most 256: the gray mean is exact while 255 crop^2 < 2^24)", t->desc.crop);
     TraceScope ts("pvr_trainer_forward_augmented");
     return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, false, out, out_stride, stream, false, windows, color, gray_sums);
+}
+
+pvr_status pvr_trainer_forward_rects(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,
+                                     const int32_t *rects, const void *color, uint32_t *gray_sums, float *boundary, int32_t reuse, float *out,
+                                     int64_t out_stride, void *stream) {
+    if (!rects || (boundary && reuse))            // no rectangle is read: the augmented entry point with null windows, with its own refusals
+        return pvr_trainer_forward_augmented(t, params, bn_buffers, frames, n, h, w, nullptr, color, gray_sums, boundary, reuse, out, out_stride, stream);
+    PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward_rects: null argument (only a reuse pass, which starts at the first trained "
+                "op, reads no frames)");
+    PVR_REQUIRE(((uintptr_t)rects & 3) == 0, "pvr_trainer_forward_rects: rects_dev %p is not 4-byte aligned (n x (top, left, height, width) int32)",
+                (const void *)rects);
+    if (color) {
+        PVR_REQUIRE(((uintptr_t)color & 3) == 0, "pvr_trainer_forward_rects: color_dev %p is not 4-byte aligned (n x (float b, float c, float s, int32 order))",
+                    color);
+        PVR_REQUIRE(gray_sums && ((uintptr_t)gray_sums & 3) == 0, "pvr_trainer_forward_rects: gray_sums_dev %p is null or not 4-byte aligned (n uint32 of "
+                    "device scratch, the caller's)", (void *)gray_sums);
+        PVR_REQUIRE(t->desc.crop <= 256, "pvr_trainer_forward_rects: crop %d (at most 256: the gray mean is exact while 255 crop^2 < 2^24)", t->desc.crop);
+    }
+    if (boundary && t->train_from <= 0) {
+        set_error("pvr_trainer_forward_rects: everything trains (pvr_trainer_set_train_from stage 0): there is no frozen prefix and no boundary tensor to "
+                  "keep; pass a null boundary_dev");
+        return PVR_ERR_STATE;
+    }
+    PVR_REQUIRE(((uintptr_t)boundary & 15) == 0, "pvr_trainer_forward_rects: boundary_dev %p is not 16-byte aligned (the launches move it as float4s)",
+                (void *)boundary);
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward_rects: %d frames, the workspace holds max_batch = %d (with frozen BatchNorm run the "
+                "frames as passes of at most max_batch, each with its own rows of the rectangles and colour parameters; batch statistics take the whole batch "
+                "together)", n, t->desc.max_batch);
+    PVR_REQUIRE(h > 0 && w > 0, "pvr_trainer_forward_rects: bad frame size h=%d w=%d", h, w);       // (no Resize on this path: a frame may be smaller than the crop)
+    TraceScope ts("pvr_trainer_forward_rects");
+    return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, false, out, out_stride, stream, false, nullptr, color, gray_sums, rects);
 }
 
 pvr_status pvr_trainer_prefix_forward(pvr_trainer *t, const float *params, const void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,

@@ -129,7 +129,7 @@ pvr_status launch_preprocess(const uint8_t *frames, int n, int h, int w, int res
 struct WinP {
     const uint8_t *src;
     float *dst;
-    const int32_t *windows;   // n x (top, left) in the resized frame; clamped here
+    const int32_t *windows;   // n x (top, left) in the resized frame; clamped here (the rect source: n x (top, left, height, width) in the frame itself)
     int n, h, w;              // source frame size
     int rh, rw;               // size after Resize
     int crop;
@@ -176,6 +176,56 @@ __device__ __forceinline__ void window_pixel(const WinP &p, int n, int y, int x,
     }
 }
 
+// Random resized crop (pvr_op_preprocess_rects, the trainer's "preprocess rects" launch): output pixel (x, y), x and y below crop, of frame n = the bilinear
+// resize of the frame's OWN rectangle (top, left, height, width) - in the h x w frame, no Resize before it - to crop x crop, as three uint8 values held in
+// floats: torchvision's resized_crop on a uint8 tensor, F.interpolate(bilinear, align_corners=False) of the cropped array and round-half-even, in
+// window_pixel's rounding order.  Per frame and per axis scale = (float)size / (float)crop; the taps are clamped to the rectangle's last row and column,
+// not the frame's - the crop comes first - and offset by (top, left).  A crop x crop rectangle is a plain copy (the same bits: at scale 1 the weights are 1
+// and 0).  p.windows holds n x 4 int32 here; p.rh, p.rw, p.resize_needed and the scales are not read.  Hardened: height is clamped to [1, h], width to
+// [1, w], top to [0, h - height], left to [0, w - width], so whatever the array holds every tap lies inside the frame and no value is a NaN.
+__device__ __forceinline__ void rect_pixel(const WinP &p, int n, int y, int x, float (&v)[3]) {
+    int top = p.windows[4 * n], left = p.windows[4 * n + 1], rh = p.windows[4 * n + 2], rw = p.windows[4 * n + 3];
+    rh = rh < 1 ? 1 : (rh > p.h ? p.h : rh);
+    rw = rw < 1 ? 1 : (rw > p.w ? p.w : rw);
+    top = top < 0 ? 0 : (top > p.h - rh ? p.h - rh : top);
+    left = left < 0 ? 0 : (left > p.w - rw ? p.w - rw : left);
+    const uint8_t *img = p.src + ((size_t)n * p.h * p.w + (size_t)top * p.w + left) * 3;      // the rectangle's pixel (0, 0); rows stay p.w pixels apart
+    if (rh == p.crop && rw == p.crop) {
+        const uint8_t *s = img + ((size_t)y * p.w + x) * 3;
+        v[0] = (float)s[0]; v[1] = (float)s[1]; v[2] = (float)s[2];
+    } else {
+#pragma clang fp contract(off)
+        const float scale_h = (float)rh / (float)p.crop, scale_w = (float)rw / (float)p.crop;
+        float sy = __builtin_fmaf(scale_h, (float)y + 0.5f, -0.5f);
+        float sx = __builtin_fmaf(scale_w, (float)x + 0.5f, -0.5f);
+        sy = sy < 0.f ? 0.f : sy;
+        sx = sx < 0.f ? 0.f : sx;
+        int y0 = (int)sy, x0 = (int)sx;
+        y0 = y0 > rh - 1 ? rh - 1 : y0;            // (never taken for y, x < crop; it keeps the taps inside the rectangle whatever the rounding does)
+        x0 = x0 > rw - 1 ? rw - 1 : x0;
+        const int y1 = y0 + (y0 < rh - 1 ? 1 : 0), x1 = x0 + (x0 < rw - 1 ? 1 : 0);
+        const float ly = sy - (float)y0, lx = sx - (float)x0;
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        const uint8_t *r0 = img + (size_t)y0 * p.w * 3, *r1 = img + (size_t)y1 * p.w * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float p00 = (float)r0[x0 * 3 + c], p01 = (float)r0[x1 * 3 + c];
+            const float p10 = (float)r1[x0 * 3 + c], p11 = (float)r1[x1 * 3 + c];
+            const float a = __builtin_fmaf(hx, p00, lx * p01), b = __builtin_fmaf(hx, p10, lx * p11);
+            const float val = __builtin_fmaf(hy, a, ly * b);
+            v[c] = rintf(val);
+        }
+    }
+}
+
+// the two pixel sources of the image kernels and the colour kernels
+struct WindowSource {
+    static __device__ __forceinline__ void pixel(const WinP &p, int n, int y, int x, float (&v)[3]) { window_pixel(p, n, y, x, v); }
+};
+struct RectSource {
+    static __device__ __forceinline__ void pixel(const WinP &p, int n, int y, int x, float (&v)[3]) { rect_pixel(p, n, y, x, v); }
+};
+
 // /255 and Normalize of three uint8 values, channel 3 = 0: one 16-byte store per pixel, a wave's 64 along x
 __device__ __forceinline__ void store_normalized(const WinP &p, int n, int y, int x, const float (&v)[3]) {
     f32x4 o;
@@ -190,6 +240,17 @@ __global__ __launch_bounds__(256) void preprocess_windows_f32_kernel(WinP p) {
     if (x >= p.crop || y >= p.crop) return;
     float v[3];
     window_pixel(p, n, y, x, v);
+    store_normalized(p, n, y, x, v);
+}
+
+// "preprocess rects": the same grid and store, the pixel from the frame's rectangle
+__global__ __launch_bounds__(256) void preprocess_rects_f32_kernel(WinP p) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int n = blockIdx.z;
+    if (x >= p.crop || y >= p.crop) return;
+    float v[3];
+    rect_pixel(p, n, y, x, v);
     store_normalized(p, n, y, x, v);
 }
 
@@ -252,8 +313,10 @@ __device__ __forceinline__ void color_op(float (&v)[3], uint32_t op, const Frame
 // block's four waves through LDS, and one integer atomicAdd per workgroup - 16 per 224 x 224 frame: with one per four rows (224 per frame) the launch
 // was bound by the atomics on n neighbouring words, about twice the time of the image launch.  Integer addition commutes, so two runs give the same bits.
 // No lane leaves before the shuffles; a lane outside the window adds 0 and reads nothing.
+// Src: where a pixel comes from - WindowSource (window_pixel) or RectSource (rect_pixel, the random resized crop)
 constexpr int STATS_ROWS = 56;
 
+template <class Src>
 __global__ __launch_bounds__(256) void color_stats_kernel(ColP p) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int n = blockIdx.z;
@@ -264,7 +327,7 @@ __global__ __launch_bounds__(256) void color_stats_kernel(ColP p) {
             const int y = blockIdx.y * STATS_ROWS + r + (threadIdx.x >> 6);
             if (y >= p.win.crop) break;
             float v[3];
-            window_pixel(p.win, n, y, x, v);
+            Src::pixel(p.win, n, y, x, v);
             uint32_t ops = fc.ops;
             for (int k = 0; k < 3 && (ops & 3u) != 1u; ++k, ops >>= 2) color_op(v, ops & 3u, fc, 0.f);
             g += (unsigned)gray_u8(v);
@@ -278,7 +341,8 @@ __global__ __launch_bounds__(256) void color_stats_kernel(ColP p) {
     if (threadIdx.x == 0) atomicAdd(&p.gray_sums[n], part[0] + part[1] + part[2] + part[3]);
 }
 
-// "preprocess colour": the image - window_pixel, the frame's three ops in its order (contrast reads the finished sum), /255 and Normalize
+// "preprocess colour": the image - the source's pixel, the frame's three ops in its order (contrast reads the finished sum), /255 and Normalize
+template <class Src>
 __global__ __launch_bounds__(256) void preprocess_color_f32_kernel(ColP p) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -287,7 +351,7 @@ __global__ __launch_bounds__(256) void preprocess_color_f32_kernel(ColP p) {
     const FrameColor fc = frame_color(p.color, n);
     const float m = (float)p.gray_sums[n] / p.pixels;
     float v[3];
-    window_pixel(p.win, n, y, x, v);
+    Src::pixel(p.win, n, y, x, v);
     uint32_t ops = fc.ops;
 #pragma unroll
     for (int k = 0; k < 3; ++k, ops >>= 2) color_op(v, ops & 3u, fc, m);
@@ -322,12 +386,9 @@ pvr_status launch_preprocess_windows(const uint8_t *frames, int n, int h, int w,
     return PVR_OK;
 }
 
-// the two launches of pvr_op_preprocess_color, one at a time so that the trainer can name and time each; both check everything before they launch.  The
-// stats launch zeroes the n sums first (hipMemsetAsync on the same stream), so the scratch needs no state between calls.
-pvr_status launch_color_stage(int stage, const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
-                              const int32_t *windows, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream) {
-    ColP p;
-    if (pvr_status s = window_params("preprocess colour", frames, n, h, w, resize, crop, mean, std_, windows, out, p.win)) return s;
+// the colour checks and the launch of one stage, behind the source's own checks (p.win is filled)
+template <class Src>
+static pvr_status color_stage(int stage, ColP &p, int n, int crop, const void *color, uint32_t *gray_sums, hipStream_t stream) {
     PVR_REQUIRE(((uintptr_t)color & 3) == 0, "preprocess colour: color_dev %p is not 4-byte aligned (n x (float b, float c, float s, int32 order))", color);
     PVR_REQUIRE(((uintptr_t)gray_sums & 3) == 0, "preprocess colour: gray_sums_dev %p is not 4-byte aligned (n uint32 of scratch)", (void *)gray_sums);
     PVR_REQUIRE((int64_t)crop * crop <= (1 << 16), "preprocess colour: crop %d (at most 256: 255 crop^2 must stay below 2^24 for the gray mean to be exact)",
@@ -336,12 +397,63 @@ pvr_status launch_color_stage(int stage, const uint8_t *frames, int n, int h, in
     dim3 grid((crop + 63) / 64, (crop + 3) / 4, n);
     if (stage == 0) {
         PVR_HIP_TRY(hipMemsetAsync(gray_sums, 0, (size_t)n * sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(color_stats_kernel, dim3(grid.x, (crop + STATS_ROWS - 1) / STATS_ROWS, n), dim3(256), 0, stream, p);
+        hipLaunchKernelGGL(color_stats_kernel<Src>, dim3(grid.x, (crop + STATS_ROWS - 1) / STATS_ROWS, n), dim3(256), 0, stream, p);
     } else {
-        hipLaunchKernelGGL(preprocess_color_f32_kernel, grid, dim3(256), 0, stream, p);
+        hipLaunchKernelGGL(preprocess_color_f32_kernel<Src>, grid, dim3(256), 0, stream, p);
     }
     PVR_LAUNCH_CHECK();
     return PVR_OK;
+}
+
+// the two launches of pvr_op_preprocess_color, one at a time so that the trainer can name and time each; both check everything before they launch.  The
+// stats launch zeroes the n sums first (hipMemsetAsync on the same stream), so the scratch needs no state between calls.
+pvr_status launch_color_stage(int stage, const uint8_t *frames, int n, int h, int w, int resize, int crop, const float *mean, const float *std_,
+                              const int32_t *windows, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream) {
+    ColP p;
+    if (pvr_status s = window_params("preprocess colour", frames, n, h, w, resize, crop, mean, std_, windows, out, p.win)) return s;
+    return color_stage<WindowSource>(stage, p, n, crop, color, gray_sums, stream);
+}
+
+// the checks and parameters of the launches that read a rectangle per frame; what: the launch's name in the refusals.  No Resize comes before the
+// rectangle, so a frame may be smaller than the crop.
+static pvr_status rect_params(const char *what, const uint8_t *frames, int n, int h, int w, int crop, const float *mean, const float *std_,
+                              const int32_t *rects, float *out, WinP &p) {
+    PVR_REQUIRE(n > 0 && h > 0 && w > 0 && crop > 0, "%s: bad shape n=%d h=%d w=%d crop=%d", what, n, h, w, crop);
+    PVR_REQUIRE(n <= 65535, "%s: %d frames in one launch (at most 65535: one grid plane per frame)", what, n);
+    PVR_REQUIRE(((uintptr_t)rects & 3) == 0, "%s: rects_dev %p is not 4-byte aligned (n x (top, left, height, width) int32)", what, (const void *)rects);
+    PVR_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out_dev %p is not 16-byte aligned (a pixel is one float4 store)", what, (void *)out);
+    p.src = frames; p.dst = out; p.windows = rects; p.n = n; p.h = h; p.w = w; p.crop = crop;
+    p.rh = h; p.rw = w; p.resize_needed = 0; p.scale_h = p.scale_w = 1.0f;        // (not read by rect_pixel: every frame has its own)
+    p.m0 = mean[0]; p.m1 = mean[1]; p.m2 = mean[2]; p.s0 = std_[0]; p.s1 = std_[1]; p.s2 = std_[2];
+    return PVR_OK;
+}
+
+// the arguments have passed the callers' null checks
+pvr_status launch_preprocess_rects(const uint8_t *frames, int n, int h, int w, int crop, const float *mean, const float *std_, const int32_t *rects,
+                                   float *out, hipStream_t stream) {
+    WinP p;
+    if (pvr_status s = rect_params("preprocess rects", frames, n, h, w, crop, mean, std_, rects, out, p)) return s;
+    dim3 grid((crop + 63) / 64, (crop + 3) / 4, n);
+    hipLaunchKernelGGL(preprocess_rects_f32_kernel, grid, dim3(256), 0, stream, p);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// launch_color_stage with the rectangle as the pixel source: the same two launches, checks and scratch
+pvr_status launch_color_stage_rects(int stage, const uint8_t *frames, int n, int h, int w, int crop, const float *mean, const float *std_,
+                                    const int32_t *rects, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream) {
+    ColP p;
+    if (pvr_status s = rect_params("preprocess colour", frames, n, h, w, crop, mean, std_, rects, out, p.win)) return s;
+    return color_stage<RectSource>(stage, p, n, crop, color, gray_sums, stream);
+}
+
+__global__ __launch_bounds__(256) void crop_rects_kernel(unsigned long long seed, unsigned long long call, long long first_frame, long long n, int h, int w,
+                                                         float lo, float hi, int32_t *__restrict__ rects) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    int32_t r[4];
+    crop_rect(seed, call, (uint64_t)(first_frame + i), h, w, lo, hi, r);
+    rects[4 * i] = r[0]; rects[4 * i + 1] = r[1]; rects[4 * i + 2] = r[2]; rects[4 * i + 3] = r[3];
 }
 
 __global__ __launch_bounds__(256) void color_params_kernel(unsigned long long seed, unsigned long long call, long long first_frame, long long n, float sb,
@@ -399,6 +511,38 @@ pvr_status pvr_op_preprocess_color(const uint8_t *frames, int32_t n, int32_t h, 
     PVR_REQUIRE(gray_sums, "pvr_op_preprocess_color: null gray_sums_dev (n uint32 of device scratch, the caller's)");
     for (int stage = 0; stage < 2; ++stage)
         if (pvr_status s = pvr::launch_color_stage(stage, frames, n, h, w, resize, crop, mean, std_, windows, color, gray_sums, out, (hipStream_t)stream))
+            return s;
+    return PVR_OK;
+}
+
+void pvr_host_crop_rects(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t h, int32_t w, float scale_lo, float scale_hi,
+                         int32_t *rects) {
+    for (int64_t i = 0; rects && i < n; ++i) pvr::crop_rect(seed, call, (uint64_t)(first_frame + i), h, w, scale_lo, scale_hi, rects + 4 * i);
+}
+
+pvr_status pvr_op_crop_rects(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, int32_t h, int32_t w, float scale_lo, float scale_hi,
+                             int32_t *rects, void *stream) {
+    PVR_REQUIRE(rects, "pvr_op_crop_rects: null rects_dev (n x (top, left, height, width) int32 of device memory)");
+    PVR_REQUIRE(((uintptr_t)rects & 3) == 0, "pvr_op_crop_rects: rects_dev %p is not 4-byte aligned (four int32 per frame)", (void *)rects);
+    PVR_REQUIRE(n >= 1 && n <= (1ll << 31), "pvr_op_crop_rects: n = %lld frames (1 .. 2^31)", (long long)n);
+    PVR_REQUIRE(first_frame >= 0, "pvr_op_crop_rects: first_frame = %lld (a frame index of the step, 0 or above)", (long long)first_frame);
+    PVR_REQUIRE(h >= 1 && w >= 1, "pvr_op_crop_rects: frame size h = %d, w = %d (1 or above)", h, w);
+    PVR_REQUIRE(scale_lo > 0.f && scale_lo <= scale_hi && scale_hi <= 1.0f, "pvr_op_crop_rects: scale (%g, %g) (the rectangle's share of the frame's area: "
+                "finite, 0 < lo <= hi <= 1)", (double)scale_lo, (double)scale_hi);
+    hipLaunchKernelGGL(pvr::crop_rects_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long)seed,
+                       (unsigned long long)call, (long long)first_frame, (long long)n, (int)h, (int)w, scale_lo, scale_hi, rects);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+pvr_status pvr_op_preprocess_rects(const uint8_t *frames, int32_t n, int32_t h, int32_t w, int32_t crop, const float *mean, const float *std_,
+                                   const int32_t *rects, const void *color, uint32_t *gray_sums, float *out, void *stream) {
+    PVR_REQUIRE(frames && mean && std_ && out, "pvr_op_preprocess_rects: null argument");
+    PVR_REQUIRE(rects, "pvr_op_preprocess_rects: null rects_dev (n x (top, left, height, width) int32 of device memory)");
+    if (!color) return pvr::launch_preprocess_rects(frames, n, h, w, crop, mean, std_, rects, out, (hipStream_t)stream);
+    PVR_REQUIRE(gray_sums, "pvr_op_preprocess_rects: color_dev without gray_sums_dev (n uint32 of device scratch, the caller's)");
+    for (int stage = 0; stage < 2; ++stage)
+        if (pvr_status s = pvr::launch_color_stage_rects(stage, frames, n, h, w, crop, mean, std_, rects, color, gray_sums, out, (hipStream_t)stream))
             return s;
     return PVR_OK;
 }

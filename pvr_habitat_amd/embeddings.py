@@ -531,13 +531,27 @@ class HipTrainableResNet(_Node):
     that runs the stem again.  Without random_crop every frame's window is the centre one.  color_params(color_seed, call, n, strengths) predicts a
     step's parameters on the host.  Off by default; with it off nothing moves, and random_crop's windows keep their bits with it on.  Eval mode keeps
     the un-jittered centre crop.  Not with prefix_cache, build_prefix_cache or forward_cached: a cache holds the prefix's output for ONE image per frame;
-    prefix_once is the compatible mode."""
+    prefix_once is the compatible mode.
+
+    random_resized_crop: torchvision's RandomResizedCrop(224, scale=(lo, hi), ratio=(3/4, 4/3)) per frame and step - the crop MoCo's checkpoints were
+    pre-trained with: a rectangle of random area (uniform in [lo, hi] of the frame's) and aspect ratio (log-uniform in [3/4, 4/3]) of the ORIGINAL uint8
+    frame, resized to 224 x 224.  It takes the place of Resize(256) plus the window and sits before color_jitter, / 255 and Normalize.  (lo, hi) is the
+    scale range, a scalar s means (s, 1.0), None is off.  In training mode the step's (n, 4) rectangles (top, left, height, width; include/pvr_train.h)
+    are drawn once on the device (pvr_op_crop_rects with seed = crop_seed and call = crop_call, the per-forward counter of the other two modes); every pass
+    is handed its rows (pvr_trainer_forward_rects: the launch "preprocess rects", or with color_jitter the colour pair reading the rectangle, writes the
+    fp32 image), and so is every recompute pass that runs the stem again - the rectangles are parked where random_crop's windows are.  crop_rects(
+    crop_seed, call, n, h, w, scale) predicts a step's rectangles on the host.  A frame smaller than the crop is legal (no Resize runs).  Off by default;
+    with it off nothing moves.  Eval mode keeps Resize(256) and the centre crop.  Not with random_crop (both choose the window), and not with prefix_cache,
+    build_prefix_cache or forward_cached; it composes with color_jitter, prefix_once, frozen BatchNorm chunking and the split modes."""
 
     def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0):
+                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0,
+                 random_resized_crop=None):
         super().__init__()
         assert variant in _TRAINABLE, variant
         check_random_crop(random_crop, prefix_cache)
+        rrc_scale = crop_scale(random_resized_crop)
+        check_random_resized_crop(rrc_scale, prefix_cache, random_crop=random_crop)
         strengths = color_strengths(color_jitter)
         check_color_jitter(strengths, prefix_cache)
         _lib.require_gpu()
@@ -579,6 +593,7 @@ class HipTrainableResNet(_Node):
         self.crop_seed = int(crop_seed)          # random_crop: Philox key of the windows
         self.crop_call = 0                       # random_crop: the next training forward's draw; it goes up by one per forward and a caller may set it
         self._windows = None                     # random_crop: the step's windows between _forward_raw and its consumer (parked as _boundary is)
+        self._rrc_scale = rrc_scale              # random_resized_crop: the (lo, hi) share of the frame's area, None when off (seed and call: crop_seed, crop_call)
         self._color_jitter = strengths           # color_jitter: the three strengths, None when off
         self.color_seed = int(color_seed)        # color_jitter: Philox key of the parameters (the call number is crop_call)
         self._color = None                       # color_jitter: the step's parameters between _forward_raw and its consumer (parked as _windows is)
@@ -693,6 +708,11 @@ class HipTrainableResNet(_Node):
         return self._random_crop
 
     @property
+    def random_resized_crop(self):
+        """the (lo, hi) scale range of a training forward's random resized crop, None when off (see the class docstring)"""
+        return self._rrc_scale
+
+    @property
     def color_jitter(self):
         """the (brightness, contrast, saturation) strengths of a training forward's colour jitter, None when off (see the class docstring)"""
         return self._color_jitter
@@ -718,6 +738,7 @@ class HipTrainableResNet(_Node):
             raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
         check_random_crop(self._random_crop, True, 'build_prefix_cache')
         check_color_jitter(self._color_jitter, True, 'build_prefix_cache')
+        check_random_resized_crop(self._rrc_scale, True, 'build_prefix_cache')
         return self._build_prefix_cache(int(frames_u8.shape[0]), [(0, frames_u8)])
 
     def _build_prefix_cache(self, n_frames, blocks):
@@ -727,6 +748,7 @@ class HipTrainableResNet(_Node):
             raise ValueError('build_prefix_cache needs train_from: with everything training there is no frozen prefix whose output could be cached')
         check_random_crop(self._random_crop, True, 'build_prefix_cache')
         check_color_jitter(self._color_jitter, True, 'build_prefix_cache')
+        check_random_resized_crop(self._rrc_scale, True, 'build_prefix_cache')
         L = _lib.lib()
         _lib.check(L.pvr_trainer_set_prefix_fused(self._handle, 1))
         vp = lambda t: C.c_void_p(t.data_ptr())
@@ -767,6 +789,7 @@ class HipTrainableResNet(_Node):
         only the trained parameters to autograd.  The bits of forward(frames[rows])."""
         check_random_crop(self._random_crop, True, 'forward_cached')
         check_color_jitter(self._color_jitter, True, 'forward_cached')
+        check_random_resized_crop(self._rrc_scale, True, 'forward_cached')
         self.check_prefix_cache(cache)
         if not self.training:
             raise RuntimeError('forward_cached is a training-mode forward (the cache holds the input of the trained stages): in eval mode embed the '
@@ -859,18 +882,24 @@ class HipTrainableResNet(_Node):
             self._windows = torch.empty((n, 2), dtype=torch.int32, device=frames_u8.device)
             _lib.check(_lib.lib().pvr_op_crop_windows(self.crop_seed, self.crop_call, 0, n, max_top, max_left, C.c_void_p(self._windows.data_ptr()),
                                                       _lib.stream_ptr()))
+        # random_resized_crop: the step's rectangles (n, 4) of the original frames, drawn once under the same call number and parked in the windows' place
+        # (the two modes exclude each other): every consumer hands _windows on as it is, and a pass tells the two by the row length
+        if self._rrc_scale is not None:
+            self._windows = torch.empty((n, 4), dtype=torch.int32, device=frames_u8.device)
+            _lib.check(_lib.lib().pvr_op_crop_rects(self.crop_seed, self.crop_call, 0, n, h, w, self._rrc_scale[0], self._rrc_scale[1],
+                                                    C.c_void_p(self._windows.data_ptr()), _lib.stream_ptr()))
         # color_jitter: the step's parameters, drawn once under the same call number and parked the same way; without random_crop every frame's window
         # is the centre one
         self._color = None
         if self._color_jitter is not None:
-            max_top, max_left = self.crop_range(h, w)
             if self._windows is None:
+                max_top, max_left = self.crop_range(h, w)
                 self._windows = torch.tensor([int(round(max_top / 2.0)), int(round(max_left / 2.0))], dtype=torch.int32,
-                                             device=frames_u8.device).repeat(n, 1)
+                                                 device=frames_u8.device).repeat(n, 1)
             self._color = torch.empty((n, 4), dtype=torch.int32, device=frames_u8.device)
             _lib.check(_lib.lib().pvr_op_color_params(self.color_seed, self.crop_call, 0, n, *self._color_jitter, C.c_void_p(self._color.data_ptr()),
                                                       _lib.stream_ptr()))
-        if self._random_crop or self._color_jitter is not None:
+        if self._random_crop or self._color_jitter is not None or self._rrc_scale is not None:
             self.crop_call += 1
         for lo, hi in self._passes(n):            # (one pass unless BatchNorm is frozen; the last pass's activations stay held)
             self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary, windows=self._windows, color=self._color)
@@ -879,8 +908,20 @@ class HipTrainableResNet(_Node):
     def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False, windows=None, color=None):
         """one pass over frames [lo, hi).  boundary: the step's (n, boundary_floats) cache - this pass writes its rows (reuse False) or starts at the first
         trained op on what they hold (reuse True).  windows (random_crop): the step's (n, 2) int32 windows - this pass crops at its rows.  color
-        (color_jitter, with windows): the step's (n, 4) parameters - this pass jitters its rows"""
+        (color_jitter, with windows): the step's (n, 4) parameters - this pass jitters its rows.  windows of four columns (random_resized_crop): the
+        step's rectangles - this pass resizes each frame's own rectangle to the crop, with or without color"""
         vp = lambda t: C.c_void_p(t.data_ptr())
+        if windows is not None and windows.shape[1] == 4:
+            reuse = reuse and boundary is not None                            # (as below: without a boundary cache a recompute pass makes the same image again)
+            if color is not None and self._gray_sums is None:
+                self._gray_sums = torch.empty((self._max_batch,), dtype=torch.int32, device=color.device)
+            _lib.check(_lib.lib().pvr_trainer_forward_rects(self._handle, vp(self._flat), vp(self._bufs), None if reuse else vp(frames_u8[lo:hi]), hi - lo,
+                                                            frames_u8.shape[1], frames_u8.shape[2], vp(windows[lo:hi]),
+                                                            None if color is None else vp(color[lo:hi]),
+                                                            None if color is None else vp(self._gray_sums),
+                                                            None if boundary is None else vp(boundary[lo:hi]), 1 if reuse else 0, vp(out), out.stride(0),
+                                                            _lib.stream_ptr()))
+            return
         if color is not None:
             reuse = reuse and boundary is not None                            # (as below: without a boundary cache a recompute pass makes the same image again)
             if self._gray_sums is None:
@@ -911,14 +952,15 @@ class HipTrainableResNet(_Node):
         pvr_trainer_backward.  Several (frozen BatchNorm): the last pass first - its activations are still held - then every other pass in frame
         order, each recomputed and added by pvr_trainer_backward_acc.  boundary (prefix_once): the cache that forward filled; a recomputed pass
         starts at the first trained op on its rows.  windows (random_crop): the windows that forward drew; a recomputed pass that runs the stem crops
-        at its rows again.  color (color_jitter): the parameters that forward drew, for the same passes."""
+        at its rows again (random_resized_crop: the rectangles, four columns, in the same place).  color (color_jitter): the parameters that forward
+        drew, for the same passes."""
         L = _lib.lib()
         vp = lambda t: C.c_void_p(t.data_ptr())
         passes = self._passes(frames_u8.shape[0])
         assert dout.shape[0] == frames_u8.shape[0] and dout.stride(1) == 1
         assert (boundary is not None) == self._prefix_once, 'prefix_once: the backward takes the boundary cache of its forward'
-        assert (windows is not None) == (self._random_crop or self._color_jitter is not None), \
-            'random_crop / color_jitter: the backward takes the windows of its forward'
+        assert (windows is not None) == (self._random_crop or self._color_jitter is not None or self._rrc_scale is not None), \
+            'random_crop / color_jitter / random_resized_crop: the backward takes the windows or rectangles of its forward'
         assert (color is not None) == (self._color_jitter is not None), 'color_jitter: the backward takes the colour parameters of its forward'
         if len(passes) == 1:
             _lib.check(L.pvr_trainer_backward(self._handle, vp(self._flat), vp(dout), dout.stride(0), vp(grads), _lib.stream_ptr()))
@@ -1056,6 +1098,52 @@ def check_color_jitter(strengths, prefix_cache=False, what='prefix_cache'):
                          'is the compatible mode' % what)
 
 
+def crop_scale(random_resized_crop):
+    """the random_resized_crop keyword -> the (lo, hi) scale range as fp32 values, or None when the mode is off (None or False); a scalar s means (s, 1.0).
+    A ValueError names a scale that is not finite or not 0 < lo <= hi <= 1, and a value that is neither a number nor two of them"""
+    if random_resized_crop is None or random_resized_crop is False:
+        return None
+    try:
+        v = tuple(float(x) for x in random_resized_crop) if hasattr(random_resized_crop, '__len__') else (float(random_resized_crop), 1.0)
+    except (TypeError, ValueError):
+        v = ()
+    if len(v) != 2:
+        raise ValueError('random_resized_crop=%r: the scale range (lo, hi) of the rectangle\'s share of the frame\'s area, or one number for (lo, 1.0) '
+                         '(the ratio range is fixed at (3/4, 4/3))' % (random_resized_crop,))
+    v = tuple(float(np.float32(x)) if np.isfinite(x) else x for x in v)
+    if not (np.isfinite(v[0]) and np.isfinite(v[1]) and 0 < v[0] <= v[1] <= 1):
+        raise ValueError('random_resized_crop=%r: a scale range is finite with 0 < lo <= hi <= 1 (the rectangle\'s area is uniform in [lo, hi] of the '
+                         'frame\'s; MoCo\'s is (0.2, 1.0), and None switches the mode off)' % (random_resized_crop,))
+    return v
+
+
+def crop_rects(seed, call, n, h, w, scale, first_frame=0):
+    """the (n, 4) int32 rectangles (top, left, height, width) random_resized_crop draws in (h, w) frames first_frame .. first_frame + n of training
+    forward number `call` under crop_seed `seed` (pvr_host_crop_rects: host arithmetic, no GPU needed; bit for bit what the device draws).  scale: a
+    scalar lo, for (lo, 1.0), or (lo, hi)"""
+    v = crop_scale(scale)
+    if v is None:
+        raise ValueError('crop_rects: scale=%r (a scale range (lo, hi), or one number for (lo, 1.0))' % (scale,))
+    if int(h) < 1 or int(w) < 1:
+        raise ValueError('crop_rects: a %dx%d frame (both sizes are 1 or above)' % (h, w))
+    out = np.zeros((int(n), 4), np.int32)
+    if n > 0:
+        _lib.lib().pvr_host_crop_rects(int(seed), int(call), int(first_frame), int(n), int(h), int(w), v[0], v[1], out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def check_random_resized_crop(scale, prefix_cache=False, what='prefix_cache', random_crop=False):
+    """random_resized_crop changes a frame's image from step to step: a ValueError together with the prefix cache (`what` names the keyword or the
+    method), and together with random_crop, which chooses the window too.  scale: what crop_scale returned"""
+    if scale is not None and random_crop:
+        raise ValueError('random_resized_crop with random_crop: both choose the frame\'s window - random_crop moves a 224 x 224 window in the frame after '
+                         'Resize(256), random_resized_crop resizes a random rectangle of the original frame to 224 x 224; switch one of them off')
+    if scale is not None and prefix_cache:
+        raise ValueError('random_resized_crop with %s: the cache holds the frozen prefix\'s output for ONE window per frame (the deterministic centre crop), '
+                         'and the rectangle changes in every step; prefix_once, which keeps the prefix\'s output for the frames and rectangles of one step, '
+                         'is the compatible mode' % what)
+
+
 def check_prefix_once(prefix_once, train_from):
     """prefix_once keeps the frozen prefix's boundary tensor across the passes of a step: a ValueError where nothing is frozen"""
     if prefix_once and train_from is None:
@@ -1152,7 +1240,7 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
 
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
                    conv_split16=False, train_from=None, prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None,
-                   color_seed=0):
+                   color_seed=0, random_resized_crop=None):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -1164,6 +1252,8 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     check_random_crop(random_crop, prefix_cache)
     strengths = color_strengths(color_jitter)
     check_color_jitter(strengths, prefix_cache)
+    rrc_scale = crop_scale(random_resized_crop)
+    check_random_resized_crop(rrc_scale, prefix_cache, random_crop=random_crop)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
@@ -1173,7 +1263,8 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
                               **({'train_from': train_from} if train_from is not None else {}), **({'prefix_once': True} if prefix_once else {}),
                               **({'prefix_cache': True} if prefix_cache else {}),
                               **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}),
-                              **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}))
+                              **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}),
+                              **({'random_resized_crop': rrc_scale, 'crop_seed': crop_seed} if rrc_scale else {}))
 
 
 class UberModel(nn.Module):
@@ -1369,7 +1460,7 @@ class EmbeddingNet(nn.Module):
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
                  compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0):
+                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0, random_resized_crop=None):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -1408,6 +1499,12 @@ class EmbeddingNet(nn.Module):
             raise ValueError('color_jitter is a mode of the trainable encoder (train=True): a frozen encoder embeds the un-jittered centre crop of every '
                              'frame')
         check_color_jitter(strengths, prefix_cache)
+        rrc_scale = crop_scale(random_resized_crop)              # (a ValueError names a bad scale)
+        if rrc_scale is not None and not train:
+            raise ValueError('random_resized_crop is a mode of the trainable encoder (train=True): a frozen encoder embeds the centre crop of every frame '
+                             '(crops=5 adds the four corner windows)')
+        check_random_resized_crop(rrc_scale, prefix_cache, random_crop=random_crop)
+        # random_resized_crop (train=True only): a training forward resizes a random rectangle of every frame to the crop; crop_seed keys the draw
         # color_jitter (train=True only): a training forward jitters brightness, contrast and saturation per frame; color_seed keys the draw
         # random_crop (train=True only): a training forward crops a random window per frame; crop_seed keys the draw (HipTrainableResNet.crop_call counts it)
         # prefix_cache (train=True with train_from only): the workspace mode of cached steps (build_prefix_cache / forward_cached of the encoder)
@@ -1424,7 +1521,8 @@ class EmbeddingNet(nn.Module):
                                                          **({'prefix_once': True} if prefix_once else {}),
                                                          **({'prefix_cache': True} if prefix_cache else {}),
                                                          **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}),
-                                                         **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}))
+                                                         **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}),
+                                                         **({'random_resized_crop': rrc_scale, 'crop_seed': crop_seed} if rrc_scale else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

@@ -126,6 +126,30 @@ def check_color_jitter_flag(flags):
     return strengths
 
 
+def check_random_resized_crop_flag(flags):
+    """--embedding_random_resized_crop LO HI is a mode of --train_embedding, and not of --embedding_random_crop or --embedding_prefix_cache: a ValueError
+    otherwise, and for a scale that is not finite or not 0 < LO <= HI <= 1.  -> the (lo, hi) scale range, or None when the mode is off (no flag)"""
+    given = getattr(flags, 'embedding_random_resized_crop', None)
+    if given is None:
+        return None
+    from .embeddings import crop_scale
+    try:
+        scale = crop_scale(tuple(given))
+    except ValueError as e:
+        raise ValueError('--embedding_random_resized_crop: %s' % e)
+    if not getattr(flags, 'train_embedding', False):
+        raise ValueError('--embedding_random_resized_crop needs --train_embedding: it resizes a random rectangle of every frame to the crop in the '
+                         'training steps of a trainable encoder (a frozen encoder embeds the centre crop)')
+    if getattr(flags, 'embedding_random_crop', False):
+        raise ValueError('--embedding_random_resized_crop with --embedding_random_crop: both choose the frame\'s window - the one moves a 224 x 224 window in '
+                         'the frame after Resize(256), the other resizes a random rectangle of the original frame to 224 x 224; give one of the two flags')
+    if getattr(flags, 'embedding_prefix_cache', False):
+        raise ValueError('--embedding_random_resized_crop with --embedding_prefix_cache: the cache holds the frozen prefix\'s output for ONE window per '
+                         'frame (the deterministic centre crop), and the rectangle changes in every step; --embedding_prefix_once, which keeps the '
+                         'prefix\'s output for the frames and rectangles of one step, is the compatible mode')
+    return scale
+
+
 def prefix_cache_bytes(flags, n_dataset_frames):
     """--embedding_prefix_cache: (bytes of the boundary tensors of all n_dataset_frames = samples x frames dataset frames, bytes per frame of a pass's
     staging tensor), both next to the workspace; (0, 0) without the flag"""
@@ -270,6 +294,10 @@ def run_end_to_end(flags, make_env=None):
     if color_jitter is not None:
         print('  ', 'colour jitter: every frame of a step gets its own brightness, contrast and saturation factor, strengths %g %g %g, in a random '
               'order, seed %d (--embedding_color_jitter)' % (color_jitter + (flags.run_id,)))
+    rrc_scale = check_random_resized_crop_flag(flags)
+    if rrc_scale is not None:
+        print('  ', 'random resized crop: every frame of a step is replaced by a random rectangle of itself, %g .. %g of its area and 3/4 .. 4/3 in '
+              'aspect ratio, resized to the crop, seed %d (--embedding_random_resized_crop)' % (rrc_scale + (flags.run_id,)))
     world = max(rank_world()[1], int(os.environ.get('WORLD_SIZE', '1')))
     if world > 1:
         raise NotImplementedError('--train_embedding with a world size of %d: data-parallel encoder training is not built (the trainable encoder and its '
@@ -328,6 +356,8 @@ def run_end_to_end(flags, make_env=None):
         split16 = dict(split16, random_crop=True, crop_seed=flags.run_id)
     if color_jitter is not None:                                # (likewise)
         split16 = dict(split16, color_jitter=color_jitter, color_seed=flags.run_id)
+    if rrc_scale is not None:                                   # (likewise)
+        split16 = dict(split16, random_resized_crop=rrc_scale, crop_seed=flags.run_id)
     if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
         if not flags.pretrained_embedding:
             print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')
@@ -371,7 +401,7 @@ def run_end_to_end(flags, make_env=None):
               % (pc.n_frames, pc.nbytes / 2 ** 30, pc.fill_seconds, pc.n_frames / max(pc.fill_seconds, 1e-9)))
     for frames in range(init_frames, flags.max_frames, B * T):
         epoch = frames // (B * T)
-        model.embedding.crop_call = epoch                       # (--embedding_random_crop, --embedding_color_jitter: the iteration names the draw, so a resumed run draws what an uninterrupted one would)
+        model.embedding.crop_call = epoch                       # (--embedding_random_crop, --embedding_color_jitter, --embedding_random_resized_crop: the iteration names the draw, so a resumed run draws what an uninterrupted one would)
         starting_i = sample_with_minimum_distance(n=n_samples, k=B, d=T)
         if prefix_cache:                                        # (T, B) sample indices: a step reads its frames' boundary tensors, no uint8 frame
             o = dataset.rows(starting_i, T)
@@ -430,6 +460,7 @@ def run(flags, make_env=None):
     check_prefix_cache_flag(flags)
     check_random_crop_flag(flags)
     check_color_jitter_flag(flags)
+    check_random_resized_crop_flag(flags)
     if getattr(flags, 'train_embedding', False):
         return run_end_to_end(flags, make_env)
     rank, world = rank_world()

@@ -786,7 +786,8 @@ class HipJointRMSprop(object):
 
     With a random_crop encoder the step takes the windows the trainer's forward drew (there is no autograd node to carry them) and hands them to
     _backward_raw next to the boundary cache, so the recompute passes crop where the forward did; step_cached is unreachable with that mode.  A
-    color_jitter encoder's colour parameters take the same way, next to the windows."""
+    color_jitter encoder's colour parameters take the same way, next to the windows; a random_resized_crop encoder's rectangles travel in the windows'
+    place."""
 
     def __init__(self, model, lr=1e-4, alpha=0.99, eps=1e-5, momentum=0, max_grad_norm=40.0, max_epochs=None):
         if float(momentum) != 0:
