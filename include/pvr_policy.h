@@ -196,6 +196,66 @@ pvr_status pvr_policy_last_dlogits(pvr_policy *pol, float *dlogits_out, int32_t 
  * (unit-parity entry point; the arithmetic is the one pvr_debug_set_gemm_mode selects) */
 pvr_status pvr_op_gemm_f32(const float *A, const float *B, const float *bias, float *C, int32_t M, int32_t N,
                            int32_t K, int32_t a_km, int32_t b_kn, int32_t relu, void *hip_stream);
+/* pvr_op_gemm_f32 with the backward pass's ReLU mask: C[m][n] = 0 where mask[m][n] <= 0 (mask [M][N] fp32, may be NULL), applied after bias and relu -
+ * in the GEMM kernel, or in the slice sum when the shape takes split-K */
+pvr_status pvr_op_gemm_f32_masked(const float *A, const float *B, const float *bias, const float *mask, float *C, int32_t M, int32_t N,
+                                  int32_t K, int32_t a_km, int32_t b_kn, int32_t relu, void *hip_stream);
+
+/* Unit entry points of the policy's kernels (tests/test_gpu_policy_kernels.py holds each to a float64 reference).  No handle, no state: device pointers
+ * and a stream; each enqueues exactly the launches pvr_policy_forward / _backward enqueue for that operation, through the same launch code.  Buffers
+ * read as float4s must be 16-byte aligned (refused otherwise).
+ * `form` of a reduction over R rows: -1 as the plan chooses (two-stage from R >= 512 when the column count is a multiple of 4), 0 one launch,
+ * 1 two-stage (row groups of 64, then a fixed-order sum of the group partials).  pvr_debug_policy_two_stage_launches counts the reductions that took
+ * the two-stage form, in the plan and here. */
+int64_t pvr_debug_policy_two_stage_launches(void);
+/* out0[c] (and out1[c] when out1 != NULL) = sum_r X[r][c], X [R][C] */
+pvr_status pvr_op_policy_colsum(const float *X, float *out0, float *out1, int32_t R, int32_t C, int32_t form, void *hip_stream);
+/* Training-mode BatchNorm1d statistics of X [R][C] as the forward takes them: mean = colsum / n_global, sumsq = sum_r (x - mean)^2,
+ * invstd = 1 / sqrt(sumsq / n_global + 1e-5), running_mean / running_var updated in place with momentum 0.1 (the unbiased variance
+ * sumsq / (n_global - 1) goes into running_var), *num_batches_tracked += 1 (may be NULL).  n_global = R, or the global row count under SyncBN. */
+pvr_status pvr_op_policy_bn_stats(const float *X, int32_t R, int32_t C, float n_global, int32_t form, float *mean, float *invstd, float *sumsq,
+                                  float *running_mean, float *running_var, int64_t *num_batches_tracked, void *hip_stream);
+/* y = (x - mean) * invstd * gamma + beta; is_var != 0: the third argument is a variance (eval mode), invstd = 1 / sqrt(var + 1e-5).  C % 4 == 0 */
+pvr_status pvr_op_policy_bn_apply(const float *x, const float *mean, const float *invstd_or_var, const float *gamma, const float *beta, float *y,
+                                  int32_t R, int32_t C, int32_t is_var, void *hip_stream);
+/* dgamma[c] = sum_r dY (X - mean) invstd, dbeta[c] = sum_r dY */
+pvr_status pvr_op_policy_bn_backward_sums(const float *X, const float *dY, const float *mean, const float *invstd, float *dgamma, float *dbeta,
+                                          int32_t R, int32_t C, int32_t form, void *hip_stream);
+/* xhat = (x - mean) * invstd.  C % 4 == 0 */
+pvr_status pvr_op_policy_bn_xhat(const float *x, const float *mean, const float *invstd, float *xhat, int32_t R, int32_t C, void *hip_stream);
+/* The fold of the BatchNorm affine gradients into fc1's weight gradient: S_dW [H][O] holds S = dz1^T xhat on entry and dW1 = gamma S + beta db1^T on
+ * return; dgamma[c] = sum_j W1[j][c] S[j][c], dbeta[c] = sum_j W1[j][c] db1[j].  O % 128 == 0 */
+pvr_status pvr_op_policy_bn_fold(float *S_dW, const float *W1, const float *db1, const float *gamma, const float *beta, float *dgamma, float *dbeta,
+                                 int32_t H, int32_t O, void *hip_stream);
+/* dx = gamma invstd (dy - dbeta / n_stat - xhat dgamma / n_stat): from x (xhat formed inside), or in place on dx = dy from a stored xhat (C % 4 == 0) */
+pvr_status pvr_op_policy_bn_dx(const float *x, const float *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
+                               const float *dbeta, float *dx, int32_t R, int32_t C, int32_t n_stat, void *hip_stream);
+pvr_status pvr_op_policy_bn_dx_xhat(float *dx, const float *xhat, const float *invstd, const float *gamma, const float *dgamma, const float *dbeta,
+                                    int32_t R, int32_t C, int32_t n_stat, void *hip_stream);
+/* nd = |1 - (done != 0)|;  out[t][b][:] = nd[t][b] * (t == 0 ? h_init[b] : hs[t-1][b]) (hs (T,B,H), h_init (B,H));  out [N][16] = in [N][A] zero-padded;
+ * out[0] = (fixed-order sum of loss_row[0..n)) / n */
+pvr_status pvr_op_policy_notdone(const uint8_t *done, float *nd, int32_t n, void *hip_stream);
+pvr_status pvr_op_policy_hprev(const float *hs, const float *h_init, const float *nd, float *out, int32_t T, int32_t B, int32_t H, void *hip_stream);
+pvr_status pvr_op_policy_dlogits_pad(const float *in, float *out, int32_t N, int32_t A, void *hip_stream);
+pvr_status pvr_op_policy_loss_mean(const float *loss_row, int32_t n, float *out, void *hip_stream);
+/* One step of one LSTM layer (the per-step launch).  G [B][4H] holds the input projection with b_ih on entry and the activated gates i,f,g,o on return;
+ * gates = G + b_hh + (nd * h_prev) W_hh^T, c_out = f (nd * c_prev) + i g, h_out = o tanh(c_out).  H a multiple of 1024 */
+pvr_status pvr_op_policy_lstm_fwd_step(float *G, const float *h_prev, const float *c_prev, const float *nd, const float *W_hh, const float *b_hh,
+                                       float *h_out, float *c_out, int32_t B, int32_t H, void *hip_stream);
+/* One BPTT step of one layer (the two per-step launches).  G [B][4H]: activated gates of step t in, gate gradients dG out; dc_carry [B][H] in / out.
+ * dh = dh_ext + nd_next * (dG_next W_hh), the recurrent product through partial ([16][B][H] scratch); dG_next == NULL is step T-1: no recurrent
+ * term, dc_carry is not read, W_hh / nd_next / partial may be NULL. */
+pvr_status pvr_op_policy_lstm_bwd_step(const float *dG_next, const float *W_hh, const float *nd_next, const float *dh_ext, float *dc_carry, float *G,
+                                       const float *c_t, const float *c_prev, const float *nd, float *partial, int32_t B, int32_t H, void *hip_stream);
+/* Heads + BC loss: logits [N][A], baseline [N], action [N] = argmax (first index on ties); with target != NULL also loss_row [N] (NaN for a target
+ * outside [0, A)) and dlogits [N][16] = (softmax - onehot) / N, columns A..15 zero.  Without a target loss_row and dlogits may be NULL. */
+pvr_status pvr_op_policy_heads(const float *out, const float *Wp, const float *bp, const float *Wb, const float *bb, const int64_t *target,
+                               float *logits, float *baseline, int64_t *action, float *loss_row, float *dlogits, int32_t N, int32_t H, int32_t A,
+                               void *hip_stream);
+/* dWp [A][H] = dlogits^T out, dbp [A] = column sums of dlogits (form as above), dout [N][H] = dlogits Wp.  dlogits is the padded [N][16] */
+pvr_status pvr_op_policy_head_backward(const float *dlogits, const float *out, const float *Wp, float *dWp, float *dbp, float *dout, int32_t N,
+                                       int32_t H, int32_t A, int32_t form, void *hip_stream);
+
 /* How every fp32 GEMM of the policy is computed (process-wide; the reference's counterpart is torch's fp32 matmul, src/models.py:66-73):
  *   0  fp32 MFMA (v_mfma_f32_16x16x4_f32: the ascending-k fma chain; the default, rounds 1-3)
  *   1  bf16 MFMA on an exact three-term split of both operands, six products per pair, fp32 accumulation (round 3, opt-in: 2.7 x closer

@@ -292,13 +292,32 @@ static pvr_status colreduce2(ColP c, hipStream_t st) {
     return PVR_OK;
 }
 
-pvr_status colsum(const float *X, float *out0, float *out1, int R, int C, hipStream_t st) {
-    ColP c = {};
-    c.X = X; c.out0 = out0; c.out1 = out1; c.R = R; c.C = C;
-    if (R >= 512 && C % 4 == 0) return colreduce2<0>(c, st);
-    hipLaunchKernelGGL(colreduce_kernel<0>, dim3((C + 31) / 32), dim3(256), 0, st, c);
+// Which form a reduction over R rows takes: form -1 = by shape (two-stage from 512 rows, when the float4 loads of the two-stage kernels
+// are possible), 0 = one launch, 1 = two-stage (the unit entry points force either at any R; refused where `vec4` does not hold)
+static std::atomic<long long> g_two_stage_launches{0};          // pvr_debug_policy_two_stage_launches
+static pvr_status two_stage_form(int form, int R, bool vec4, bool *two) {
+    PVR_REQUIRE(form >= -1 && form <= 1, "policy: reduction form must be -1 (by shape), 0 (one launch) or 1 (two-stage), got %d", form);
+    PVR_REQUIRE(form != 1 || vec4, "policy: the two-stage reduction reads float4s: its column count must be a multiple of 4");
+    *two = form == 1 || (form < 0 && R >= 512 && vec4);
+    if (*two) g_two_stage_launches.fetch_add(1);
+    return PVR_OK;
+}
+
+// MODE 0 / 3 / 2 in the form `form` asks for
+template <int MODE>
+static pvr_status colreduce(ColP c, int form, hipStream_t st) {
+    bool two;
+    TRY_(two_stage_form(form, c.R, c.C % 4 == 0, &two));
+    if (two) return colreduce2<MODE>(c, st);
+    hipLaunchKernelGGL(colreduce_kernel<MODE>, dim3((c.C + 31) / 32), dim3(256), 0, st, c);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
+}
+
+pvr_status colsum(const float *X, float *out0, float *out1, int R, int C, hipStream_t st, int form = -1) {
+    ColP c = {};
+    c.X = X; c.out0 = out0; c.out1 = out1; c.R = R; c.C = C;
+    return colreduce<0>(c, form, st);
 }
 
 inline int blocks_for(size_t n, int cap = 4096) {
@@ -332,6 +351,122 @@ static pvr_status dp_bucket(pvr_policy *pol, float *Gd, int64_t off, int64_t cou
 }
 
 
+// ---- launches shared by the plan (forward_core / backward_core / loss_backward) and the unit entry points pvr_op_policy_*: one place per grid -------
+static pvr_status launch_notdone(const uint8_t *done, float *nd, int N, hipStream_t st) {
+    hipLaunchKernelGGL(notdone_kernel, dim3((N + 255) / 256), dim3(256), 0, st, done, nd, N);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// BatchNorm1d batch statistics as the training forward takes them: column sums -> mean, centred sum of squares -> invstd and the running
+// estimates.  `sums` / `sq` are [O] scratch (sums may be invstd itself); sync_pol != NULL all-reduces both sums over the ranks (SyncBN).
+static pvr_status bn_batch_stats(const float *obs, int N, int O, float ng, float *sums, float *sq, float *mean, float *invstd, float *running_mean,
+                                 float *running_var, long long *nbt, int form, pvr_policy *sync_pol, hipStream_t st) {
+    TRY(colsum(obs, sums, nullptr, N, O, st, form));
+    if (sync_pol) TRY(dp_allreduce(sync_pol, sums, O, st));
+    hipLaunchKernelGGL(scale_kernel, dim3((O + 255) / 256), dim3(256), 0, st, mean, sums, 1.0f / ng, O);
+    ColP c2 = {};
+    c2.X = obs; c2.mean_in = mean; c2.out0 = sq; c2.R = N; c2.C = O;
+    TRY(colreduce<3>(c2, form, st));
+    if (sync_pol) TRY(dp_allreduce(sync_pol, sq, O, st));
+    hipLaunchKernelGGL(bn_sync_final_kernel, dim3((O + 255) / 256), dim3(256), 0, st, sq, mean, ng, invstd, running_mean, running_var, nbt, O);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status launch_bn_apply(const float *x, const float *mean, const float *invstd_or_var, const float *gamma, const float *beta, float *y, int N,
+                                  int O, int is_var, hipStream_t st) {
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, x, mean, invstd_or_var, gamma, beta, y, (size_t)N * O / 4, O,
+                       is_var);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status launch_bn_xhat(const float *x, const float *mean, const float *invstd, float *xhat, int N, int O, hipStream_t st) {
+    hipLaunchKernelGGL(bn_xhat_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, x, mean, invstd, xhat, (size_t)N * O / 4, O);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// S_dW [H][O]: S = dz1^T xhat in, dW1 out; dgamma / dbeta [O] out (bn_fold_grads_kernel + colfinal_kernel<1>)
+static pvr_status bn_fold_grads(float *S_dW, const float *W1, const float *db1, const float *gamma, const float *beta, float *dgamma, float *dbeta, int H,
+                                int O, hipStream_t st) {
+    constexpr int RPG = 64;
+    const int G = (H + RPG - 1) / RPG;
+    float *part;
+    TRY(col_scratch((size_t)2 * G * O, &part));
+    hipLaunchKernelGGL(bn_fold_grads_kernel, dim3(O / 128, G), dim3(256), 0, st, S_dW, W1, db1, gamma, beta, part, H, O, RPG);
+    hipLaunchKernelGGL(colfinal_kernel<1>, dim3((O + 255) / 256), dim3(256), 0, st, part, dgamma, dbeta, G, O);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status launch_bn_dx(const float *x, const float *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
+                               const float *dbeta, float *dx, int N, int O, int n_stat, hipStream_t st) {
+    hipLaunchKernelGGL(bn_dx_kernel, dim3(blocks_for((size_t)N * O)), dim3(256), 0, st, x, dy, mean, invstd, gamma, dgamma, dbeta, dx, N, O, n_stat);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status launch_bn_dx_xhat(float *dx, const float *xhat, const float *invstd, const float *gamma, const float *dgamma, const float *dbeta, int N,
+                                    int O, int n_stat, hipStream_t st) {
+    hipLaunchKernelGGL(bn_dx_xhat_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, dx, xhat, invstd, gamma, dgamma, dbeta, (size_t)N * O / 4,
+                       O, n_stat);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static void launch_lstm_fwd_step(const LstmFwdP &f, hipStream_t st) { hipLaunchKernelGGL(lstm_fwd_step_kernel, dim3(f.H / 4), dim3(256), 0, st, f); }
+static void launch_lstm_bwd_rec(const LstmRecP &r, hipStream_t st) { hipLaunchKernelGGL(lstm_bwd_rec_kernel, dim3(256), dim3(256), 0, st, r); }
+static void launch_lstm_bwd_cell(const LstmCellBP &c, hipStream_t st) {
+    hipLaunchKernelGGL(lstm_bwd_cell_kernel, dim3((c.B * c.H + 255) / 256), dim3(256), 0, st, c);
+}
+
+static pvr_status launch_heads(const HeadP &hp, hipStream_t st) {
+    hipLaunchKernelGGL(heads_kernel, dim3((hp.N + 3) / 4), dim3(256), 0, st, hp);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status launch_loss_mean(const float *loss_row, int N, float *out, hipStream_t st) {
+    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, st, loss_row, N, 1.0f / (float)N, out);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status launch_dlogits_pad(const float *in, float *out, int N, int A, hipStream_t st) {
+    hipLaunchKernelGGL(dlogits_pad_kernel, dim3((N * 16 + 255) / 256), dim3(256), 0, st, in, out, N, A);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+static pvr_status launch_hprev(const float *hs, const float *h_init, const float *nd, float *out, int T, int B, int H, hipStream_t st) {
+    hipLaunchKernelGGL(hprev_kernel, dim3(blocks_for((size_t)T * B * H / 4)), dim3(256), 0, st, hs, h_init, nd, out, T, B, H);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// heads backward: dWp [A][H], dbp [A] (one launch, or row-group partials + a fixed-order sum from 512 rows), then dout [N][H] = dl Wp
+static pvr_status head_backward(const float *dl, const float *out, const float *Wp, float *dWp, float *dbp, float *dout, int N, int H, int A, int form,
+                                hipStream_t st) {
+    bool two;
+    TRY(two_stage_form(form, N, H % 4 == 0, &two));
+    if (two) {
+        constexpr int RPG = 64;
+        const int G = (N + RPG - 1) / RPG;
+        float *part;
+        TRY(col_scratch((size_t)G * A * (H + 4), &part));
+        hipLaunchKernelGGL(head_dw_part_kernel, dim3((H / 4 + 31) / 32, G), dim3(256), 0, st, dl, out, part, N, H, A, RPG);
+        hipLaunchKernelGGL(head_dw_final_kernel, dim3((A * (H + 1) + 255) / 256), dim3(256), 0, st, part, dWp, dbp, G, H, A);
+    } else {
+        hipLaunchKernelGGL(head_dw_kernel, dim3((H + 1 + 31) / 32), dim3(256), 0, st, dl, out, dWp, dbp, N, H, A);
+    }
+    hipLaunchKernelGGL(head_dx_kernel, dim3(blocks_for((size_t)N * H)), dim3(256), 0, st, dl, Wp, dout, N, H, A);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+
 // forward through the workspace; logits/baseline/action land in pol->logits etc.  `target` non-null also
 // produces dlogits and per-row losses.
 pvr_status forward_core(pvr_policy *pol, const float *P, const pvr_policy_bn *bn, const void *obs_in, const uint8_t *done,
@@ -341,7 +476,7 @@ pvr_status forward_core(pvr_policy *pol, const float *P, const pvr_policy_bn *bn
     const int N = T * B, H = d.hidden, O = d.obs_size;
     // torch: "Expected more than 1 value per channel when training" (nn.BatchNorm1d on one row): no unbiased variance to put in running_var
     PVR_REQUIRE(!(d.batch_norm && training && N == 1), "policy: BatchNorm in training mode needs more than one row (T * B = 1), as torch.nn.BatchNorm1d does");
-    hipLaunchKernelGGL(notdone_kernel, dim3((N + 255) / 256), dim3(256), 0, st, done, pol->nd, N);
+    TRY(launch_notdone(done, pol->nd, N, st));
     const float *obs = (const float *)obs_in;
     if (d.conv_frames > 0) {
         // models.py:163-170: x/255, per-frame transpose(1,3), 5 x (conv3x3 s2 p1 + ELU), cat(-1), view(T*B,-1)
@@ -375,25 +510,13 @@ pvr_status forward_core(pvr_policy *pol, const float *P, const pvr_policy_bn *bn
                 const float ng = (float)N * (float)(sync ? pol->dp_world : 1);
                 float *sums = sync ? pol->sync_buf : pol->bn_invstd;                // (bn_invstd doubles as scratch until the final kernel)
                 float *sq = sync ? pol->sync_buf + O : pol->da0;                    // (da0 is free during the forward pass)
-                TRY(colsum(obs, sums, nullptr, N, O, st));
-                if (sync) TRY(dp_allreduce(pol, pol->sync_buf, O, st));
-                hipLaunchKernelGGL(scale_kernel, dim3((O + 255) / 256), dim3(256), 0, st, pol->bn_mean, sums, 1.0f / ng, O);
-                ColP c2 = {};
-                c2.X = obs; c2.mean_in = pol->bn_mean; c2.out0 = sq; c2.R = N; c2.C = O;
-                if (N >= 512 && O % 4 == 0) TRY(colreduce2<3>(c2, st));
-                else hipLaunchKernelGGL(colreduce_kernel<3>, dim3((O + 31) / 32), dim3(256), 0, st, c2);
-                PVR_LAUNCH_CHECK();
-                if (sync) TRY(dp_allreduce(pol, pol->sync_buf + O, O, st));
-                hipLaunchKernelGGL(bn_sync_final_kernel, dim3((O + 255) / 256), dim3(256), 0, st, sq, pol->bn_mean, ng,
-                                   pol->bn_invstd, bn->running_mean, bn->running_var, (long long *)bn->num_batches_tracked, O);
+                TRY(bn_batch_stats(obs, N, O, ng, sums, sq, pol->bn_mean, pol->bn_invstd, bn->running_mean, bn->running_var,
+                                   (long long *)bn->num_batches_tracked, -1, sync ? pol : nullptr, st));
             }
-            hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, obs, pol->bn_mean, pol->bn_invstd,
-                               P + pol->o_bnw, P + pol->o_bnb, pol->a0, (size_t)N * O / 4, O, 0);
+            TRY(launch_bn_apply(obs, pol->bn_mean, pol->bn_invstd, P + pol->o_bnw, P + pol->o_bnb, pol->a0, N, O, 0, st));
         } else {
-            hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, obs, bn->running_mean,
-                               bn->running_var, P + pol->o_bnw, P + pol->o_bnb, pol->a0, (size_t)N * O / 4, O, 1);
+            TRY(launch_bn_apply(obs, bn->running_mean, bn->running_var, P + pol->o_bnw, P + pol->o_bnb, pol->a0, N, O, 1, st));
         }
-        PVR_LAUNCH_CHECK();
         x0 = pol->a0;
     }
     TRY(gemm(x0, P + pol->o_fc1w, P + pol->o_fc1b, nullptr, pol->a1, N, H, O, false, false, 1, st));
@@ -428,7 +551,7 @@ pvr_status forward_core(pvr_policy *pol, const float *P, const pvr_policy_bn *bn
                                               : hipMemsetAsync(ctr, 0, 16, s_);
             if (me != hipSuccess) {                              // without the pre-fill the hand-off has no meaning: per-step launches instead
                 fill_err = me;
-                for (int t = t0; t < t1; ++t) { LstmFwdP f = fwd_job(l, t); hipLaunchKernelGGL(lstm_fwd_step_kernel, dim3(H / 4), dim3(256), 0, s_, f); }
+                for (int t = t0; t < t1; ++t) launch_lstm_fwd_step(fwd_job(l, t), s_);
                 return;
             }
             q.G = pol->G[l];
@@ -439,7 +562,7 @@ pvr_status forward_core(pvr_policy *pol, const float *P, const pvr_policy_bn *bn
             hipLaunchKernelGGL(lstm_fwd_seq_kernel, dim3(H / 4), dim3(256), 0, s_, q);
             return;
         }
-        for (int t = t0; t < t1; ++t) { LstmFwdP f = fwd_job(l, t); hipLaunchKernelGGL(lstm_fwd_step_kernel, dim3(H / 4), dim3(256), 0, s_, f); }
+        for (int t = t0; t < t1; ++t) launch_lstm_fwd_step(fwd_job(l, t), s_);
     };
     TRY(gemm(pol->a2, P + pol->o_wih[0], P + pol->o_bih[0], nullptr, pol->G[0], N, 4 * H, H, false, false, 0, st));
     const int NCH = (pol->pipeline || pol->chunkwave) && T >= 8 ? 4 : 1, CH = (T + NCH - 1) / NCH;
@@ -508,8 +631,7 @@ pvr_status forward_core(pvr_policy *pol, const float *P, const pvr_policy_bn *bn
     hp.logits = pol->logits; hp.baseline = pol->baseline; hp.dlogits = pol->dlogits; hp.loss_row = pol->loss_row;
     hp.action = pol->action; hp.target = target; hp.N = N; hp.H = H; hp.A = d.num_actions;
     hp.sample = pol->sample_on && training && !target; hp.seed = pol->sample_seed; hp.call = hp.sample ? pol->sample_call++ : 0;
-    hipLaunchKernelGGL(heads_kernel, dim3((N + 3) / 4), dim3(256), 0, st, hp);
-    PVR_LAUNCH_CHECK();
+    TRY(launch_heads(hp, st));
     if (fill_err != hipSuccess) {
         // the recurrence ran through per-step launches (results are valid); the failed memset is still an error of this call
         set_error("policy: hipMemsetAsync of the persistent recurrence's hand-off words failed: %s", hipGetErrorString(fill_err));
@@ -528,18 +650,7 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
     const int N = T * B, H = d.hidden, O = d.obs_size, A = d.num_actions;
     const float *obs = d.conv_frames > 0 ? pol->feat : (const float *)obs_in;
     // ---- heads backward --------------------------------------------------------------------------------------------
-    if (N >= 512 && H % 4 == 0) {
-        constexpr int RPG = 64;
-        const int G = (N + RPG - 1) / RPG;
-        float *part;
-        TRY(col_scratch((size_t)G * A * (H + 4), &part));
-        hipLaunchKernelGGL(head_dw_part_kernel, dim3((H / 4 + 31) / 32, G), dim3(256), 0, st, pol->dlogits, pol->Hs[1], part, N, H, A, RPG);
-        hipLaunchKernelGGL(head_dw_final_kernel, dim3((A * (H + 1) + 255) / 256), dim3(256), 0, st, part, Gd + pol->o_pw, Gd + pol->o_pb, G, H, A);
-    } else {
-        hipLaunchKernelGGL(head_dw_kernel, dim3((H + 1 + 31) / 32), dim3(256), 0, st, pol->dlogits, pol->Hs[1], Gd + pol->o_pw, Gd + pol->o_pb, N, H, A);
-    }
-    hipLaunchKernelGGL(head_dx_kernel, dim3(blocks_for((size_t)N * H)), dim3(256), 0, st, pol->dlogits, P + pol->o_pw, pol->dA, N, H, A);
-    PVR_LAUNCH_CHECK();
+    TRY(head_backward(pol->dlogits, pol->Hs[1], P + pol->o_pw, Gd + pol->o_pw, Gd + pol->o_pb, pol->dA, N, H, A, -1, st));
     // ---- LSTM backward, layer 1 then layer 0 ------------------------------------------------------------------------
     float *scr_dc[2] = {pol->dc_carry, pol->dc_carry1}, *scr_rec[2] = {pol->rec_partial, pol->rec_partial1}, *scr_hp[2] = {pol->hprev, pol->hprev1};
     // opt-in, one launch per step (round 3): W_hh^T of both layers first, then lstm_bwd_step2_kernel per (wavefronted) step
@@ -566,39 +677,10 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
         return c;
     };
 #endif
-    auto bwd_steps = [&](int l, int t_hi, int t_lo, const float *dh_ext_, hipStream_t s_) {          // t = t_hi-1 ... t_lo
-        for (int t = t_hi - 1; t >= t_lo; --t) {
-#ifdef PVR_EXPERIMENTS
-            if (fused) {
-                LstmStep2P q = {};
-                q.active[0] = 1; q.j[0] = step_job(l, t, dh_ext_);
-                hipLaunchKernelGGL(lstm_bwd_step2_kernel, dim3(H / 16, 1), dim3(256), 0, s_, q);
-                continue;
-            }
-#endif
-            const bool has_next = t < T - 1;
-            if (has_next) {
-                LstmRecP r;
-                r.dG_next = pol->G[l] + (size_t)(t + 1) * B * 4 * H; r.W = P + pol->o_whh[l]; r.partial = scr_rec[l]; r.B = B; r.H = H;
-                hipLaunchKernelGGL(lstm_bwd_rec_kernel, dim3(256), dim3(256), 0, s_, r);
-            }
-            LstmCellBP c;
-            c.partial = has_next ? scr_rec[l] : nullptr;
-            c.nd_next = has_next ? pol->nd + (size_t)(t + 1) * B : nullptr;
-            c.dh_ext = dh_ext_ + (size_t)t * B * H;
-            c.dc_carry = scr_dc[l];
-            c.G = pol->G[l] + (size_t)t * B * 4 * H;
-            c.c_t = pol->Cs[l] + (size_t)t * B * H;
-            c.c_prev = t == 0 ? pol->zeros : pol->Cs[l] + (size_t)(t - 1) * B * H;
-            c.nd = pol->nd + (size_t)t * B;
-            c.B = B; c.H = H;
-            hipLaunchKernelGGL(lstm_bwd_cell_kernel, dim3((B * H + 255) / 256), dim3(256), 0, s_, c);
-        }
-    };
     // dW_hh = dG^T (nd * h_prev), dW_ih = dG^T x_in, db_ih = db_hh = colsum(dG)
     auto weight_grads = [&](int l, hipStream_t s_) -> pvr_status {
         const float *xin = l == 0 ? pol->a2 : pol->Hs[0];
-        hipLaunchKernelGGL(hprev_kernel, dim3(blocks_for((size_t)N * H / 4)), dim3(256), 0, s_, pol->Hs[l], pol->zeros, pol->nd, scr_hp[l], T, B, H);
+        TRY(launch_hprev(pol->Hs[l], pol->zeros, pol->nd, scr_hp[l], T, B, H, s_));
         TRY(gemm(pol->G[l], scr_hp[l], nullptr, nullptr, Gd + pol->o_whh[l], 4 * H, H, N, true, true, 0, s_));
         TRY(gemm(pol->G[l], xin, nullptr, nullptr, Gd + pol->o_wih[l], 4 * H, H, N, true, true, 0, s_));
         return colsum(pol->G[l], Gd + pol->o_bih[l], Gd + pol->o_bhh[l], N, 4 * H, s_);
@@ -625,6 +707,20 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
         c.nd = pol->nd + (size_t)t * B;
         c.B = B; c.H = H;
         return c;
+    };
+    auto bwd_steps = [&](int l, int t_hi, int t_lo, const float *dh_ext_, hipStream_t s_) {          // t = t_hi-1 ... t_lo
+        for (int t = t_hi - 1; t >= t_lo; --t) {
+#ifdef PVR_EXPERIMENTS
+            if (fused) {
+                LstmStep2P q = {};
+                q.active[0] = 1; q.j[0] = step_job(l, t, dh_ext_);
+                hipLaunchKernelGGL(lstm_bwd_step2_kernel, dim3(H / 16, 1), dim3(256), 0, s_, q);
+                continue;
+            }
+#endif
+            if (t < T - 1) launch_lstm_bwd_rec(rec_job(l, t), s_);
+            launch_lstm_bwd_cell(cell_job(l, t, dh_ext_), s_);
+        }
     };
     // persistent BPTT: the chunk waves below, each as ONE launch (both layers' step ranges as the two jobs of lstm_bwd_seq_kernel)
 #ifdef PVR_EXPERIMENTS
@@ -747,17 +843,10 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
     const bool bn_fold = d.batch_norm && !need_dobs && bn_fold_on && O % 128 == 0 && H % 64 == 0;
     if (bn_fold) {
         float *xhat = pol->da0;                                                    // (free: nothing needs d(loss)/d(a0) on this path)
-        hipLaunchKernelGGL(bn_xhat_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, obs, pol->bn_mean, pol->bn_invstd, xhat, (size_t)N * O / 4, O);
+        TRY(launch_bn_xhat(obs, pol->bn_mean, pol->bn_invstd, xhat, N, O, st));
         TRY(gemm(dz1, xhat, nullptr, nullptr, Gd + pol->o_fc1w, H, O, N, true, true, 0, st));         // S = dz1^T xhat
         TRY(colsum(dz1, Gd + pol->o_fc1b, nullptr, N, H, st));
-        constexpr int RPG = 64;
-        const int G = (H + RPG - 1) / RPG;
-        float *part;
-        TRY(col_scratch((size_t)2 * G * O, &part));
-        hipLaunchKernelGGL(bn_fold_grads_kernel, dim3(O / 128, G), dim3(256), 0, st, Gd + pol->o_fc1w, P + pol->o_fc1w, Gd + pol->o_fc1b, P + pol->o_bnw,
-                           P + pol->o_bnb, part, H, O, RPG);
-        hipLaunchKernelGGL(colfinal_kernel<1>, dim3((O + 255) / 256), dim3(256), 0, st, part, Gd + pol->o_bnw, Gd + pol->o_bnb, G, O);
-        PVR_LAUNCH_CHECK();
+        TRY(bn_fold_grads(Gd + pol->o_fc1w, P + pol->o_fc1w, Gd + pol->o_fc1b, P + pol->o_bnw, P + pol->o_bnb, Gd + pol->o_bnw, Gd + pol->o_bnb, H, O, st));
         TRY(dp_bucket(pol, Gd, b_fc, b_l0 - b_fc, 2, st));
     } else {
     TRY(gemm(dz1, x0, nullptr, nullptr, Gd + pol->o_fc1w, H, O, N, true, true, 0, st));
@@ -770,8 +859,7 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
         ColP c = {};
         c.X = obs; c.dY = pol->da0; c.mean_in = pol->bn_mean; c.invstd_in = pol->bn_invstd;
         c.out0 = Gd + pol->o_bnw; c.out1 = Gd + pol->o_bnb; c.R = N; c.C = O;
-        if (N >= 512 && O % 4 == 0) TRY(colreduce2<2>(c, st));
-        else hipLaunchKernelGGL(colreduce_kernel<2>, dim3((O + 31) / 32), dim3(256), 0, st, c);
+        TRY(colreduce<2>(c, -1, st));
         if (need_dobs) {
             const float *dg = Gd + pol->o_bnw, *db = Gd + pol->o_bnb;
             int n_bn = N;
@@ -782,11 +870,9 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
                 TRY(dp_allreduce(pol, pol->sync_buf, 2 * O, st));
                 dg = pol->sync_buf; db = pol->sync_buf + O; n_bn = N * pol->dp_world;
             }
-            hipLaunchKernelGGL(bn_dx_kernel, dim3(blocks_for((size_t)N * O)), dim3(256), 0, st, obs, pol->da0, pol->bn_mean, pol->bn_invstd,
-                               P + pol->o_bnw, dg, db, pol->dfeat, N, O, n_bn);
+            TRY(launch_bn_dx(obs, pol->da0, pol->bn_mean, pol->bn_invstd, P + pol->o_bnw, dg, db, pol->dfeat, N, O, n_bn, st));
             dfeat = pol->dfeat;
         }
-        PVR_LAUNCH_CHECK();
     }
     if (need_dobs) {
         // ---- conv stack backward (models.py:107-118) ----------------------------------------------------------------
@@ -838,13 +924,9 @@ static pvr_status backward_core(pvr_policy *pol, const float *P, const void *obs
             // the fold path never formed da0 = dz1 W1: form it in the caller's buffer, then apply torch's training-mode BatchNorm input
             // gradient in place, with xhat as bn_xhat_kernel left it (pol->da0) and dgamma / dbeta from the finished gradient
             TRY(gemm(dz1, P + pol->o_fc1w, nullptr, nullptr, dobs, N, O, H, false, true, 0, st));
-            hipLaunchKernelGGL(bn_dx_xhat_kernel, dim3(blocks_for((size_t)N * O / 4)), dim3(256), 0, st, dobs, pol->da0, pol->bn_invstd, P + pol->o_bnw,
-                               Gd + pol->o_bnw, Gd + pol->o_bnb, (size_t)N * O / 4, O, N);
-            PVR_LAUNCH_CHECK();
+            TRY(launch_bn_dx_xhat(dobs, pol->da0, pol->bn_invstd, P + pol->o_bnw, Gd + pol->o_bnw, Gd + pol->o_bnb, N, O, N, st));
         } else {
-            hipLaunchKernelGGL(bn_dx_kernel, dim3(blocks_for((size_t)N * O)), dim3(256), 0, st, obs, pol->da0, pol->bn_mean, pol->bn_invstd, P + pol->o_bnw,
-                               Gd + pol->o_bnw, Gd + pol->o_bnb, dobs, N, O, N);
-            PVR_LAUNCH_CHECK();
+            TRY(launch_bn_dx(obs, pol->da0, pol->bn_mean, pol->bn_invstd, P + pol->o_bnw, Gd + pol->o_bnw, Gd + pol->o_bnb, dobs, N, O, N, st));
         }
     }
     if (dp_active(pol)) {
@@ -884,7 +966,7 @@ static pvr_status loss_backward(pvr_policy *pol, const float *params, const pvr_
                                 const long long *actions, int T, int B, float *grads, hipStream_t st, float *dobs = nullptr) {
     const int N = T * B;
     TRY(forward_core(pol, params, bn, obs, done, pol->zeros, pol->zeros, T, B, 1, actions, st));
-    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, st, pol->loss_row, N, 1.0f / (float)N, pol->stats);
+    TRY(launch_loss_mean(pol->loss_row, N, pol->stats, st));
     return backward_core(pol, params, obs, T, B, grads, st, dobs);
 }
 
@@ -1215,8 +1297,7 @@ static pvr_status policy_backward_dlogits_impl(pvr_policy *pol, const float *par
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const int N = T * B;
-    hipLaunchKernelGGL(dlogits_pad_kernel, dim3((N * 16 + 255) / 256), dim3(256), 0, st, dlogits, pol->dlogits, N, pol->d.num_actions);
-    PVR_LAUNCH_CHECK();
+    TRY(launch_dlogits_pad(dlogits, pol->dlogits, N, pol->d.num_actions, st));
     pol->fwd_T = pol->fwd_B = 0;                                  // (backward reuses activation buffers as scratch: one backward per forward)
     return backward_core(pol, params, obs, T, B, grads, st, dobs);
 }
@@ -1388,6 +1469,166 @@ pvr_status pvr_op_gemm_f32(const float *A, const float *B, const float *bias, fl
     ScratchScope scratch_scope(nullptr);
     return gemm(A, B, bias, nullptr, C, M, N, K, a_km != 0, b_kn != 0, relu, (hipStream_t)hip_stream);
 }
+
+pvr_status pvr_op_gemm_f32_masked(const float *A, const float *B, const float *bias, const float *mask, float *C, int32_t M, int32_t N, int32_t K,
+                                  int32_t a_km, int32_t b_kn, int32_t relu, void *hip_stream) {
+    PVR_REQUIRE(A && B && C, "pvr_op_gemm_f32_masked: null pointer");
+    PVR_REQUIRE(M > 0 && N > 0 && K > 0, "pvr_op_gemm_f32_masked: M, N, K must be positive");
+    ScratchScope scratch_scope(nullptr);
+    return gemm(A, B, bias, mask, C, M, N, K, a_km != 0, b_kn != 0, relu, (hipStream_t)hip_stream);
+}
+
+// ---- unit entry points of the policy kernels (tests/test_gpu_policy_kernels.py): stateless, the plan's own launch helpers ---------------------------
+#define OP_ALIGNED(p) (((uintptr_t)(p) & 15) == 0)
+
+int64_t pvr_debug_policy_two_stage_launches(void) { return (int64_t)g_two_stage_launches.load(); }
+
+pvr_status pvr_op_policy_colsum(const float *X, float *out0, float *out1, int32_t R, int32_t C, int32_t form, void *hip_stream) {
+    PVR_REQUIRE(X && out0 && R > 0 && C > 0, "pvr_op_policy_colsum: null pointer, or R = %d / C = %d not positive", R, C);
+    PVR_REQUIRE(OP_ALIGNED(X), "pvr_op_policy_colsum: X must be 16-byte aligned");
+    ScratchScope scratch_scope(nullptr);
+    return colsum(X, out0, out1, R, C, (hipStream_t)hip_stream, form);
+}
+
+pvr_status pvr_op_policy_bn_stats(const float *X, int32_t R, int32_t C, float n_global, int32_t form, float *mean, float *invstd, float *sumsq,
+                                  float *running_mean, float *running_var, int64_t *num_batches_tracked, void *hip_stream) {
+    PVR_REQUIRE(X && mean && invstd && sumsq && running_mean && running_var, "pvr_op_policy_bn_stats: null pointer");
+    PVR_REQUIRE(R > 0 && C > 0 && n_global > 1.f, "pvr_op_policy_bn_stats: R = %d, C = %d must be positive and n_global = %g above 1", R, C, (double)n_global);
+    PVR_REQUIRE(OP_ALIGNED(X) && OP_ALIGNED(mean), "pvr_op_policy_bn_stats: X and mean must be 16-byte aligned");
+    ScratchScope scratch_scope(nullptr);
+    return bn_batch_stats(X, R, C, n_global, invstd, sumsq, mean, invstd, running_mean, running_var, (long long *)num_batches_tracked, form, nullptr,
+                          (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_bn_apply(const float *x, const float *mean, const float *invstd_or_var, const float *gamma, const float *beta, float *y, int32_t R,
+                                  int32_t C, int32_t is_var, void *hip_stream) {
+    PVR_REQUIRE(x && mean && invstd_or_var && gamma && beta && y, "pvr_op_policy_bn_apply: null pointer");
+    PVR_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && OP_ALIGNED(x) && OP_ALIGNED(y), "pvr_op_policy_bn_apply: R, C positive, C %% 4 == 0, x and y 16-byte aligned");
+    return launch_bn_apply(x, mean, invstd_or_var, gamma, beta, y, R, C, is_var != 0, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_bn_backward_sums(const float *X, const float *dY, const float *mean, const float *invstd, float *dgamma, float *dbeta, int32_t R,
+                                          int32_t C, int32_t form, void *hip_stream) {
+    PVR_REQUIRE(X && dY && mean && invstd && dgamma && dbeta && R > 0 && C > 0, "pvr_op_policy_bn_backward_sums: null pointer, or R / C not positive");
+    PVR_REQUIRE(OP_ALIGNED(X) && OP_ALIGNED(dY) && OP_ALIGNED(mean) && OP_ALIGNED(invstd), "pvr_op_policy_bn_backward_sums: inputs must be 16-byte aligned");
+    ScratchScope scratch_scope(nullptr);
+    ColP c = {};
+    c.X = X; c.dY = dY; c.mean_in = mean; c.invstd_in = invstd; c.out0 = dgamma; c.out1 = dbeta; c.R = R; c.C = C;
+    return colreduce<2>(c, form, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_bn_xhat(const float *x, const float *mean, const float *invstd, float *xhat, int32_t R, int32_t C, void *hip_stream) {
+    PVR_REQUIRE(x && mean && invstd && xhat, "pvr_op_policy_bn_xhat: null pointer");
+    PVR_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && OP_ALIGNED(x) && OP_ALIGNED(xhat) && OP_ALIGNED(mean) && OP_ALIGNED(invstd),
+                "pvr_op_policy_bn_xhat: R, C positive, C %% 4 == 0, 16-byte aligned buffers");
+    return launch_bn_xhat(x, mean, invstd, xhat, R, C, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_bn_fold(float *S_dW, const float *W1, const float *db1, const float *gamma, const float *beta, float *dgamma, float *dbeta,
+                                 int32_t H, int32_t O, void *hip_stream) {
+    PVR_REQUIRE(S_dW && W1 && db1 && gamma && beta && dgamma && dbeta, "pvr_op_policy_bn_fold: null pointer");
+    PVR_REQUIRE(H > 0 && O > 0 && O % 128 == 0, "pvr_op_policy_bn_fold: H = %d must be positive and O = %d a positive multiple of 128 (the plan's condition)", H, O);
+    PVR_REQUIRE(OP_ALIGNED(S_dW) && OP_ALIGNED(W1) && OP_ALIGNED(gamma) && OP_ALIGNED(beta), "pvr_op_policy_bn_fold: 16-byte aligned buffers required");
+    ScratchScope scratch_scope(nullptr);
+    return bn_fold_grads(S_dW, W1, db1, gamma, beta, dgamma, dbeta, H, O, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_bn_dx(const float *x, const float *dy, const float *mean, const float *invstd, const float *gamma, const float *dgamma,
+                               const float *dbeta, float *dx, int32_t R, int32_t C, int32_t n_stat, void *hip_stream) {
+    PVR_REQUIRE(x && dy && mean && invstd && gamma && dgamma && dbeta && dx, "pvr_op_policy_bn_dx: null pointer");
+    PVR_REQUIRE(R > 0 && C > 0 && n_stat > 0, "pvr_op_policy_bn_dx: R, C, n_stat must be positive");
+    return launch_bn_dx(x, dy, mean, invstd, gamma, dgamma, dbeta, dx, R, C, n_stat, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_bn_dx_xhat(float *dx, const float *xhat, const float *invstd, const float *gamma, const float *dgamma, const float *dbeta,
+                                    int32_t R, int32_t C, int32_t n_stat, void *hip_stream) {
+    PVR_REQUIRE(dx && xhat && invstd && gamma && dgamma && dbeta, "pvr_op_policy_bn_dx_xhat: null pointer");
+    PVR_REQUIRE(R > 0 && C > 0 && C % 4 == 0 && n_stat > 0, "pvr_op_policy_bn_dx_xhat: R, C, n_stat positive and C %% 4 == 0");
+    PVR_REQUIRE(OP_ALIGNED(dx) && OP_ALIGNED(xhat) && OP_ALIGNED(invstd) && OP_ALIGNED(gamma) && OP_ALIGNED(dgamma) && OP_ALIGNED(dbeta),
+                "pvr_op_policy_bn_dx_xhat: 16-byte aligned buffers required");
+    return launch_bn_dx_xhat(dx, xhat, invstd, gamma, dgamma, dbeta, R, C, n_stat, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_notdone(const uint8_t *done, float *nd, int32_t n, void *hip_stream) {
+    PVR_REQUIRE(done && nd && n > 0, "pvr_op_policy_notdone: null pointer or n = %d", n);
+    return launch_notdone(done, nd, n, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_hprev(const float *hs, const float *h_init, const float *nd, float *out, int32_t T, int32_t B, int32_t H, void *hip_stream) {
+    PVR_REQUIRE(hs && h_init && nd && out, "pvr_op_policy_hprev: null pointer");
+    PVR_REQUIRE(T > 0 && B > 0 && H > 0 && H % 4 == 0 && OP_ALIGNED(hs) && OP_ALIGNED(h_init) && OP_ALIGNED(out),
+                "pvr_op_policy_hprev: T, B, H positive, H %% 4 == 0, 16-byte aligned buffers");
+    return launch_hprev(hs, h_init, nd, out, T, B, H, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_dlogits_pad(const float *in, float *out, int32_t N, int32_t A, void *hip_stream) {
+    PVR_REQUIRE(in && out && N > 0 && A > 0 && A <= 16, "pvr_op_policy_dlogits_pad: null pointer, N = %d not positive or A = %d outside 1..16", N, A);
+    return launch_dlogits_pad(in, out, N, A, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_loss_mean(const float *loss_row, int32_t n, float *out, void *hip_stream) {
+    PVR_REQUIRE(loss_row && out && n > 0, "pvr_op_policy_loss_mean: null pointer or n = %d", n);
+    return launch_loss_mean(loss_row, n, out, (hipStream_t)hip_stream);
+}
+
+static pvr_status lstm_shape_check(const char *fn, int B, int H) {
+    PVR_REQUIRE(B > 0 && H > 0 && H % 1024 == 0, "%s: B = %d must be positive and H = %d a positive multiple of 1024", fn, B, H);
+    return PVR_OK;
+}
+
+pvr_status pvr_op_policy_lstm_fwd_step(float *G, const float *h_prev, const float *c_prev, const float *nd, const float *W_hh, const float *b_hh,
+                                       float *h_out, float *c_out, int32_t B, int32_t H, void *hip_stream) {
+    PVR_REQUIRE(G && h_prev && c_prev && nd && W_hh && b_hh && h_out && c_out, "pvr_op_policy_lstm_fwd_step: null pointer");
+    TRY(lstm_shape_check("pvr_op_policy_lstm_fwd_step", B, H));
+    PVR_REQUIRE(OP_ALIGNED(h_prev) && OP_ALIGNED(W_hh), "pvr_op_policy_lstm_fwd_step: h_prev and W_hh must be 16-byte aligned");
+    LstmFwdP f;
+    f.G = G; f.h_prev = h_prev; f.c_prev = c_prev; f.nd = nd; f.W = W_hh; f.bhh = b_hh; f.h_out = h_out; f.c_out = c_out; f.B = B; f.H = H;
+    launch_lstm_fwd_step(f, (hipStream_t)hip_stream);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+pvr_status pvr_op_policy_lstm_bwd_step(const float *dG_next, const float *W_hh, const float *nd_next, const float *dh_ext, float *dc_carry, float *G,
+                                       const float *c_t, const float *c_prev, const float *nd, float *partial, int32_t B, int32_t H, void *hip_stream) {
+    PVR_REQUIRE(dh_ext && dc_carry && G && c_t && c_prev && nd, "pvr_op_policy_lstm_bwd_step: null pointer");
+    PVR_REQUIRE(!dG_next || (W_hh && nd_next && partial), "pvr_op_policy_lstm_bwd_step: with dG_next, W_hh, nd_next and partial ([16][B][H] scratch) are needed");
+    TRY(lstm_shape_check("pvr_op_policy_lstm_bwd_step", B, H));
+    PVR_REQUIRE(!dG_next || (OP_ALIGNED(dG_next) && OP_ALIGNED(W_hh)), "pvr_op_policy_lstm_bwd_step: dG_next and W_hh must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (dG_next) {
+        LstmRecP r;
+        r.dG_next = dG_next; r.W = W_hh; r.partial = partial; r.B = B; r.H = H;
+        launch_lstm_bwd_rec(r, st);
+    }
+    LstmCellBP c;
+    c.partial = dG_next ? partial : nullptr; c.nd_next = dG_next ? nd_next : nullptr; c.dh_ext = dh_ext; c.dc_carry = dc_carry; c.G = G; c.c_t = c_t;
+    c.c_prev = c_prev; c.nd = nd; c.B = B; c.H = H;
+    launch_lstm_bwd_cell(c, st);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+pvr_status pvr_op_policy_heads(const float *out, const float *Wp, const float *bp, const float *Wb, const float *bb, const int64_t *target, float *logits,
+                               float *baseline, int64_t *action, float *loss_row, float *dlogits, int32_t N, int32_t H, int32_t A, void *hip_stream) {
+    PVR_REQUIRE(out && Wp && bp && Wb && bb && logits && baseline && action, "pvr_op_policy_heads: null pointer");
+    PVR_REQUIRE(!target || (loss_row && dlogits), "pvr_op_policy_heads: a target needs loss_row and dlogits");
+    PVR_REQUIRE(N > 0 && H > 0 && H % 4 == 0 && A > 0 && A <= 16, "pvr_op_policy_heads: N = %d, H = %d (multiple of 4), A = %d (1..16)", N, H, A);
+    PVR_REQUIRE(OP_ALIGNED(out) && OP_ALIGNED(Wp) && OP_ALIGNED(Wb), "pvr_op_policy_heads: out, Wp and Wb must be 16-byte aligned");
+    HeadP hp;
+    hp.out = out; hp.Wp = Wp; hp.bp = bp; hp.Wb = Wb; hp.bb = bb; hp.logits = logits; hp.baseline = baseline; hp.dlogits = dlogits; hp.loss_row = loss_row;
+    hp.action = (long long *)action; hp.target = (const long long *)target; hp.N = N; hp.H = H; hp.A = A; hp.sample = 0; hp.seed = 0; hp.call = 0;
+    return launch_heads(hp, (hipStream_t)hip_stream);
+}
+
+pvr_status pvr_op_policy_head_backward(const float *dlogits, const float *out, const float *Wp, float *dWp, float *dbp, float *dout, int32_t N, int32_t H,
+                                       int32_t A, int32_t form, void *hip_stream) {
+    PVR_REQUIRE(dlogits && out && Wp && dWp && dbp && dout, "pvr_op_policy_head_backward: null pointer");
+    PVR_REQUIRE(N > 0 && H > 0 && A > 0 && A <= 16, "pvr_op_policy_head_backward: N = %d, H = %d, A = %d (1..16)", N, H, A);
+    PVR_REQUIRE(OP_ALIGNED(out), "pvr_op_policy_head_backward: out must be 16-byte aligned");
+    ScratchScope scratch_scope(nullptr);
+    return head_backward(dlogits, out, Wp, dWp, dbp, dout, N, H, A, form, (hipStream_t)hip_stream);
+}
+#undef OP_ALIGNED
 
 pvr_status pvr_debug_set_gemm_mode(int32_t mode) {
     PVR_REQUIRE(mode >= -1 && mode <= 3, "pvr_debug_set_gemm_mode: mode must be -1 (default), 0 (fp32 MFMA), 1 / 2 / 3 (split-bf16 MFMA: automatic / 128 / 64 tiles)");

@@ -357,13 +357,12 @@ static __global__ __launch_bounds__(256) void transpose_kernel(const float *__re
 // ---------------------------------------------------------------------------------------------------------
 // column reductions over the N = T*B rows (fixed order: 8 row groups per column, then an LDS tree)
 //   MODE 0: out[c] = sum_r X[r][c]
-//   MODE 1: BN statistics (models.py:31-34, training): mean, 1/sqrt(var_biased+eps), running-stat update
+//   MODE 3: out[c] = sum_r (X[r][c] - mean[c])^2   (BN statistics, models.py:31-34: second pass; bn_sync_final_kernel finishes them)
 //   MODE 2: BN affine grads: dgamma[c] = sum_r dY[r][c]*(X[r][c]-mean[c])*invstd[c], dbeta[c] = sum_r dY[r][c]
 // ---------------------------------------------------------------------------------------------------------
 struct ColP {
     const float *X, *dY, *mean_in, *invstd_in;
-    float *out0, *out1, *running_mean, *running_var;
-    long long *nbt;
+    float *out0, *out1;
     int R, C;
     int out_stride;   // MODE 0 with two outputs (bias_ih and bias_hh get the same sum): out1 optional
 };
@@ -376,8 +375,6 @@ static __global__ __launch_bounds__(256) void colreduce_kernel(ColP p) {
     const bool ok = c < p.C;
     float a0 = 0.f, a1 = 0.f;
     if (MODE == 0) {
-        if (ok) for (int r = g; r < p.R; r += 8) a0 += p.X[(size_t)r * p.C + c];
-    } else if (MODE == 1) {
         if (ok) for (int r = g; r < p.R; r += 8) a0 += p.X[(size_t)r * p.C + c];
     } else if (MODE == 3) {          // centred sum of squares around a given mean (SyncBN second pass)
         if (ok) {
@@ -401,27 +398,8 @@ static __global__ __launch_bounds__(256) void colreduce_kernel(ColP p) {
     for (int i = 0; i < 8; ++i) { t0 += s0[i][cx]; t1 += s1[i][cx]; }
     if (MODE == 0 || MODE == 3) {
         if (ok && g == 0) { p.out0[c] = t0; if (p.out1) p.out1[c] = t0; }
-    } else if (MODE == 2) {
-        if (ok && g == 0) { p.out0[c] = t0; p.out1[c] = t1; }
     } else {
-        const float mean = t0 / (float)p.R;
-        __syncthreads();
-        float v = 0.f;
-        if (ok) for (int r = g; r < p.R; r += 8) { const float d = p.X[(size_t)r * p.C + c] - mean; v += d * d; }
-        s0[g][cx] = v;
-        __syncthreads();
-        if (ok && g == 0) {
-            float vs = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) vs += s0[i][cx];
-            const float var_b = vs / (float)p.R;
-            p.out0[c] = mean;
-            p.out1[c] = 1.0f / sqrtf(var_b + 1e-5f);
-            // momentum 0.1, unbiased variance in the running estimate (torch BatchNorm1d)
-            p.running_mean[c] = 0.9f * p.running_mean[c] + 0.1f * mean;
-            p.running_var[c] = 0.9f * p.running_var[c] + 0.1f * (var_b * (float)p.R / (float)(p.R - 1));
-            if (c == 0 && p.nbt) *p.nbt += 1;
-        }
+        if (ok && g == 0) { p.out0[c] = t0; p.out1[c] = t1; }
     }
 }
 
@@ -1296,9 +1274,11 @@ static __global__ __launch_bounds__(256) void heads_kernel(HeadP p) {
         const bool tg_ok = tgl >= 0 && tgl < p.A;                 // torch's nll_loss raises for a target outside [0, A): fail loudly here too
         const int tg = tg_ok ? (int)tgl : 0;
         p.loss_row[n] = tg_ok ? lse - l[tg] : __builtin_nanf("");   // NaN loss (and NaN gradient norm downstream) instead of an out-of-bounds read
+        // softmax normalised by division: the probabilities of a row add up to 1 to rounding whatever the library's expf / logf do.  expf(l - lse)
+        // left every row sum about 3e-8 above 1 (a bias of logf and the second expf), which d(loss)/d(policy.bias) adds up over all T*B rows
         const float inv = 1.0f / (float)p.N;
         for (int a = 0; a < 16; ++a)
-            p.dlogits[(size_t)n * 16 + a] = a < p.A ? (expf(l[a] - lse) - (a == tg ? 1.f : 0.f)) * inv : 0.f;
+            p.dlogits[(size_t)n * 16 + a] = a < p.A ? (expf(l[a] - mx) / se - (a == tg ? 1.f : 0.f)) * inv : 0.f;
     }
 }
 

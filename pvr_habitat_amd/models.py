@@ -98,6 +98,28 @@ def _plib():
         L.pvr_debug_set_gemm_mode.argtypes = [i32]
         L.pvr_op_gemm_f32.restype = C.c_int
         L.pvr_op_gemm_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
+        # unit entry points of the policy kernels (include/pvr_policy.h)
+        L.pvr_debug_policy_two_stage_launches.restype = i64
+        L.pvr_debug_policy_two_stage_launches.argtypes = []
+        for name, args in (('gemm_f32_masked', [vp] * 5 + [i32] * 6 + [vp]),
+                           ('policy_colsum', [vp, vp, vp, i32, i32, i32, vp]),
+                           ('policy_bn_stats', [vp, i32, i32, f32, i32] + [vp] * 7),
+                           ('policy_bn_apply', [vp] * 6 + [i32, i32, i32, vp]),
+                           ('policy_bn_backward_sums', [vp] * 6 + [i32, i32, i32, vp]),
+                           ('policy_bn_xhat', [vp] * 4 + [i32, i32, vp]),
+                           ('policy_bn_fold', [vp] * 7 + [i32, i32, vp]),
+                           ('policy_bn_dx', [vp] * 8 + [i32, i32, i32, vp]),
+                           ('policy_bn_dx_xhat', [vp] * 6 + [i32, i32, i32, vp]),
+                           ('policy_notdone', [vp, vp, i32, vp]),
+                           ('policy_hprev', [vp] * 4 + [i32, i32, i32, vp]),
+                           ('policy_dlogits_pad', [vp, vp, i32, i32, vp]),
+                           ('policy_loss_mean', [vp, i32, vp, vp]),
+                           ('policy_lstm_fwd_step', [vp] * 8 + [i32, i32, vp]),
+                           ('policy_lstm_bwd_step', [vp] * 10 + [i32, i32, vp]),
+                           ('policy_heads', [vp] * 11 + [i32, i32, i32, vp]),
+                           ('policy_head_backward', [vp] * 6 + [i32, i32, i32, i32, vp])):
+            fn = getattr(L, 'pvr_op_' + name)
+            fn.restype, fn.argtypes = C.c_int, args
         L._policy_bound = True
     return L
 
