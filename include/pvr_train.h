@@ -302,6 +302,59 @@ pvr_status pvr_trainer_forward_rects(pvr_trainer *tr, const float *params_dev, v
                                      int32_t w, const int32_t *rects_dev, const void *color_dev, uint32_t *gray_sums_dev, float *boundary_dev,
                                      int32_t reuse, float *out_dev, int64_t out_stride, void *hip_stream);
 
+/* Random grayscale and Gaussian blur per frame and step (the Python modes random_grayscale and gaussian_blur): the last two augmentations of MoCo v2's
+ * recipe, torchvision's RandomGrayscale(p) and RandomApply([GaussianBlur(23, sigma = (lo, hi))], p) on the uint8 values of a frame's image - after the
+ * window or rectangle and the colour jitter, grayscale first and blur second, before / 255 and Normalize.  A frame's parameters are two 32-bit words: float
+ * sigma (0: not blurred) and int32 gray (0 or 1).  A blurred pixel is no function of one source pixel, so the image is made from a staged uint8 copy.
+ * pvr_op_blur_params / pvr_host_blur_params: the parameters of frames first_frame .. first_frame + n into device / host memory (n x 2 words).  Frame f
+ *   draws four words from Philox-4x32-10 with counter (f, call), as the windows do, and key (seed_lo, seed_hi ^ 0x424C5552): a stream of its own, so
+ *   pvr_op_crop_windows, pvr_op_crop_rects and pvr_op_color_params keep their bits at the same (seed, call).  With u_j the uniform in the open interval
+ *   (0, 1) that pvr_op_color_params makes of word j: the frame is blurred if u_0 < p_blur, with sigma = fma(hi - lo, u_1, lo) in [lo, hi], and grayed if
+ *   u_2 < p_gray; p = 1 always applies and p = 0 never does.  Both functions run one inline (csrc/sample_rng.h) and agree bit for bit; the result depends on
+ *   (seed, call, frame) and the four numbers alone: rows lo .. hi of one draw equal a draw with first_frame = lo.  pvr_op_blur_params refuses by name,
+ *   launching nothing: a null or not 4-byte aligned blur_dev, n < 1, a negative first_frame, a probability outside [0, 1] or not finite, a sigma range
+ *   that is not finite or not 0 < lo <= hi; the host function treats such a range as (1, 1) and writes nothing through a null pointer.
+ * pvr_op_preprocess_staged: frames -> each frame's crop x crop uint8 pixels, 4 bytes per pixel (r, g, b, 0), into staged_dev - (n, crop, crop, 4) uint8,
+ *   16-byte aligned, the caller's scratch as gray_sums_dev is.  The pixel source is the window (windows_dev, as pvr_op_preprocess_windows reads it, with
+ *   resize) or the rectangle (rects_dev, as pvr_op_preprocess_rects reads it; resize is not used), exactly one of them.  color_dev != NULL needs
+ *   gray_sums_dev and runs the launch "colour stats" of pvr_op_preprocess_color as it is, then the frame's colour ops on every pixel.  Then ONE launch,
+ *   "stage image".  It runs the device inlines of the un-staged kernels, so the staged bytes are exactly the uint8 values those kernels normalise.
+ *   Refused by name, launching nothing: a null frames_dev or staged_dev, both or neither pixel source, what the source's own op refuses for n, h, w,
+ *   crop and the alignment of its array, staged_dev not 16-byte aligned, more than 65535 frames, and with colour a null or misaligned gray_sums_dev, a
+ *   misaligned color_dev, a crop above 256.
+ * pvr_op_blur_normalize: the staged pixels -> per frame grayscale if flagged (trunc(((0.2989 r) + (0.587 g)) + (0.114 b)) on all three channels:
+ *   rgb_to_grayscale(num_output_channels = 3) on uint8), blur if sigma > 0, (v / 255 - mean) / std into the dense fp32 NHWC4 image: one launch, "blur
+ *   normalize".  The blur is torchvision's gaussian_blur on a uint8 tensor with kernel size 23 (fixed; PIL's radius semantics are not offered): 1-D weights
+ *   pdf_i = exp(-0.5 (i / sigma)^2), i = -11 .. 11, over their sum, the 2-D kernel their outer product, reflect padding of 11, the sum in fp32 with no
+ *   rounding between the two axes, then round-half-even to uint8.  The kernel sums the two axes one after the other (a separable filter in LDS:
+ *   csrc/preprocess.hip), torchvision all 529 products at once: the fp32 sums differ by rounding alone, so the uint8 result equals the exactly rounded
+ *   one except where the exact sum lies within 1.9e-3 of a .5 tie (tests/gaussian_blur_refs.py derives the bound), and is never more than one step
+ *   off.  Hardened in the kernel: a NaN or non-positive sigma means no blur, sigma is clamped to at most 16, tap 0's pdf is 1 by definition (a tiny sigma
+ *   is the identity, never 0 / 0), a non-zero gray word counts as 1, every read is reflected and clamped into the frame: no value of blur_dev can produce
+ *   a NaN image or a read outside the frame.  Plain vector loads and stores, no atomics: two runs give the same bits.  A frame with sigma 0 and gray 0
+ *   gets the bits of the un-staged kernels.  Refused by name, launching nothing: a null staged_dev, mean, std_, blur_dev or out_dev, staged_dev or out_dev
+ *   not 16-byte or blur_dev not 4-byte aligned, n < 1, crop < 12 (a reflect padding of 11 needs 12 pixels), crop > 256, more than 65535 frames.
+ * pvr_trainer_forward_staged: pvr_trainer_forward_rects plus windows_dev, blur_dev and staged_dev.  blur_dev == NULL: exactly pvr_trainer_forward_rects
+ *   (with rects_dev) or pvr_trainer_forward_augmented (without) - the same launches, names, bits and refusals.  blur_dev != NULL needs staged_dev and
+ *   exactly one of windows_dev and rects_dev (the centre window for every frame where no random crop is wanted, as the colour jitter does): "stage image"
+ *   (with color_dev "colour stats" before it) and "blur normalize" stand where the image launches stood; everything after is unchanged, and the held
+ *   forward's image is the augmented one, so conv1's weight gradient sees it.  reuse != 0 (with boundary_dev): nothing before the first trained op runs
+ *   and no array is read.  The handle keeps nothing about the parameters: a recompute pass that runs the stem again is handed the same rows again.
+ *   pvr_trainer_prefix_forward keeps the plain centre crop.  Refused by name, launching nothing: what pvr_trainer_forward_rects refuses, both or neither
+ *   pixel source, a misaligned windows_dev or blur_dev, a null or misaligned staged_dev, a crop outside 12 .. 256. */
+pvr_status pvr_op_blur_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float p_blur, float sigma_lo, float sigma_hi, float p_gray,
+                              void *blur_dev, void *hip_stream);
+void pvr_host_blur_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float p_blur, float sigma_lo, float sigma_hi, float p_gray,
+                          void *blur_host);
+pvr_status pvr_op_preprocess_staged(const uint8_t *frames_dev, int32_t n, int32_t h, int32_t w, int32_t resize, int32_t crop, const int32_t *windows_dev,
+                                    const int32_t *rects_dev, const void *color_dev, uint32_t *gray_sums_dev, void *staged_dev, void *hip_stream);
+pvr_status pvr_op_blur_normalize(const void *staged_dev, int32_t n, int32_t crop, const float *mean, const float *std_, const void *blur_dev,
+                                 float *out_dev, void *hip_stream);
+pvr_status pvr_trainer_forward_staged(pvr_trainer *tr, const float *params_dev, void *bn_buffers_dev, const uint8_t *frames_dev, int32_t n, int32_t h,
+                                      int32_t w, const int32_t *windows_dev, const int32_t *rects_dev, const void *color_dev, uint32_t *gray_sums_dev,
+                                      const void *blur_dev, void *staged_dev, float *boundary_dev, int32_t reuse, float *out_dev, int64_t out_stride,
+                                      void *hip_stream);
+
 /* per-launch timing (scripts/train_step_times.py): on != 0 brackets every launch of the following forwards / backwards with
  * events (the calls then synchronise); pvr_trainer_launch_time reads launch `index` of the last forward + backward: its name,
  * milliseconds and algorithmic FLOPs (0 for byte kernels); returns the name's length, 0 past the end */

@@ -147,6 +147,12 @@ _SIGS = {
                                           C.c_void_p, C.c_void_p]),
     'pvr_trainer_forward_rects': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    'pvr_op_blur_params': (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    'pvr_host_blur_params': (None, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'pvr_op_preprocess_staged': (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 6),
+    'pvr_op_blur_normalize': (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pvr_trainer_forward_staged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7 +
+                                   [C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_conv_bn_frozen_forward_split16_scratch_floats': (C.c_int64, [C.c_int32] * 8),
     'pvr_op_conv_bn_frozen_forward_split16': (C.c_int, [C.c_void_p] * 8 + [C.c_int32] * 9 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'pvr_op_conv_fwd_split16_scratch_floats':(C.c_int64, [C.c_int32] * 8),

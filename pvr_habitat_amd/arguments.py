@@ -84,6 +84,18 @@ def make_parser():
                              'with --embedding_color_jitter.  Not with --embedding_random_crop (both choose the window), and not with '
                              '--embedding_prefix_cache, whose cache holds the frozen prefix\'s output for ONE window per frame; --embedding_prefix_once is '
                              'the compatible mode')
+    parser.add_argument('--embedding_gaussian_blur', type=float, nargs=3, default=None, metavar=('P', 'LO', 'HI'),
+                        help='with --train_embedding: with probability P a frame of a training step is blurred as torchvision\'s GaussianBlur(kernel_size=23, '
+                             'sigma=(LO, HI)) blurs a uint8 tensor, sigma uniform in [LO, HI] - after the crop, the colour jitter and the grayscale, before '
+                             '/ 255 and Normalize (MoCo v2\'s blur is 0.5 0.1 2.0; evaluation keeps the plain centre crop).  The kernel size is fixed at 23.  '
+                             'Default off.  The draw is a function of --run_id, the iteration and the frame, so a resumed run draws what an uninterrupted '
+                             'one would.  Composes with --embedding_random_grayscale, --embedding_random_crop or --embedding_random_resized_crop and '
+                             '--embedding_color_jitter.  Not with --embedding_prefix_cache; --embedding_prefix_once is the compatible mode')
+    parser.add_argument('--embedding_random_grayscale', type=float, default=None, metavar='P',
+                        help='with --train_embedding: with probability P the three channels of a frame of a training step are replaced by its gray value, '
+                             'torchvision\'s RandomGrayscale on a uint8 tensor - after the crop and the colour jitter, before the blur (MoCo v2\'s is 0.2; '
+                             'evaluation keeps the plain centre crop).  Default off.  The draw is a function of --run_id, the iteration and the frame.  Not '
+                             'with --embedding_prefix_cache; --embedding_prefix_once is the compatible mode')
     parser.add_argument('--batch_norm', action='store_true')
     # not in the reference (src/arguments.py): 5 = corner + centre windows per frame (BASELINE config 5 extension), 1 = CenterCrop
     parser.add_argument('--crops', type=int, default=1, choices=[1, 5])

@@ -71,6 +71,15 @@ pvr_status launch_preprocess_rects(const uint8_t *frames, int n, int h, int w, i
                                    float *out, hipStream_t stream);
 pvr_status launch_color_stage_rects(int stage, const uint8_t *frames, int n, int h, int w, int crop, const float *mean, const float *std_,
                                     const int32_t *rects, const void *color, uint32_t *gray_sums, float *out, hipStream_t stream);
+// the staged image path (grayscale and blur): "colour stats" as above with either source, "stage image" - the source's uint8 pixels after the colour ops,
+// 4 bytes per pixel, into the caller's (n, crop, crop, 4) scratch - and "blur normalize" - grayscale, GaussianBlur(23, sigma), /255 and Normalize per
+// frame by blur: n x (float sigma, int32 gray).  Exactly one of windows and rects is non-null
+pvr_status launch_staged_color_stats(const uint8_t *frames, int n, int h, int w, int resize, int crop, const int32_t *windows, const int32_t *rects,
+                                     const void *color, uint32_t *gray_sums, void *staged, hipStream_t stream);
+pvr_status launch_stage_image(const uint8_t *frames, int n, int h, int w, int resize, int crop, const int32_t *windows, const int32_t *rects,
+                              const void *color, uint32_t *gray_sums, void *staged, hipStream_t stream);
+pvr_status launch_blur_normalize(const void *staged, int n, int crop, const float *mean, const float *std_, const void *blur, float *out,
+                                 hipStream_t stream);
 pvr_status launch_stem(const void *, const void *, const float *, void *, int, int, int, hipStream_t);
 pvr_status launch_maxpool(const void *, void *, int, int, int, int, int, hipStream_t);
 // (c1_*: layer1.0.conv1 inside the stem - stem.hip, StemC1; only when stem_conv1_capable(sw))

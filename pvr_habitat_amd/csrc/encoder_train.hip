@@ -426,10 +426,12 @@ namespace {
 // color, gray_sums (pvr_trainer_forward_augmented, with windows): n x (float b, c, s, int32 order) and n uint32 of the caller's scratch - the window's
 // uint8 values are colour-jittered before /255 and Normalize, by two launches in place of that one.  rects (pvr_trainer_forward_rects, without windows):
 // n x (top, left, height, width) on the device - the image is each frame's own rectangle resized to crop x crop (no Resize before it), by one launch, or
-// with color by the two colour launches reading that source.
+// with color by the two colour launches reading that source.  blur, staged (pvr_trainer_forward_staged, with windows or rects): n x (float sigma, int32
+// gray) and (n, crop, crop, 4) uint8 of the caller's scratch - the source's uint8 values (after the colour ops, with color) are staged and then grayed,
+// blurred and normalised per frame: "stage image" and "blur normalize" stand where the image launch stood, behind "colour stats" with color.
 pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w, float *boundary, bool reuse,
                         float *out, int64_t out_stride, void *stream, bool prefix_only = false, const int32_t *windows = nullptr, const void *color = nullptr,
-                        uint32_t *gray_sums = nullptr, const int32_t *rects = nullptr) {
+                        uint32_t *gray_sums = nullptr, const int32_t *rects = nullptr, const void *blur = nullptr, void *staged = nullptr) {
     hipStream_t st = (hipStream_t)stream;
     pvr_status s;
     if ((s = ensure_workspace(t))) return s;
@@ -451,7 +453,13 @@ pvr_status forward_pass(pvr_trainer *t, const float *params, void *bn_buffers, c
                                        op.mean, op.rstd, rows, op.cout, op.relu, t->bn_scratch, t->bn_floats, st);
     };
     if (!reuse) {
-        if (rects && color) {                     // a random resized crop and a colour jitter per frame: the colour pair on the rectangle's pixels
+        if (blur) {                               // grayscale and blur per frame: the uint8 image is staged, then filtered and normalised
+            if (color)
+                TR_RUN("colour stats", 0,
+                       launch_staged_color_stats(frames, n, h, w, t->desc.resize, t->desc.crop, windows, rects, color, gray_sums, staged, st));
+            TR_RUN("stage image", 0, launch_stage_image(frames, n, h, w, t->desc.resize, t->desc.crop, windows, rects, color, gray_sums, staged, st));
+            TR_RUN("blur normalize", 0, launch_blur_normalize(staged, n, t->desc.crop, t->desc.mean, t->desc.std_, blur, t->d_imgf, st));
+        } else if (rects && color) {              // a random resized crop and a colour jitter per frame: the colour pair on the rectangle's pixels
             TR_RUN("colour stats", 0, launch_color_stage_rects(0, frames, n, h, w, t->desc.crop, t->desc.mean, t->desc.std_, rects, color, gray_sums, t->d_imgf, st));
             TR_RUN("preprocess colour", 0,
                    launch_color_stage_rects(1, frames, n, h, w, t->desc.crop, t->desc.mean, t->desc.std_, rects, color, gray_sums, t->d_imgf, st));
@@ -661,6 +669,52 @@ pvr_status pvr_trainer_forward_rects(pvr_trainer *t, const float *params, void *
     PVR_REQUIRE(h > 0 && w > 0, "pvr_trainer_forward_rects: bad frame size h=%d w=%d", h, w);       // (no Resize on this path: a frame may be smaller than the crop)
     TraceScope ts("pvr_trainer_forward_rects");
     return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, false, out, out_stride, stream, false, nullptr, color, gray_sums, rects);
+}
+
+pvr_status pvr_trainer_forward_staged(pvr_trainer *t, const float *params, void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,
+                                      const int32_t *windows, const int32_t *rects, const void *color, uint32_t *gray_sums, const void *blur, void *staged,
+                                      float *boundary, int32_t reuse, float *out, int64_t out_stride, void *stream) {
+    if (!blur || (boundary && reuse))             // no blur parameter is read: the rectangle or the window entry point, with its own refusals
+        return rects ? pvr_trainer_forward_rects(t, params, bn_buffers, frames, n, h, w, rects, color, gray_sums, boundary, reuse, out, out_stride, stream)
+                     : pvr_trainer_forward_augmented(t, params, bn_buffers, frames, n, h, w, windows, color, gray_sums, boundary, reuse, out, out_stride,
+                                                     stream);
+    PVR_REQUIRE(t && params && bn_buffers && frames && out, "pvr_trainer_forward_staged: null argument (only a reuse pass, which starts at the first trained "
+                "op, reads no frames)");
+    PVR_REQUIRE((windows != nullptr) != (rects != nullptr), "pvr_trainer_forward_staged: blur_dev with %s (exactly one pixel source: pass the centre window, "
+                "nearbyint((resized size - crop) / 2), for every frame where no random crop is wanted)", windows ? "both windows_dev and rects_dev"
+                : "neither windows_dev nor rects_dev");
+    PVR_REQUIRE(((uintptr_t)windows & 3) == 0 && ((uintptr_t)rects & 3) == 0, "pvr_trainer_forward_staged: windows_dev %p / rects_dev %p is not 4-byte "
+                "aligned (int32 rows)", (const void *)windows, (const void *)rects);
+    PVR_REQUIRE(((uintptr_t)blur & 3) == 0, "pvr_trainer_forward_staged: blur_dev %p is not 4-byte aligned (n x (float sigma, int32 gray))", blur);
+    PVR_REQUIRE(staged && ((uintptr_t)staged & 15) == 0, "pvr_trainer_forward_staged: staged_dev %p is null or not 16-byte aligned ((n, crop, crop, 4) uint8 "
+                "of device scratch, the caller's)", staged);
+    if (color) {
+        PVR_REQUIRE(((uintptr_t)color & 3) == 0, "pvr_trainer_forward_staged: color_dev %p is not 4-byte aligned (n x (float b, float c, float s, int32 "
+                    "order))", color);
+        PVR_REQUIRE(gray_sums && ((uintptr_t)gray_sums & 3) == 0, "pvr_trainer_forward_staged: gray_sums_dev %p is null or not 4-byte aligned (n uint32 of "
+                    "device scratch, the caller's)", (void *)gray_sums);
+    }
+    PVR_REQUIRE(t->desc.crop >= 12 && t->desc.crop <= 256, "pvr_trainer_forward_staged: crop %d (12 .. 256: a reflect padding of 11, and the gray mean is "
+                "exact while 255 crop^2 < 2^24)", t->desc.crop);
+    if (boundary && t->train_from <= 0) {
+        set_error("pvr_trainer_forward_staged: everything trains (pvr_trainer_set_train_from stage 0): there is no frozen prefix and no boundary tensor to "
+                  "keep; pass a null boundary_dev");
+        return PVR_ERR_STATE;
+    }
+    PVR_REQUIRE(((uintptr_t)boundary & 15) == 0, "pvr_trainer_forward_staged: boundary_dev %p is not 16-byte aligned (the launches move it as float4s)",
+                (void *)boundary);
+    PVR_REQUIRE(n > 0 && n <= t->desc.max_batch, "pvr_trainer_forward_staged: %d frames, the workspace holds max_batch = %d (with frozen BatchNorm run the "
+                "frames as passes of at most max_batch, each with its own rows of the parameter arrays; batch statistics take the whole batch together)", n,
+                t->desc.max_batch);
+    PVR_REQUIRE(h > 0 && w > 0, "pvr_trainer_forward_staged: bad frame size h=%d w=%d", h, w);
+    if (windows) {
+        int rh, rw;
+        resized_size(h, w, t->desc.resize, &rh, &rw);
+        PVR_REQUIRE(rh >= t->desc.crop && rw >= t->desc.crop, "pvr_trainer_forward_staged: resized frame %dx%d (of %dx%d) smaller than crop %d", rh, rw, h, w,
+                    t->desc.crop);
+    }
+    TraceScope ts("pvr_trainer_forward_staged");
+    return forward_pass(t, params, bn_buffers, frames, n, h, w, boundary, false, out, out_stride, stream, false, windows, color, gray_sums, rects, blur, staged);
 }
 
 pvr_status pvr_trainer_prefix_forward(pvr_trainer *t, const float *params, const void *bn_buffers, const uint8_t *frames, int32_t n, int32_t h, int32_t w,

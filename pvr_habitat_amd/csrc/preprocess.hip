@@ -447,6 +447,224 @@ pvr_status launch_color_stage_rects(int stage, const uint8_t *frames, int n, int
     return color_stage<RectSource>(stage, p, n, crop, color, gray_sums, stream);
 }
 
+// Grayscale and Gaussian blur (pvr_op_preprocess_staged + pvr_op_blur_normalize, the trainer's "stage image" and "blur normalize" launches): the two
+// augmentations that follow the colour jitter in MoCo v2's recipe.  A blurred pixel is no function of one source pixel, so the image is made in two steps:
+// "stage image" writes the uint8 values the un-staged kernels would normalise - the source's pixel, then the frame's colour ops - as 4 bytes per pixel
+// (r, g, b, 0), and "blur normalize" reads them back, a 23 x 23 neighbourhood per pixel.
+struct StageP {
+    ColP col;                 // col.win.dst is not written; col.color == nullptr: no colour ops, and gray_sums is not read
+    uint32_t *staged;         // (n, crop, crop) packed pixels, r in the lowest byte
+};
+
+template <class Src>
+__global__ __launch_bounds__(256) void stage_image_kernel(StageP p) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int n = blockIdx.z;
+    if (x >= p.col.win.crop || y >= p.col.win.crop) return;
+    float v[3];
+    Src::pixel(p.col.win, n, y, x, v);
+    if (p.col.color) {        // (uniform over the launch) exactly preprocess_color_f32_kernel's ops
+        const FrameColor fc = frame_color(p.col.color, n);
+        const float m = (float)p.col.gray_sums[n] / p.col.pixels;
+        uint32_t ops = fc.ops;
+#pragma unroll
+        for (int k = 0; k < 3; ++k, ops >>= 2) color_op(v, ops & 3u, fc, m);
+    }
+    // every value is an integer in [0, 255] held in a float (a resize rounds, a blend clamps and truncates): the conversion is exact
+    p.staged[((size_t)n * p.col.win.crop + y) * p.col.win.crop + x] = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16);
+}
+
+// "blur normalize": per frame grayscale if flagged (gray_u8 on all three channels: torchvision's rgb_to_grayscale(num_output_channels=3) on uint8), then
+// torchvision's GaussianBlur(23, sigma) on the uint8 values if sigma > 0, then store_normalized.  The blur's weights are pdf_i = exp(-0.5 (i / sigma)^2),
+// i = -11 .. 11, over their sum; the 2-D kernel is their outer product, so the filter is separable: a horizontal 23-tap pass and a vertical one, both in
+// fp32 with nothing rounded in between, reflect padding of 11, and one rintf (half to even) at the end.  torchvision sums the 529 products of the 2-D
+// kernel in fp32; the separable sum differs from it by rounding alone, about 1e-4 of a uint8 step (tests/gaussian_blur_refs.py derives the bound and the
+// share of pixels near a .5 tie that it leaves undecided).
+// A workgroup of 256 owns a BLUR_W x BLUR_H output tile of one frame.  It loads the tile plus an 11-pixel halo as packed uint8x4 into LDS, the reflection
+// resolved (and the grayscale applied) at load time; the horizontal pass writes three fp32 planes of (BLUR_H + 22) x BLUR_W to LDS - one packed load feeds
+// the three channels' sums; the vertical pass reads them, each lane producing BLUR_VR outputs down a column from a sliding run of BLUR_VR + 22 loads, so
+// a loaded value feeds up to BLUR_VR taps.  In both passes a wave's 64 lanes lie along x: consecutive lanes read consecutive banks.  The 12 distinct
+// weights are computed once per workgroup.  LDS: 54 x 86 x 4 + 3 x 54 x 64 x 4 + 48 = 60096 bytes, two workgroups (8 waves) per CU.
+// A frame with sigma == 0 takes a branch that is uniform over the workgroup and touches no LDS: the staged pixel, gray if flagged, normalised.
+// Hardened: a NaN or non-positive sigma means no blur, sigma is clamped to at most 16, tap 0's pdf is 1 by definition (a tiny sigma gives the identity,
+// never 0 / 0), any non-zero gray word counts as 1, and every read is reflected and then clamped into the frame: no value of the array can produce a NaN
+// image or a read outside the frame.  Plain loads and stores, no atomics.
+constexpr int BLUR_R = 11, BLUR_W = 64, BLUR_H = 32, BLUR_VR = 8;
+constexpr int BLUR_IW = BLUR_W + 2 * BLUR_R, BLUR_IH = BLUR_H + 2 * BLUR_R;
+
+struct BlurP {
+    WinP win;                 // dst, crop, mean and std: what store_normalized reads
+    const uint32_t *staged;   // (n, crop, crop) packed pixels
+    const uint32_t *blur;     // n x (float sigma, int32 gray)
+};
+
+__device__ __forceinline__ uint32_t gray_packed(uint32_t px) {
+    const float v[3] = {(float)(px & 255u), (float)((px >> 8) & 255u), (float)((px >> 16) & 255u)};
+    const uint32_t g = (uint32_t)gray_u8(v);      // (0.2989 + 0.587 + 0.114) * 255 < 256: at most 255
+    return g | (g << 8) | (g << 16);
+}
+
+__global__ __launch_bounds__(256) void blur_normalize_kernel(BlurP p) {
+    const int n = blockIdx.z, crop = p.win.crop;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * BLUR_W, y0 = blockIdx.y * BLUR_H;
+    float sigma = __uint_as_float(p.blur[2 * n]);
+    sigma = sigma > 0.f ? (sigma > 16.0f ? 16.0f : sigma) : 0.f;         // (a NaN compares false: no blur)
+    const bool gray = p.blur[2 * n + 1] != 0u;
+    const uint32_t *img = p.staged + (size_t)n * crop * crop;
+    if (sigma == 0.f) {                           // uniform over the workgroup: no LDS, no barrier
+        const int x = x0 + lane;
+        if (x >= crop) return;
+        for (int r = wave; r < BLUR_H; r += 4) {
+            const int y = y0 + r;
+            if (y >= crop) break;
+            uint32_t px = img[(size_t)y * crop + x];
+            if (gray) px = gray_packed(px);
+            const float v[3] = {(float)(px & 255u), (float)((px >> 8) & 255u), (float)((px >> 16) & 255u)};
+            store_normalized(p.win, n, y, x, v);
+        }
+        return;
+    }
+    __shared__ uint32_t s_in[BLUR_IH][BLUR_IW];
+    __shared__ float s_h[3][BLUR_IH][BLUR_W];
+    __shared__ float s_w[BLUR_R + 1];
+    if (threadIdx.x <= BLUR_R) {
+        const float t = (float)threadIdx.x / sigma;
+        s_w[threadIdx.x] = threadIdx.x == 0 ? 1.0f : expf(-0.5f * (t * t));
+    }
+    for (int i = threadIdx.x; i < BLUR_IH * BLUR_IW; i += 256) {
+        const int r = i / BLUR_IW, c = i - r * BLUR_IW;
+        int y = y0 - BLUR_R + r, x = x0 - BLUR_R + c;
+        y = y < 0 ? -y : (y >= crop ? 2 * (crop - 1) - y : y);          // reflect (crop >= 12: one reflection lands inside) ...
+        x = x < 0 ? -x : (x >= crop ? 2 * (crop - 1) - x : x);
+        y = y < 0 ? 0 : (y > crop - 1 ? crop - 1 : y);                  // ... then clamp: a tile that overhangs the frame reads inside it for the
+        x = x < 0 ? 0 : (x > crop - 1 ? crop - 1 : x);                  // outputs it will not store
+        const uint32_t px = img[(size_t)y * crop + x];
+        s_in[r][c] = gray ? gray_packed(px) : px;
+    }
+    __syncthreads();
+    float wt[BLUR_R + 1];                         // the normalised weights, the sum taken in one fixed order by every lane
+    {
+        float sum = 0.f;
+#pragma unroll
+        for (int i = BLUR_R; i >= 1; --i) sum += s_w[i];
+        sum = 2.0f * sum + s_w[0];
+#pragma unroll
+        for (int i = 0; i <= BLUR_R; ++i) wt[i] = s_w[i] / sum;
+    }
+    // horizontal pass: a wave takes every fourth row of the haloed tile
+    for (int r = wave; r < BLUR_IH; r += 4) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 2 * BLUR_R + 1; ++k) {
+            const uint32_t px = s_in[r][lane + k];
+            const float w = wt[k < BLUR_R ? BLUR_R - k : k - BLUR_R];
+            a0 = __builtin_fmaf(w, (float)(px & 255u), a0);
+            a1 = __builtin_fmaf(w, (float)((px >> 8) & 255u), a1);
+            a2 = __builtin_fmaf(w, (float)((px >> 16) & 255u), a2);
+        }
+        s_h[0][r][lane] = a0; s_h[1][r][lane] = a1; s_h[2][r][lane] = a2;
+    }
+    __syncthreads();
+    // vertical pass: a wave takes BLUR_VR output rows, a lane one column of them
+    const int x = x0 + lane, yb = wave * BLUR_VR;
+    float o[3][BLUR_VR];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int j = 0; j < BLUR_VR; ++j) o[c][j] = 0.f;
+#pragma unroll
+        for (int r = 0; r < BLUR_VR + 2 * BLUR_R; ++r) {
+            const float v = s_h[c][yb + r][lane];
+#pragma unroll
+            for (int j = 0; j < BLUR_VR; ++j) {
+                const int k = r - j;              // the tap of output row j that row r is
+                if (k >= 0 && k <= 2 * BLUR_R) o[c][j] = __builtin_fmaf(wt[k < BLUR_R ? BLUR_R - k : k - BLUR_R], v, o[c][j]);
+            }
+        }
+    }
+    if (x >= crop) return;
+#pragma unroll
+    for (int j = 0; j < BLUR_VR; ++j) {
+        const int y = y0 + yb + j;
+        if (y >= crop) break;
+        float v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float r = rintf(o[c][j]);       // torch.round (half to even) then .to(uint8); the clamp never acts on a convex sum of uint8 values
+            v[c] = r < 0.f ? 0.f : (r > 255.0f ? 255.0f : r);
+        }
+        store_normalized(p.win, n, y, x, v);
+    }
+}
+
+// "stage image": the checks of the source's launcher, then the staging kernel.  color == nullptr: no colour ops.  The arguments have passed the
+// callers' null checks
+pvr_status launch_stage_image(const uint8_t *frames, int n, int h, int w, int resize, int crop, const int32_t *windows, const int32_t *rects,
+                              const void *color, uint32_t *gray_sums, void *staged, hipStream_t stream) {
+    PVR_REQUIRE(((uintptr_t)staged & 15) == 0, "stage image: staged_dev %p is not 16-byte aligned ((n, crop, crop, 4) uint8 of the caller's scratch)", staged);
+    PVR_REQUIRE((windows != nullptr) != (rects != nullptr), "stage image: exactly one pixel source, windows_dev (n x (top, left)) or rects_dev (n x (top, "
+                "left, height, width))");
+    const float mean[3] = {0.f, 0.f, 0.f}, std_[3] = {1.f, 1.f, 1.f};     // (not read: the staged values are not normalised)
+    StageP p;
+    pvr_status s = windows ? window_params("stage image", frames, n, h, w, resize, crop, mean, std_, windows, (float *)staged, p.col.win)
+                           : rect_params("stage image", frames, n, h, w, crop, mean, std_, rects, (float *)staged, p.col.win);
+    if (s) return s;
+    if (color) {
+        PVR_REQUIRE(((uintptr_t)color & 3) == 0, "stage image: color_dev %p is not 4-byte aligned (n x (float b, float c, float s, int32 order))", color);
+        PVR_REQUIRE(gray_sums && ((uintptr_t)gray_sums & 3) == 0, "stage image: gray_sums_dev %p is null or not 4-byte aligned (n uint32 of scratch)",
+                    (void *)gray_sums);
+        PVR_REQUIRE((int64_t)crop * crop <= (1 << 16), "stage image: crop %d (at most 256: 255 crop^2 must stay below 2^24 for the gray mean to be exact)", crop);
+    }
+    p.col.color = (const uint32_t *)color; p.col.gray_sums = gray_sums; p.col.pixels = (float)(crop * crop);
+    p.staged = (uint32_t *)staged;
+    dim3 grid((crop + 63) / 64, (crop + 3) / 4, n);
+    if (windows) hipLaunchKernelGGL(stage_image_kernel<WindowSource>, grid, dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(stage_image_kernel<RectSource>, grid, dim3(256), 0, stream, p);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+// the "colour stats" launch of the staged path: launch_color_stage's or launch_color_stage_rects' stage 0, as it is (the image pointer is only checked)
+pvr_status launch_staged_color_stats(const uint8_t *frames, int n, int h, int w, int resize, int crop, const int32_t *windows, const int32_t *rects,
+                                     const void *color, uint32_t *gray_sums, void *staged, hipStream_t stream) {
+    const float mean[3] = {0.f, 0.f, 0.f}, std_[3] = {1.f, 1.f, 1.f};
+    PVR_REQUIRE(((uintptr_t)staged & 15) == 0, "stage image: staged_dev %p is not 16-byte aligned ((n, crop, crop, 4) uint8 of the caller's scratch)", staged);
+    PVR_REQUIRE((windows != nullptr) != (rects != nullptr), "stage image: exactly one pixel source, windows_dev (n x (top, left)) or rects_dev (n x (top, "
+                "left, height, width))");
+    return windows ? launch_color_stage(0, frames, n, h, w, resize, crop, mean, std_, windows, color, gray_sums, (float *)staged, stream)
+                   : launch_color_stage_rects(0, frames, n, h, w, crop, mean, std_, rects, color, gray_sums, (float *)staged, stream);
+}
+
+pvr_status launch_blur_normalize(const void *staged, int n, int crop, const float *mean, const float *std_, const void *blur, float *out,
+                                 hipStream_t stream) {
+    PVR_REQUIRE(n > 0, "blur normalize: bad shape n=%d crop=%d", n, crop);
+    PVR_REQUIRE(n <= 65535, "blur normalize: %d frames in one launch (at most 65535: one grid plane per frame)", n);
+    PVR_REQUIRE(crop >= BLUR_R + 1, "blur normalize: crop %d (at least 12: a reflect padding of 11 needs 12 pixels)", crop);
+    PVR_REQUIRE(crop <= 256, "blur normalize: crop %d (at most 256, as the colour launches)", crop);
+    PVR_REQUIRE(((uintptr_t)staged & 15) == 0, "blur normalize: staged_dev %p is not 16-byte aligned ((n, crop, crop, 4) uint8)", staged);
+    PVR_REQUIRE(((uintptr_t)blur & 3) == 0, "blur normalize: blur_dev %p is not 4-byte aligned (n x (float sigma, int32 gray))", blur);
+    PVR_REQUIRE(((uintptr_t)out & 15) == 0, "blur normalize: out_dev %p is not 16-byte aligned (a pixel is one float4 store)", (void *)out);
+    BlurP p;
+    p.win.src = nullptr; p.win.dst = out; p.win.windows = nullptr; p.win.n = n; p.win.h = p.win.w = p.win.rh = p.win.rw = crop; p.win.crop = crop;
+    p.win.resize_needed = 0; p.win.scale_h = p.win.scale_w = 1.0f;
+    p.win.m0 = mean[0]; p.win.m1 = mean[1]; p.win.m2 = mean[2]; p.win.s0 = std_[0]; p.win.s1 = std_[1]; p.win.s2 = std_[2];
+    p.staged = (const uint32_t *)staged; p.blur = (const uint32_t *)blur;
+    hipLaunchKernelGGL(blur_normalize_kernel, dim3((crop + BLUR_W - 1) / BLUR_W, (crop + BLUR_H - 1) / BLUR_H, n), dim3(256), 0, stream, p);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+__global__ __launch_bounds__(256) void blur_params_kernel(unsigned long long seed, unsigned long long call, long long first_frame, long long n, float p_blur,
+                                                          float lo, float hi, float p_gray, uint32_t *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t w[2];
+    blur_params(seed, call, (uint64_t)(first_frame + i), p_blur, lo, hi, p_gray, w);
+    out[2 * i] = w[0]; out[2 * i + 1] = w[1];
+}
+
 __global__ __launch_bounds__(256) void crop_rects_kernel(unsigned long long seed, unsigned long long call, long long first_frame, long long n, int h, int w,
                                                          float lo, float hi, int32_t *__restrict__ rects) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -566,6 +784,51 @@ pvr_status pvr_op_color_params(uint64_t seed, uint64_t call, int64_t first_frame
                        (unsigned long long)call, (long long)first_frame, (long long)n, strength_b, strength_c, strength_s, (uint32_t *)params);
     PVR_LAUNCH_CHECK();
     return PVR_OK;
+}
+
+void pvr_host_blur_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float p_blur, float sigma_lo, float sigma_hi, float p_gray,
+                          void *params) {
+    for (int64_t i = 0; params && i < n; ++i)
+        pvr::blur_params(seed, call, (uint64_t)(first_frame + i), p_blur, sigma_lo, sigma_hi, p_gray, (uint32_t *)params + 2 * i);
+}
+
+pvr_status pvr_op_blur_params(uint64_t seed, uint64_t call, int64_t first_frame, int64_t n, float p_blur, float sigma_lo, float sigma_hi, float p_gray,
+                              void *params, void *stream) {
+    PVR_REQUIRE(params, "pvr_op_blur_params: null blur_dev (n x (float sigma, int32 gray) of device memory)");
+    PVR_REQUIRE(((uintptr_t)params & 3) == 0, "pvr_op_blur_params: blur_dev %p is not 4-byte aligned (two 32-bit words per frame)", params);
+    PVR_REQUIRE(n >= 1 && n <= (1ll << 31), "pvr_op_blur_params: n = %lld frames (1 .. 2^31)", (long long)n);
+    PVR_REQUIRE(first_frame >= 0, "pvr_op_blur_params: first_frame = %lld (a frame index of the step, 0 or above)", (long long)first_frame);
+    PVR_REQUIRE(p_blur >= 0.f && p_blur <= 1.0f && p_gray >= 0.f && p_gray <= 1.0f, "pvr_op_blur_params: probabilities %g (blur), %g (grayscale) (finite, "
+                "in [0, 1])", (double)p_blur, (double)p_gray);
+    PVR_REQUIRE(sigma_lo > 0.f && sigma_lo <= sigma_hi && sigma_hi <= 3.4e38f, "pvr_op_blur_params: sigma range (%g, %g) (finite, 0 < lo <= hi)",
+                (double)sigma_lo, (double)sigma_hi);
+    hipLaunchKernelGGL(pvr::blur_params_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long)seed,
+                       (unsigned long long)call, (long long)first_frame, (long long)n, p_blur, sigma_lo, sigma_hi, p_gray, (uint32_t *)params);
+    PVR_LAUNCH_CHECK();
+    return PVR_OK;
+}
+
+pvr_status pvr_op_preprocess_staged(const uint8_t *frames, int32_t n, int32_t h, int32_t w, int32_t resize, int32_t crop, const int32_t *windows,
+                                    const int32_t *rects, const void *color, uint32_t *gray_sums, void *staged, void *stream) {
+    PVR_REQUIRE(frames, "pvr_op_preprocess_staged: null frames_dev");
+    PVR_REQUIRE(staged, "pvr_op_preprocess_staged: null staged_dev ((n, crop, crop, 4) uint8 of device scratch, the caller's)");
+    PVR_REQUIRE((windows != nullptr) != (rects != nullptr), "pvr_op_preprocess_staged: exactly one pixel source, windows_dev (n x (top, left)) or rects_dev "
+                "(n x (top, left, height, width))");
+    if (color) {
+        PVR_REQUIRE(gray_sums, "pvr_op_preprocess_staged: color_dev without gray_sums_dev (n uint32 of device scratch, the caller's)");
+        // (everything the second launch checks, before the first one runs: a refusal launches nothing)
+        PVR_REQUIRE(((uintptr_t)staged & 15) == 0, "pvr_op_preprocess_staged: staged_dev %p is not 16-byte aligned", staged);
+        if (pvr_status s = pvr::launch_staged_color_stats(frames, n, h, w, resize, crop, windows, rects, color, gray_sums, staged, (hipStream_t)stream))
+            return s;
+    }
+    return pvr::launch_stage_image(frames, n, h, w, resize, crop, windows, rects, color, gray_sums, staged, (hipStream_t)stream);
+}
+
+pvr_status pvr_op_blur_normalize(const void *staged, int32_t n, int32_t crop, const float *mean, const float *std_, const void *blur, float *out,
+                                 void *stream) {
+    PVR_REQUIRE(staged && mean && std_ && out, "pvr_op_blur_normalize: null argument");
+    PVR_REQUIRE(blur, "pvr_op_blur_normalize: null blur_dev (n x (float sigma, int32 gray) of device memory)");
+    return pvr::launch_blur_normalize(staged, n, crop, mean, std_, blur, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -138,4 +138,19 @@ __host__ __device__ inline void crop_rect(uint64_t seed, uint64_t call, uint64_t
     out[3] = (int32_t)cw;
 }
 
+// The blur and grayscale parameters of one frame (pvr_op_blur_params / pvr_host_blur_params, include/pvr_train.h): counter (frame, call) as crop_window's,
+// key (seed_lo, seed_hi ^ 'BLUR'), so the stream is independent of the windows', the rectangles' and the colour parameters' and leaves them untouched.
+// With u_j = uniform_open01(word j): word 0 decides the blur (u_0 < p_blur), word 1 gives sigma = fma(hi - lo, u_1, lo) in [lo, hi], word 2 decides the
+// grayscale (u_2 < p_gray).  u lies in the open interval (0, 1), so p = 1 always applies and p = 0 (or a NaN) never does.  out: two 32-bit words, float
+// sigma (0: not blurred) and int32 gray (0 or 1).  The only multiply-add is the fma written out, so host and device agree bit for bit.  A sigma range that
+// is not finite or not 0 < lo <= hi counts as (1, 1) (the callers refuse it before).
+__host__ __device__ inline void blur_params(uint64_t seed, uint64_t call, uint64_t frame, float p_blur, float lo, float hi, float p_gray, uint32_t *out) {
+    uint32_t c[4] = {(uint32_t)frame, (uint32_t)(frame >> 32), (uint32_t)call, (uint32_t)(call >> 32)};
+    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32) ^ 0x424C5552u);
+    if (!(lo > 0.f && lo <= hi && hi <= 3.4e38f)) lo = hi = 1.0f;
+    const float sigma = uniform_open01(c[0]) < p_blur ? fmaf(hi - lo, uniform_open01(c[1]), lo) : 0.f;
+    __builtin_memcpy(&out[0], &sigma, 4);
+    out[1] = uniform_open01(c[2]) < p_gray ? 1u : 0u;
+}
+
 }  // namespace pvr

@@ -397,6 +397,7 @@ class _EncoderFunction(torch.autograd.Function):
         ctx.boundary, model._boundary = model._boundary, None       # (prefix_once: the cache lives on the node, exactly as long as the frames do)
         ctx.windows, model._windows = model._windows, None          # (random_crop: the step's windows, for the recompute passes that run the stem again)
         ctx.color, model._color = model._color, None                # (color_jitter: the step's parameters, parked and handed on exactly as the windows are)
+        ctx.blur, model._blur = model._blur, None                   # (gaussian_blur / random_grayscale: likewise)
         return out
 
     @staticmethod
@@ -407,8 +408,8 @@ class _EncoderFunction(torch.autograd.Function):
                                'encoder overwrote them (one backward per forward, right after it)')
         dout = dout.contiguous().float()
         g = torch.empty_like(m._flat)
-        m._backward_raw(ctx.frames, dout, g, ctx.boundary, ctx.windows, ctx.color)
-        ctx.frames = ctx.boundary = ctx.windows = ctx.color = None
+        m._backward_raw(ctx.frames, dout, g, ctx.boundary, ctx.windows, ctx.color, ctx.blur)
+        ctx.frames = ctx.boundary = ctx.windows = ctx.color = ctx.blur = None
         return (None, None) + tuple(g[o:o + n].view(shp) for o, n, shp in m._trained_slots)
 
 
@@ -542,13 +543,28 @@ class HipTrainableResNet(_Node):
     fp32 image), and so is every recompute pass that runs the stem again - the rectangles are parked where random_crop's windows are.  crop_rects(
     crop_seed, call, n, h, w, scale) predicts a step's rectangles on the host.  A frame smaller than the crop is legal (no Resize runs).  Off by default;
     with it off nothing moves.  Eval mode keeps Resize(256) and the centre crop.  Not with random_crop (both choose the window), and not with prefix_cache,
-    build_prefix_cache or forward_cached; it composes with color_jitter, prefix_once, frozen BatchNorm chunking and the split modes."""
+    build_prefix_cache or forward_cached; it composes with color_jitter, prefix_once, frozen BatchNorm chunking and the split modes.
+
+    gaussian_blur, random_grayscale: the last two augmentations of MoCo v2's recipe, per frame and step.  gaussian_blur=(p, lo, hi): with probability p a
+    frame is blurred as torchvision's GaussianBlur(kernel_size=23, sigma=(lo, hi)) blurs a uint8 tensor, sigma uniform in [lo, hi] (MoCo v2: (0.5, 0.1,
+    2.0); the kernel size is fixed at 23, PIL's radius semantics are not offered).  random_grayscale=p: with probability p the three channels of a frame
+    become its gray value, torchvision's rgb_to_grayscale(num_output_channels=3) on uint8 (MoCo v2: 0.2).  None or a probability of 0: off.  Order per
+    frame: window or rectangle, colour jitter, grayscale, blur, / 255, Normalize.  In training mode the step's (n, 2) parameters (float sigma, 0 for not
+    blurred, and int32 gray; include/pvr_train.h) are drawn once on the device (pvr_op_blur_params with seed = blur_seed and call = crop_call) and parked
+    as the colour parameters are; every pass is handed its rows (pvr_trainer_forward_staged: the launches "stage image" - the uint8 image into a staging
+    buffer of max_batch x 224 x 224 x 4 bytes, made once next to the gray sums - and "blur normalize" stand where the image launch stood), and so is
+    every recompute pass that runs the stem again.  blur_params(blur_seed, call, n, gaussian_blur, random_grayscale) predicts a step's parameters on the
+    host.  Off by default; with both off nothing moves, and the windows, rectangles and colour parameters keep their bits with them on.  Eval mode keeps
+    the plain centre crop.  Not with prefix_cache, build_prefix_cache or forward_cached; they compose with each other, random_crop or
+    random_resized_crop, color_jitter, prefix_once, frozen BatchNorm chunking, train_from and the split modes."""
 
     def __init__(self, state_dict, variant='conv5', max_batch=None, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
                  prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0,
-                 random_resized_crop=None):
+                 random_resized_crop=None, gaussian_blur=None, random_grayscale=None, blur_seed=0):
         super().__init__()
         assert variant in _TRAINABLE, variant
+        blur, gray = blur_spec(gaussian_blur), gray_prob(random_grayscale)
+        check_gaussian_blur(blur, gray, prefix_cache)
         check_random_crop(random_crop, prefix_cache)
         rrc_scale = crop_scale(random_resized_crop)
         check_random_resized_crop(rrc_scale, prefix_cache, random_crop=random_crop)
@@ -598,6 +614,11 @@ class HipTrainableResNet(_Node):
         self.color_seed = int(color_seed)        # color_jitter: Philox key of the parameters (the call number is crop_call)
         self._color = None                       # color_jitter: the step's parameters between _forward_raw and its consumer (parked as _windows is)
         self._gray_sums = None                   # color_jitter: max_batch uint32 of scratch for a pass's gray sums (the trainer's workspace holds none)
+        self._gaussian_blur = blur               # gaussian_blur: (p, sigma lo, sigma hi), None when off
+        self._random_grayscale = gray            # random_grayscale: the probability, None when off
+        self.blur_seed = int(blur_seed)          # gaussian_blur / random_grayscale: Philox key of the parameters (the call number is crop_call)
+        self._blur = None                        # the step's (n, 2) blur parameters between _forward_raw and its consumer (parked as _color is)
+        self._staged = None                      # max_batch x crop x crop x 4 bytes of scratch for a pass's staged uint8 image (made once, as _gray_sums is)
         self._resize, self._crop = int(tr.resize), int(tr.crop)
         if self._prefix_once or self._prefix_cache:
             _lib.check(L.pvr_trainer_set_prefix_fused(h, 1))
@@ -713,6 +734,16 @@ class HipTrainableResNet(_Node):
         return self._rrc_scale
 
     @property
+    def gaussian_blur(self):
+        """the (p, sigma lo, sigma hi) of a training forward's Gaussian blur, None when off (see the class docstring)"""
+        return self._gaussian_blur
+
+    @property
+    def random_grayscale(self):
+        """the probability of a training forward's grayscale, None when off (see the class docstring)"""
+        return self._random_grayscale
+
+    @property
     def color_jitter(self):
         """the (brightness, contrast, saturation) strengths of a training forward's colour jitter, None when off (see the class docstring)"""
         return self._color_jitter
@@ -739,6 +770,7 @@ class HipTrainableResNet(_Node):
         check_random_crop(self._random_crop, True, 'build_prefix_cache')
         check_color_jitter(self._color_jitter, True, 'build_prefix_cache')
         check_random_resized_crop(self._rrc_scale, True, 'build_prefix_cache')
+        check_gaussian_blur(self._gaussian_blur, self._random_grayscale, True, 'build_prefix_cache')
         return self._build_prefix_cache(int(frames_u8.shape[0]), [(0, frames_u8)])
 
     def _build_prefix_cache(self, n_frames, blocks):
@@ -749,6 +781,7 @@ class HipTrainableResNet(_Node):
         check_random_crop(self._random_crop, True, 'build_prefix_cache')
         check_color_jitter(self._color_jitter, True, 'build_prefix_cache')
         check_random_resized_crop(self._rrc_scale, True, 'build_prefix_cache')
+        check_gaussian_blur(self._gaussian_blur, self._random_grayscale, True, 'build_prefix_cache')
         L = _lib.lib()
         _lib.check(L.pvr_trainer_set_prefix_fused(self._handle, 1))
         vp = lambda t: C.c_void_p(t.data_ptr())
@@ -790,6 +823,7 @@ class HipTrainableResNet(_Node):
         check_random_crop(self._random_crop, True, 'forward_cached')
         check_color_jitter(self._color_jitter, True, 'forward_cached')
         check_random_resized_crop(self._rrc_scale, True, 'forward_cached')
+        check_gaussian_blur(self._gaussian_blur, self._random_grayscale, True, 'forward_cached')
         self.check_prefix_cache(cache)
         if not self.training:
             raise RuntimeError('forward_cached is a training-mode forward (the cache holds the input of the trained stages): in eval mode embed the '
@@ -899,18 +933,44 @@ class HipTrainableResNet(_Node):
             self._color = torch.empty((n, 4), dtype=torch.int32, device=frames_u8.device)
             _lib.check(_lib.lib().pvr_op_color_params(self.color_seed, self.crop_call, 0, n, *self._color_jitter, C.c_void_p(self._color.data_ptr()),
                                                       _lib.stream_ptr()))
-        if self._random_crop or self._color_jitter is not None or self._rrc_scale is not None:
+        # gaussian_blur / random_grayscale: the step's (n, 2) parameters, drawn once under the same call number and parked the same way; without a random
+        # window every frame's window is the centre one
+        self._blur = None
+        if self._gaussian_blur is not None or self._random_grayscale is not None:
+            if self._windows is None:
+                max_top, max_left = self.crop_range(h, w)
+                self._windows = torch.tensor([int(round(max_top / 2.0)), int(round(max_left / 2.0))], dtype=torch.int32,
+                                             device=frames_u8.device).repeat(n, 1)
+            self._blur = torch.empty((n, 2), dtype=torch.int32, device=frames_u8.device)
+            _lib.check(_lib.lib().pvr_op_blur_params(self.blur_seed, self.crop_call, 0, n, *(self._gaussian_blur or (0.0, 1.0, 1.0)),
+                                                     self._random_grayscale or 0.0, C.c_void_p(self._blur.data_ptr()), _lib.stream_ptr()))
+        if self._random_crop or self._color_jitter is not None or self._rrc_scale is not None or self._blur is not None:
             self.crop_call += 1
         for lo, hi in self._passes(n):            # (one pass unless BatchNorm is frozen; the last pass's activations stay held)
-            self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary, windows=self._windows, color=self._color)
+            self._forward_pass(frames_u8, lo, hi, out[lo:hi], self._boundary, windows=self._windows, color=self._color, blur=self._blur)
         return out
 
-    def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False, windows=None, color=None):
+    def _forward_pass(self, frames_u8, lo, hi, out, boundary=None, reuse=False, windows=None, color=None, blur=None):
         """one pass over frames [lo, hi).  boundary: the step's (n, boundary_floats) cache - this pass writes its rows (reuse False) or starts at the first
         trained op on what they hold (reuse True).  windows (random_crop): the step's (n, 2) int32 windows - this pass crops at its rows.  color
         (color_jitter, with windows): the step's (n, 4) parameters - this pass jitters its rows.  windows of four columns (random_resized_crop): the
-        step's rectangles - this pass resizes each frame's own rectangle to the crop, with or without color"""
+        step's rectangles - this pass resizes each frame's own rectangle to the crop, with or without color.  blur (gaussian_blur / random_grayscale, with
+        windows of either kind): the step's (n, 2) parameters - this pass stages its uint8 image and grays and blurs its rows"""
         vp = lambda t: C.c_void_p(t.data_ptr())
+        if blur is not None:
+            reuse = reuse and boundary is not None                            # (as below: without a boundary cache a recompute pass makes the same image again)
+            if color is not None and self._gray_sums is None:
+                self._gray_sums = torch.empty((self._max_batch,), dtype=torch.int32, device=blur.device)
+            if self._staged is None:
+                self._staged = torch.empty((self._max_batch, self._crop, self._crop, 4), dtype=torch.uint8, device=blur.device)
+            rects = windows.shape[1] == 4
+            _lib.check(_lib.lib().pvr_trainer_forward_staged(self._handle, vp(self._flat), vp(self._bufs), None if reuse else vp(frames_u8[lo:hi]), hi - lo,
+                                                             frames_u8.shape[1], frames_u8.shape[2], None if rects else vp(windows[lo:hi]),
+                                                             vp(windows[lo:hi]) if rects else None, None if color is None else vp(color[lo:hi]),
+                                                             None if color is None else vp(self._gray_sums), vp(blur[lo:hi]), vp(self._staged),
+                                                             None if boundary is None else vp(boundary[lo:hi]), 1 if reuse else 0, vp(out), out.stride(0),
+                                                             _lib.stream_ptr()))
+            return
         if windows is not None and windows.shape[1] == 4:
             reuse = reuse and boundary is not None                            # (as below: without a boundary cache a recompute pass makes the same image again)
             if color is not None and self._gray_sums is None:
@@ -947,20 +1007,22 @@ class HipTrainableResNet(_Node):
                                                            h, w, vp(boundary[lo:hi]), 1 if reuse else 0, vp(out),
                                                            out.stride(0), _lib.stream_ptr()))
 
-    def _backward_raw(self, frames_u8, dout, grads, boundary=None, windows=None, color=None):
+    def _backward_raw(self, frames_u8, dout, grads, boundary=None, windows=None, color=None, blur=None):
         """d(loss)/d(embeddings) of the training forward that just ran on frames_u8 -> the flat gradient `grads` (fully written).  One pass: one
         pvr_trainer_backward.  Several (frozen BatchNorm): the last pass first - its activations are still held - then every other pass in frame
         order, each recomputed and added by pvr_trainer_backward_acc.  boundary (prefix_once): the cache that forward filled; a recomputed pass
         starts at the first trained op on its rows.  windows (random_crop): the windows that forward drew; a recomputed pass that runs the stem crops
         at its rows again (random_resized_crop: the rectangles, four columns, in the same place).  color (color_jitter): the parameters that forward
-        drew, for the same passes."""
+        drew, for the same passes; blur (gaussian_blur / random_grayscale): the blur parameters, likewise."""
         L = _lib.lib()
         vp = lambda t: C.c_void_p(t.data_ptr())
         passes = self._passes(frames_u8.shape[0])
         assert dout.shape[0] == frames_u8.shape[0] and dout.stride(1) == 1
         assert (boundary is not None) == self._prefix_once, 'prefix_once: the backward takes the boundary cache of its forward'
-        assert (windows is not None) == (self._random_crop or self._color_jitter is not None or self._rrc_scale is not None), \
-            'random_crop / color_jitter / random_resized_crop: the backward takes the windows or rectangles of its forward'
+        staged = self._gaussian_blur is not None or self._random_grayscale is not None
+        assert (windows is not None) == (self._random_crop or self._color_jitter is not None or self._rrc_scale is not None or staged), \
+            'random_crop / color_jitter / random_resized_crop / gaussian_blur / random_grayscale: the backward takes the windows or rectangles of its forward'
+        assert (blur is not None) == staged, 'gaussian_blur / random_grayscale: the backward takes the blur parameters of its forward'
         assert (color is not None) == (self._color_jitter is not None), 'color_jitter: the backward takes the colour parameters of its forward'
         if len(passes) == 1:
             _lib.check(L.pvr_trainer_backward(self._handle, vp(self._flat), vp(dout), dout.stride(0), vp(grads), _lib.stream_ptr()))
@@ -971,7 +1033,7 @@ class HipTrainableResNet(_Node):
         again = torch.empty((self._max_batch, self.out_size), dtype=torch.float32, device=dout.device)       # the recomputed embeddings are not used
         for i, (lo, hi) in enumerate(passes[-1:] + passes[:-1]):
             if i:
-                self._forward_pass(frames_u8, lo, hi, again[:hi - lo], boundary, reuse=True, windows=windows, color=color)
+                self._forward_pass(frames_u8, lo, hi, again[:hi - lo], boundary, reuse=True, windows=windows, color=color, blur=blur)
             _lib.check(L.pvr_trainer_backward_acc(self._handle, vp(self._flat), vp(dout[lo:hi]), dout.stride(0), vp(grads), 1 if i else 0, vp(sc), sc.numel(),
                                                   _lib.stream_ptr()))
 
@@ -1096,6 +1158,70 @@ def check_color_jitter(strengths, prefix_cache=False, what='prefix_cache'):
         raise ValueError('color_jitter with %s: the cache holds the frozen prefix\'s output for ONE image per frame (the un-jittered centre crop), and the '
                          'jitter changes the image in every step; prefix_once, which keeps the prefix\'s output for the frames and images of one step, '
                          'is the compatible mode' % what)
+
+
+def blur_spec(gaussian_blur):
+    """the gaussian_blur keyword -> (p, sigma lo, sigma hi) as fp32 values, or None when the mode is off (None, False or p = 0).  A ValueError names a
+    probability outside [0, 1] or not finite, a sigma range that is not finite or not 0 < lo <= hi, and a value that is not three numbers"""
+    if gaussian_blur is None or gaussian_blur is False:
+        return None
+    try:
+        v = tuple(float(x) for x in gaussian_blur)
+    except (TypeError, ValueError):
+        v = ()
+    if len(v) != 3:
+        raise ValueError('gaussian_blur=%r: three numbers (p, lo, hi) - the probability that a frame is blurred and the range its sigma is drawn from '
+                         '(MoCo v2: (0.5, 0.1, 2.0); the kernel size is fixed at 23)' % (gaussian_blur,))
+    if not (np.isfinite(v[0]) and 0 <= v[0] <= 1):
+        raise ValueError('gaussian_blur=%r: the probability p = %r is a finite number in [0, 1] (0 switches the mode off)' % (gaussian_blur, v[0]))
+    if not (np.isfinite(v[1]) and np.isfinite(v[2]) and 0 < v[1] <= v[2] <= 3e38):
+        raise ValueError('gaussian_blur=%r: the sigma range (%r, %r) is finite with 0 < lo <= hi (the kernel clamps a sigma above 16)'
+                         % (gaussian_blur, v[1], v[2]))
+    v = tuple(float(np.float32(x)) for x in v)
+    if not v[1] > 0:
+        raise ValueError('gaussian_blur=%r: the sigma range\'s lo is 0 in fp32 (finite with 0 < lo <= hi)' % (gaussian_blur,))
+    return v if v[0] > 0 else None
+
+
+def gray_prob(random_grayscale):
+    """the random_grayscale keyword -> the probability as an fp32 value, or None when the mode is off (None, False or 0).  A ValueError names a
+    probability outside [0, 1] or not finite, and a value that is not a number"""
+    if random_grayscale is None or random_grayscale is False:
+        return None
+    try:
+        p = float(random_grayscale)
+    except (TypeError, ValueError):
+        raise ValueError('random_grayscale=%r: one number, the probability that a frame is replaced by its gray values (MoCo v2: 0.2)'
+                         % (random_grayscale,))
+    if not (np.isfinite(p) and 0 <= p <= 1):
+        raise ValueError('random_grayscale=%r: a probability is a finite number in [0, 1] (0 switches the mode off)' % (random_grayscale,))
+    p = float(np.float32(p))
+    return p if p > 0 else None
+
+
+BLUR_DTYPE = np.dtype([('sigma', np.float32), ('gray', np.int32)])
+
+
+def blur_params(seed, call, n, gaussian_blur=None, random_grayscale=None, first_frame=0):
+    """the n parameter rows gaussian_blur and random_grayscale draw for frames first_frame .. first_frame + n of training forward number `call` under
+    blur_seed `seed`: a structured array with the fields sigma (float32, 0: not blurred) and gray (int32, 0 or 1), 8 bytes per row as the device holds
+    them.  pvr_host_blur_params: host arithmetic, no GPU needed; bit for bit what the device draws.  gaussian_blur: (p, lo, hi) or None;
+    random_grayscale: p or None"""
+    b, g = blur_spec(gaussian_blur) or (0.0, 1.0, 1.0), gray_prob(random_grayscale) or 0.0
+    out = np.zeros(int(n), BLUR_DTYPE)
+    if n > 0:
+        _lib.lib().pvr_host_blur_params(int(seed), int(call), int(first_frame), int(n), b[0], b[1], b[2], g, out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def check_gaussian_blur(blur, gray, prefix_cache=False, what='prefix_cache'):
+    """gaussian_blur and random_grayscale change a frame's image from step to step: a ValueError together with the prefix cache (`what` names the
+    keyword or the method).  blur, gray: what blur_spec and gray_prob returned"""
+    for name, on in (('gaussian_blur', blur is not None), ('random_grayscale', gray is not None)):
+        if on and prefix_cache:
+            raise ValueError('%s with %s: the cache holds the frozen prefix\'s output for ONE image per frame (the plain centre crop), and the mode '
+                             'changes the image in every step; prefix_once, which keeps the prefix\'s output for the frames and images of one step, '
+                             'is the compatible mode' % (name, what))
 
 
 def crop_scale(random_resized_crop):
@@ -1240,7 +1366,7 @@ def trainer_workspace_bytes(embedding_name, max_batch, wgrad_split16=False, conv
 
 def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=None, chunk=None, host=False, freeze_bn=False, wgrad_split16=False,
                    conv_split16=False, train_from=None, prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None,
-                   color_seed=0, random_resized_crop=None):
+                   color_seed=0, random_resized_crop=None, gaussian_blur=None, random_grayscale=None, blur_seed=0):
     """_get_embedding(..., train=True): the module for the scope the trainer is built for; everything else keeps raising NotImplementedError"""
     if embedding_name not in _SINGLE and embedding_name not in _UBER and embedding_name not in _CLIP and embedding_name not in _NOT_BUILT \
             and embedding_name not in ('random', 'mae_base', 'mae_large', 'mae_huge'):
@@ -1254,6 +1380,8 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
     check_color_jitter(strengths, prefix_cache)
     rrc_scale = crop_scale(random_resized_crop)
     check_random_resized_crop(rrc_scale, prefix_cache, random_crop=random_crop)
+    blur, gray = blur_spec(gaussian_blur), gray_prob(random_grayscale)
+    check_gaussian_blur(blur, gray, prefix_cache)
     if host:
         raise NotImplementedError("training the embedding on the host backend (disable_cuda) is not built: %s" % _TRAINABLE_MSG)
     if compute_dtype is not None and _dtype_from_env(compute_dtype) != _lib.PVR_F32:
@@ -1264,7 +1392,9 @@ def _get_trainable(embedding_name, pretrained, compute_dtype=None, max_batch=Non
                               **({'prefix_cache': True} if prefix_cache else {}),
                               **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}),
                               **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}),
-                              **({'random_resized_crop': rrc_scale, 'crop_seed': crop_seed} if rrc_scale else {}))
+                              **({'random_resized_crop': rrc_scale, 'crop_seed': crop_seed} if rrc_scale else {}),
+                              **({'gaussian_blur': blur} if blur else {}), **({'blur_seed': blur_seed} if blur or gray else {}),
+                              **({'random_grayscale': gray} if gray else {}))
 
 
 class UberModel(nn.Module):
@@ -1460,7 +1590,8 @@ class EmbeddingNet(nn.Module):
 
     def __init__(self, embedding_name, in_channels=3, pretrained=True, train=False, disable_cuda=False,
                  compute_dtype=None, max_batch=None, chunk=None, crops=1, freeze_bn=False, wgrad_split16=False, conv_split16=False, train_from=None,
-                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0, random_resized_crop=None):
+                 prefix_once=False, prefix_cache=False, random_crop=False, crop_seed=0, color_jitter=None, color_seed=0, random_resized_crop=None,
+                 gaussian_blur=None, random_grayscale=None, blur_seed=0):
         super(EmbeddingNet, self).__init__()
         self.embedding_name = embedding_name
         if self.embedding_name == 'true_state':
@@ -1504,6 +1635,12 @@ class EmbeddingNet(nn.Module):
             raise ValueError('random_resized_crop is a mode of the trainable encoder (train=True): a frozen encoder embeds the centre crop of every frame '
                              '(crops=5 adds the four corner windows)')
         check_random_resized_crop(rrc_scale, prefix_cache, random_crop=random_crop)
+        blur, gray = blur_spec(gaussian_blur), gray_prob(random_grayscale)      # (a ValueError names a bad probability or sigma range)
+        for name, on in (('gaussian_blur', blur), ('random_grayscale', gray)):
+            if on is not None and not train:
+                raise ValueError('%s is a mode of the trainable encoder (train=True): a frozen encoder embeds the plain centre crop of every frame' % name)
+        check_gaussian_blur(blur, gray, prefix_cache)
+        # gaussian_blur, random_grayscale (train=True only): a training forward grays and blurs frames with the given probabilities; blur_seed keys the draw
         # random_resized_crop (train=True only): a training forward resizes a random rectangle of every frame to the crop; crop_seed keys the draw
         # color_jitter (train=True only): a training forward jitters brightness, contrast and saturation per frame; color_seed keys the draw
         # random_crop (train=True only): a training forward crops a random window per frame; crop_seed keys the draw (HipTrainableResNet.crop_call counts it)
@@ -1522,7 +1659,9 @@ class EmbeddingNet(nn.Module):
                                                          **({'prefix_cache': True} if prefix_cache else {}),
                                                          **({'random_crop': True, 'crop_seed': crop_seed} if random_crop else {}),
                                                          **({'color_jitter': strengths, 'color_seed': color_seed} if strengths else {}),
-                                                         **({'random_resized_crop': rrc_scale, 'crop_seed': crop_seed} if rrc_scale else {}))
+                                                         **({'random_resized_crop': rrc_scale, 'crop_seed': crop_seed} if rrc_scale else {}),
+                                                         **({'gaussian_blur': blur} if blur else {}), **({'blur_seed': blur_seed} if blur or gray else {}),
+                                                         **({'random_grayscale': gray} if gray else {}))
         assert crops in (1, 5), 'crops: 1 (the reference CenterCrop) or 5 (corner + centre windows, FiveCrop order)'
         if crops == 5:
             self.embedding = FiveCrop(self.embedding)

@@ -150,6 +150,33 @@ def check_random_resized_crop_flag(flags):
     return scale
 
 
+def check_gaussian_blur_flags(flags):
+    """--embedding_gaussian_blur P LO HI and --embedding_random_grayscale P are modes of --train_embedding, and not of --embedding_prefix_cache: a
+    ValueError otherwise, and for a probability outside [0, 1] or a sigma range that is not finite or not 0 < LO <= HI.  -> ((p, lo, hi) or None, p or
+    None): None where a mode is off (no flag, or a probability of 0)"""
+    from .embeddings import blur_spec, gray_prob
+    out = []
+    for flag, given, conv in (('--embedding_gaussian_blur', getattr(flags, 'embedding_gaussian_blur', None), lambda v: blur_spec(tuple(v))),
+                              ('--embedding_random_grayscale', getattr(flags, 'embedding_random_grayscale', None), gray_prob)):
+        if given is None:
+            out.append(None)
+            continue
+        try:
+            out.append(conv(given))
+        except ValueError as e:
+            raise ValueError('%s: %s' % (flag, e))
+        if out[-1] is None:                                     # (a probability of 0: off, nothing to refuse)
+            continue
+        if not getattr(flags, 'train_embedding', False):
+            raise ValueError('%s needs --train_embedding: it changes the image of a frame in the training steps of a trainable encoder (a frozen '
+                             'encoder embeds the plain centre crop)' % flag)
+        if getattr(flags, 'embedding_prefix_cache', False):
+            raise ValueError('%s with --embedding_prefix_cache: the cache holds the frozen prefix\'s output for ONE image per frame (the plain centre '
+                             'crop), and the mode changes the image in every step; --embedding_prefix_once, which keeps the prefix\'s output for the '
+                             'frames and images of one step, is the compatible mode' % flag)
+    return tuple(out)
+
+
 def prefix_cache_bytes(flags, n_dataset_frames):
     """--embedding_prefix_cache: (bytes of the boundary tensors of all n_dataset_frames = samples x frames dataset frames, bytes per frame of a pass's
     staging tensor), both next to the workspace; (0, 0) without the flag"""
@@ -298,6 +325,13 @@ def run_end_to_end(flags, make_env=None):
     if rrc_scale is not None:
         print('  ', 'random resized crop: every frame of a step is replaced by a random rectangle of itself, %g .. %g of its area and 3/4 .. 4/3 in '
               'aspect ratio, resized to the crop, seed %d (--embedding_random_resized_crop)' % (rrc_scale + (flags.run_id,)))
+    blur, gray = check_gaussian_blur_flags(flags)
+    if blur is not None:
+        print('  ', 'gaussian blur: a frame of a step is blurred with probability %g, 23 x 23 taps, sigma %g .. %g, seed %d '
+              '(--embedding_gaussian_blur)' % (blur + (flags.run_id,)))
+    if gray is not None:
+        print('  ', 'random grayscale: a frame of a step is replaced by its gray values with probability %g, seed %d (--embedding_random_grayscale)'
+              % (gray, flags.run_id))
     world = max(rank_world()[1], int(os.environ.get('WORLD_SIZE', '1')))
     if world > 1:
         raise NotImplementedError('--train_embedding with a world size of %d: data-parallel encoder training is not built (the trainable encoder and its '
@@ -358,6 +392,10 @@ def run_end_to_end(flags, make_env=None):
         split16 = dict(split16, color_jitter=color_jitter, color_seed=flags.run_id)
     if rrc_scale is not None:                                   # (likewise)
         split16 = dict(split16, random_resized_crop=rrc_scale, crop_seed=flags.run_id)
+    if blur is not None:                                        # (likewise)
+        split16 = dict(split16, gaussian_blur=blur, blur_seed=flags.run_id)
+    if gray is not None:                                        # (likewise)
+        split16 = dict(split16, random_grayscale=gray, blur_seed=flags.run_id)
     if getattr(flags, 'freeze_embedding_bn', False):            # the encoder is sized by the chunk; a step of T x B x frames runs as passes of it
         if not flags.pretrained_embedding:
             print('   WARNING! --freeze_embedding_bn with --disable_pretrained_embedding: a randomly initialised trunk with running statistics 0 / 1 is not normalised.')
@@ -401,7 +439,7 @@ def run_end_to_end(flags, make_env=None):
               % (pc.n_frames, pc.nbytes / 2 ** 30, pc.fill_seconds, pc.n_frames / max(pc.fill_seconds, 1e-9)))
     for frames in range(init_frames, flags.max_frames, B * T):
         epoch = frames // (B * T)
-        model.embedding.crop_call = epoch                       # (--embedding_random_crop, --embedding_color_jitter, --embedding_random_resized_crop: the iteration names the draw, so a resumed run draws what an uninterrupted one would)
+        model.embedding.crop_call = epoch                       # (--embedding_random_crop, --embedding_color_jitter, --embedding_random_resized_crop, --embedding_gaussian_blur, --embedding_random_grayscale: the iteration names the draw, so a resumed run draws what an uninterrupted one would)
         starting_i = sample_with_minimum_distance(n=n_samples, k=B, d=T)
         if prefix_cache:                                        # (T, B) sample indices: a step reads its frames' boundary tensors, no uint8 frame
             o = dataset.rows(starting_i, T)
@@ -461,6 +499,7 @@ def run(flags, make_env=None):
     check_random_crop_flag(flags)
     check_color_jitter_flag(flags)
     check_random_resized_crop_flag(flags)
+    check_gaussian_blur_flags(flags)
     if getattr(flags, 'train_embedding', False):
         return run_end_to_end(flags, make_env)
     rank, world = rank_world()

@@ -809,7 +809,7 @@ class HipJointRMSprop(object):
     With a random_crop encoder the step takes the windows the trainer's forward drew (there is no autograd node to carry them) and hands them to
     _backward_raw next to the boundary cache, so the recompute passes crop where the forward did; step_cached is unreachable with that mode.  A
     color_jitter encoder's colour parameters take the same way, next to the windows; a random_resized_crop encoder's rectangles travel in the windows'
-    place."""
+    place, and a gaussian_blur / random_grayscale encoder's blur parameters next to the colour parameters."""
 
     def __init__(self, model, lr=1e-4, alpha=0.99, eps=1e-5, momentum=0, max_grad_norm=40.0, max_epochs=None):
         if float(momentum) != 0:
@@ -884,12 +884,14 @@ class HipJointRMSprop(object):
             # one pvr_trainer_backward, or the chunk walk of a frozen-BatchNorm encoder (prefix_once: its recompute passes start at the first trained op)
             windows, enc._windows = getattr(enc, '_windows', None), None     # (random_crop: the step's windows, for the recompute passes that run the stem)
             color, enc._color = getattr(enc, '_color', None), None           # (color_jitter: the step's colour parameters, for the same passes)
+            blur, enc._blur = getattr(enc, '_blur', None), None              # (gaussian_blur / random_grayscale: the step's blur parameters, likewise)
             if rows is None:
                 enc._backward_raw(frames, dobs, g['embedding'], *(() if boundary is None else (boundary,)),
-                                  **({} if windows is None else {'windows': windows}), **({} if color is None else {'color': color}))
+                                  **({} if windows is None else {'windows': windows}), **({} if color is None else {'color': color}),
+                                  **({} if blur is None else {'blur': blur}))
             else:                                                             # (each recompute pass gathers its rows of the prefix cache again)
                 enc._backward_raw_cached(cache, crows, dobs, g['embedding'])
-            del boundary, windows, color
+            del boundary, windows, color, blur
             arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
             counts = (C.c_int64 * 2)(pol._n_train, enc._flat.numel())
             _lib.check(L.pvr_joint_apply_rmsprop(2, arr((pol._flat, enc._flat)), arr((self.square_avg['policy'], self.square_avg['embedding'])),
